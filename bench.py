@@ -8,18 +8,23 @@ factor + solve H p = -g   (reference optimizer/trajectory_optimi
 `idto_hip_gn_step` of the C-ABI.  fp64, synthetic trajectory,
 inputs resident in HBM before the timed region.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode shard|replicas]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode shard|replicas] [--full] [--dump-outputs DIR]
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`).  --full adds
+everything else this file measures or checks, each outside the timed region: per-kernel durations and the roofline,
+the per-step latency distribution, batches, the CPU baseline, the full trust-region iteration, the MPC re-plan and,
+for N > 1, the other multi-rank mode, the sharded-versus-unsharded bit check and config 5.  --dump-outputs DIR writes
+what the last timed step computed (rank 0) as DIR/<name>.npy, fp64.
 For N > 1 launch with `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`:
   shard (default) ONE problem (BASELINE config 4): the (k, column) perturbation grid is split into
            contiguous k-ranges, one per rank; one all-gather (RCCL) of the dtau/dq slab, then
            every rank assembles and solves redundantly; value = that problem's iterations/s
            ("scaling": "strong").  One MI355X already runs all N=40 fd blocks concurrently (40
-           of 256 CUs), so this mode cannot beat one GPU at this size: DESIGN.md §7.  The
+           of 256 CUs), so this mode cannot beat one GPU at this size: DESIGN.md §7.  With --full the
            replicas rate of the same ranks is reported as the extra "replicas_mode".
   replicas every rank iterates its own problem (same model and horizon, trajectory seed = rank;
            BASELINE config 5 style: `--mode replicas --config allegro_hand --num-steps 60`) with
            no data-path collective; value = total iterations/s over all ranks ("weak").
-The timed region of `value` contains no events and no host synchronisation; per-kernel
+The timed region of `value` contains no events and no host synchronisation; with --full, per-kernel
 durations (HIP events) and the per-step latency distribution (one synchronisation per step) are
 measured in separate passes afterwards.
 Prints ONE JSON line on rank 0.
@@ -98,6 +103,46 @@ def latency_model(kern_ms, names):
                                     "note": "this_run_us includes the assembly workgroups when the launch assembles g and H itself; "
                                             "the row model is of the solver alone"}
     return out
+
+
+def roofline(dev, kern, fused_run, N, nq, nv):
+    """The dominant kernel of the step against HBM bandwidth, from the per-kernel HIP-event pass `kern` ((avg ms, launches)
+    per timing slot) and the launch structure the context last ran."""
+    algb = algorithmic_bytes(N, nq, nv)
+    # the fused launch: SURVEY.md §8d's B_alg of the whole iteration (every intermediate written
+    # once and read once): 2,605,184 B for mini_cheetah N=40
+    algb.append(8 * (2 * 3 * N * nv * nq + 2 * 3 * (N + 1) * nq * nq + 2 * 5 * (N + 1) * nq * nq
+                     + 4 * (N + 1) * nq + 2 * (N + 1) * nv + 3 * N * nv))
+    dom = 3 if fused_run else int(np.argmax([k[0] for k in kern[:3]]))
+    names = list(KERNELS)
+    if dev.get_option("last_solver") == 2:   # nested dissection over seven workgroups (csrc/penta_nd.h)
+        names[2] = "penta_nd_kernel"
+    elif dev.get_option("last_solver") == 4:   # ... with pipelined chains, five workgroups (csrc/penta_pipe.h)
+        names[2] = "penta_pipe_kernel"
+    elif dev.get_option("last_solver") == 6:   # the small models: scalar band factorisation, one workgroup (csrc/penta_band.h)
+        names[2] = "penta_band_kernel"
+    elif dev.get_option("last_solver") == 7:   # ... and their whole step in one workgroup of one launch (csrc/gn_small.h)
+        names[3] = "gn_small_kernel"
+    if dev.get_option("last_assembly") == 1:   # products formed by fd_kernel, combined here (kernels.h)
+        names[1] = "assemble_terms_kernel"
+    asm_inside = dev.get_option("last_assembly") == 4   # the solver's launch assembled g and H itself (penta_pipe.h PipeAsm)
+    if asm_inside:
+        names[1] = "(inside %s)" % names[2]
+        algb[2] += algb[1]   # ... so its algorithmic bytes are the assembly's plus the solver's (DESIGN.md §6.3: 2.6 MB)
+    dur_s = kern[dom][0] * 1e-3
+    achieved = algb[dom] / dur_s / 1e9 if dur_s > 0 else 0.0
+    traffic, traffic_src = pmc_traffic(names[dom])
+    return {"bound": "hbm", "kernel": names[dom], "achieved": achieved, "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "traffic_source": traffic_src,
+            "algorithmic_bytes_per_launch": algb[dom], "avg_launch_ms": kern[dom][0],
+            "launches_timed": kern[dom][1],
+            "all_kernels_avg_ms": {names[i]: kern[i][0] for i in range(4) if kern[i][1] > 0},
+            "wasted_traffic_ratio": (traffic / algb[dom]) if traffic else None,
+            "algorithmic_bytes_include_the_assembly": bool(asm_inside and dom == 2),
+            "latency_model": latency_model(kern, names),
+            "note": "latency/dependency-bound path (SURVEY.md §8d): the HBM fraction is intrinsically small; "
+                    "latency_model states the bounds that apply and the achieved fraction of those"}
 
 
 def host_cpu_limit():
@@ -239,9 +284,20 @@ def mpc_replan(cfg, model, device, replans=50):
             "what": "idto_mpc_update (C++ ModelPredictiveController on the device), the example YAML's horizon and mpc_iters"}
 
 
+# what one idto_hip_gn_step hands its caller (include/idto_hip.h): the step, the gradient and Hessian bands it solves, and
+# v, a, tau on the way; all of it fp64 and small (0.4 MB for mini_cheetah N=40), so it is written whole
+DUMP_ARRAYS = ("step", "gradient", "H_A", "H_B", "H_C", "tau", "v", "a")
+
+
+def dump_outputs(dev, outdir):
+    os.makedirs(outdir, exist_ok=True)
+    for name in DUMP_ARRAYS:
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(dev.get(name), dtype=np.float64))
+
+
 SHARD_NOTE = ("sharding ONE N=40 problem cannot beat one GPU: its 40 finite-difference workgroups already run side by side "
               "on 40 of the 256 CUs, the all-gather adds a hand-over, and the block solve (a dependent chain) does not "
-              "shard - DESIGN.md §7; the aggregate of independent problems is reported as replicas_mode / config5_workload")
+              "shard - DESIGN.md §7; with --full, the aggregate of independent problems is reported as replicas_mode / config5_workload")
 
 
 def self_launch_command(argv, gpus, visible_gpus, port=None):
@@ -270,10 +326,14 @@ def main():
     ap.add_argument("--mode", choices=["shard", "replicas"], default="shard")
     ap.add_argument("--config", default="mini_cheetah")
     ap.add_argument("--num-steps", type=int, default=40, help="horizon N")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-full", action="store_true", help="skip the informational full-iteration measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check (see the module docstring); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-full", action="store_true",
+                    help="with --full: skip the informational full-iteration, MPC and batched trust-region measurements")
     ap.add_argument("--batch", type=int, default=16,
-                    help="also report the aggregate rate of this many independent problems on one GPU (0/1: skip)")
+                    help="with --full: also report the aggregate rate of this many independent problems on one GPU (0/1: skip)")
     ap.add_argument("--set", action="append", default=[], metavar="OPTION=INT",
                     help="a context option of the C-ABI (idto_hip_set_option), e.g. asm_in_solver=0: profiling aid")
     args = ap.parse_args()
@@ -406,41 +466,44 @@ def main():
         step()
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(dev, args.dump_outputs)
 
-    # ---- separate pass 1: per-kernel durations, HIP events around every launch (on the context's
-    # stream); never part of `value`, so `value` does not depend on --steps
-    dev.timing_enable(1)
-    dev.timing_reset()
-    for _ in range(max(20, min(100, args.steps))):
-        step()
-    barrier()
-    dev.timing_enable(False)
-    kern = []
-    for w in range(4):
-        ms, n = dev.timing_get(w)
-        kern.append((ms, n))
-    fused_run = kern[3][1] > 0   # the iteration ran as one persistent launch (csrc/fused.h)
-    # ---- separate pass 2: latency of ONE step (launch -> results complete), synchronised per step
-    lat = []
-    for _ in range(max(50, min(200, args.steps))):
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        step()
-        torch.cuda.synchronize()
-        lat.append(1e3 * (time.perf_counter() - t1))
-    lat = np.sort(np.array(lat))
-    latency = {"median": float(np.median(lat)), "p10": float(lat[int(0.1 * (len(lat) - 1))]),
-               "p90": float(lat[int(0.9 * (len(lat) - 1))]), "samples": len(lat),
-               "what": "one step with a host synchronisation before and after (ms); `value` is the "
-                       "back-to-back rate of the timed region"}
-    p = dev.get("step")
-    g = dev.get("gradient")
-    assert np.all(np.isfinite(p)) and np.all(np.isfinite(g))
+    if args.full:
+        # ---- separate pass 1: per-kernel durations, HIP events around every launch (on the context's
+        # stream); never part of `value`, so `value` does not depend on --steps
+        dev.timing_enable(1)
+        dev.timing_reset()
+        for _ in range(max(20, min(100, args.steps))):
+            step()
+        barrier()
+        dev.timing_enable(False)
+        kern = []
+        for w in range(4):
+            ms, n = dev.timing_get(w)
+            kern.append((ms, n))
+        fused_run = kern[3][1] > 0   # the iteration ran as one persistent launch (csrc/fused.h)
+        # ---- separate pass 2: latency of ONE step (launch -> results complete), synchronised per step
+        lat = []
+        for _ in range(max(50, min(200, args.steps))):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            step()
+            torch.cuda.synchronize()
+            lat.append(1e3 * (time.perf_counter() - t1))
+        lat = np.sort(np.array(lat))
+        latency = {"median": float(np.median(lat)), "p10": float(lat[int(0.1 * (len(lat) - 1))]),
+                   "p90": float(lat[int(0.9 * (len(lat) - 1))]), "samples": len(lat),
+                   "what": "one step with a host synchronisation before and after (ms); `value` is the "
+                           "back-to-back rate of the timed region"}
+        p = dev.get("step")
+        g = dev.get("gradient")
+        assert np.all(np.isfinite(p)) and np.all(np.isfinite(g))
 
     # ---- the other multi-rank mode on the same ranks, outside the timed region of `value`
     # (every rank takes the same branch: collectives inside)
     other_extra, other_key = None, None
-    if world > 1 and exch is not None:
+    if args.full and world > 1 and exch is not None:
         other_key = "replicas_mode" if sharded else "shard_mode"
         try:
             if sharded:
@@ -476,7 +539,7 @@ def main():
 
     # ---- the sharded result against the same problem on one device (every rank: same bits expected everywhere)
     bit_identical = None
-    if world > 1 and sharded and exch is not None:
+    if args.full and world > 1 and sharded and exch is not None:
         try:
             dev.set_shard(exch.lo, exch.hi)
             dev.set_q(q)
@@ -495,7 +558,7 @@ def main():
     # ---- BASELINE config 5 on the same ranks (informational, outside the timed region of `value`): allegro_hand
     # + sphere, 60 steps, one warm-started problem per GPU, no collective on the data path
     config5 = None
-    if world > 1:
+    if args.full and world > 1:
         try:
             c5, m5 = load_config("allegro_hand"), load_model("allegro_hand")
             N5 = 60
@@ -528,7 +591,7 @@ def main():
             config5 = {"error": str(e)[:200]}
 
     batch_extra = None
-    if world == 1 and args.batch > 1:
+    if args.full and world == 1 and args.batch > 1:
         # informational (never `value`): B independent problems resident on this ONE GPU and advanced by
         # ONE host thread with one launch per kernel (idto_hip_create_batch / idto_hip_gn_step_batch,
         # grid.y = problem) - one problem leaves most of the 256 CUs idle, a batched / sampling MPC
@@ -561,7 +624,7 @@ def main():
     # through whole trust-region iterations (scaling, dogleg, trial point, ratio, accept / reject on the device) by
     # idto_hip_tr_solve_batch: one launch set per iteration for all of them, one host thread, one wait
     batch_tr = None
-    if world == 1 and args.batch > 1 and not args.no_full:
+    if args.full and world == 1 and args.batch > 1 and not args.no_full:
         try:
             c5, m5 = load_config("allegro_hand"), load_model("allegro_hand")
             N5, B5, it5 = 60, 8, 10
@@ -621,30 +684,6 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
 
     if rank == 0:
-        algb = algorithmic_bytes(N, nq, nv)
-        # the fused launch: SURVEY.md §8d's B_alg of the whole iteration (every intermediate written
-        # once and read once): 2,605,184 B for mini_cheetah N=40
-        algb.append(8 * (2 * 3 * N * nv * nq + 2 * 3 * (N + 1) * nq * nq + 2 * 5 * (N + 1) * nq * nq
-                         + 4 * (N + 1) * nq + 2 * (N + 1) * nv + 3 * N * nv))
-        dom = 3 if fused_run else int(np.argmax([k[0] for k in kern[:3]]))
-        names = list(KERNELS)
-        if dev.get_option("last_solver") == 2:   # nested dissection over seven workgroups (csrc/penta_nd.h)
-            names[2] = "penta_nd_kernel"
-        elif dev.get_option("last_solver") == 4:   # ... with pipelined chains, five workgroups (csrc/penta_pipe.h)
-            names[2] = "penta_pipe_kernel"
-        elif dev.get_option("last_solver") == 6:   # the small models: scalar band factorisation, one workgroup (csrc/penta_band.h)
-            names[2] = "penta_band_kernel"
-        elif dev.get_option("last_solver") == 7:   # ... and their whole step in one workgroup of one launch (csrc/gn_small.h)
-            names[3] = "gn_small_kernel"
-        if dev.get_option("last_assembly") == 1:   # products formed by fd_kernel, combined here (kernels.h)
-            names[1] = "assemble_terms_kernel"
-        asm_inside = dev.get_option("last_assembly") == 4   # the solver's launch assembled g and H itself (penta_pipe.h PipeAsm)
-        if asm_inside:
-            names[1] = "(inside %s)" % names[2]
-            algb[2] += algb[1]   # ... so its algorithmic bytes are the assembly's plus the solver's (2.6 MB)
-        dur_s = kern[dom][0] * 1e-3
-        achieved = algb[dom] / dur_s / 1e9 if dur_s > 0 else 0.0
-        traffic, traffic_src = pmc_traffic(names[dom])
         out = {
             "metric": f"Gauss-Newton iters/sec (grad+Hessian+solve), {args.config} N={N}",
             "value": value, "unit": "GN iters/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -660,18 +699,9 @@ def main():
                                         f"of the dtau/dq slabs ({'ncclAllGather inside libidto_hip.so' if exchange == 'rccl' else 'torch.distributed'}), "
                                         f"redundant assemble+solve" if sharded else
                                         f"{world} independent replicas"))},
-            "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": algb[dom], "avg_launch_ms": kern[dom][0],
-                         "launches_timed": kern[dom][1],
-                         "all_kernels_avg_ms": {names[i]: kern[i][0] for i in range(4) if kern[i][1] > 0},
-                         "wasted_traffic_ratio": (traffic / algb[dom]) if traffic else None,
-                         "algorithmic_bytes_include_the_assembly": bool(asm_inside and dom == 2),
-                         "latency_model": latency_model(kern, names),
-                         "note": "latency/dependency-bound path (SURVEY.md §8d): the HBM fraction is intrinsically small; "
-                                 "latency_model states the bounds that apply and the achieved fraction of those"},
         }
+        if args.full:
+            out["roofline"] = roofline(dev, kern, fused_run, N, nq, nv)
         notes = []
         if world > 1:
             notes.append(SHARD_NOTE)
@@ -689,20 +719,21 @@ def main():
             out["bit_identical_to_unsharded"] = bit_identical
         if config5 is not None:
             out["config5_workload"] = config5
-        try:   # which RCCL this process resolved (libidto_hip.so checks the major version where a communicator is created)
-            rp, rv = hip.rccl_info()
-            out["rccl"] = {"path": rp, "version_code": rv}
-        except Exception as e:
-            out["rccl"] = {"error": str(e)[:120]}
-        out["step_latency_ms"] = latency
+        if args.full:
+            try:   # which RCCL this process resolved (libidto_hip.so checks the major version where a communicator is created)
+                rp, rv = hip.rccl_info()
+                out["rccl"] = {"path": rp, "version_code": rv}
+            except Exception as e:
+                out["rccl"] = {"error": str(e)[:120]}
+            out["step_latency_ms"] = latency
         if batch_extra is not None:
             out["batch_mode"] = batch_extra
         if batch_tr is not None:
             out["batch_trust_region"] = batch_tr
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.config, N)
             out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
-        if world == 1 and not args.no_full:
+        if args.full and world == 1 and not args.no_full:
             out["full_iteration"] = full_iteration(cfg, model, N, local_rank, not args.no_cpu)
             try:
                 out["mpc_replan"] = mpc_replan(cfg, model, local_rank)

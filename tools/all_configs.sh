@@ -4,10 +4,10 @@ R=${ROUND:-r04}
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 OUT=gpurun_out/${R}_all_configs.txt
-echo "python bench.py --config <c> --num-steps <N> --batch <B> --no-full --steps 100 --warmup 10   (1x MI355X; HIP-event kernel times in us)" > $OUT
+echo "python bench.py --config <c> --num-steps <N> --full --batch <B> --no-full --steps 100 --warmup 10   (1x MI355X; HIP-event kernel times in us)" > $OUT
 for cfg in "acrobot 40 16" "spinner 40 16" "hopper 50 16" "mini_cheetah 40 16" "allegro_hand 60 8"; do
   set -- $cfg
-  timeout 600 python bench.py --config $1 --num-steps $2 --batch $3 --no-full --steps 100 --warmup 10 2>/dev/null | tail -1 > /tmp/line.json
+  timeout 600 python bench.py --config $1 --num-steps $2 --full --batch $3 --no-full --steps 100 --warmup 10 2>/dev/null | tail -1 > /tmp/line.json
   python - "$1" "$2" <<'PY' >> $OUT
 import json, sys
 b = json.loads(open('/tmp/line.json').read())

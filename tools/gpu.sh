@@ -20,7 +20,7 @@ cd "$ROOT"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 quiet() { grep -v amdgpu.ids; }
-BENCH_SHORT="python bench.py --steps 200 --warmup 20 --no-cpu"
+BENCH_SHORT="python bench.py --steps 200 --warmup 20 --no-cpu --full"
 BENCH_KERNELS="python $ROOT/bench.py --steps 100 --warmup 10 --no-cpu --no-full --batch 0"
 bench_line() { python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(round(d["value"]), d["ms_per_step"], d["roofline"]["all_kernels_avg_ms"])'; }
 
@@ -45,7 +45,7 @@ solver)
 variants)
   for v in "$@"; do
     L=build/variants/$v/libidto_hip.so; [ "$v" = base ] && L=idto_amd/libidto_hip.so
-    for rep in 1 2; do echo "$v: $(IDTO_HIP_LIB=$L timeout 200 python bench.py --steps 300 --warmup 30 --no-cpu --no-full --batch 0 2>&1 | tail -1 | bench_line)"; done
+    for rep in 1 2; do echo "$v: $(IDTO_HIP_LIB=$L timeout 200 python bench.py --steps 300 --warmup 30 --full --no-cpu --no-full --batch 0 2>&1 | tail -1 | bench_line)"; done
     IDTO_HIP_LIB=$L timeout 120 python tools/nd_timeline.py 2>&1 | grep "elimination of row\|^separator \|joiner \|producer "
   done
   ;;
@@ -64,7 +64,7 @@ stress)
   } | tee gpurun_out/${R}_solver_stress.txt
   ;;
 batch32)
-  line() { timeout 600 python bench.py --config allegro_hand --num-steps 60 --batch 8 --no-full --no-cpu --steps 100 --warmup 10 2>/dev/null | tail -1 | python -c "
+  line() { timeout 600 python bench.py --config allegro_hand --num-steps 60 --full --batch 8 --no-full --no-cpu --steps 100 --warmup 10 2>/dev/null | tail -1 | python -c "
 import json,sys
 b=json.loads(sys.stdin.read()); k=b['roofline']['all_kernels_avg_ms']
 print(round(b['value']), {n: round(1e3*v,1) for n,v in k.items()}, [(e['problems'], round(e['value'])) for e in (b.get('batch_mode') or [])])"; }
@@ -83,7 +83,7 @@ prof)
   ;;
 two-ranks)
   IDTO_BENCH_SAME_GPU=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 \
-    bench.py --gpus 2 --steps 40 --warmup 5 2>&1 | tail -3 | cut -c1-3000 | tee gpurun_out/bench_2rank_same_gpu.log
+    bench.py --gpus 2 --steps 40 --warmup 5 --full 2>&1 | tail -3 | cut -c1-3000
   timeout 300 python -m pytest tests/test_gpu_multi.py -q 2>&1 | tail -3
   ;;
 check)
@@ -91,7 +91,7 @@ check)
   rocminfo 2>/dev/null | grep -E "Marketing Name|gfx" | head -4
   timeout 1700 python -m pytest tests -m gpu -x -q 2>&1 | quiet | tail -25 | tee gpurun_out/${R}_pytest_gpu.txt
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | quiet | tail -5 | tee gpurun_out/${R}_smoke.txt
-  timeout 900 python bench.py 2>&1 | tail -1 | tee gpurun_out/${R}_bench.json
+  timeout 900 python bench.py --full 2>&1 | tail -1
   timeout 120 python tools/nd_timeline.py 2>&1 | quiet | tee gpurun_out/${R}_nd_timeline.txt
   IDTO_TIMELINE_GN_STEP=1 timeout 120 python tools/nd_timeline.py 2>&1 | quiet | tee gpurun_out/${R}_nd_timeline_gn_step.txt
   timeout 120 python tools/nd_timeline.py allegro_hand 60 2>&1 | quiet | tee gpurun_out/${R}_nd_timeline_allegro.txt

@@ -256,12 +256,14 @@ __host__ __device__ inline int asm_terms_stride(int nq) { return 6 * nq * nq + 3
 // mode 0: tau only (one evaluation); mode 1: forward differences (TO.cc:426-563).
 // Dynamic LDS layout (doubles): see the carve-up below.
 // the instantiated tree shapes of id_fast.h (DevModel::fast_shape; 0 = any model: id_eval<MAXC>)
-template <int SHAPE> struct FastShape { static constexpr int MAXC = 0, NP = 1, CJ = -1, J0 = 0, K0 = 0, W2 = -1; };
-template <> struct FastShape<1> { static constexpr int MAXC = 2, NP = 1, CJ = -1, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_WORLD, W2 = -1; };             // acrobot
-template <> struct FastShape<2> { static constexpr int MAXC = 3, NP = 1, CJ = -1, J0 = IDTO_JOINT_PLANAR, K0 = PK_WORLD, W2 = -1; };               // hopper
-template <> struct FastShape<3> { static constexpr int MAXC = 3, NP = 4, CJ = IDTO_JOINT_FLOATING, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_COMMON, W2 = -1; };  // mini_cheetah
-template <> struct FastShape<4> { static constexpr int MAXC = 4, NP = 4, CJ = IDTO_JOINT_FLOATING, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_WORLD, W2 = -1; };   // allegro_hand + ball
-template <> struct FastShape<5> { static constexpr int MAXC = 3, NP = 1, CJ = -1, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_WORLD, W2 = 2; };              // spinner: two-link finger + the spinner, off the world
+// GS: bodies whose weight is switched off are allowed (id_fast.h); the other shapes are chosen only when every body has it
+template <int SHAPE> struct FastShape { static constexpr int MAXC = 0, NP = 1, CJ = -1, J0 = 0, K0 = 0, W2 = -1, GS = 0; };
+template <> struct FastShape<1> { static constexpr int MAXC = 2, NP = 1, CJ = -1, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_WORLD, W2 = -1, GS = 0; };             // acrobot
+template <> struct FastShape<2> { static constexpr int MAXC = 3, NP = 1, CJ = -1, J0 = IDTO_JOINT_PLANAR, K0 = PK_WORLD, W2 = -1, GS = 0; };               // hopper
+template <> struct FastShape<3> { static constexpr int MAXC = 3, NP = 4, CJ = IDTO_JOINT_FLOATING, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_COMMON, W2 = -1, GS = 0; };  // mini_cheetah
+template <> struct FastShape<4> { static constexpr int MAXC = 4, NP = 4, CJ = IDTO_JOINT_FLOATING, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_WORLD, W2 = -1, GS = 0; };   // allegro_hand + ball
+template <> struct FastShape<5> { static constexpr int MAXC = 3, NP = 1, CJ = -1, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_WORLD, W2 = 2, GS = 0; };              // spinner: two-link finger + the spinner, off the world
+template <> struct FastShape<6> { static constexpr int MAXC = 7, NP = 1, CJ = IDTO_JOINT_FLOATING, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_WORLD, W2 = -1, GS = 1; };   // a free object + an arm of seven revolute bodies off the world (jaco, jaco_ball)
 
 template <int MAXC, int SHAPE = 0>
 IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem& P, const double* __restrict__ q,
@@ -568,6 +570,7 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
     using FS = FastShape<SHAPE>;
     FastTab FT;
     FT.body = Ml.f_body; FT.cbody = Ml.f_cbody; FT.pairs = Ml.f_pairs; FT.seg = Ml.f_seg; FT.maxpp = Ml.f_maxpp;
+    FT.gslots = Ml.gslots; FT.gcommon = Ml.gcommon;
     const int grp = tid / FS::NP, path = tid % FS::NP;
     for (int e0 = 0; e0 < ce; e0 += groups) {
       const int el = (e0 == 0) ? grp : e0 + (groups - 1 - grp);
@@ -583,7 +586,7 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
           in.sda = (in.kind == 2) ? -eda[el] : ((in.kind == 1) ? eda[el] : 0.0);
           in.keep = (in.kind == 3) ? 0ull : ~0ull;
           in.keep0 = (in.kind == 2) ? ~0ull : 0ull;
-          id_eval_fast<FS::MAXC, FS::NP, FS::CJ, FS::J0, FS::K0, FS::W2>(FT, Ml.gravity, cp, path, full, in, etau + el * nv
+          id_eval_fast<FS::MAXC, FS::NP, FS::CJ, FS::J0, FS::K0, FS::W2, FS::GS>(FT, Ml.gravity, cp, path, full, in, etau + el * nv
 #ifdef IDTO_FD_STAMPS
                                                                  , (e0 == 0) ? idto_fd_st : nullptr
 #endif
@@ -591,7 +594,7 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
         } else {
           InLds in;
           in.q = eq + el * nq; in.v = ev + el * nv; in.a = ea + el * nv;
-          id_eval_fast<FS::MAXC, FS::NP, FS::CJ, FS::J0, FS::K0, FS::W2>(FT, Ml.gravity, cp, path, full, in, etau + (c0 + el) * nv);
+          id_eval_fast<FS::MAXC, FS::NP, FS::CJ, FS::J0, FS::K0, FS::W2, FS::GS>(FT, Ml.gravity, cp, path, full, in, etau + (c0 + el) * nv);
         }
       }
     }

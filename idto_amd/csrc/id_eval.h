@@ -70,6 +70,10 @@ struct DevModel {
   const double* f_cbody;
   const double* f_pairs;
   const int* f_seg;
+  // per-body gravity switch (idto_model_t::gravity_enabled), resolved at create: bit path * IDTO_MAX_CHAIN + slot is set
+  // when that chain body's weight is applied, gcommon when the common body's is (all set: every body, the default)
+  unsigned long long gslots;
+  int gcommon;
 };
 
 // The model with every table pointer rebased from the global blob to a copy at `dst`
@@ -269,6 +273,13 @@ IDTO_DEV PairForce contact_pair(const DevModel& M, const DevContact& cp, int ga,
   return out;
 }
 
+// The gravity a body's inertial wrench subtracts: g, or exact zeros for a body whose weight is switched off - then
+// (acom - 0) * m is acom * m bit for bit, the oracle's expression with a zero gravity vector.
+IDTO_DEV V3 body_gravity(bool on, V3 g) { return mk(on ? g.x : 0.0, on ? g.y : 0.0, on ? g.z : 0.0); }
+IDTO_DEV bool slot_gravity(unsigned long long gslots, int path, int s) {
+  return ((gslots >> (path * IDTO_MAX_CHAIN + s)) & 1ull) != 0;
+}
+
 // Inertial wrench of body b about its origin, world frame.
 IDTO_DEV void inertial_wrench(const DevModel& M, int b, const M3& R, V3 w, V3 al, V3 a, V3 g, V3* f_in, V3* n_in) {
   const V3 cW = R * ldv3(M.com + 3 * b);
@@ -346,7 +357,7 @@ IDTO_DEV void id_eval(const DevModel& M, const DevContact& cp, int path, bool fu
     cb_al = j.al_rel;
     cb_a = j.a_rel;
     cb_hW = j.hW;
-    inertial_wrench(M, cbody, cb.R, cb.w, cb_al, cb_a, g, &cb_fin, &cb_nin);
+    inertial_wrench(M, cbody, cb.R, cb.w, cb_al, cb_a, body_gravity(M.gcommon != 0, g), &cb_fin, &cb_nin);
   }
 
   // ---- own chain: forward pass
@@ -380,7 +391,7 @@ IDTO_DEV void id_eval(const DevModel& M, const DevContact& cp, int path, bool fu
       bs[s].v = (vp + cross(wp, r[s])) + j.v_rel;
       const V3 al = (alp + j.al_rel) + cross(wp, j.w_rel);
       const V3 acc = (((ap + cross(alp, r[s])) + cross(wp, cross(wp, r[s]))) + cross(wp, j.v_rel) * 2.0) + j.a_rel;
-      inertial_wrench(M, b, bs[s].R, bs[s].w, al, acc, g, &fin[s], &nin[s]);
+      inertial_wrench(M, b, bs[s].R, bs[s].w, al, acc, body_gravity(slot_gravity(M.gslots, path, s), g), &fin[s], &nin[s]);
       al_prev = al;
       a_prev = acc;
     }

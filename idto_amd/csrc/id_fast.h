@@ -298,6 +298,8 @@ struct FastTab {
   const double* pairs;   // [npaths][maxpp] records of FP_STRIDE doubles, in processing order
   const int* seg;        // [npaths][MAXC + 2] start | count << 16: pairs without a chain body that come first, slots 0 .. MAXC-1, the rest
   int maxpp;
+  unsigned long long gslots;   // DevModel::gslots / gcommon: read by the shapes with a per-body gravity switch (GS) only
+  int gcommon;
 };
 
 // Where an evaluation's q, v, a come from.  InLds: arrays some other phase has built.
@@ -340,12 +342,14 @@ struct InFwd {
   IDTO_DEV InFwd laundered() const { InFwd o = *this; o.v1 = lds_launder(v1); o.N1 = lds_launder(N1); return o; }
 };
 
+// GS: the shape's bodies may have their weight switched off (DevModel::gslots, gcommon); the shapes without it are built
+// only for models whose every body has gravity, and their code is what it was without the switch.
 // tau = ID(q, v, a) for the lane's path: id_eval<MAXC> for a model of shape (CJ, J0, K0).
 // W2 >= 1 (the spinner: finger of two links + the spinner itself in ONE path): slot W2 hangs off the world again, and the
 // pairs of its group touch slot W2 - 1 as their other body (pair_eval's "common" argument is that slot's state; the
 // force on it is taken out of its wrench after the group - the slot has no pairs of its own, BuildModel checks, so the
 // order of the generic sum, fin - (0 + f), is kept).
-template <int MAXC, int NP, int CJ, int J0, int K0, int W2, class In>
+template <int MAXC, int NP, int CJ, int J0, int K0, int W2, int GS = 0, class In>
 IDTO_DEV void id_eval_fast(const FastTab& T, const double* gravity, const DevContact& cp, int path, bool full,
                            const In& in_fwd, double* tau, long long* idto_fd_st = nullptr) {
   const In& in = in_fwd;
@@ -416,7 +420,7 @@ IDTO_DEV void id_eval_fast(const FastTab& T, const double* gravity, const DevCon
     cb.v = zero + v_rel;
     cb_al = zero + al_rel;
     cb_a = zero + a_rel;
-    inertial_wrench_rec(ct, cb.R, cb.w, cb_al, cb_a, g, &cb_fin, &cb_nin);
+    inertial_wrench_rec(ct, cb.R, cb.w, cb_al, cb_a, GS ? body_gravity(T.gcommon != 0, g) : g, &cb_fin, &cb_nin);
     pin(cb_fin); pin(cb_nin);
     if (full) pair_group<false>(plist, seg[0], cp, cb, cb, &cfe, &cne, &cfe, &cne);
   }
@@ -481,7 +485,7 @@ IDTO_DEV void id_eval_fast(const FastTab& T, const double* gravity, const DevCon
       }
     }
     V3 fin, nin;
-    inertial_wrench_rec(rec, bs.R, bs.w, al, acc, g, &fin, &nin);
+    inertial_wrench_rec(rec, bs.R, bs.w, al, acc, GS ? body_gravity(slot_gravity(T.gslots, path, s), g) : g, &fin, &nin);
     pin(fin); pin(nin); pin(r[s]); pin(hW[s]);
     if (s == MAXC - 1) FD_STAMP(8);
     if (s + 1 < MAXC) prefetch_record(bt + (s + 1) * FB_STRIDE, rc_next);   // ... the next slot's, across this slot's pairs

@@ -96,6 +96,7 @@ struct DevBuf {
 struct HostModelCopy {
   idto_model_t m;
   std::vector<int> parent, jtype, qstart, vstart, actuated, geom_body, geom_type, pair_a, pair_b, body_path, pair_path;
+  std::vector<int> gravity_enabled;
   std::vector<double> X_PF, axis, mass, com, inertia, damping, geom_X, geom_size;
   void Set(const idto_model_t& s) {
     m = s;
@@ -105,6 +106,7 @@ struct HostModelCopy {
     parent = ci(s.parent, nb); jtype = ci(s.jtype, nb); qstart = ci(s.qstart, nb); vstart = ci(s.vstart, nb);
     actuated = ci(s.actuated, s.nv); geom_body = ci(s.geom_body, ng); geom_type = ci(s.geom_type, ng);
     pair_a = ci(s.pair_a, np); pair_b = ci(s.pair_b, np); body_path = ci(s.body_path, nb); pair_path = ci(s.pair_path, np);
+    gravity_enabled = ci(s.gravity_enabled, nb);
     X_PF = cd(s.X_PF, (size_t)12 * nb); axis = cd(s.axis, (size_t)3 * nb); mass = cd(s.mass, nb); com = cd(s.com, (size_t)3 * nb);
     inertia = cd(s.inertia, (size_t)6 * nb); damping = cd(s.damping, s.nv); geom_X = cd(s.geom_X, (size_t)12 * ng);
     geom_size = cd(s.geom_size, (size_t)3 * ng);
@@ -113,6 +115,7 @@ struct HostModelCopy {
     m.pair_a = pair_a.data(); m.pair_b = pair_b.data(); m.body_path = body_path.data(); m.pair_path = pair_path.data();
     m.X_PF = X_PF.data(); m.axis = axis.data(); m.mass = mass.data(); m.com = com.data(); m.inertia = inertia.data();
     m.damping = damping.data(); m.geom_X = geom_X.data(); m.geom_size = geom_size.data();
+    m.gravity_enabled = gravity_enabled.empty() ? nullptr : gravity_enabled.data();
   }
 };
 struct HostProblemCopy {
@@ -502,6 +505,16 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
       return -1;
     }
   if (m->common_body >= 0 && m->parent[m->common_body] >= 0) { g_err = "the common body must be attached to the world"; return -1; }
+  // per-body gravity switch: 0 or 1 per body, NULL = every body
+  bool all_gravity = true;
+  if (m->gravity_enabled)
+    for (int i = 0; i < nb; ++i) {
+      if (m->gravity_enabled[i] != 0 && m->gravity_enabled[i] != 1) {
+        g_err = "gravity_enabled entries must be 0 or 1";
+        return -1;
+      }
+      all_gravity = all_gravity && m->gravity_enabled[i] == 1;
+    }
   for (int i = 0; i < nb; ++i) {
     if (i == m->common_body) { slot_of[i] = -1; continue; }
     const int p = m->body_path[i];
@@ -552,6 +565,12 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
   M.nb = nb; M.nq = m->nq; M.nv = m->nv; M.npaths = K; M.common_body = m->common_body;
   M.ngeoms = m->ngeoms; M.npairs = m->npairs; M.maxpp = maxpp;
   for (int i = 0; i < 3; ++i) M.gravity[i] = m->gravity[i];
+  M.gslots = 0; M.gcommon = 1;
+  for (int i = 0; i < nb; ++i) {
+    const bool on = !m->gravity_enabled || m->gravity_enabled[i] == 1;
+    if (i == m->common_body) M.gcommon = on ? 1 : 0;
+    else if (on) M.gslots |= 1ull << (m->body_path[i] * IDTO_MAX_CHAIN + slot_of[i]);
+  }
   // one blob: double tables, then int tables (two per double slot)
   std::vector<double> dbl;
   std::vector<int> ints;
@@ -618,6 +637,11 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
       else if (maxc == 3 && K == 1 && cj == -1 && j0 == IDTO_JOINT_PLANAR && k0 == PK_WORLD) fast_shape = 2;     // hopper
       else if (maxc == 3 && K == 4 && cj == IDTO_JOINT_FLOATING && j0 == IDTO_JOINT_REVOLUTE && k0 == PK_COMMON) fast_shape = 3;   // mini_cheetah
       else if (maxc == 4 && K == 4 && cj == IDTO_JOINT_FLOATING && j0 == IDTO_JOINT_REVOLUTE && k0 == PK_WORLD) fast_shape = 4;    // allegro_hand + ball
+      // (shapes 1 - 5 apply gravity to every body: a model with a body switched off is theirs only through id_eval)
+      if (!all_gravity) fast_shape = 0;
+      // a free object + one arm of seven revolute bodies off the world, any gravity switches (the Jaco examples)
+      if (maxc == 7 && K == 1 && cj == IDTO_JOINT_FLOATING && j0 == IDTO_JOINT_REVOLUTE && k0 == PK_WORLD && w2 < 0)
+        fast_shape = 6;
     }
     // processing order of a path's pairs: [pairs without a chain body that come first | slot 0 | ... | slot maxc-1 |
     // the other pairs without a chain body].  The sums that have an order are those onto one chain body (its pairs stay
@@ -3075,7 +3099,7 @@ int idto_hip_get_option(idto_hip_ctx* c, const char* name, int* value) {
   if (std::strcmp(name, "two_sided") == 0) { *value = c->two_sided; return 0; }
   if (std::strcmp(name, "reference_solver") == 0) { *value = c->reference_solver; return 0; }
   if (std::strcmp(name, "gradients_method") == 0) { *value = c->gradients_method; return 0; }
-  if (std::strcmp(name, "fast_shape") == 0) { *value = c->M.fast_shape; return 0; }   // id_fast.h: 0 none, 1 acrobot, 2 hopper, 3 mini_cheetah, 4 allegro_hand, 5 spinner
+  if (std::strcmp(name, "fast_shape") == 0) { *value = c->M.fast_shape; return 0; }   // id_fast.h: 0 none, 1 acrobot, 2 hopper, 3 mini_cheetah, 4 allegro_hand, 5 spinner, 6 free object + one 7-body arm
   if (std::strcmp(name, "fd_fast") == 0) { *value = c->fd_fast ? 1 : 0; return 0; }
   g_err = std::string("unknown option ") + name;
   return -1;

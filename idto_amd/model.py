@@ -39,6 +39,7 @@ class CModel(C.Structure):
         ("npairs", C.c_int), ("pair_a", C.POINTER(C.c_int)), ("pair_b", C.POINTER(C.c_int)),
         ("npaths", C.c_int), ("common_body", C.c_int),
         ("body_path", C.POINTER(C.c_int)), ("pair_path", C.POINTER(C.c_int)),
+        ("gravity_enabled", C.POINTER(C.c_int)),
     ]
 
 
@@ -123,6 +124,9 @@ class Model:
     common_body: int = -1
     body_path: np.ndarray = None
     pair_path: np.ndarray = None
+    # [nb] 1: gravity acts on the body, 0: not (Drake's set_gravity_enabled(instance, false) for every body of the
+    # instance); None = every body
+    gravity_enabled: np.ndarray = None
 
     # ---- derived ------------------------------------------------------------
     @property
@@ -190,12 +194,16 @@ class Model:
         if self.pair_path is None:
             self.pair_path = np.zeros(self.npairs, dtype=np.int32)
         self.pair_path = _i(self.pair_path)
+        if self.gravity_enabled is None:
+            self.gravity_enabled = np.ones(nb, dtype=np.int32)
+        self.gravity_enabled = _i(self.gravity_enabled).reshape(nb)
         self.validate()
         return self
 
     def validate(self):
         nb = self.nbodies
         assert self.npaths in (1, 2, 4, 8), "npaths must be a power of two <= 8"
+        assert all(int(x) in (0, 1) for x in self.gravity_enabled), "gravity_enabled entries must be 0 or 1"
         for i in range(nb):
             assert self.parent[i] < i, "bodies must be topologically ordered"
             if int(self.jtype[i]) == 3:
@@ -260,6 +268,9 @@ class Model:
         m.gravity = (C.c_double * 3)(*self.gravity)
         m.ngeoms, m.npairs = self.ngeoms, self.npairs
         m.npaths, m.common_body = self.npaths, self.common_body
+        if not self.gravity_enabled.all():   # (NULL: every body)
+            keep["gravity_enabled"] = self.gravity_enabled
+            m.gravity_enabled = iptr(self.gravity_enabled)
         return m, keep
 
     # ---- text format ----------------------------------------------------------
@@ -285,6 +296,8 @@ class Model:
                 f.write(f"  inertia {fmt(self.inertia[i])}\n")
             f.write(f"damping {fmt(self.damping)}\n")
             f.write("actuated " + " ".join(str(int(x)) for x in self.actuated) + "\n")
+            if not self.gravity_enabled.all():   # (optional: absent = every body)
+                f.write("gravity_enabled " + " ".join(str(int(x)) for x in self.gravity_enabled) + "\n")
             f.write(f"ngeoms {self.ngeoms}\n")
             for g in range(self.ngeoms):
                 f.write(f"geom {g} body {int(self.geom_body[g])} type {inv_g[int(self.geom_type[g])]} "
@@ -338,6 +351,8 @@ def load_model(name_or_path: str) -> Model:
     m.parent = _i(m.parent); m.jtype = _i(m.jtype)
     expect("damping"); m.damping = floats(m.nv)
     expect("actuated"); m.actuated = [int(nxt()) for _ in range(m.nv)]
+    if toks[pos] == "gravity_enabled":
+        nxt(); m.gravity_enabled = [int(nxt()) for _ in range(nb)]
     expect("ngeoms"); ng = int(nxt())
     gb, gt, gs, gx = [], [], [], []
     for g in range(ng):

@@ -28,6 +28,7 @@ class ModelFile {
   std::vector<std::string> body_names;
   std::vector<int> parent, jtype, qstart, vstart, actuated, geom_body, geom_type, pair_a, pair_b, body_path, pair_path;
   std::vector<double> X_PF, axis, mass, com, inertia, damping, geom_X, geom_size;
+  std::vector<int> gravity_enabled;   // [nbodies] from the optional `gravity_enabled` line; empty = every body
   double gravity[3] = {0.0, 0.0, -9.81};
   int npaths = 1, common_body = -1, nq = 0, nv = 0;
 
@@ -55,6 +56,7 @@ class ModelFile {
     m.geom_X = geom_X.data(); m.geom_size = geom_size.data();
     m.npairs = (int)pair_a.size(); m.pair_a = pair_a.data(); m.pair_b = pair_b.data();
     m.npaths = npaths; m.common_body = common_body; m.body_path = body_path.data(); m.pair_path = pair_path.data();
+    m.gravity_enabled = gravity_enabled.empty() ? nullptr : gravity_enabled.data();
     return m;
   }
 
@@ -112,6 +114,10 @@ class ModelFile {
     }
     expect("damping"); floats(&m.damping, m.nv);
     expect("actuated"); for (int i = 0; i < m.nv; ++i) m.actuated.push_back(integer());
+    if (pos < tok.size() && tok[pos] == "gravity_enabled") {   // optional: absent = gravity on every body
+      ++pos;
+      for (int i = 0; i < nb; ++i) m.gravity_enabled.push_back(integer());
+    }
     expect("ngeoms"); const int ng = integer();
     for (int g = 0; g < ng; ++g) {
       expect("geom");

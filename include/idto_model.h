@@ -85,6 +85,14 @@ typedef struct idto_model {
   int common_body;          /* body index or -1 */
   const int* body_path;     /* [nbodies] path of each body, -1 for the common body */
   const int* pair_path;     /* [npairs] path that evaluates the pair */
+
+  /* Per-body gravity switch, Drake's MultibodyPlant::set_gravity_enabled(model_instance, false) mapped onto the
+   * bodies of that instance (reference examples/jaco/jaco.cc:48: the arm's weight is not modelled).  A body whose
+   * entry is 0 gets the inertial force acom * m, without the - g term; its joint damping and contact are unchanged.
+   * Every entry must be 0 or 1 (idto_hip_create refuses anything else).  NULL: gravity acts on every body, which is
+   * what a caller that does not know of this field (it is the struct's last member) gets from a zero-initialised
+   * struct. */
+  const int* gravity_enabled; /* [nbodies] 1 = the body's weight is applied, 0 = not; NULL = every body */
 } idto_model_t;
 
 typedef struct idto_contact_params {

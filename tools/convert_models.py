@@ -159,13 +159,17 @@ def parse_urdf(path, reg):
     return links, order, joints, actuated, groups
 
 
-def parse_sdf(path, reg):
+def parse_sdf(path, reg, prefix=""):
+    """prefix: put in front of every link name (two instances of one file in one plant: dual_jaco)."""
     model = _parse_xml(path).find("model")
     links, joints, groups, order = {}, [], [], []
     X_ML = {}
     for le in model.findall("link"):
-        L = Link(le.get("name"))
+        L = Link(prefix + le.get("name"))
         X_ML[L.name] = parse_pose(le.findtext("pose"))
+        rel = le.find("pose").get("relative_to") if le.find("pose") is not None else None
+        if rel:   # (nub_link of the Jaco arm, reference models/j2s7s300_arm_sphere_collision_v2.sdf)
+            X_ML[L.name] = X_ML[prefix + rel] @ X_ML[L.name]
         ine = le.find("inertial")
         if ine is not None:
             L.mass = float(ine.findtext("mass"))
@@ -191,24 +195,25 @@ def parse_sdf(path, reg):
         order.append(L.name)
     for je in model.findall("joint"):
         J = Joint()
-        J.name, J.type = je.get("name"), je.get("type")
-        J.parent, J.child = je.findtext("parent"), je.findtext("child")
+        J.name, J.type = prefix + je.get("name"), je.get("type")
+        J.parent, J.child = prefix + je.findtext("parent"), prefix + je.findtext("child")
         assert je.find("pose") is None, "joint <pose> not supported"
         J.X_PJ = X_ML[J.parent].inv() @ X_ML[J.child]
         ax = je.find("axis")
         if ax is not None:
             xe = ax.find("xyz")
             a = np.array([float(v) for v in xe.text.split()])
-            if xe.get("expressed_in") == "__model__":
+            # (SDFormat 1.6 <use_parent_model_frame>1: the axis is in the model frame, as expressed_in="__model__" later)
+            if xe.get("expressed_in") == "__model__" or ax.findtext("use_parent_model_frame", "0").strip() == "1":
                 a = X_ML[J.child].R.T @ a
             J.axis = a / np.linalg.norm(a)
             J.damping = float(ax.findtext("dynamics/damping", "0"))
         joints.append(J)
     for ge in model:
         if ge.tag.endswith("collision_filter_group"):
-            members = [m.text for m in ge if m.tag.endswith("member")]
-            ignored = [m.text for m in ge if m.tag.endswith("ignored_collision_filter_group")]
-            groups.append((ge.get("name"), members, ignored))
+            members = [prefix + m.text for m in ge if m.tag.endswith("member")]
+            ignored = [prefix + m.text for m in ge if m.tag.endswith("ignored_collision_filter_group")]
+            groups.append((prefix + ge.get("name"), members, ignored))
     # every joint of these models is actuated by the example (allegro: all 16 finger joints)
     actuated = {j.name for j in joints}
     return links, order, joints, actuated, groups, X_ML
@@ -229,8 +234,10 @@ def planar_frame(axis):
 
 
 def build_model(name, links, link_order, joints, actuated, groups, spec, extra_world_geoms=(), gravity=(0, 0, -9.81),
-                world_weld=None):
-    """spec: dict(common=<link name or None>, paths=[[link names]])"""
+                world_weld=None, gravity_off=()):
+    """spec: dict(common=<link name or None>, paths=[[link names]]); world_weld: (root link, X_WL) or a list of them;
+    gravity_off: the links whose bodies have no weight (Drake's set_gravity_enabled(instance, false))"""
+    welds = dict([world_weld] if isinstance(world_weld, tuple) else (world_weld or []))
     children = {}
     for J in joints:
         children.setdefault(J.parent, []).append(J)
@@ -276,8 +283,8 @@ def build_model(name, links, link_order, joints, actuated, groups, spec, extra_w
     if "world" in children:
         visit("world", -1, X())
     for r in roots:
-        if world_weld and r == world_weld[0]:
-            visit(r, -1, world_weld[1])
+        if r in welds:
+            visit(r, -1, welds[r])
         else:
             b = add_body(r, -1, "floating", X(), np.array([0, 0, 1.0]), [0.0] * 6, [0] * 6)
             visit(r, b, X())
@@ -307,6 +314,7 @@ def build_model(name, links, link_order, joints, actuated, groups, spec, extra_w
     m.mass, m.com, m.inertia = mass, com, inertia
     m.damping = [d for b in bodies for d in b["damping"]]
     m.actuated = [a for b in bodies for a in b["act"]]
+    m.gravity_enabled = [0 if b["name"] in gravity_off else 1 for b in bodies]
 
     # geometries in registration order
     geoms = []
@@ -470,5 +478,70 @@ def convert_all():
     return out
 
 
+OUT_EXAMPLES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "examples")
+CONFIG_KEYS = ["q_init", "v_init", "q_nom_start", "q_nom_end", "q_nom_relative_to_q_init", "q_guess", "Qq", "Qv", "R",
+               "Qfq", "Qfv", "time_step", "num_steps", "max_iters", "method", "linesearch", "scaling", "scaling_method",
+               "equality_constraints", "normalize_quaternions", "linear_solver", "Delta0", "Delta_max", "num_threads",
+               "gradients_method", "contact_stiffness", "dissipation_velocity", "smoothing_factor",
+               "friction_coefficient", "stiction_velocity", "exact_hessian", "tolerances", "mpc_iters",
+               "controller_frequency"]
+
+
+def jaco_ground(reg):
+    """Box(25, 25, 1) centred at z = -0.5 on the world body (examples/jaco/jaco.cc:64-67; the table is visual only)."""
+    g = ("box", [12.5, 12.5, 0.5], X(np.eye(3), [0, 0, -0.5]), reg[0])
+    reg[0] += 1
+    return g
+
+
+def convert_examples():
+    """The Jaco arm examples as test fixtures (tests/golden/examples/): the arm's weight is switched off, the object's is
+    not (examples/jaco/jaco.cc:42-48, examples/jaco_ball/jaco_ball.cc:50-70).
+
+    dual_jaco (examples/dual_jaco/dual_jaco.cc:40-58) is not written: the spheres of the two arms' links 6, 7 and nub
+    are candidate pairs of each other in Drake, and a pair between two chains is outside the star decomposition the
+    device evaluates (include/idto_model.h)."""
+    os.makedirs(OUT_EXAMPLES, exist_ok=True)
+    arm_file = f"{REF}/models/j2s7s300_arm_sphere_collision_v2.sdf"
+    X_arm = X(rpy_to_R(0, 0, math.pi / 2), [0, 0.27, 0.11])
+    arm_links = [f"j2s7s300_link_{k}" for k in range(1, 8)]
+    out = {}
+
+    reg = [0]
+    l, o, j, a, g, _ = parse_sdf(arm_file, reg)
+    lb, ob, jb, ab, gb, _ = parse_sdf(f"{REF}/models/box_15cm.sdf", reg)
+    l.update(lb); o += ob; j += jb; g += gb
+    out["jaco"] = build_model("jaco", l, o, j, a, g, dict(common="box", paths=[arm_links]),
+                              extra_world_geoms=[jaco_ground(reg)], world_weld=("base", X_arm), gravity_off=set(arm_links))
+
+    reg = [0]
+    l, o, j, a, g, _ = parse_sdf(arm_file, reg)
+    # ball added in code (jaco_ball.cc:58-70): m = 0.3, r = 0.06, solid sphere
+    ball = Link("ball")
+    ball.mass = 0.3
+    ball.I = np.eye(3) * (0.4 * 0.3 * 0.06 ** 2)
+    ball.geoms.append(("sphere", [0.06, 0, 0], X(), reg[0]))
+    reg[0] += 1
+    l["ball"] = ball
+    o.append("ball")
+    out["jaco_ball"] = build_model("jaco_ball", l, o, j, a, g, dict(common="ball", paths=[arm_links]),
+                                   extra_world_geoms=[jaco_ground(reg)], world_weld=("base", X_arm),
+                                   gravity_off=set(arm_links))
+
+    for name, m in out.items():
+        m.save(os.path.join(OUT_EXAMPLES, f"{name}.model"))
+        print(f"{name}: nb={m.nbodies} nq={m.nq} nv={m.nv} geoms={m.ngeoms} pairs={m.npairs} "
+              f"paths={m.npaths} common={m.common_body} unactuated={m.unactuated_dofs} gravity={list(m.gravity_enabled)}")
+        src = yaml.safe_load(open(f"{REF}/examples/{name}/{name}.yaml"))
+        cfg = {"model": name, "source": f"reference examples/{name}/{name}.yaml"}
+        for k in CONFIG_KEYS:
+            if k in src:
+                cfg[k] = src[k]
+        with open(os.path.join(OUT_EXAMPLES, f"{name}.yaml"), "w") as f:
+            yaml.safe_dump(cfg, f, sort_keys=False, default_flow_style=None)
+    return out
+
+
 if __name__ == "__main__":
     convert_all()
+    convert_examples()

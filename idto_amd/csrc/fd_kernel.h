@@ -264,6 +264,12 @@ template <> struct FastShape<3> { static constexpr int MAXC = 3, NP = 4, CJ = ID
 template <> struct FastShape<4> { static constexpr int MAXC = 4, NP = 4, CJ = IDTO_JOINT_FLOATING, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_WORLD, W2 = -1, GS = 0; };   // allegro_hand + ball
 template <> struct FastShape<5> { static constexpr int MAXC = 3, NP = 1, CJ = -1, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_WORLD, W2 = 2, GS = 0; };              // spinner: two-link finger + the spinner, off the world
 template <> struct FastShape<6> { static constexpr int MAXC = 7, NP = 1, CJ = IDTO_JOINT_FLOATING, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_WORLD, W2 = -1, GS = 1; };   // a free object + an arm of seven revolute bodies off the world (jaco, jaco_ball)
+// Not a tree shape: SHAPE_XCH selects the generic evaluation with the exchange area of shared pairs (id_eval<MAXC, true>,
+// models with DevModel::nxb > 0; DevModel::fast_shape stays 0 for them)
+constexpr int SHAPE_XCH = 7;
+// the part of fd_body's LDS that id_eval<MAXC, true> exchanges the chain states through: a record per chain body that a
+// pair touches, for each of the block's concurrent evaluations
+__host__ __device__ inline int fd_xch_doubles(int nxb, int threads, int npaths) { return (threads / npaths) * nxb * XREC; }
 
 template <int MAXC, int SHAPE = 0>
 IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem& P, const double* __restrict__ q,
@@ -271,6 +277,7 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
                       double* __restrict__ a_out, double* __restrict__ nplus_out, const int k, int mode,
                       int stop_after, int echunk, double* __restrict__ terms) {
   extern __shared__ double lds[];
+  constexpr bool FAST = SHAPE != 0 && SHAPE != SHAPE_XCH;   // id_fast.h's straight-line evaluation
   const int tid = threadIdx.x, nt = blockDim.x;
   if (stop_after == 10) return;   // (profiling aid: the launch alone)
 #ifdef IDTO_FD_STAMPS
@@ -314,7 +321,7 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
   double* edump = ea + EC * nv; // [nv] write-only dump row for surplus lanes
   double* mblob = edump + nv;    // [M.blob_n] the model tables
   // (a kernel of a fast shape needs the gathered records and three int tables only: DevModel::fast_lo / fast_n)
-  const int blob_lo = (SHAPE != 0) ? M.fast_lo : 0, blob_n = (SHAPE != 0) ? M.fast_n : M.blob_n;
+  const int blob_lo = FAST ? M.fast_lo : 0, blob_n = FAST ? M.fast_n : M.blob_n;
   int* colinfo = reinterpret_cast<int*>(mblob + blob_n + (blob_n & 1));  // [nq] non-zero rows of N+ column c
   // (terms != nullptr) the record and its weighted copy for the assembly products: 6 blocks of nq
   // columns, column stride nvp (16-byte aligned columns), + tau_k R' and the diagonal of R'
@@ -322,6 +329,8 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
   // (16-byte aligned: asm_dot reads double2; 8 bytes off, the products below took twice as long)
   double* rec = reinterpret_cast<double*>(colinfo + nq + (nq & 1));   // [P | T | M | P R' | T R' | M R'] then diag R'
   rec += (rec - lds) & 1;
+  // (SHAPE_XCH) the exchange area of the concurrent evaluations (fd_xch_doubles), behind the record and diag R'
+  double* xch = rec + (terms ? 6 * psz + nvp : 0);
 
   // N+_k and N+_{k+1} (TO.cc:1633-1647).  The model's table holds the constant entries (NaN where a quaternion block
   // goes); the 3 x 4 block of a floating joint is formed here, entry by entry, by twelve lanes of wavefront 0 (q_k) and of
@@ -493,14 +502,14 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
   };
   // (a fast shape with forward differences: the last wavefront writes them after its evaluations - the cheap
   // mass-matrix columns - while the others are still in their contact pairs)
-  const bool late_outputs = (SHAPE != 0) && !central && stop_after != 1;
+  const bool late_outputs = FAST && !central && stop_after != 1;
   if (!late_outputs) trajectory_outputs(tid, nt);
 
   FD_STAMP(3);
   if (stop_after == 1) return;  // (profiling aid: phase timing by truncation) after N+, v, a
   // ---- evaluation inputs (TO.cc:501-521): the perturbations were formed with N+ / v above
   // (a fast shape with forward differences: every lane forms the inputs of its own evaluation, id_fast.h InFwd)
-  const bool own_inputs = (SHAPE != 0) && !central;
+  const bool own_inputs = FAST && !central;
   for (int c0 = 0; c0 < E; c0 += (own_inputs ? E : EC)) {
   const int ce = own_inputs ? E : ((E - c0 < EC) ? E - c0 : EC);  // evaluations [c0, c0 + ce) in this pass
   if (!own_inputs) {
@@ -562,7 +571,7 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
   // Surplus groups (e >= E) re-run evaluation 0 into a dump row so that every lane
   // of a wavefront takes part in the butterfly sums inside id_eval.
   const int groups = nt / K;
-  if constexpr (SHAPE != 0) {
+  if constexpr (FAST) {
     // Straight-line evaluation (id_fast.h).  The lanes of a surplus group stay idle (a group's butterfly
     // partners are its own lanes); evaluations beyond the first round go to the LAST groups: with forward
     // differences those hold the cheap mass-matrix columns, as do the evaluations left over (allegro:
@@ -606,7 +615,10 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
     const int ee = (el < ce) ? el : 0;
     const bool full = central || c0 + ee < 1 + nP + nT;
     double* tau_dst = (el < ce) ? etau + (c0 + ee) * nv : edump;
-    id_eval<MAXC>(Ml, cp, path, full, eq + ee * nq, ev + ee * nv, ea + ee * nv, tau_dst);
+    if constexpr (SHAPE == SHAPE_XCH)
+      id_eval<MAXC, true>(Ml, cp, path, full, eq + ee * nq, ev + ee * nv, ea + ee * nv, tau_dst, xch + (tid / K) * Ml.nxb * XREC);
+    else
+      id_eval<MAXC>(Ml, cp, path, full, eq + ee * nq, ev + ee * nv, ea + ee * nv, tau_dst);
   }
   }
   __syncthreads();

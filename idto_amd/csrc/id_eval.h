@@ -74,6 +74,14 @@ struct DevModel {
   // when that chain body's weight is applied, gcommon when the common body's is (all set: every body, the default)
   unsigned long long gslots;
   int gcommon;
+  // shared pairs (a pair between the chains of two paths, include/idto_model.h), evaluated by id_eval<MAXC, true> through
+  // an exchange area per evaluation: one record (XREC doubles, id_eval.h) per chain body that some pair touches.  nxb: how many
+  // records (0: the model has no shared pair, every table below is unused); xrec: the record of (path, slot), -1 = none;
+  // pair_xa / pair_xb: the record of the pair's body A / B, -1 the common body, -2 the world
+  int nxb;
+  const int* xrec;      // [npaths*IDTO_MAX_CHAIN]
+  const int* pair_xa;   // [npairs]
+  const int* pair_xb;
 };
 
 // The model with every table pointer rebased from the global blob to a copy at `dst`
@@ -93,6 +101,7 @@ IDTO_DEV DevModel rebase_model(const DevModel& M, const double* dst) {
   L.path_npairs = i(M.path_npairs); L.path_pairs = i(M.path_pairs);
   L.pair_ga = i(M.pair_ga); L.pair_gb = i(M.pair_gb); L.pair_sa = i(M.pair_sa); L.pair_sb = i(M.pair_sb);
   L.f_body = d(M.f_body); L.f_cbody = d(M.f_cbody); L.f_pairs = d(M.f_pairs); L.f_seg = i(M.f_seg);
+  L.xrec = i(M.xrec); L.pair_xa = i(M.pair_xa); L.pair_xb = i(M.pair_xb);
   L.blob = dst;
   return L;
 }
@@ -107,6 +116,32 @@ struct BodyState {  // what later stages need of a body
   M3 R;
   V3 p, w, v;
 };
+
+// A body's record in the exchange area of id_eval<MAXC, true>: R (row-major), p, w, v - the doubles contact_pair reads -,
+// then the contact force and moment on the body (XEXT: summed there by the lane that owns the body)
+constexpr int XREC = 24, XEXT = 18;
+IDTO_DEV void put_state(double* x, const BodyState& b) {
+#pragma unroll
+  for (int i = 0; i < 9; ++i) x[i] = b.R.m[i];
+  x[9] = b.p.x; x[10] = b.p.y; x[11] = b.p.z;
+  x[12] = b.w.x; x[13] = b.w.y; x[14] = b.w.z;
+  x[15] = b.v.x; x[16] = b.v.y; x[17] = b.v.z;
+}
+IDTO_DEV BodyState get_state(const double* x) {
+  BodyState b;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) b.R.m[i] = x[i];
+  b.p = mk(x[9], x[10], x[11]); b.w = mk(x[12], x[13], x[14]); b.v = mk(x[15], x[16], x[17]);
+  return b;
+}
+// The lanes of one evaluation are adjacent lanes of ONE wavefront, whose LDS accesses are carried out in issue order:
+// between the records' stores and the other lanes' loads only the compiler has to be held back (no instruction is
+// emitted for a wavefront-scope fence).
+IDTO_DEV void wave_exchange_point() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 struct JointOut {
   M3 R_FM;
@@ -333,9 +368,16 @@ IDTO_DEV void project_tau(int jtype, int vs, const double* xpf, V3 hW, V3 f, V3 
 // writes the common body's).  `full` selects gravity + damping + contact, otherwise
 // the mass-matrix column mode.  Must be called by all `npaths` lanes of the
 // evaluation together (it contains cross-lane butterfly sums).
-template <int MAXC>
+// XCH (models with shared pairs, M.nxb > 0): `xs` is the evaluation's exchange area in LDS (M.nxb records).  Each lane
+// stores the state of its chain bodies that a pair touches as the forward pass forms them, and the pair loop reads
+// every chain body of a pair from there - its own ones and those of another lane of the evaluation - so that the chain
+// states are not kept in registers across the loop.  Both lanes of a shared pair run contact_pair on the same doubles
+// and get the same bits; each adds its own side, into the contact sum of its body's record, in the pair order of the
+// path's list.  The sums live in the records rather than in registers for the same reason: with
+// them in registers the MAXC = 8 kernel spills vector registers to scratch.
+template <int MAXC, bool XCH = false>
 IDTO_DEV void id_eval(const DevModel& M, const DevContact& cp, int path, bool full, const double* q, const double* v,
-                      const double* a, double* tau) {
+                      const double* a, double* tau, double* xs = nullptr) {
   const V3 zero = mk(0, 0, 0);
   const V3 g = full ? mk(M.gravity[0], M.gravity[1], M.gravity[2]) : zero;
 
@@ -365,6 +407,7 @@ IDTO_DEV void id_eval(const DevModel& M, const DevContact& cp, int path, bool fu
   V3 r[MAXC], hW[MAXC], fin[MAXC], nin[MAXC], fext[MAXC], next[MAXC];
   const int nch = M.nchain[path];
   V3 al_prev = zero, a_prev = zero;
+  if constexpr (XCH) wave_exchange_point();   // (the previous evaluation's loads of this area come first)
 #pragma unroll
   for (int s = 0; s < MAXC; ++s) {
     bs[s].R = ident3(); bs[s].p = zero; bs[s].w = zero; bs[s].v = zero;
@@ -394,8 +437,17 @@ IDTO_DEV void id_eval(const DevModel& M, const DevContact& cp, int path, bool fu
       inertial_wrench(M, b, bs[s].R, bs[s].w, al, acc, body_gravity(slot_gravity(M.gslots, path, s), g), &fin[s], &nin[s]);
       al_prev = al;
       a_prev = acc;
+      if constexpr (XCH) {
+        const int x = M.xrec[path * IDTO_MAX_CHAIN + s];
+        if (full && x >= 0) {
+          put_state(xs + XREC * x, bs[s]);
+#pragma unroll
+          for (int i = 0; i < 6; ++i) xs[XREC * x + XEXT + i] = 0.0;
+        }
+      }
     }
   }
+  if constexpr (XCH) wave_exchange_point();
 
   // ---- contact pairs of this path (TO.cc:247-386)
   V3 cfe = zero, cne = zero;  // this path's partial contact wrench on the common body
@@ -403,25 +455,42 @@ IDTO_DEV void id_eval(const DevModel& M, const DevContact& cp, int path, bool fu
     const int np = M.path_npairs[path];
     for (int k = 0; k < np; ++k) {
       const int pi = M.path_pairs[path * M.maxpp + k];
-      const int sa = M.pair_sa[pi], sb = M.pair_sb[pi];
+      int sa = M.pair_sa[pi], sb = M.pair_sb[pi];
       BodyState A, B;
       A.R = ident3(); A.p = zero; A.w = zero; A.v = zero;
       B = A;
       if (sa == -1) A = cb;
       if (sb == -1) B = cb;
+      if constexpr (XCH) {
+        // chain bodies from the exchange area; a body of another path (a shared pair) gets no force from this lane
+        const int xa = M.pair_xa[pi], xb = M.pair_xb[pi];
+        if (xa >= 0) { A = get_state(xs + XREC * xa); if (M.xrec[path * IDTO_MAX_CHAIN + sa] != xa) sa = -3; }
+        if (xb >= 0) { B = get_state(xs + XREC * xb); if (M.xrec[path * IDTO_MAX_CHAIN + sb] != xb) sb = -3; }
+      } else {
 #pragma unroll
-      for (int s = 0; s < MAXC; ++s) {
-        if (sa == s) A = bs[s];
-        if (sb == s) B = bs[s];
+        for (int s = 0; s < MAXC; ++s) {
+          if (sa == s) A = bs[s];
+          if (sb == s) B = bs[s];
+        }
       }
       const PairForce pf = contact_pair(M, cp, M.pair_ga[pi], M.pair_gb[pi], A, B);
       if (pf.active) {
         if (sa == -1) { cfe = cfe + pf.fA; cne = cne + pf.nA; }
         if (sb == -1) { cfe = cfe + pf.fB; cne = cne + pf.nB; }
+        if constexpr (XCH) {   // (sa / sb >= 0: a body of this lane, its record is xa / xb)
+          auto add = [&](int x, V3 f, V3 n) {
+            double* e = xs + XREC * x + XEXT;
+            const V3 fe = mk(e[0], e[1], e[2]) + f, ne = mk(e[3], e[4], e[5]) + n;
+            e[0] = fe.x; e[1] = fe.y; e[2] = fe.z; e[3] = ne.x; e[4] = ne.y; e[5] = ne.z;
+          };
+          if (sa >= 0) add(M.pair_xa[pi], pf.fA, pf.nA);
+          if (sb >= 0) add(M.pair_xb[pi], pf.fB, pf.nB);
+        } else {
 #pragma unroll
-        for (int s = 0; s < MAXC; ++s) {
-          if (sa == s) { fext[s] = fext[s] + pf.fA; next[s] = next[s] + pf.nA; }
-          if (sb == s) { fext[s] = fext[s] + pf.fB; next[s] = next[s] + pf.nB; }
+          for (int s = 0; s < MAXC; ++s) {
+            if (sa == s) { fext[s] = fext[s] + pf.fA; next[s] = next[s] + pf.nA; }
+            if (sb == s) { fext[s] = fext[s] + pf.fB; next[s] = next[s] + pf.nB; }
+          }
         }
       }
     }
@@ -434,6 +503,14 @@ IDTO_DEV void id_eval(const DevModel& M, const DevContact& cp, int path, bool fu
   for (int s = MAXC - 1; s >= 0; --s) {
     if (s < nch) {
       const int b = M.chain[path * IDTO_MAX_CHAIN + s];
+      if constexpr (XCH) {
+        const int x = M.xrec[path * IDTO_MAX_CHAIN + s];
+        if (full && x >= 0) {
+          const double* e = xs + XREC * x + XEXT;
+          fext[s] = mk(e[0], e[1], e[2]);
+          next[s] = mk(e[3], e[4], e[5]);
+        }
+      }
       V3 f = fin[s] - fext[s];
       V3 n = nin[s] - next[s];
       // slot s+1 hangs off slot s ?

@@ -534,19 +534,34 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
   int maxc = 1;
   for (int p = 0; p < K; ++p) maxc = std::max(maxc, nchain[p]);
   c->maxc = maxc;
-  std::vector<int> path_npairs(K, 0);
-  for (int i = 0; i < m->npairs; ++i) path_npairs[m->pair_path[i]]++;
+  // a pair stays inside one path (with the common body / the world), or joins chain bodies of two paths: a shared pair,
+  // which both paths evaluate (pair_path must name one of the two) - it goes into both pair lists, in index order
+  std::vector<int> path_npairs(K, 0), pair_other(m->npairs, -1);   // pair_other: the second path of a shared pair
+  for (int i = 0; i < m->npairs; ++i) {
+    const int p = m->pair_path[i];
+    if (p < 0 || p >= K) { g_err = "pair without a valid path"; return -1; }
+    const int ba = m->geom_body[m->pair_a[i]], bb = m->geom_body[m->pair_b[i]];
+    const bool chain_a = ba >= 0 && ba != m->common_body, chain_b = bb >= 0 && bb != m->common_body;
+    if (chain_a && chain_b && m->body_path[ba] != m->body_path[bb] && (m->body_path[ba] == p || m->body_path[bb] == p))
+      pair_other[i] = m->body_path[ba] == p ? m->body_path[bb] : m->body_path[ba];
+    path_npairs[p]++;
+    if (pair_other[i] >= 0) path_npairs[pair_other[i]]++;
+  }
   int maxpp = 1;
   for (int p = 0; p < K; ++p) maxpp = std::max(maxpp, path_npairs[p]);
   std::vector<int> path_pairs((size_t)K * maxpp, 0), fill(K, 0), sa(m->npairs), sb(m->npairs);
   for (int i = 0; i < m->npairs; ++i) {
     const int p = m->pair_path[i];
     path_pairs[(size_t)p * maxpp + fill[p]++] = i;
+    if (pair_other[i] >= 0) path_pairs[(size_t)pair_other[i] * maxpp + fill[pair_other[i]]++] = i;
     const int ba = m->geom_body[m->pair_a[i]], bb = m->geom_body[m->pair_b[i]];
     sa[i] = ba < 0 ? -2 : slot_of[ba];
     sb[i] = bb < 0 ? -2 : slot_of[bb];
     for (int b : {ba, bb})
-      if (b >= 0 && b != m->common_body && m->body_path[b] != p) { g_err = "pair touches a body outside its path"; return -1; }
+      if (pair_other[i] < 0 && b >= 0 && b != m->common_body && m->body_path[b] != p) {
+        g_err = "pair touches a body outside its path";
+        return -1;
+      }
     // box-box is implemented for ONE configuration only (id_eval.h signed_distance): A = a box on a
     // moving body, B = a world-fixed, axis-aligned box whose top face acts as the half-space
     // z <= top (the ground boxes of the reference's examples).  Anything else would silently get
@@ -559,6 +574,24 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
         g_err = "box-box contact pairs must be (box on a moving body, world-fixed axis-aligned box), in this order";
         return -1;
       }
+    }
+  }
+  // shared pairs: the exchange records of id_eval<MAXC, true> - one per chain body that some pair touches, numbered
+  // path by path, slot by slot - and each pair's two records
+  bool shared = false;
+  for (int i = 0; i < m->npairs; ++i) shared = shared || pair_other[i] >= 0;
+  int nxb = 0;
+  std::vector<int> xrec((size_t)K * IDTO_MAX_CHAIN, -1), pair_xa(m->npairs, -1), pair_xb(m->npairs, -1);
+  if (shared) {
+    for (int i = 0; i < m->npairs; ++i)
+      for (int b : {m->geom_body[m->pair_a[i]], m->geom_body[m->pair_b[i]]})
+        if (b >= 0 && b != m->common_body) xrec[(size_t)m->body_path[b] * IDTO_MAX_CHAIN + slot_of[b]] = 0;
+    for (int& x : xrec)
+      if (x == 0) x = nxb++;
+    for (int i = 0; i < m->npairs; ++i) {
+      const int ba = m->geom_body[m->pair_a[i]], bb = m->geom_body[m->pair_b[i]];
+      pair_xa[i] = sa[i] >= 0 ? xrec[(size_t)m->body_path[ba] * IDTO_MAX_CHAIN + sa[i]] : sa[i];
+      pair_xb[i] = sb[i] >= 0 ? xrec[(size_t)m->body_path[bb] * IDTO_MAX_CHAIN + sb[i]] : sb[i];
     }
   }
   DevModel& M = c->M;
@@ -618,6 +651,7 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
     for (int p = 0; p < K; ++p) ok = ok && nchain[p] == maxc;
     const int cj = cbody >= 0 ? m->jtype[cbody] : -1;
     if (cbody >= 0 && cj != IDTO_JOINT_FLOATING) ok = false;
+    if (shared) ok = false;   // (every shape's pair records are per path: a model with shared pairs has none of them)
     int j0 = -1, k0 = -1, w2 = -1;   // w2: a later slot of the (single) path that hangs off the world again (the spinner)
     for (int p = 0; p < K && ok; ++p)
       for (int s = 0; s < maxc; ++s) {
@@ -757,6 +791,9 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
                i_pnp = addi(path_npairs.data(), path_npairs.size()), i_pp = addi(path_pairs.data(), path_pairs.size()),
                i_ga = addi(m->pair_a, m->npairs), i_gb = addi(m->pair_b, m->npairs), i_sa = addi(sa.data(), sa.size()),
                i_sb = addi(sb.data(), sb.size());
+  // (the exchange tables only where there are shared pairs: other models stage the blob they staged before)
+  const size_t i_xrec = shared ? addi(xrec.data(), xrec.size()) : i_par, i_xa = shared ? addi(pair_xa.data(), pair_xa.size()) : i_par,
+               i_xb = shared ? addi(pair_xb.data(), pair_xb.size()) : i_par;
   const size_t nd = dbl.size(), ni = ints.size();
   std::vector<double> blob(nd + (ni + 1) / 2 + 1, 0.0);
   std::memcpy(blob.data(), dbl.data(), nd * sizeof(double));
@@ -776,6 +813,7 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
   M.fast_shape = fast_shape; M.f_maxpp = f_maxpp;
   M.fast_lo = (int)fast_lo; M.fast_n = (int)(nd + (i_fast_end + 1) / 2 - fast_lo);
   M.f_body = bd + o_fbody; M.f_cbody = bd + o_fcbody; M.f_pairs = bd + o_fpairs; M.f_seg = bi + i_fseg;
+  M.nxb = nxb; M.xrec = bi + i_xrec; M.pair_xa = bi + i_xa; M.pair_xb = bi + i_xb;
   return 0;
 }
 
@@ -791,7 +829,8 @@ int FdLds(const idto_hip_ctx* c, int mode, int ec, bool with_terms = false, bool
   const int nq = c->nq, nv = c->nv, E = FdEvals(c, mode), nvp = (nv + 1) & ~1;
   const int rec = with_terms ? 6 * nvp * nq + nvp + 1 : 0;   // the record, its weighted copy, diag R' (+1: 16-byte alignment)
   const int blob_n = (fast && c->fd_fast && c->M.fast_shape) ? c->M.fast_n : c->M.blob_n;   // what fd_body stages of the model
-  return (int)sizeof(double) * (3 * nq + 2 * nv * nq + 3 * nv + 3 * E + E * nv + ec * (nq + 2 * nv) + nv + blob_n + 2 + nq / 2 + 2 + rec);
+  const int xch = c->M.nxb ? fd_xch_doubles(c->M.nxb, mode >= 1 ? c->fd_threads : 64, c->npaths) : 0;   // shared pairs' exchange
+  return (int)sizeof(double) * (3 * nq + 2 * nv * nq + 3 * nv + 3 * E + E * nv + ec * (nq + 2 * nv) + nv + blob_n + 2 + nq / 2 + 2 + rec + xch);
 }
 
 // fd_kernel also forms the single-record products of the Gauss-Newton assembly (diagonal weights,
@@ -820,6 +859,7 @@ int LaunchFd(idto_hip_ctx* c, int mode, int kb, int ke, AltSel alt = AltSel{null
   fl.k_begin = kb; fl.mode = mode; fl.stop_after = c->fd_stop; fl.echunk = ec; fl.pstride = c->pstride; fl.terms = terms;
   fl.alt = alt;
   fl.shape = c->fd_fast ? c->M.fast_shape : 0;   // id_fast.h: the straight-line evaluation of the model's tree shape
+  if (c->M.nxb) fl.shape = SHAPE_XCH;             // shared pairs: the generic evaluation with the exchange (whatever fd_fast says)
   fl.maxc = c->maxc;
   fd_launch(fl);
   HIP_OK(hipGetLastError());
@@ -1735,6 +1775,7 @@ static int LaunchLdl(idto_hip_ctx* c, const double* b, double sign, double* xo, 
 
 // ---- one persistent launch for the whole Gauss-Newton iteration (fused.h)
 static int FusedVariant(const idto_hip_ctx* c) {  // instantiated (MAXC, K) combinations: the reference's example models
+  if (c->M.nxb) return 0;   // (gn_fused_kernel embeds id_eval without the exchange of shared pairs)
   const int mc = c->maxc <= 2 ? 2 : (c->maxc <= 3 ? 3 : (c->maxc <= 4 ? 4 : 8));
   if (mc == 2 && c->nq == 2) return 1;
   if (mc == 3 && c->nq == 3) return 2;
@@ -1819,6 +1860,7 @@ static int SmallLds(const idto_hip_ctx* c, const LdlPlan& p, int* lds_small) {
 }
 static bool SmallEligible(const idto_hip_ctx* c) {
   if (!c->gn_small || !c->fd_fast || c->gradients_method != 0 || !c->weights_diagonal || c->reference_solver) return false;
+  if (c->M.nxb) return false;   // (id_eval_fast has no shared pairs)
   if (!(c->M.fast_shape == 1 || c->M.fast_shape == 5) || c->M.nfloat != 0 || c->nq != c->nv || c->npaths != 1) return false;
   if (!((c->M.fast_shape == 1 && c->nq == 2) || (c->M.fast_shape == 5 && c->nq == 3))) return false;   // (the instantiations)
   if (c->k_begin != 0 || c->k_end != c->N || c->fd_stop || c->asm_stop || c->solver_debug || c->ldl_npos > 0) return false;

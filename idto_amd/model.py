@@ -242,10 +242,15 @@ class Model:
                 nchild[par] = nchild.get(par, 0) + 1
                 assert nchild[par] <= 1, "chain bodies may have at most one child"
                 assert self.body_path[par] == self.body_path[i]
+        # a pair stays inside one path (with the common body / the world), or joins the chains of two paths (a shared
+        # pair: both evaluate it, pair_path names one of the two)
         for k in range(self.npairs):
             p = int(self.pair_path[k])
-            for g in (int(self.pair_a[k]), int(self.pair_b[k])):
-                b = int(self.geom_body[g])
+            bodies = [int(self.geom_body[int(g)]) for g in (self.pair_a[k], self.pair_b[k])]
+            chain_paths = {int(self.body_path[b]) for b in bodies if b != -1 and b != self.common_body}
+            if len(chain_paths) == 2 and p in chain_paths:
+                continue
+            for b in bodies:
                 assert b == -1 or b == self.common_body or int(self.body_path[b]) == p, \
                     f"pair {k} touches body {b} outside path {p}"
 

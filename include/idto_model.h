@@ -74,17 +74,20 @@ typedef struct idto_model {
    * optional common root body (computed by every path) plus npaths disjoint
    * chains hanging off the world or off the common body.  It fixes the
    * association order of the floating-point sums over children / contact
-   * pairs (DESIGN.md §3.2) so that a serial CPU evaluation and the
-   * lane-parallel HIP evaluation produce identical bits.
+   * pairs (DESIGN.md §3.2, §3.2.1) so that a serial CPU evaluation and the
+   * lane-parallel HIP evaluation produce identical bits.  Each chain body sums the wrenches of all pairs that touch it
+   * in ascending pair index, shared pairs (below) included; the common body sums per path, then over the paths.
    * HARD LIMIT: this is the only topology the device evaluates - a tree whose branching happens
    * at the world and at ONE body (no closed loops, no second branching body further down a
    * chain), chains of at most IDTO_MAX_CHAIN bodies.  It covers the reference's five example
    * models; the reference itself takes any MultibodyPlant (TO.cc:271-279).  idto_hip_create
-   * rejects a model whose tables do not describe such a tree. */
+   * rejects a model whose tables do not describe such a tree.  A contact pair stays inside one chain (with the common body
+   * or the world), or joins chain bodies of two different paths: a shared pair, which the lanes of both paths evaluate
+   * (dual_jaco's two hands); any other pair is refused. */
   int npaths;               /* power of two, <= IDTO_MAX_PATHS */
   int common_body;          /* body index or -1 */
   const int* body_path;     /* [nbodies] path of each body, -1 for the common body */
-  const int* pair_path;     /* [npairs] path that evaluates the pair */
+  const int* pair_path;     /* [npairs] path that evaluates the pair; a shared pair: one of its two bodies' paths */
 
   /* Per-body gravity switch, Drake's MultibodyPlant::set_gravity_enabled(model_instance, false) mapped onto the
    * bodies of that instance (reference examples/jaco/jaco.cc:48: the arm's weight is not modelled).  A body whose

@@ -27,6 +27,9 @@ LIMITS = {
     # (the free object + seven-body arm of the Jaco examples: one path, so the records' addresses are uniform - more of the
     # kernel's values live in scalar registers, and more of those are spilled to lanes; no vector register is spilled)
     "fd_kernel<8, 6>": (0, 20, 161 + 24),
+    # (models with shared pairs: the generic evaluation with the chain states and contact sums in LDS - the generic
+    # fd_kernel<8, 0> keeps them in registers and spills 584 vector registers to scratch)
+    "fd_kernel<8, 7>": (0, 20, 139 + 24),
     "penta_pipe_kernel<19, false>": (0, 36, 102 + 24),
     "penta_pipe_kernel<2, false>": (0, 0, 137 + 24),
     "penta_pipe_kernel<3, false>": (0, 0, 106 + 24),

@@ -366,8 +366,10 @@ def build_model(name, links, link_order, joints, actuated, groups, spec, extra_w
             if bi == bj or (min(bi, bj), max(bi, bj)) in adjacent or excluded(geoms[i][5], geoms[j][5]):
                 continue
             paths = {body_path[b] for b in (bi, bj) if b >= 0 and b != m.common_body}
-            assert len(paths) <= 1, f"{name}: pair {geoms[i][5]}-{geoms[j][5]} spans two paths"
-            pa.append(i); pb.append(j); pp.append(paths.pop() if paths else 0)
+            # a pair between the chains of two paths (shared pair) is evaluated by both; its pair_path names the path of
+            # geometry A's body (include/idto_model.h)
+            pp.append(body_path[bi] if len(paths) == 2 else (paths.pop() if paths else 0))
+            pa.append(i); pb.append(j)
     m.pair_a, m.pair_b, m.pair_path = pa, pb, pp
     return m.normalize()
 
@@ -496,11 +498,11 @@ def jaco_ground(reg):
 
 def convert_examples():
     """The Jaco arm examples as test fixtures (tests/golden/examples/): the arm's weight is switched off, the object's is
-    not (examples/jaco/jaco.cc:42-48, examples/jaco_ball/jaco_ball.cc:50-70).
+    not (examples/jaco/jaco.cc:42-48, examples/jaco_ball/jaco_ball.cc:50-70, examples/dual_jaco/dual_jaco.cc:40-58).
 
-    dual_jaco (examples/dual_jaco/dual_jaco.cc:40-58) is not written: the spheres of the two arms' links 6, 7 and nub
-    are candidate pairs of each other in Drake, and a pair between two chains is outside the star decomposition the
-    device evaluates (include/idto_model.h)."""
+    dual_jaco: two instances of the arm (link names prefixed by their model instance), welded to the world on either
+    side of the box.  The spheres of the two arms' links 6, 7 and nub are candidate pairs of each other in Drake: shared
+    pairs between the model's two paths, evaluated by both (include/idto_model.h)."""
     os.makedirs(OUT_EXAMPLES, exist_ok=True)
     arm_file = f"{REF}/models/j2s7s300_arm_sphere_collision_v2.sdf"
     X_arm = X(rpy_to_R(0, 0, math.pi / 2), [0, 0.27, 0.11])
@@ -527,6 +529,19 @@ def convert_examples():
     out["jaco_ball"] = build_model("jaco_ball", l, o, j, a, g, dict(common="ball", paths=[arm_links]),
                                    extra_world_geoms=[jaco_ground(reg)], world_weld=("base", X_arm),
                                    gravity_off=set(arm_links))
+
+    reg = [0]
+    arms, l, o, j, a, g = [], {}, [], [], set(), []
+    for side, y in (("left", 0.27), ("right", -0.27)):   # dual_jaco.cc:46-57
+        pre = f"jaco_{side}::"
+        ls, os_, js, as_, gs, _ = parse_sdf(arm_file, reg, prefix=pre)
+        l.update(ls); o += os_; j += js; a |= as_; g += gs
+        arms.append(([pre + ln for ln in arm_links], (pre + "base", X(rpy_to_R(0, 0, math.pi / 2), [0, y, 0.11]))))
+    lb, ob, jb, ab, gb, _ = parse_sdf(f"{REF}/models/box_15cm.sdf", reg)
+    l.update(lb); o += ob; j += jb; g += gb
+    out["dual_jaco"] = build_model("dual_jaco", l, o, j, a, g, dict(common="box", paths=[arms[0][0], arms[1][0]]),
+                                   extra_world_geoms=[jaco_ground(reg)], world_weld=[arms[0][1], arms[1][1]],
+                                   gravity_off=set(arms[0][0]) | set(arms[1][0]))
 
     for name, m in out.items():
         m.save(os.path.join(OUT_EXAMPLES, f"{name}.model"))

@@ -194,10 +194,53 @@ struct SdResult {
   V3 n, Ca, Cb;
 };
 
-// Signed distance between two primitives (restates oracle SignedDistance()).
+// ---- capsules (include/idto_model.h): a capsule side of a pair becomes a sphere of the capsule's radius at a
+// substitute centre on its segment p + u s, s in [-h, h] (u: the geometry frame's z in the world), and the sphere-sphere /
+// sphere-box expressions of signed_distance then run unchanged.  s == 0 selects p itself: with h = 0 every rule clamps s
+// to +-0, so a zero-length capsule is its sphere bit for bit.
+constexpr double CAPSULE_PARALLEL = 1e-10;   // 1 - dot(u1, u2)^2 at or below which two segments count as parallel
+IDTO_DEV double clamp_h(double s, double h) { return __builtin_fmin(__builtin_fmax(s, -h), h); }
+IDTO_DEV V3 seg_point(V3 p, V3 u, double s) { return (s == 0.0) ? p : p + u * s; }
+// one capsule (p, u, h) against a sphere centred at x, or against a world-fixed box of identity rotation: its lower end
+IDTO_DEV V3 capsule_single(V3 p, V3 u, double h, int other, V3 x) {
+  double s;
+  if (other == IDTO_GEOM_SPHERE) s = clamp_h(dot(x - p, u), h);
+  else s = ((p + u * h).z < (p + u * (-h)).z) ? h : -h;   // (a tie: the -h end)
+  return seg_point(p, u, s);
+}
+// The substitute centres of a pair with a capsule side: *pA / *pB replaced for the capsule side(s).  Two capsules: the
+// closest points of the segments (Ericson 5.1.9 with unit directions, parameters in [-h, h]); parallel segments take the
+// middle of the overlap of segment A with B's projection onto A's line.
+IDTO_DEV void capsule_centres(int typeA, V3 uA, double hA, V3* pA, int typeB, V3 uB, double hB, V3* pB) {
+  if (typeA == IDTO_GEOM_CAPSULE && typeB == IDTO_GEOM_CAPSULE) {
+    const V3 r = *pA - *pB;
+    const double b = dot(uA, uB), c = dot(uA, r), f = dot(uB, r);
+    const double denom = 1.0 - b * b;
+    double s = (denom > CAPSULE_PARALLEL) ? clamp_h((b * f - c) / denom, hA)
+                                          : clamp_h(0.5 * (__builtin_fmax(-hA, -c - hB) + __builtin_fmin(hA, hB - c)), hA);
+    double t = b * s + f;
+    if (t < -hB || t > hB) {
+      t = clamp_h(t, hB);
+      s = clamp_h(b * t - c, hA);
+    }
+    *pA = seg_point(*pA, uA, s);
+    *pB = seg_point(*pB, uB, t);
+  } else if (typeA == IDTO_GEOM_CAPSULE) {
+    *pA = capsule_single(*pA, uA, hA, typeB, *pB);
+  } else {
+    *pB = capsule_single(*pB, uB, hB, typeA, *pA);
+  }
+}
+
+// Signed distance between two primitives (restates oracle SignedDistance(); capsules: reduced to spheres first).
 IDTO_DEV SdResult signed_distance(int typeA, const M3& RA, V3 pA, V3 sA, int typeB, const M3& RB, V3 pB, V3 sB) {
   SdResult out;
   out.valid = false; out.phi = 0; out.n = mk(0, 0, 1); out.Ca = mk(0, 0, 0); out.Cb = mk(0, 0, 0);
+  if (typeA == IDTO_GEOM_CAPSULE || typeB == IDTO_GEOM_CAPSULE) {   // (radius: size[0], as a sphere's)
+    capsule_centres(typeA, col(RA, 2), sA.y, &pA, typeB, col(RB, 2), sB.y, &pB);
+    typeA = (typeA == IDTO_GEOM_CAPSULE) ? IDTO_GEOM_SPHERE : typeA;
+    typeB = (typeB == IDTO_GEOM_CAPSULE) ? IDTO_GEOM_SPHERE : typeB;
+  }
   if (typeA == IDTO_GEOM_SPHERE && typeB == IDTO_GEOM_SPHERE) {
     const V3 d = pB - pA;
     const double dist = __builtin_sqrt(dot(d, d));
@@ -206,7 +249,8 @@ IDTO_DEV SdResult signed_distance(int typeA, const M3& RA, V3 pA, V3 sA, int typ
     out.Ca = pA + out.n * sA.x;
     out.Cb = pB - out.n * sB.x;
     out.valid = true;
-  } else if (typeA != typeB) {  // sphere-box in either order
+  } else if ((typeA == IDTO_GEOM_SPHERE && typeB == IDTO_GEOM_BOX) ||
+             (typeA == IDTO_GEOM_BOX && typeB == IDTO_GEOM_SPHERE)) {  // sphere-box in either order
     const bool sphere_is_A = (typeA == IDTO_GEOM_SPHERE);
     const V3 pS = sphere_is_A ? pA : pB;
     const double rad = sphere_is_A ? sA.x : sB.x;

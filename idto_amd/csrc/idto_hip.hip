@@ -199,6 +199,7 @@ struct idto_hip_ctx {
   hipStream_t stream = nullptr;
   bool own_stream = false;
   int nb = 0, nq = 0, nv = 0, N = 0, npaths = 1, maxc = 1;
+  bool capsules = false;   // the model has a capsule (include/idto_model.h): no fast shape, no fused launch
   double dt = 0;
   std::vector<void*> allocs;
   DevModel M;
@@ -493,6 +494,42 @@ int UploadProblemArrays(idto_hip_ctx* c, const idto_problem_t* p, int pb = 0) {
   return 0;
 }
 
+// The geometry types and the pairs a capsule may take part in (include/idto_model.h).  Host tables only: it runs before
+// any device is touched, so a refused model fails the same way with or without a GPU.
+static bool IdentityRotation(const double* X) {
+  bool ident = true;
+  for (int e = 0; e < 9; ++e) ident &= (X[e] == ((e % 4 == 0) ? 1.0 : 0.0));
+  return ident;
+}
+static int CheckGeometry(const idto_model_t* m) {
+  for (int g = 0; g < m->ngeoms; ++g) {
+    const int t = m->geom_type[g];
+    if (t != IDTO_GEOM_SPHERE && t != IDTO_GEOM_BOX && t != IDTO_GEOM_CAPSULE) {
+      g_err = "unknown geometry type (0 sphere, 1 box, 2 capsule)";
+      return -1;
+    }
+    const double* s = m->geom_size + (size_t)3 * g;
+    if (t == IDTO_GEOM_CAPSULE &&
+        !(std::isfinite(s[0]) && std::isfinite(s[1]) && std::isfinite(s[2]) && s[0] > 0 && s[1] >= 0)) {
+      g_err = "capsule size must be finite with radius > 0 and h >= 0";
+      return -1;
+    }
+  }
+  for (int i = 0; i < m->npairs; ++i) {
+    const int ga = m->pair_a[i], gb = m->pair_b[i];
+    if (ga < 0 || ga >= m->ngeoms || gb < 0 || gb >= m->ngeoms) { g_err = "pair geometry index out of range"; return -1; }
+    const int ta = m->geom_type[ga], tb = m->geom_type[gb];
+    if ((ta == IDTO_GEOM_CAPSULE && tb == IDTO_GEOM_BOX) || (ta == IDTO_GEOM_BOX && tb == IDTO_GEOM_CAPSULE)) {
+      const int box = (ta == IDTO_GEOM_BOX) ? ga : gb;
+      if (m->geom_body[box] >= 0 || !IdentityRotation(m->geom_X + (size_t)12 * box)) {
+        g_err = "capsule-box contact pairs need a world-fixed box with identity rotation";
+        return -1;
+      }
+    }
+  }
+  return 0;
+}
+
 int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
   const int nb = m->nbodies, K = m->npaths;
   if (K < 1 || K > IDTO_MAX_PATHS || (K & (K - 1))) { g_err = "npaths must be a power of two <= 8"; return -1; }
@@ -534,6 +571,9 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
   int maxc = 1;
   for (int p = 0; p < K; ++p) maxc = std::max(maxc, nchain[p]);
   c->maxc = maxc;
+  bool capsules = false;
+  for (int g = 0; g < m->ngeoms; ++g) capsules = capsules || m->geom_type[g] == IDTO_GEOM_CAPSULE;
+  c->capsules = capsules;
   // a pair stays inside one path (with the common body / the world), or joins chain bodies of two paths: a shared pair,
   // which both paths evaluate (pair_path must name one of the two) - it goes into both pair lists, in index order
   std::vector<int> path_npairs(K, 0), pair_other(m->npairs, -1);   // pair_other: the second path of a shared pair
@@ -676,6 +716,8 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
       // a free object + one arm of seven revolute bodies off the world, any gravity switches (the Jaco examples)
       if (maxc == 7 && K == 1 && cj == IDTO_JOINT_FLOATING && j0 == IDTO_JOINT_REVOLUTE && k0 == PK_WORLD && w2 < 0)
         fast_shape = 6;
+      // (id_fast.h's pair code has no capsule reduction: a model with a capsule is id_eval's)
+      if (capsules) fast_shape = 0;
     }
     // processing order of a path's pairs: [pairs without a chain body that come first | slot 0 | ... | slot maxc-1 |
     // the other pairs without a chain body].  The sums that have an order are those onto one chain body (its pairs stay
@@ -980,6 +1022,7 @@ int idto_hip_create(const idto_model_t* model, const idto_problem_t* problem, co
 int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* problems, const idto_contact_params_t* contact,
                           int device, int batch, idto_hip_ctx** out) {
   *out = nullptr;
+  if (int rc = CheckGeometry(model)) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
     g_err = "no HIP device available (the product path has no CPU fallback)";
@@ -1776,6 +1819,7 @@ static int LaunchLdl(idto_hip_ctx* c, const double* b, double sign, double* xo, 
 // ---- one persistent launch for the whole Gauss-Newton iteration (fused.h)
 static int FusedVariant(const idto_hip_ctx* c) {  // instantiated (MAXC, K) combinations: the reference's example models
   if (c->M.nxb) return 0;   // (gn_fused_kernel embeds id_eval without the exchange of shared pairs)
+  if (c->capsules) return 0;   // (capsule models: the three-launch path only)
   const int mc = c->maxc <= 2 ? 2 : (c->maxc <= 3 ? 3 : (c->maxc <= 4 ? 4 : 8));
   if (mc == 2 && c->nq == 2) return 1;
   if (mc == 3 && c->nq == 3) return 2;

@@ -18,7 +18,7 @@ import numpy as np
 JOINT_TYPES = {"revolute": 0, "prismatic": 1, "planar": 2, "floating": 3}
 JOINT_NQ = {0: 1, 1: 1, 2: 3, 3: 7}
 JOINT_NV = {0: 1, 1: 1, 2: 3, 3: 6}
-GEOM_TYPES = {"sphere": 0, "box": 1}
+GEOM_TYPES = {"sphere": 0, "box": 1, "capsule": 2}   # capsule size: [radius, h = length / 2, 0] (include/idto_model.h)
 MAX_PATHS = 8
 MAX_CHAIN = 8
 
@@ -253,6 +253,23 @@ class Model:
             for b in bodies:
                 assert b == -1 or b == self.common_body or int(self.body_path[b]) == p, \
                     f"pair {k} touches body {b} outside path {p}"
+        # geometry types; a capsule: radius > 0, h >= 0, finite, and against a box only a world-fixed one of identity
+        # rotation (the rules idto_hip_create enforces)
+        cap, box = GEOM_TYPES["capsule"], GEOM_TYPES["box"]
+        for g in range(self.ngeoms):
+            t = int(self.geom_type[g])
+            assert t in GEOM_TYPES.values(), f"geometry {g}: unknown type {t}"
+            if t == cap:
+                s = self.geom_size[g]
+                assert np.isfinite(s).all() and s[0] > 0 and s[1] >= 0, \
+                    f"geometry {g}: a capsule needs a finite size with radius > 0 and h >= 0"
+        for k in range(self.npairs):
+            ga, gb = int(self.pair_a[k]), int(self.pair_b[k])
+            types = {int(self.geom_type[ga]), int(self.geom_type[gb])}
+            if types == {cap, box}:
+                bx = ga if int(self.geom_type[ga]) == box else gb
+                assert int(self.geom_body[bx]) == -1 and np.array_equal(self.geom_X[bx][:9], np.eye(3).ravel()), \
+                    f"pair {k}: a capsule-box pair needs a world-fixed box with identity rotation"
 
     # ---- C packing ----------------------------------------------------------
     def to_c(self):

@@ -36,7 +36,10 @@ enum idto_joint_type {
 
 enum idto_geom_type {
   IDTO_GEOM_SPHERE = 0, /* size[0] = radius */
-  IDTO_GEOM_BOX = 1     /* size = half extents */
+  IDTO_GEOM_BOX = 1,    /* size = half extents */
+  IDTO_GEOM_CAPSULE = 2 /* size[0] = radius r > 0, size[1] = h >= 0: half the distance between the two hemisphere
+                         * centres (Drake's length / 2), size[2] unused (0).  The axis is the geometry frame's z: the
+                         * segment is c(s) = p + u s, s in [-h, h], u = column 2 of R_WG */
 };
 
 typedef struct idto_model {
@@ -68,7 +71,19 @@ typedef struct idto_model {
    * taken as the half-space z <= top (its x/y extent is not tested) and A's lowest vertex is the
    * witness point - the body-box / foot-box vs ground-box pairs of the reference's examples
    * (examples/mini_cheetah/mini_cheetah.cc:50-55).  idto_hip_create refuses any other box-box
-   * pair; the reference gets general closest points from Drake/FCL (TO.cc:271-279). */
+   * pair; the reference gets general closest points from Drake/FCL (TO.cc:271-279).
+   * A capsule side of a pair is replaced by a sphere of the capsule's radius at a substitute centre on its segment, and
+   * the sphere-sphere / sphere-box expressions then run unchanged:
+   *  - sphere-capsule (either order, any poses): c = p + u clamp(dot(x - p, u), -h, h), x the sphere's centre;
+   *  - capsule-capsule (any poses): the closest points of the two segments (Ericson, Real-Time Collision Detection
+   *    5.1.9, in the +-h parametrisation).  (Near-)parallel segments, 1 - dot(u1, u2)^2 <= 1e-10: s1 is the middle of
+   *    the overlap of segment 1 with segment 2's projection onto its line (clamped to [-h1, h1]), then the usual
+   *    clamped t2 and, if t2 was clamped, s1 again;
+   *  - capsule-box (either order) ONLY with a world-fixed box of identity rotation (the condition of box-box): the
+   *    segment end with the lower world z, the -h end on a tie.
+   * With h = 0 every substitute centre is p itself, bit for bit: a zero-length capsule is its sphere.  idto_hip_create
+   * refuses, before it touches a device, a geometry type other than these three, a capsule with r <= 0, h < 0 or a
+   * non-finite size, and a capsule against any other box. */
 
   /* Evaluation/summation-order specification ("star" decomposition): one
    * optional common root body (computed by every path) plus npaths disjoint

@@ -1,0 +1,106 @@
+"""Test-side restatement of the capsule rules of include/idto_model.h, and the sphere models the GPU tests compare with.
+
+A capsule side of a contact pair is evaluated as a sphere of the capsule's radius at a substitute centre on its segment
+p + u s, s in [-h, h].  The oracle knows no capsules: `frozen_sphere_model` builds, for one configuration, the model whose
+pair k is the two spheres (or sphere and box) the device evaluates there, so that the oracle can evaluate it."""
+import copy
+
+import numpy as np
+
+from idto_amd.model import GEOM_TYPES
+
+SPHERE, BOX, CAPSULE = GEOM_TYPES["sphere"], GEOM_TYPES["box"], GEOM_TYPES["capsule"]
+PARALLEL = 1e-10   # 1 - dot(u1, u2)^2 at or below which two segments count as parallel
+
+
+def clamp(s, h):
+    return min(max(s, -h), h)
+
+
+def seg_point(p, u, s):
+    return p if s == 0.0 else p + u * s
+
+
+def sphere_capsule(x, p, u, h):
+    """the point of the segment p + u s, s in [-h, h], closest to x"""
+    return seg_point(p, u, clamp(float(np.dot(x - p, u)), h))
+
+
+def capsule_capsule(p1, u1, h1, p2, u2, h2):
+    """closest points of two segments (Ericson 5.1.9, unit directions, parameters in [-h, h]); parallel segments: the
+    middle of the overlap of segment 1 with segment 2's projection onto its line"""
+    r = p1 - p2
+    b, c, f = float(u1 @ u2), float(u1 @ r), float(u2 @ r)
+    denom = 1.0 - b * b
+    if denom > PARALLEL:
+        s = clamp((b * f - c) / denom, h1)
+    else:
+        s = clamp(0.5 * (max(-h1, -c - h2) + min(h1, h2 - c)), h1)
+    t = b * s + f
+    if t < -h2 or t > h2:
+        t = clamp(t, h2)
+        s = clamp(b * t - c, h1)
+    return seg_point(p1, u1, s), seg_point(p2, u2, t)
+
+
+def capsule_box(p, u, h):
+    """the segment end with the lower world z, the -h end on a tie (the box: world-fixed, identity rotation)"""
+    return seg_point(p, u, h if (p + u * h)[2] < (p + u * -h)[2] else -h)
+
+
+def geom_world(model, X_body, g):
+    """(R_WG, p_WG) of geometry g for the body poses X_body [nb, 12] (R row-major | p)"""
+    x = np.asarray(model.geom_X[g], float)
+    Rg, pg = x[:9].reshape(3, 3), x[9:]
+    b = int(model.geom_body[g])
+    if b < 0:
+        return Rg, pg
+    Rb, pb = X_body[b][:9].reshape(3, 3), X_body[b][9:]
+    return Rb @ Rg, pb + Rb @ pg
+
+
+def substitute_centres(model, X_body, k):
+    """world centres of pair k's two sides after the capsule reduction (a box side: its own centre, unused)"""
+    ga, gb = int(model.pair_a[k]), int(model.pair_b[k])
+    ta, tb = int(model.geom_type[ga]), int(model.geom_type[gb])
+    (RA, pA), (RB, pB) = geom_world(model, X_body, ga), geom_world(model, X_body, gb)
+    hA, hB = float(model.geom_size[ga][1]), float(model.geom_size[gb][1])
+    if ta == CAPSULE and tb == CAPSULE:
+        return capsule_capsule(pA, RA[:, 2], hA, pB, RB[:, 2], hB)
+    if ta == CAPSULE:
+        pA = sphere_capsule(pB, pA, RA[:, 2], hA) if tb == SPHERE else capsule_box(pA, RA[:, 2], hA)
+    if tb == CAPSULE:
+        pB = sphere_capsule(pA, pB, RB[:, 2], hB) if ta == SPHERE else capsule_box(pB, RB[:, 2], hB)
+    return pA, pB
+
+
+def frozen_sphere_model(model, X_body):
+    """The model with one geometry per (pair, side), pair k = (2k, 2k + 1) in the same order and path: a capsule side is
+    a sphere of its radius at the substitute centre for the body poses X_body, in its body's frame; sphere and box
+    sides are copied."""
+    m = copy.deepcopy(model)
+    gb, gt, gs, gx = [], [], [], []
+    for k in range(model.npairs):
+        for g, c in zip((int(model.pair_a[k]), int(model.pair_b[k])), substitute_centres(model, X_body, k)):
+            b, t = int(model.geom_body[g]), int(model.geom_type[g])
+            x, size = np.array(model.geom_X[g], float), np.array(model.geom_size[g], float)
+            if t == CAPSULE:
+                if b >= 0:
+                    Rb, pb = X_body[b][:9].reshape(3, 3), X_body[b][9:]
+                    c = Rb.T @ (c - pb)
+                x = np.concatenate([np.eye(3).ravel(), c])
+                size, t = np.array([size[0], 0.0, 0.0]), SPHERE
+            gb.append(b); gt.append(t); gs.append(size); gx.append(x)
+    m.geom_body, m.geom_type, m.geom_size, m.geom_X = gb, gt, gs, gx
+    m.pair_a = np.arange(0, 2 * model.npairs, 2)
+    m.pair_b = m.pair_a + 1
+    m.pair_path = np.array(model.pair_path)
+    return m.normalize()
+
+
+def without_geometry(model):
+    """the model with no geometry and no pair: its oracle gives v, a, N+, the body poses and the mass matrix"""
+    m = copy.deepcopy(model)
+    m.geom_body, m.geom_type, m.geom_size, m.geom_X = [], [], np.zeros((0, 3)), np.zeros((0, 12))
+    m.pair_a, m.pair_b, m.pair_path = [], [], []
+    return m.normalize()

@@ -130,6 +130,9 @@ def parse_urdf(path, reg):
             elif g.find("box") is not None:
                 sz = [float(v) / 2 for v in g.find("box").get("size").split()]
                 L.geoms.append(("box", sz, Xg, reg[0]))
+            elif g.find("capsule") is not None:   # size: radius, half the length (include/idto_model.h)
+                c = g.find("capsule")
+                L.geoms.append(("capsule", [float(c.get("radius")), float(c.get("length")) / 2, 0], Xg, reg[0]))
             else:
                 raise ValueError(f"unsupported collision geometry in {path}:{L.name}")
             reg[0] += 1
@@ -188,6 +191,9 @@ def parse_sdf(path, reg, prefix=""):
                 L.geoms.append(("box", sz, Xg, reg[0]))
             elif g.find("sphere") is not None:
                 L.geoms.append(("sphere", [float(g.find("sphere").findtext("radius")), 0, 0], Xg, reg[0]))
+            elif g.find("capsule") is not None:
+                c = g.find("capsule")
+                L.geoms.append(("capsule", [float(c.findtext("radius")), float(c.findtext("length")) / 2, 0], Xg, reg[0]))
             else:
                 raise ValueError("unsupported collision geometry")
             reg[0] += 1
@@ -543,12 +549,27 @@ def convert_examples():
                                    extra_world_geoms=[jaco_ground(reg)], world_weld=[arms[0][1], arms[1][1]],
                                    gravity_off=set(arms[0][0]) | set(arms[1][0]))
 
+    # the capsule spinners (models/spinner_capsule.urdf: eleven finger spheres against the spinner's capsule;
+    # models/2dof_spinner_capsule.urdf: the finger's capsule against it, the first finger link welded).  The first has the
+    # spinner example's three DoFs and takes its YAML; no example runs the second, it has no YAML.
+    reg = [0]
+    l, o, j, a, g = parse_urdf(f"{REF}/models/spinner_capsule.urdf", reg)
+    out["spinner_capsule"] = build_model("spinner_capsule", l, o, j, a, g, dict(paths=[["finger_one", "finger_two", "spinner"]]))
+    reg = [0]
+    l, o, j, a, g = parse_urdf(f"{REF}/models/2dof_spinner_capsule.urdf", reg)
+    out["2dof_spinner_capsule"] = build_model("2dof_spinner_capsule", l, o, j, a, g, dict(paths=[["finger_two", "spinner"]]))
+    example_yaml = {"spinner_capsule": "spinner", "2dof_spinner_capsule": None}
+
     for name, m in out.items():
         m.save(os.path.join(OUT_EXAMPLES, f"{name}.model"))
         print(f"{name}: nb={m.nbodies} nq={m.nq} nv={m.nv} geoms={m.ngeoms} pairs={m.npairs} "
               f"paths={m.npaths} common={m.common_body} unactuated={m.unactuated_dofs} gravity={list(m.gravity_enabled)}")
-        src = yaml.safe_load(open(f"{REF}/examples/{name}/{name}.yaml"))
-        cfg = {"model": name, "source": f"reference examples/{name}/{name}.yaml"}
+        ex = example_yaml.get(name, name)
+        if ex is None:
+            continue
+        src = yaml.safe_load(open(f"{REF}/examples/{ex}/{ex}.yaml"))
+        cfg = {"model": name, "source": f"reference examples/{ex}/{ex}.yaml"
+               + ("" if ex == name else f" (models/{name}.urdf has the same DoFs)")}
         for k in CONFIG_KEYS:
             if k in src:
                 cfg[k] = src[k]

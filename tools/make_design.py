@@ -38,5 +38,14 @@ for old, new in [
 ]:
     if old in text:
         text = text.replace(old, new)
+# rows of §8's convention table that came after the carried text
+WELDED_ROW = "| welded links (cheetah feet, allegro `hand_root`)"
+CAPSULE_ROWS = (
+    "| capsule-box: the sphere at the capsule's segment end with the lower world z, the `-h` end on a tie (a capsule lying flat touches the ground along its length; Drake/FCL's witness point there is not pinned here) | `csrc/id_eval.h capsule_single`, `include/idto_model.h` | none in-tree | `QueryObject::ComputeSignedDistancePairwiseClosestPoints` for a tilted and a flat `Capsule` above the ground `Box`, compare the witness point on the capsule |\n"
+    "| (near-)parallel capsule-capsule: `1 - (u1·u2)^2 <= 1e-10` ⇒ the middle of the overlap of the two segments | `csrc/id_eval.h capsule_centres`, `tests/capsule_ref.py` | none in-tree | the same query on two parallel overlapping capsules |\n")
+if WELDED_ROW in text:
+    i = text.index(WELDED_ROW)
+    j = text.index("\n", i) + 1
+    text = text[:j] + CAPSULE_ROWS + text[j:]
 open(os.path.join(ROOT, "DESIGN.md"), "w").write(text)
 print("DESIGN.md:", len(text.splitlines()), "lines")

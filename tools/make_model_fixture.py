@@ -110,6 +110,10 @@ def read_urdf(path):
                 geoms.append(dict(type="sphere", size=[float(ge.find("sphere").get("radius"))], X_LG=urdf_origin(ce.find("origin"))))
             elif ge.find("box") is not None:
                 geoms.append(dict(type="box", size=floats(ge.find("box").get("size"), 3), X_LG=urdf_origin(ce.find("origin"))))
+            elif ge.find("capsule") is not None:   # size: [radius, length]; the axis is the geometry frame's z
+                c = ge.find("capsule")
+                geoms.append(dict(type="capsule", size=[float(c.get("radius")), float(c.get("length"))],
+                                  X_LG=urdf_origin(ce.find("origin"))))
         links[le.get("name")] = dict(mass=mass, I_C=I, X_LC=X_LC, geoms=geoms, X_WL=None)
     for je in root.findall("joint"):
         ax = je.find("axis")
@@ -168,6 +172,10 @@ def read_sdf(path, weld_link, X_W_weld):
                 geoms.append(dict(type="box", size=floats(ge.find("box").find("size").text, 3), X_LG=sdf_pose(ce.find("pose"))))
             elif ge.find("sphere") is not None:
                 geoms.append(dict(type="sphere", size=[float(ge.find("sphere").find("radius").text)], X_LG=sdf_pose(ce.find("pose"))))
+            elif ge.find("capsule") is not None:
+                c = ge.find("capsule")
+                geoms.append(dict(type="capsule", size=[float(c.find("radius").text), float(c.find("length").text)],
+                                  X_LG=sdf_pose(ce.find("pose"))))
         raw[le.get("name")] = dict(mass=mass, I_C=I, X_LC=X_LC, geoms=geoms, X_ML=sdf_pose(le.find("pose")))
     X_WM = X_W_weld @ np.linalg.inv(raw[weld_link]["X_ML"])
     for L in raw.values():
@@ -214,6 +222,15 @@ def main():
             json.dump(d, f, indent=1)
         print(name, len(d["links"]), "links,", len(d["joints"]), "movable joints, total mass",
               sum(L["mass"] for L in d["links"].values()))
+    # the capsule spinners: beside their models in tests/golden/examples/ (tests/golden/world_*.json are the five
+    # models of idto_amd/models/)
+    for name in ("spinner_capsule", "2dof_spinner_capsule"):
+        links, joints = read_urdf(f"{REF}/models/{name}.urdf")
+        d = dict(source=f"reference models/{name}.urdf", links=links, joints=joints, world_geoms=[],
+                 generator="tools/make_model_fixture.py")
+        with open(os.path.join(OUT, "examples", f"world_{name}.json"), "w") as f:
+            json.dump(d, f, indent=1)
+        print(name, len(d["links"]), "links,", len(d["joints"]), "movable joints")
 
 
 if __name__ == "__main__":

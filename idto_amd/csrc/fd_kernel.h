@@ -267,9 +267,14 @@ template <> struct FastShape<6> { static constexpr int MAXC = 7, NP = 1, CJ = ID
 // Not a tree shape: SHAPE_XCH selects the generic evaluation with the exchange area of shared pairs (id_eval<MAXC, true>,
 // models with DevModel::nxb > 0; DevModel::fast_shape stays 0 for them)
 constexpr int SHAPE_XCH = 7;
+// ... and SHAPE_STEM the one that also walks a stem below the common body (id_eval<MAXC, true, true>, DevModel::nstem > 1): its
+// exchange area has the stem's blocks behind the records (id_eval.h xch_eval_doubles)
+constexpr int SHAPE_STEM = 8;
 // the part of fd_body's LDS that id_eval<MAXC, true> exchanges the chain states through: a record per chain body that a
 // pair touches, for each of the block's concurrent evaluations
-__host__ __device__ inline int fd_xch_doubles(int nxb, int threads, int npaths) { return (threads / npaths) * nxb * XREC; }
+__host__ __device__ inline int fd_xch_doubles(int nxb, int threads, int npaths, int nstem = 0) {
+  return (threads / npaths) * xch_eval_doubles(nxb, nstem);
+}
 
 template <int MAXC, int SHAPE = 0>
 IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem& P, const double* __restrict__ q,
@@ -277,7 +282,7 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
                       double* __restrict__ a_out, double* __restrict__ nplus_out, const int k, int mode,
                       int stop_after, int echunk, double* __restrict__ terms) {
   extern __shared__ double lds[];
-  constexpr bool FAST = SHAPE != 0 && SHAPE != SHAPE_XCH;   // id_fast.h's straight-line evaluation
+  constexpr bool FAST = SHAPE != 0 && SHAPE != SHAPE_XCH && SHAPE != SHAPE_STEM;   // id_fast.h's straight-line evaluation
   const int tid = threadIdx.x, nt = blockDim.x;
   if (stop_after == 10) return;   // (profiling aid: the launch alone)
 #ifdef IDTO_FD_STAMPS
@@ -615,7 +620,10 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
     const int ee = (el < ce) ? el : 0;
     const bool full = central || c0 + ee < 1 + nP + nT;
     double* tau_dst = (el < ce) ? etau + (c0 + ee) * nv : edump;
-    if constexpr (SHAPE == SHAPE_XCH)
+    if constexpr (SHAPE == SHAPE_STEM)
+      id_eval<MAXC, true, true>(Ml, cp, path, full, eq + ee * nq, ev + ee * nv, ea + ee * nv, tau_dst,
+                                xch + (tid / K) * xch_eval_doubles(Ml.nxb, Ml.nstem));
+    else if constexpr (SHAPE == SHAPE_XCH)
       id_eval<MAXC, true>(Ml, cp, path, full, eq + ee * nq, ev + ee * nv, ea + ee * nv, tau_dst, xch + (tid / K) * Ml.nxb * XREC);
     else
       id_eval<MAXC>(Ml, cp, path, full, eq + ee * nq, ev + ee * nv, ea + ee * nv, tau_dst);

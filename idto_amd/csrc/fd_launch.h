@@ -23,7 +23,7 @@ struct FdLaunch {
   size_t pstride;
   double* terms;
   AltSel alt;
-  int shape;   // id_fast.h: the model's instantiated tree shape, 0: id_eval<MAXC>, SHAPE_XCH: id_eval<8, true> (shared pairs)
+  int shape;   // id_fast.h: the model's instantiated tree shape, 0: id_eval<MAXC>, SHAPE_XCH: id_eval<8, true> (shared pairs), SHAPE_STEM: id_eval<8, true, true>
   int maxc;
 };
 // enqueues fd_kernel<MAXC, SHAPE>; the caller checks hipGetLastError()

@@ -15,6 +15,7 @@ void fd_launch(const FdLaunch& a) {
   else if (a.shape == 5) FD_GO(3, 5);
   else if (a.shape == 6) FD_GO(8, 6);
   else if (a.shape == SHAPE_XCH) FD_GO(8, SHAPE_XCH);   // (models with shared pairs: any chain length)
+  else if (a.shape == SHAPE_STEM) FD_GO(8, SHAPE_STEM);   // (a stem below the common body; shared pairs or not)
   else if (a.maxc <= 2) FD_GO(2, 0);
   else if (a.maxc <= 3) FD_GO(3, 0);
   else if (a.maxc <= 4) FD_GO(4, 0);
@@ -26,7 +27,7 @@ void fd_launch(const FdLaunch& a) {
 
 void fd_set_max_lds(int max_lds) {
   FD_ATTR(2, 0); FD_ATTR(3, 0); FD_ATTR(4, 0); FD_ATTR(8, 0);
-  FD_ATTR(2, 1); FD_ATTR(3, 2); FD_ATTR(3, 3); FD_ATTR(4, 4); FD_ATTR(3, 5); FD_ATTR(8, 6); FD_ATTR(8, SHAPE_XCH);
+  FD_ATTR(2, 1); FD_ATTR(3, 2); FD_ATTR(3, 3); FD_ATTR(4, 4); FD_ATTR(3, 5); FD_ATTR(8, 6); FD_ATTR(8, SHAPE_XCH); FD_ATTR(8, SHAPE_STEM);
 }
 
 }  // namespace idto_dev

@@ -76,12 +76,20 @@ struct DevModel {
   int gcommon;
   // shared pairs (a pair between the chains of two paths, include/idto_model.h), evaluated by id_eval<MAXC, true> through
   // an exchange area per evaluation: one record (XREC doubles, id_eval.h) per chain body that some pair touches.  nxb: how many
-  // records (0: the model has no shared pair, every table below is unused); xrec: the record of (path, slot), -1 = none;
+  // records (0: the model has no shared pair and no stem, every table below is unused); xrec: the record of (path, slot), -1 = none;
   // pair_xa / pair_xb: the record of the pair's body A / B, -1 the common body, -2 the world
   int nxb;
   const int* xrec;      // [npaths*IDTO_MAX_CHAIN]
   const int* pair_xa;   // [npairs]
   const int* pair_xb;
+  // the stem (include/idto_model.h): the common body and its ancestors, world side first, evaluated by id_eval<MAXC, true, true>.
+  // nstem: its bodies (0 / 1: the common body, if any, is attached to the world - every table below is unused); stem: [2 *
+  // IDTO_MAX_STEM] body k of the stem, then its state record in the exchange area (-1: no pair touches it; the common body: -1);
+  // gstem: bit k set when the weight of stem body k < nstem - 1 is applied (the common body's: gcommon).  A pair's stem side has
+  // the code -4 - k in pair_sa / pair_sb and its state record in pair_xa / pair_xb.
+  int nstem;
+  const int* stem;
+  int gstem;
 };
 
 // The model with every table pointer rebased from the global blob to a copy at `dst`
@@ -102,6 +110,7 @@ IDTO_DEV DevModel rebase_model(const DevModel& M, const double* dst) {
   L.pair_ga = i(M.pair_ga); L.pair_gb = i(M.pair_gb); L.pair_sa = i(M.pair_sa); L.pair_sb = i(M.pair_sb);
   L.f_body = d(M.f_body); L.f_cbody = d(M.f_cbody); L.f_pairs = d(M.f_pairs); L.f_seg = i(M.f_seg);
   L.xrec = i(M.xrec); L.pair_xa = i(M.pair_xa); L.pair_xb = i(M.pair_xb);
+  L.stem = i(M.stem);
   L.blob = dst;
   return L;
 }
@@ -120,6 +129,12 @@ struct BodyState {  // what later stages need of a body
 // A body's record in the exchange area of id_eval<MAXC, true>: R (row-major), p, w, v - the doubles contact_pair reads -,
 // then the contact force and moment on the body (XEXT: summed there by the lane that owns the body)
 constexpr int XREC = 24, XEXT = 18;
+// id_eval<MAXC, true, true>: behind the M.nxb records of an evaluation, one block per stem body below the common one with what the
+// backward pass needs of it: the joint axis hW, the inertial wrench (fin, nin) and the offset r of the NEXT stem body from it
+constexpr int SAUX = 12, SA_HW = 0, SA_FIN = 3, SA_NIN = 6, SA_RC = 9;
+__host__ __device__ inline int xch_eval_doubles(int nxb, int nstem) { return nxb * XREC + (nstem > 1 ? nstem - 1 : 0) * SAUX; }
+IDTO_DEV void put_v3(double* x, V3 a) { x[0] = a.x; x[1] = a.y; x[2] = a.z; }
+IDTO_DEV V3 get_v3(const double* x) { return mk(x[0], x[1], x[2]); }
 IDTO_DEV void put_state(double* x, const BodyState& b) {
 #pragma unroll
   for (int i = 0; i < 9; ++i) x[i] = b.R.m[i];
@@ -419,7 +434,13 @@ IDTO_DEV void project_tau(int jtype, int vs, const double* xpf, V3 hW, V3 f, V3 
 // and get the same bits; each adds its own side, into the contact sum of its body's record, in the pair order of the
 // path's list.  The sums live in the records rather than in registers for the same reason: with
 // them in registers the MAXC = 8 kernel spills vector registers to scratch.
-template <int MAXC, bool XCH = false>
+// STEM (models whose common body has a parent, M.nstem > 1; implies XCH): every lane walks the stem from the world to the
+// common body, parent by parent, keeping only the running state (`cb` ends as the common body's); path 0 leaves what the
+// later stages need of the bodies below the common one in the exchange area - the state record of a body that a pair
+// touches, and the SAUX block.  All pairs on one such body are in ONE path's list (checked at create), so that lane forms
+// the body's contact sum in the record, in index order from +0, as it does for its own chain bodies.  Behind the butterflies
+// path 0 takes the common body's total up the stem: tot = (f_in - ext) + child, the oracle's order.
+template <int MAXC, bool XCH = false, bool STEM = false>
 IDTO_DEV void id_eval(const DevModel& M, const DevContact& cp, int path, bool full, const double* q, const double* v,
                       const double* a, double* tau, double* xs = nullptr) {
   const V3 zero = mk(0, 0, 0);
@@ -431,7 +452,44 @@ IDTO_DEV void id_eval(const DevModel& M, const DevContact& cp, int path, bool fu
   V3 cb_al = zero, cb_a = zero, cb_fin = zero, cb_nin = zero;
   V3 cb_hW = zero;
   const int cbody = M.common_body;
-  if (cbody >= 0) {
+  static_assert(!STEM || XCH, "the stem lives in the exchange area");
+  if constexpr (STEM) {
+    double* aux = xs + XREC * M.nxb;
+    wave_exchange_point();   // (the previous evaluation's loads of this area come first)
+    for (int k = 0; k < M.nstem; ++k) {
+      const int b = M.stem[k];
+      const M3 R_WF = cb.R * ldm3(M.X_PF + 12 * b);   // (k == 0: I * R_PF, as a chain root off the world)
+      const V3 d1 = cb.R * ldv3(M.X_PF + 12 * b + 9);
+      const JointOut j = joint_kin(M.jtype[b], R_WF, ldv3(M.axis + 3 * b), q + M.qstart[b], v + M.vstart[b], a + M.vstart[b]);
+      const V3 rk = d1 + j.d2;
+      const V3 al = (cb_al + j.al_rel) + cross(cb.w, j.w_rel);
+      const V3 acc = (((cb_a + cross(cb_al, rk)) + cross(cb.w, cross(cb.w, rk))) + cross(cb.w, j.v_rel) * 2.0) + j.a_rel;
+      const V3 vk = (cb.v + cross(cb.w, rk)) + j.v_rel;
+      cb.R = R_WF * j.R_FM;
+      cb.p = cb.p + rk;
+      cb.w = cb.w + j.w_rel;
+      cb.v = vk;
+      cb_al = al;
+      cb_a = acc;
+      cb_hW = j.hW;
+      const bool last = k == M.nstem - 1;
+      inertial_wrench(M, b, cb.R, cb.w, cb_al, cb_a, body_gravity(last ? M.gcommon != 0 : ((M.gstem >> k) & 1) != 0, g), &cb_fin,
+                      &cb_nin);
+      if (path == 0) {
+        if (k > 0) put_v3(aux + SAUX * (k - 1) + SA_RC, rk);
+        if (!last) {
+          double* ak = aux + SAUX * k;
+          put_v3(ak + SA_HW, cb_hW); put_v3(ak + SA_FIN, cb_fin); put_v3(ak + SA_NIN, cb_nin);
+          const int x = M.stem[IDTO_MAX_STEM + k];
+          if (full && x >= 0) {
+            put_state(xs + XREC * x, cb);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) xs[XREC * x + XEXT + i] = 0.0;
+          }
+        }
+      }
+    }
+  } else if (cbody >= 0) {
     const M3 cb_RWF = ldm3(M.X_PF + 12 * cbody);  // parent is the world: I * R_PF
     const V3 d1 = ldv3(M.X_PF + 12 * cbody + 9);
     const JointOut j = joint_kin(M.jtype[cbody], cb_RWF, ldv3(M.axis + 3 * cbody), q + M.qstart[cbody],
@@ -508,8 +566,17 @@ IDTO_DEV void id_eval(const DevModel& M, const DevContact& cp, int path, bool fu
       if constexpr (XCH) {
         // chain bodies from the exchange area; a body of another path (a shared pair) gets no force from this lane
         const int xa = M.pair_xa[pi], xb = M.pair_xb[pi];
-        if (xa >= 0) { A = get_state(xs + XREC * xa); if (M.xrec[path * IDTO_MAX_CHAIN + sa] != xa) sa = -3; }
-        if (xb >= 0) { B = get_state(xs + XREC * xb); if (M.xrec[path * IDTO_MAX_CHAIN + sb] != xb) sb = -3; }
+        // (a stem body, code <= -4: this lane is the one that evaluates its pairs, the sum in its record is this lane's)
+        if (xa >= 0) {
+          A = get_state(xs + XREC * xa);
+          if (STEM && sa <= -4) sa = 0;
+          else if (M.xrec[path * IDTO_MAX_CHAIN + sa] != xa) sa = -3;
+        }
+        if (xb >= 0) {
+          B = get_state(xs + XREC * xb);
+          if (STEM && sb <= -4) sb = 0;
+          else if (M.xrec[path * IDTO_MAX_CHAIN + sb] != xb) sb = -3;
+        }
       } else {
 #pragma unroll
         for (int s = 0; s < MAXC; ++s) {
@@ -576,9 +643,25 @@ IDTO_DEV void id_eval(const DevModel& M, const DevContact& cp, int path, bool fu
     const V3 ext_n = tree_sum(cne, M.npaths);
     const V3 ch_f = tree_sum(root_f, M.npaths);
     const V3 ch_n = tree_sum(root_n, M.npaths);
-    const V3 f = (cb_fin - ext_f) + ch_f;
-    const V3 n = (cb_nin - ext_n) + ch_n;
+    V3 f = (cb_fin - ext_f) + ch_f;
+    V3 n = (cb_nin - ext_n) + ch_n;
     if (path == 0) project_tau(M.jtype[cbody], M.vstart[cbody], M.X_PF + 12 * cbody, cb_hW, f, n, full, M.damping, v, tau);
+    if constexpr (STEM) {
+      wave_exchange_point();   // (the contact sums of the stem's records are another lane's stores)
+      if (path == 0) {
+        const double* aux = xs + XREC * M.nxb;
+        for (int k = M.nstem - 2; k >= 0; --k) {
+          const double* ak = aux + SAUX * k;
+          const int b = M.stem[k], x = M.stem[IDTO_MAX_STEM + k];
+          V3 ef = zero, en = zero;
+          if (full && x >= 0) { ef = get_v3(xs + XREC * x + XEXT); en = get_v3(xs + XREC * x + XEXT + 3); }
+          const V3 child_f = f, child_n = n + cross(get_v3(ak + SA_RC), f);
+          f = (get_v3(ak + SA_FIN) - ef) + child_f;
+          n = (get_v3(ak + SA_NIN) - en) + child_n;
+          project_tau(M.jtype[b], M.vstart[b], M.X_PF + 12 * b, get_v3(ak + SA_HW), f, n, full, M.damping, v, tau);
+        }
+      }
+    }
   }
 }
 

@@ -530,6 +530,52 @@ static int CheckGeometry(const idto_model_t* m) {
   return 0;
 }
 
+// The stem (include/idto_model.h): the common body and its ancestors.  Host tables only, as CheckGeometry.
+static int CheckStem(const idto_model_t* m) {
+  const int nb = m->nbodies;
+  if (m->common_body >= nb) { g_err = "common body out of range"; return -1; }
+  std::vector<int> stem, stem_idx(nb, -1);   // (common body first here)
+  for (int b = m->common_body; b >= 0; b = m->parent[b]) {
+    if (m->parent[b] >= b) { g_err = "bodies must be numbered so that parent[i] < i"; return -1; }
+    if ((int)stem.size() == IDTO_MAX_STEM) {
+      g_err = "the stem (the common body and its ancestors) is longer than IDTO_MAX_STEM bodies";
+      return -1;
+    }
+    stem_idx[b] = (int)stem.size();
+    stem.push_back(b);
+  }
+  if (stem.size() < 2) return 0;
+  for (size_t k = 1; k < stem.size(); ++k) {
+    int children = 0;
+    for (int i = 0; i < nb; ++i) children += m->parent[i] == stem[k];
+    if (children != 1) {
+      g_err = "a stem body below the common body has a second child (chains hang off the common body or the world)";
+      return -1;
+    }
+    if (m->body_path[stem[k]] != -1) { g_err = "a stem body must have body_path -1"; return -1; }
+  }
+  std::vector<int> stem_path(nb, -1);
+  for (int i = 0; i < m->npairs; ++i) {
+    const int ga = m->pair_a[i], gb = m->pair_b[i];
+    if (ga < 0 || ga >= m->ngeoms || gb < 0 || gb >= m->ngeoms) { g_err = "pair geometry index out of range"; return -1; }
+    const int ba = m->geom_body[ga], bb = m->geom_body[gb];
+    if (ba >= nb || bb >= nb) { g_err = "geometry body out of range"; return -1; }
+    if (ba >= 0 && bb >= 0 && stem_idx[ba] >= 0 && stem_idx[bb] >= 0) {
+      g_err = "contact pair between two stem bodies (the common body included)";
+      return -1;
+    }
+    for (int b : {ba, bb})
+      if (b >= 0 && stem_idx[b] > 0) {
+        if (stem_path[b] >= 0 && stem_path[b] != m->pair_path[i]) {
+          g_err = "the pairs of one stem body name different paths (pair_path)";
+          return -1;
+        }
+        stem_path[b] = m->pair_path[i];
+      }
+  }
+  return 0;
+}
+
 int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
   const int nb = m->nbodies, K = m->npaths;
   if (K < 1 || K > IDTO_MAX_PATHS || (K & (K - 1))) { g_err = "npaths must be a power of two <= 8"; return -1; }
@@ -541,7 +587,14 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
       g_err = "planar and floating joints must be attached to the world";
       return -1;
     }
-  if (m->common_body >= 0 && m->parent[m->common_body] >= 0) { g_err = "the common body must be attached to the world"; return -1; }
+  // the stem: the common body and its ancestors, world side first (stem_idx: a body's place in it, -1 for every other body).
+  // A body below the common one carries nothing but the next stem body, and has no path of its own.
+  // (CheckStem has seen the tables)
+  std::vector<int> stem, stem_idx(nb, -1);
+  for (int b = m->common_body; b >= 0; b = m->parent[b]) stem.push_back(b);
+  std::reverse(stem.begin(), stem.end());
+  const int nstem = (int)stem.size();
+  for (int k = 0; k < nstem; ++k) stem_idx[stem[k]] = k;
   // per-body gravity switch: 0 or 1 per body, NULL = every body
   bool all_gravity = true;
   if (m->gravity_enabled)
@@ -554,6 +607,7 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
     }
   for (int i = 0; i < nb; ++i) {
     if (i == m->common_body) { slot_of[i] = -1; continue; }
+    if (stem_idx[i] >= 0) { slot_of[i] = -4 - stem_idx[i]; continue; }   // (a stem body below the common one: id_eval.h)
     const int p = m->body_path[i];
     if (p < 0 || p >= K) { g_err = "body without a valid path"; return -1; }
     const int s = nchain[p]++;
@@ -576,12 +630,17 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
   c->capsules = capsules;
   // a pair stays inside one path (with the common body / the world), or joins chain bodies of two paths: a shared pair,
   // which both paths evaluate (pair_path must name one of the two) - it goes into both pair lists, in index order
+  // A stem body below the common one: all its pairs are in ONE path's list, so that one lane forms its contact sum in
+  // index order; its partner in a pair is the world or a chain body.
   std::vector<int> path_npairs(K, 0), pair_other(m->npairs, -1);   // pair_other: the second path of a shared pair
+  std::vector<int> stem_path(IDTO_MAX_STEM, -1);
   for (int i = 0; i < m->npairs; ++i) {
     const int p = m->pair_path[i];
     if (p < 0 || p >= K) { g_err = "pair without a valid path"; return -1; }
     const int ba = m->geom_body[m->pair_a[i]], bb = m->geom_body[m->pair_b[i]];
-    const bool chain_a = ba >= 0 && ba != m->common_body, chain_b = bb >= 0 && bb != m->common_body;
+    const bool chain_a = ba >= 0 && stem_idx[ba] < 0, chain_b = bb >= 0 && stem_idx[bb] < 0;
+    for (int b : {ba, bb})
+      if (b >= 0 && stem_idx[b] >= 0 && b != m->common_body) stem_path[stem_idx[b]] = p;
     if (chain_a && chain_b && m->body_path[ba] != m->body_path[bb] && (m->body_path[ba] == p || m->body_path[bb] == p))
       pair_other[i] = m->body_path[ba] == p ? m->body_path[bb] : m->body_path[ba];
     path_npairs[p]++;
@@ -598,7 +657,7 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
     sa[i] = ba < 0 ? -2 : slot_of[ba];
     sb[i] = bb < 0 ? -2 : slot_of[bb];
     for (int b : {ba, bb})
-      if (pair_other[i] < 0 && b >= 0 && b != m->common_body && m->body_path[b] != p) {
+      if (pair_other[i] < 0 && b >= 0 && stem_idx[b] < 0 && m->body_path[b] != p) {
         g_err = "pair touches a body outside its path";
         return -1;
       }
@@ -620,28 +679,36 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
   // path by path, slot by slot - and each pair's two records
   bool shared = false;
   for (int i = 0; i < m->npairs; ++i) shared = shared || pair_other[i] >= 0;
+  // (a model with a stem has the same records, shared pairs or not, and behind them one for each stem body below the
+  // common one that a pair touches: stem_tab[IDTO_MAX_STEM + k])
   int nxb = 0;
   std::vector<int> xrec((size_t)K * IDTO_MAX_CHAIN, -1), pair_xa(m->npairs, -1), pair_xb(m->npairs, -1);
-  if (shared) {
+  std::vector<int> stem_tab(2 * IDTO_MAX_STEM, -1);
+  for (int k = 0; k < nstem; ++k) stem_tab[k] = stem[k];
+  const bool xtab = shared || nstem > 1;
+  if (xtab) {
     for (int i = 0; i < m->npairs; ++i)
       for (int b : {m->geom_body[m->pair_a[i]], m->geom_body[m->pair_b[i]]})
-        if (b >= 0 && b != m->common_body) xrec[(size_t)m->body_path[b] * IDTO_MAX_CHAIN + slot_of[b]] = 0;
+        if (b >= 0 && stem_idx[b] < 0) xrec[(size_t)m->body_path[b] * IDTO_MAX_CHAIN + slot_of[b]] = 0;
     for (int& x : xrec)
       if (x == 0) x = nxb++;
+    for (int k = 0; k + 1 < nstem; ++k)
+      if (stem_path[k] >= 0) stem_tab[IDTO_MAX_STEM + k] = nxb++;
     for (int i = 0; i < m->npairs; ++i) {
       const int ba = m->geom_body[m->pair_a[i]], bb = m->geom_body[m->pair_b[i]];
-      pair_xa[i] = sa[i] >= 0 ? xrec[(size_t)m->body_path[ba] * IDTO_MAX_CHAIN + sa[i]] : sa[i];
-      pair_xb[i] = sb[i] >= 0 ? xrec[(size_t)m->body_path[bb] * IDTO_MAX_CHAIN + sb[i]] : sb[i];
+      pair_xa[i] = sa[i] >= 0 ? xrec[(size_t)m->body_path[ba] * IDTO_MAX_CHAIN + sa[i]] : (sa[i] <= -4 ? stem_tab[IDTO_MAX_STEM - 4 - sa[i]] : sa[i]);
+      pair_xb[i] = sb[i] >= 0 ? xrec[(size_t)m->body_path[bb] * IDTO_MAX_CHAIN + sb[i]] : (sb[i] <= -4 ? stem_tab[IDTO_MAX_STEM - 4 - sb[i]] : sb[i]);
     }
   }
   DevModel& M = c->M;
   M.nb = nb; M.nq = m->nq; M.nv = m->nv; M.npaths = K; M.common_body = m->common_body;
   M.ngeoms = m->ngeoms; M.npairs = m->npairs; M.maxpp = maxpp;
   for (int i = 0; i < 3; ++i) M.gravity[i] = m->gravity[i];
-  M.gslots = 0; M.gcommon = 1;
+  M.gslots = 0; M.gcommon = 1; M.gstem = 0; M.nstem = nstem;
   for (int i = 0; i < nb; ++i) {
     const bool on = !m->gravity_enabled || m->gravity_enabled[i] == 1;
     if (i == m->common_body) M.gcommon = on ? 1 : 0;
+    else if (stem_idx[i] >= 0) M.gstem |= (on ? 1 : 0) << stem_idx[i];
     else if (on) M.gslots |= 1ull << (m->body_path[i] * IDTO_MAX_CHAIN + slot_of[i]);
   }
   // one blob: double tables, then int tables (two per double slot)
@@ -692,6 +759,7 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
     const int cj = cbody >= 0 ? m->jtype[cbody] : -1;
     if (cbody >= 0 && cj != IDTO_JOINT_FLOATING) ok = false;
     if (shared) ok = false;   // (every shape's pair records are per path: a model with shared pairs has none of them)
+    if (nstem > 1) ok = false;   // (... and no shape has a stem below its common body)
     int j0 = -1, k0 = -1, w2 = -1;   // w2: a later slot of the (single) path that hangs off the world again (the spinner)
     for (int p = 0; p < K && ok; ++p)
       for (int s = 0; s < maxc; ++s) {
@@ -834,8 +902,9 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
                i_ga = addi(m->pair_a, m->npairs), i_gb = addi(m->pair_b, m->npairs), i_sa = addi(sa.data(), sa.size()),
                i_sb = addi(sb.data(), sb.size());
   // (the exchange tables only where there are shared pairs: other models stage the blob they staged before)
-  const size_t i_xrec = shared ? addi(xrec.data(), xrec.size()) : i_par, i_xa = shared ? addi(pair_xa.data(), pair_xa.size()) : i_par,
-               i_xb = shared ? addi(pair_xb.data(), pair_xb.size()) : i_par;
+  const size_t i_xrec = xtab ? addi(xrec.data(), xrec.size()) : i_par, i_xa = xtab ? addi(pair_xa.data(), pair_xa.size()) : i_par,
+               i_xb = xtab ? addi(pair_xb.data(), pair_xb.size()) : i_par;
+  const size_t i_stem = nstem > 1 ? addi(stem_tab.data(), stem_tab.size()) : i_par;
   const size_t nd = dbl.size(), ni = ints.size();
   std::vector<double> blob(nd + (ni + 1) / 2 + 1, 0.0);
   std::memcpy(blob.data(), dbl.data(), nd * sizeof(double));
@@ -856,6 +925,7 @@ int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
   M.fast_lo = (int)fast_lo; M.fast_n = (int)(nd + (i_fast_end + 1) / 2 - fast_lo);
   M.f_body = bd + o_fbody; M.f_cbody = bd + o_fcbody; M.f_pairs = bd + o_fpairs; M.f_seg = bi + i_fseg;
   M.nxb = nxb; M.xrec = bi + i_xrec; M.pair_xa = bi + i_xa; M.pair_xb = bi + i_xb;
+  M.stem = bi + i_stem;
   return 0;
 }
 
@@ -867,12 +937,26 @@ int FdEvals(const idto_hip_ctx* c, int mode) {
 // dynamic LDS of fd_kernel when it builds the inputs of `ec` evaluations per pass
 // (fast: fd_kernel<MAXC, SHAPE != 0>, which stages only the shape's records of the model; the fused launch runs the
 // generic evaluation and stages the whole blob)
-int FdLds(const idto_hip_ctx* c, int mode, int ec, bool with_terms = false, bool fast = true) {
+// threads: of the block (0: the context's fd_threads, 64 for a launch of tau alone)
+int FdLds(const idto_hip_ctx* c, int mode, int ec, bool with_terms = false, bool fast = true, int threads = 0) {
   const int nq = c->nq, nv = c->nv, E = FdEvals(c, mode), nvp = (nv + 1) & ~1;
   const int rec = with_terms ? 6 * nvp * nq + nvp + 1 : 0;   // the record, its weighted copy, diag R' (+1: 16-byte alignment)
   const int blob_n = (fast && c->fd_fast && c->M.fast_shape) ? c->M.fast_n : c->M.blob_n;   // what fd_body stages of the model
-  const int xch = c->M.nxb ? fd_xch_doubles(c->M.nxb, mode >= 1 ? c->fd_threads : 64, c->npaths) : 0;   // shared pairs' exchange
+  // (the exchange of shared pairs and of a stem, per concurrent evaluation: id_eval.h xch_eval_doubles)
+  if (!threads) threads = mode >= 1 ? c->fd_threads : 64;
+  const int xch = fd_xch_doubles(c->M.nxb, threads, c->npaths, c->M.nstem);
   return (int)sizeof(double) * (3 * nq + 2 * nv * nq + 3 * nv + 3 * E + E * nv + ec * (nq + 2 * nv) + nv + blob_n + 2 + nq / 2 + 2 + rec + xch);
+}
+
+// Threads of fd_kernel's block.  A stem model keeps a record per touched body and concurrent evaluation in LDS (punyo: 1.8 KB
+// an evaluation): where the carve-up of one round does not fit beside them, the block shrinks by a wavefront at a time and
+// the launch goes in rounds (punyo, forward differences: 48 concurrent evaluations - the 43 with contact and 5 mass-matrix
+// columns in the first round, the other 15 columns, which have no contact, in the second).
+static int FdBlock(const idto_hip_ctx* c, int mode) {
+  if (mode == 0) return 64;
+  int t = c->fd_threads;
+  while (c->M.nstem > 1 && t > 64 && FdLds(c, mode, t / c->npaths, false, true, t) > 160 * 1024) t -= 64;
+  return t;
 }
 
 // fd_kernel also forms the single-record products of the Gauss-Newton assembly (diagonal weights,
@@ -883,15 +967,15 @@ int LaunchFd(idto_hip_ctx* c, int mode, int kb, int ke, AltSel alt = AltSel{null
   c->partials_ahead = false;   // (whatever idto_hip_eval_tau_partials left is about to be overwritten; it sets the flag after its own launch)
   if (ke <= kb) return 0;
   if (mode >= 1) mode = 1 + c->gradients_method;  // 1 forward, 2 central, 3 central (4th order)
-  dim3 grid(ke - kb, c->batch), block(mode >= 1 ? c->fd_threads : 64);
+  dim3 grid(ke - kb, c->batch), block(FdBlock(c, mode));
   // evaluations per pass: all of them if they fit in LDS, otherwise the largest multiple of
   // the number of evaluations the block runs concurrently
   const int E = FdEvals(c, mode), groups = (int)block.x / c->npaths;
   int ec = E;
   bool fold = FoldTerms(c, mode);
-  if (fold && FdLds(c, mode, std::min(ec, groups), true) > 160 * 1024) fold = false;
-  while (ec > groups && FdLds(c, mode, ec, fold) > 160 * 1024) ec = ((ec - 1) / groups) * groups;
-  const int lds = FdLds(c, mode, ec, fold);
+  if (fold && FdLds(c, mode, std::min(ec, groups), true, true, block.x) > 160 * 1024) fold = false;
+  while (ec > groups && FdLds(c, mode, ec, fold, true, block.x) > 160 * 1024) ec = ((ec - 1) / groups) * groups;
+  const int lds = FdLds(c, mode, ec, fold, true, block.x);
   if (lds > 160 * 1024) { g_err = "finite-difference evaluation set does not fit in LDS"; return -1; }
   double* terms = fold ? c->terms : nullptr;
   if (mode >= 1) c->terms_valid = fold && kb == 0 && ke == c->N;
@@ -902,6 +986,7 @@ int LaunchFd(idto_hip_ctx* c, int mode, int kb, int ke, AltSel alt = AltSel{null
   fl.alt = alt;
   fl.shape = c->fd_fast ? c->M.fast_shape : 0;   // id_fast.h: the straight-line evaluation of the model's tree shape
   if (c->M.nxb) fl.shape = SHAPE_XCH;             // shared pairs: the generic evaluation with the exchange (whatever fd_fast says)
+  if (c->M.nstem > 1) fl.shape = SHAPE_STEM;      // a stem below the common body: ... and the walk along it
   fl.maxc = c->maxc;
   fd_launch(fl);
   HIP_OK(hipGetLastError());
@@ -1023,6 +1108,7 @@ int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* probl
                           int device, int batch, idto_hip_ctx** out) {
   *out = nullptr;
   if (int rc = CheckGeometry(model)) return rc;
+  if (int rc = CheckStem(model)) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
     g_err = "no HIP device available (the product path has no CPU fallback)";
@@ -1197,9 +1283,10 @@ int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* probl
   int threads = ((E * K + 63) / 64) * 64;
   if (threads > 256) threads = 256;  // one wave per SIMD: the evaluation keeps its bodies in up to 512 VGPRs
   c->fd_threads = threads;
+  threads = FdBlock(c, 1);   // (a stem model: fewer where the exchange records leave no room, LaunchFd decides per mode)
   // smallest LDS carve-up of the finite-difference kernel: the inputs of one round of concurrent
   // evaluations per pass (LaunchFd uses more when they fit)
-  c->fd_lds = FdLds(c, 1, threads / K);
+  c->fd_lds = FdLds(c, 1, threads / K, false, true, threads);
   c->asm_lds = (int)sizeof(double) * (3 * nq + 5 * (int)bsz + 4 * nv + nq + std::max(nq, nv) + (int)bsz + 3 * (int)qq + nq);
   c->asm_diag_lds = (int)sizeof(double) * (14 * ((nv + 1) & ~1) * nq + 2 * (int)bsz + 10 * nv + 6 * nq + 2);
   c->asm_terms_lds = (int)sizeof(double) * (5 * ((nv + 1) & ~1) * nq + 4 * nv + nq + 2);
@@ -1818,7 +1905,7 @@ static int LaunchLdl(idto_hip_ctx* c, const double* b, double sign, double* xo, 
 
 // ---- one persistent launch for the whole Gauss-Newton iteration (fused.h)
 static int FusedVariant(const idto_hip_ctx* c) {  // instantiated (MAXC, K) combinations: the reference's example models
-  if (c->M.nxb) return 0;   // (gn_fused_kernel embeds id_eval without the exchange of shared pairs)
+  if (c->M.nxb || c->M.nstem > 1) return 0;   // (gn_fused_kernel embeds id_eval without the exchange of shared pairs / the stem)
   if (c->capsules) return 0;   // (capsule models: the three-launch path only)
   const int mc = c->maxc <= 2 ? 2 : (c->maxc <= 3 ? 3 : (c->maxc <= 4 ? 4 : 8));
   if (mc == 2 && c->nq == 2) return 1;
@@ -1904,7 +1991,7 @@ static int SmallLds(const idto_hip_ctx* c, const LdlPlan& p, int* lds_small) {
 }
 static bool SmallEligible(const idto_hip_ctx* c) {
   if (!c->gn_small || !c->fd_fast || c->gradients_method != 0 || !c->weights_diagonal || c->reference_solver) return false;
-  if (c->M.nxb) return false;   // (id_eval_fast has no shared pairs)
+  if (c->M.nxb || c->M.nstem > 1) return false;   // (id_eval_fast has no shared pairs and no stem)
   if (!(c->M.fast_shape == 1 || c->M.fast_shape == 5) || c->M.nfloat != 0 || c->nq != c->nv || c->npaths != 1) return false;
   if (!((c->M.fast_shape == 1 && c->nq == 2) || (c->M.fast_shape == 5 && c->nq == 3))) return false;   // (the instantiations)
   if (c->k_begin != 0 || c->k_end != c->N || c->fd_stop || c->asm_stop || c->solver_debug || c->ldl_npos > 0) return false;

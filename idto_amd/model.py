@@ -21,6 +21,7 @@ JOINT_NV = {0: 1, 1: 1, 2: 3, 3: 6}
 GEOM_TYPES = {"sphere": 0, "box": 1, "capsule": 2}   # capsule size: [radius, h = length / 2, 0] (include/idto_model.h)
 MAX_PATHS = 8
 MAX_CHAIN = 8
+MAX_STEM = 4   # bodies of the stem: the common body and its ancestors (include/idto_model.h IDTO_MAX_STEM)
 
 MODEL_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "models")
 
@@ -200,6 +201,15 @@ class Model:
         self.validate()
         return self
 
+    @property
+    def stem(self):
+        """The common body and its ancestors, world side first ([] without a common body)."""
+        out, b = [], int(self.common_body)
+        while b >= 0 and len(out) <= self.nbodies:
+            out.append(b)
+            b = int(self.parent[b])
+        return out[::-1]
+
     def validate(self):
         nb = self.nbodies
         assert self.npaths in (1, 2, 4, 8), "npaths must be a power of two <= 8"
@@ -211,12 +221,31 @@ class Model:
                 assert np.allclose(self.X_PF[i], [1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0]), "floating X_PF must be identity"
         # star decomposition: every non-common body follows its predecessor in the
         # same path, or hangs off the common body / the world
+        # the stem: the common body and its ancestors; a body below the common one carries the next stem body and nothing
+        # else, has no path, and all its pairs are evaluated by one path (the rules idto_hip_create enforces)
+        stem = self.stem
+        assert len(stem) <= MAX_STEM, f"the stem is longer than MAX_STEM = {MAX_STEM} bodies"
+        below = set(stem[:-1])
+        for b in below:
+            assert sum(int(x) == b for x in self.parent) == 1, f"stem body {b} has a second child"
+            assert int(self.body_path[b]) == -1, f"stem body {b} must have path -1"
+        stem_path = {}
+        for k in range(self.npairs):
+            bodies = [int(self.geom_body[int(g)]) for g in (self.pair_a[k], self.pair_b[k])]
+            if len(stem) > 1:
+                assert not all(b in stem for b in bodies), f"pair {k} joins two stem bodies"
+            for b in bodies:
+                if b in below:
+                    assert stem_path.setdefault(b, int(self.pair_path[k])) == int(self.pair_path[k]), \
+                        f"the pairs of stem body {b} name different paths"
         last_in_path = {}
         count = {}
         for i in range(nb):
             p = int(self.body_path[i])
             if i == self.common_body:
-                assert p == -1 and self.parent[i] == -1
+                assert p == -1
+                continue
+            if i in below:
                 continue
             assert 0 <= p < self.npaths
             par = int(self.parent[i])
@@ -238,7 +267,7 @@ class Model:
         nchild = {}
         for i in range(nb):
             par = int(self.parent[i])
-            if par >= 0 and par != self.common_body:
+            if par >= 0 and par != self.common_body and par not in below:
                 nchild[par] = nchild.get(par, 0) + 1
                 assert nchild[par] <= 1, "chain bodies may have at most one child"
                 assert self.body_path[par] == self.body_path[i]
@@ -247,11 +276,11 @@ class Model:
         for k in range(self.npairs):
             p = int(self.pair_path[k])
             bodies = [int(self.geom_body[int(g)]) for g in (self.pair_a[k], self.pair_b[k])]
-            chain_paths = {int(self.body_path[b]) for b in bodies if b != -1 and b != self.common_body}
+            chain_paths = {int(self.body_path[b]) for b in bodies if b != -1 and b not in stem}
             if len(chain_paths) == 2 and p in chain_paths:
                 continue
             for b in bodies:
-                assert b == -1 or b == self.common_body or int(self.body_path[b]) == p, \
+                assert b == -1 or b in stem or int(self.body_path[b]) == p, \
                     f"pair {k} touches body {b} outside path {p}"
         # geometry types; a capsule: radius > 0, h >= 0, finite, and against a box only a world-fixed one of identity
         # rotation (the rules idto_hip_create enforces)

@@ -26,6 +26,7 @@ extern "C" {
 
 #define IDTO_MAX_PATHS 8   /* lanes cooperating on one inverse-dynamics evaluation */
 #define IDTO_MAX_CHAIN 8   /* bodies in one path's own chain */
+#define IDTO_MAX_STEM 4    /* bodies of the stem: the common body and its ancestors (1: the common body sits on the world) */
 
 enum idto_joint_type {
   IDTO_JOINT_REVOLUTE = 0,  /* 1 q, 1 v: rotation about `axis` (unit, in F) */
@@ -86,23 +87,34 @@ typedef struct idto_model {
    * non-finite size, and a capsule against any other box. */
 
   /* Evaluation/summation-order specification ("star" decomposition): one
-   * optional common root body (computed by every path) plus npaths disjoint
+   * optional common body (computed by every path), the stem it sits on, plus npaths disjoint
    * chains hanging off the world or off the common body.  It fixes the
    * association order of the floating-point sums over children / contact
-   * pairs (DESIGN.md §3.2, §3.2.1) so that a serial CPU evaluation and the
+   * pairs (DESIGN.md §3.2, §3.2.1, §3.2.3) so that a serial CPU evaluation and the
    * lane-parallel HIP evaluation produce identical bits.  Each chain body sums the wrenches of all pairs that touch it
    * in ascending pair index, shared pairs (below) included; the common body sums per path, then over the paths.
-   * HARD LIMIT: this is the only topology the device evaluates - a tree whose branching happens
-   * at the world and at ONE body (no closed loops, no second branching body further down a
-   * chain), chains of at most IDTO_MAX_CHAIN bodies.  It covers the reference's five example
+   * The STEM is the common body plus its ancestors up to the world, found by following `parent` from `common_body`: at
+   * most IDTO_MAX_STEM bodies (1: the common body is attached to the world).  A stem body below the common one has
+   * exactly one child, the next stem body, and body_path -1; it sums the wrenches of all pairs that touch it in
+   * ascending pair index from +0, and the backward pass takes tot = (f_in - ext) + child up the stem (a humanoid's
+   * torso on a lifting column: the punyo example).  The lane that evaluates such a pair is the one `pair_path` names, and
+   * all pairs that touch one stem body must name the same path, so that one lane forms the body's sum; if the pair's
+   * other body is a chain body, that is the chain body's path.  Planar and floating joints are attached to the world, so
+   * only the first body of a stem may have one.
+   * HARD LIMIT: this is the only topology the device evaluates - a tree that is one unbranched stem from the world up to
+   * ONE body, and branches at the world and at that body (no closed loops, no second branching body further down a
+   * chain or on the stem), chains of at most IDTO_MAX_CHAIN bodies.  It covers the reference's example
    * models; the reference itself takes any MultibodyPlant (TO.cc:271-279).  idto_hip_create
-   * rejects a model whose tables do not describe such a tree.  A contact pair stays inside one chain (with the common body
-   * or the world), or joins chain bodies of two different paths: a shared pair, which the lanes of both paths evaluate
-   * (dual_jaco's two hands); any other pair is refused. */
+   * rejects a model whose tables do not describe such a tree - before it touches a device, each with a message of its
+   * own: a stem longer than IDTO_MAX_STEM, a stem body with a second child, a stem body with a path other than -1, pairs
+   * on one stem body that name different paths, a pair between two stem bodies (the common body included).  A contact
+   * pair stays inside one chain (with the common body, a stem body or the world), or joins chain bodies of two different
+   * paths: a shared pair, which the lanes of both paths evaluate (dual_jaco's two hands); any other pair is refused. */
   int npaths;               /* power of two, <= IDTO_MAX_PATHS */
-  int common_body;          /* body index or -1 */
-  const int* body_path;     /* [nbodies] path of each body, -1 for the common body */
-  const int* pair_path;     /* [npairs] path that evaluates the pair; a shared pair: one of its two bodies' paths */
+  int common_body;          /* body index or -1; it may have a parent: the stem */
+  const int* body_path;     /* [nbodies] path of each body, -1 for the common body and every other stem body */
+  const int* pair_path;     /* [npairs] path that evaluates the pair; a shared pair: one of its two bodies' paths; a
+                             * stem body's pairs: one path for all of them */
 
   /* Per-body gravity switch, Drake's MultibodyPlant::set_gravity_enabled(model_instance, false) mapped onto the
    * bodies of that instance (reference examples/jaco/jaco.cc:48: the arm's weight is not modelled).  A body whose

@@ -30,6 +30,9 @@ LIMITS = {
     # (models with shared pairs: the generic evaluation with the chain states and contact sums in LDS - the generic
     # fd_kernel<8, 0> keeps them in registers and spills 584 vector registers to scratch)
     "fd_kernel<8, 7>": (0, 20, 139 + 24),
+    # (models with a stem below the common body: the same evaluation, and every lane walks the stem in a loop - its bodies'
+    # records and the blocks of the backward pass are in LDS too, beside the chain bodies')
+    "fd_kernel<8, 8>": (0, 20, 132 + 24),
     "penta_pipe_kernel<19, false>": (0, 36, 102 + 24),
     "penta_pipe_kernel<2, false>": (0, 0, 137 + 24),
     "penta_pipe_kernel<3, false>": (0, 0, 106 + 24),

@@ -95,6 +95,7 @@ class Joint:
     def __init__(self):
         self.name = self.type = self.parent = self.child = None
         self.X_PJ = X()                 # joint (= child link) frame in the parent LINK frame
+        self.X_JC = None                # SDF joint <pose>: the child link in the joint frame (None: they coincide)
         self.axis = np.array([0, 0, 1.0])
         self.damping = 0.0
         self.auto_floating = False
@@ -179,7 +180,10 @@ def parse_sdf(path, reg, prefix=""):
             Xi = parse_pose(ine.findtext("pose"))
             L.com = Xi.p
             ie = ine.find("inertia")
-            I = inertia_matrix(*[float(ie.findtext(k, "0")) for k in ("ixx", "iyy", "izz", "ixy", "ixz", "iyz")])
+            if ie is None:   # libsdformat's default <inertia>: ixx = iyy = izz = 1, no products (every link of punyoid.sdf)
+                I = np.eye(3)
+            else:
+                I = inertia_matrix(*[float(ie.findtext(k, "0")) for k in ("ixx", "iyy", "izz", "ixy", "ixz", "iyz")])
             L.I = Xi.R @ I @ Xi.R.T
         for ce in le.findall("collision"):
             Xg = parse_pose(ce.findtext("pose"))
@@ -203,15 +207,23 @@ def parse_sdf(path, reg, prefix=""):
         J = Joint()
         J.name, J.type = prefix + je.get("name"), je.get("type")
         J.parent, J.child = prefix + je.findtext("parent"), prefix + je.findtext("child")
-        assert je.find("pose") is None, "joint <pose> not supported"
         J.X_PJ = X_ML[J.parent].inv() @ X_ML[J.child]
+        R_MJ = X_ML[J.child].R
+        if je.find("pose") is not None:
+            # SDFormat: the joint frame J is given in the child link frame C, and the axis in J.  The body frame becomes
+            # J (it coincides with the frame on the parent at q = 0); the link hangs in its body at X_JC = X_CJ^-1.
+            assert je.find("pose").get("relative_to") is None, "joint <pose relative_to> not supported"
+            X_CJ = parse_pose(je.findtext("pose"))
+            J.X_PJ = J.X_PJ @ X_CJ
+            J.X_JC = X_CJ.inv()
+            R_MJ = R_MJ @ X_CJ.R
         ax = je.find("axis")
         if ax is not None:
             xe = ax.find("xyz")
             a = np.array([float(v) for v in xe.text.split()])
             # (SDFormat 1.6 <use_parent_model_frame>1: the axis is in the model frame, as expressed_in="__model__" later)
             if xe.get("expressed_in") == "__model__" or ax.findtext("use_parent_model_frame", "0").strip() == "1":
-                a = X_ML[J.child].R.T @ a
+                a = R_MJ.T @ a
             J.axis = a / np.linalg.norm(a)
             J.damping = float(ax.findtext("dynamics/damping", "0"))
         joints.append(J)
@@ -262,19 +274,23 @@ def build_model(name, links, link_order, joints, actuated, groups, spec, extra_w
         link_body[link] = (body, X_BL)
         for J in children.get(link, []):
             if J.type == "fixed":
+                X_BC = X_BL @ J.X_PJ if J.X_JC is None else X_BL @ J.X_PJ @ J.X_JC
                 if body >= 0:
-                    bodies[body]["links"].append((J.child, X_BL @ J.X_PJ))
-                visit(J.child, body, X_BL @ J.X_PJ)
+                    bodies[body]["links"].append((J.child, X_BC))
+                visit(J.child, body, X_BC)
             else:
                 act = 1 if J.name in actuated else 0
                 Xpf = X_BL @ J.X_PJ
-                if J.type in ("revolute", "continuous"):
-                    b = add_body(J.child, body, "revolute", Xpf, J.axis, [J.damping], [act])
-                    visit(J.child, b, X())
-                elif J.type == "prismatic":
-                    b = add_body(J.child, body, "prismatic", Xpf, J.axis, [J.damping], [act])
-                    visit(J.child, b, X())
+                if J.type in ("revolute", "continuous", "prismatic"):
+                    b = add_body(J.child, body, "prismatic" if J.type == "prismatic" else "revolute", Xpf, J.axis,
+                                 [J.damping], [act])
+                    if J.X_JC is None:
+                        visit(J.child, b, X())
+                    else:   # (the body frame is the joint frame: the link sits at X_JC in it, as a planar joint's link does)
+                        bodies[b]["links"] = [(J.child, J.X_JC)]
+                        visit(J.child, b, J.X_JC)
                 elif J.type == "planar":
+                    assert J.X_JC is None
                     R_JI = planar_frame(J.axis)
                     XJI = X(R_JI, np.zeros(3))
                     # body frame stays the child link frame L (= J at q = 0): the
@@ -342,8 +358,12 @@ def build_model(name, links, link_order, joints, actuated, groups, spec, extra_w
     bidx = {b["name"]: i for i, b in enumerate(bodies)}
     m.common_body = bidx[spec["common"]] if spec.get("common") else -1
     body_path = [-2] * nb
-    if m.common_body >= 0:
-        body_path[m.common_body] = -1
+    # (the stem: the common body and its ancestors have no path, include/idto_model.h)
+    stem, sb_ = set(), m.common_body
+    while sb_ >= 0:
+        body_path[sb_] = -1
+        stem.add(sb_)
+        sb_ = bodies[sb_]["parent"]
     for p, chain in enumerate(spec["paths"]):
         for ln in chain:
             body_path[bidx[ln]] = p
@@ -371,11 +391,19 @@ def build_model(name, links, link_order, joints, actuated, groups, spec, extra_w
             bi, bj = geoms[i][1], geoms[j][1]
             if bi == bj or (min(bi, bj), max(bi, bj)) in adjacent or excluded(geoms[i][5], geoms[j][5]):
                 continue
-            paths = {body_path[b] for b in (bi, bj) if b >= 0 and b != m.common_body}
+            paths = {body_path[b] for b in (bi, bj) if b >= 0 and body_path[b] >= 0}
             # a pair between the chains of two paths (shared pair) is evaluated by both; its pair_path names the path of
             # geometry A's body (include/idto_model.h)
             pp.append(body_path[bi] if len(paths) == 2 else (paths.pop() if paths else 0))
             pa.append(i); pb.append(j)
+    # all pairs of one stem body below the common one name one path: that of the chain bodies it meets (validate refuses
+    # a body that meets two paths); its pairs with the world follow
+    for sbody in stem - {m.common_body}:
+        mine = [k for k in range(len(pa)) if sbody in (geoms[pa[k]][1], geoms[pb[k]][1])]
+        met = {body_path[b] for k in mine for b in (geoms[pa[k]][1], geoms[pb[k]][1]) if b >= 0 and body_path[b] >= 0}
+        for k in mine:
+            if len(met) == 1 and -1 in (geoms[pa[k]][1], geoms[pb[k]][1]):
+                pp[k] = min(met)
     m.pair_a, m.pair_b, m.pair_path = pa, pb, pp
     return m.normalize()
 
@@ -508,7 +536,10 @@ def convert_examples():
 
     dual_jaco: two instances of the arm (link names prefixed by their model instance), welded to the world on either
     side of the box.  The spheres of the two arms' links 6, 7 and nub are candidate pairs of each other in Drake: shared
-    pairs between the model's two paths, evaluated by both (include/idto_model.h)."""
+    pairs between the model's two paths, evaluated by both (include/idto_model.h).
+
+    punyo: the humanoid of models/punyoid.sdf picking up a ball.  Its tree branches at the torso, which sits on a stem of
+    three bodies (include/idto_model.h): common = torso, the arms and the ball are the paths."""
     os.makedirs(OUT_EXAMPLES, exist_ok=True)
     arm_file = f"{REF}/models/j2s7s300_arm_sphere_collision_v2.sdf"
     X_arm = X(rpy_to_R(0, 0, math.pi / 2), [0, 0.27, 0.11])
@@ -559,6 +590,23 @@ def convert_examples():
     l, o, j, a, g = parse_urdf(f"{REF}/models/2dof_spinner_capsule.urdf", reg)
     out["2dof_spinner_capsule"] = build_model("2dof_spinner_capsule", l, o, j, a, g, dict(paths=[["finger_two", "spinner"]]))
     example_yaml = {"spinner_capsule": "spinner", "2dof_spinner_capsule": None}
+
+    # punyo (examples/punyo/punyo.cc:46-90): the humanoid of models/punyoid.sdf, `base` welded to the world at the origin,
+    # weightless; a free ball (m = 1, r = 0.2, solid sphere) and the ground.  The tree branches at the torso, which sits on
+    # the stem waist (prismatic) -> two massless-ish glue links -> torso (include/idto_model.h).
+    reg = [0]
+    l, o, j, a, g, _ = parse_sdf(f"{REF}/models/punyoid.sdf", reg)
+    humanoid = set(o)
+    ball = Link("ball")
+    ball.mass = 1.0
+    ball.I = np.eye(3) * (0.4 * 1.0 * 0.2 ** 2)
+    ball.geoms.append(("sphere", [0.2, 0, 0], X(), reg[0]))
+    reg[0] += 1
+    l["ball"] = ball
+    o.append("ball")
+    arm = lambda s: [f"glue_torso_arm{s}", f"arm_{s}", f"glue_arm_forearm{s}", f"forearm_{s}", f"hand_{s}"]
+    out["punyo"] = build_model("punyo", l, o, j, a, g, dict(common="torso", paths=[arm("L"), arm("R"), ["ball"]]),
+                               extra_world_geoms=[ground_box(reg)], world_weld=("base", X()), gravity_off=humanoid)
 
     for name, m in out.items():
         m.save(os.path.join(OUT_EXAMPLES, f"{name}.model"))

@@ -79,6 +79,11 @@ vals = {
     "R6_SMALL_ITER": small_iter_table(),
     "R6_FULLITER_OTHERS": ", ".join(f"{k} {float(v):.3f}" for k, v in fi.items() if k != "mini_cheetah"),
 }
+# §3.2.3: the stem's numbers are those of profiles/punyo_kernel_stats.txt (tools/punyo_prof.py; not a round's file)
+punyo = open(os.path.join(ROOT, "profiles", "punyo_kernel_stats.txt")).read()
+pm_ = lambda pat: re.search(pat, punyo).group(1)
+vals.update({"PUNYO_FD": pm_(r"fd_kernel<8, 8>.*?median\s+([\d.]+) us"), "PUNYO_CUT": pm_(r"fd_kernel<8, 7>.*?median\s+([\d.]+) us"),
+             "PUNYO_ITER": pm_(r"punyo solve:.*?median ([\d.]+) ms"), "PUNYO_LDL": pm_(r"penta_ldl_kernel<30.*?median\s+([\d.]+) us")})
 src = os.path.join(ROOT, "tools", "design", "DESIGN.in.md")
 text = open(src).read()
 subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_design.py")])

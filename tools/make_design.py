@@ -43,9 +43,14 @@ WELDED_ROW = "| welded links (cheetah feet, allegro `hand_root`)"
 CAPSULE_ROWS = (
     "| capsule-box: the sphere at the capsule's segment end with the lower world z, the `-h` end on a tie (a capsule lying flat touches the ground along its length; Drake/FCL's witness point there is not pinned here) | `csrc/id_eval.h capsule_single`, `include/idto_model.h` | none in-tree | `QueryObject::ComputeSignedDistancePairwiseClosestPoints` for a tilted and a flat `Capsule` above the ground `Box`, compare the witness point on the capsule |\n"
     "| (near-)parallel capsule-capsule: `1 - (u1·u2)^2 <= 1e-10` ⇒ the middle of the overlap of the two segments | `csrc/id_eval.h capsule_centres`, `tests/capsule_ref.py` | none in-tree | the same query on two parallel overlapping capsules |\n")
+# (punyo: what could not be pinned against Drake - the tree holds no number that depends on them)
+PUNYO_ROWS = (
+    "| an SDF `<inertial>` without `<inertia>` (every link of `models/punyoid.sdf`): libsdformat's default, ixx = iyy = izz = 1 with zero products - the glue links of 0.1 kg included | `tools/convert_models.py parse_sdf`; independently `tools/make_model_fixture.py` (`tests/golden/examples/world_punyo.json`) | none in-tree (the file gives masses only) | `plant.GetBodyByName(\"waist\").default_rotational_inertia()` after `Parser.AddModels` |\n"
+    "| an SDF joint `<pose>` is in the child link's frame, the axis in that joint frame; the body frame here is the joint frame, the link hangs in it at the inverse pose (punyo's shoulder, elbow and wrist joints: 0.05 - 0.16 m off the link origin, two turned by pi, so that `shoulderR_joint2` and `elbowR_joint2` turn about -y of the model) | `tools/convert_models.py parse_sdf` (`X_JC`), `build_model`; independently `tools/make_model_fixture.py read_sdf` | SDFormat 1.7 semantics; `models/punyoid.sdf:575-583, 660-668, 695-703` | FK of `hand_R` at q with `shoulderR_joint2` = 0.5 against the model's `X_PF` chain; the sign of the DoF |\n"
+    "| punyo's q: height, three torso joints, the arm of `shoulderL_joint1` (declared first), the arm of `shoulderR_joint1`, the ball - depth-first in joint declaration order; `punyo.yaml` comments the first arm as \"right\" | `tools/convert_models.py build_model` (visiting order), `tests/golden/examples/punyo.model` | every vector of `examples/punyo/punyo.yaml` is the same for both arms, so no number of the fixture depends on it | `plant.GetJointByName(\"shoulderL_joint1\").position_start()` against `shoulderR_joint1`'s |\n")
 if WELDED_ROW in text:
     i = text.index(WELDED_ROW)
     j = text.index("\n", i) + 1
-    text = text[:j] + CAPSULE_ROWS + text[j:]
+    text = text[:j] + CAPSULE_ROWS + PUNYO_ROWS + text[j:]
 open(os.path.join(ROOT, "DESIGN.md"), "w").write(text)
 print("DESIGN.md:", len(text.splitlines()), "lines")

@@ -163,6 +163,8 @@ def read_sdf(path, weld_link, X_W_weld):
             i = ine.find("inertia")
             g = lambda k: float(i.find(k).text) if i is not None and i.find(k) is not None else 0.0
             I = np.array([[g("ixx"), g("ixy"), g("ixz")], [g("ixy"), g("iyy"), g("iyz")], [g("ixz"), g("iyz"), g("izz")]])
+            if i is None:   # an <inertial> without <inertia> (models/punyoid.sdf): libsdformat's default, the unit tensor
+                I = np.eye(3)
         geoms = []
         for ce in le.findall("collision"):
             ge = ce.find("geometry")
@@ -176,7 +178,10 @@ def read_sdf(path, weld_link, X_W_weld):
                 c = ge.find("capsule")
                 geoms.append(dict(type="capsule", size=[float(c.find("radius").text), float(c.find("length").text)],
                                   X_LG=sdf_pose(ce.find("pose"))))
-        raw[le.get("name")] = dict(mass=mass, I_C=I, X_LC=X_LC, geoms=geoms, X_ML=sdf_pose(le.find("pose")))
+        X_ML = sdf_pose(le.find("pose"))
+        if le.find("pose") is not None and le.find("pose").get("relative_to"):   # (a link named earlier in the file)
+            X_ML = raw[le.find("pose").get("relative_to")]["X_ML"] @ X_ML
+        raw[le.get("name")] = dict(mass=mass, I_C=I, X_LC=X_LC, geoms=geoms, X_ML=X_ML)
     X_WM = X_W_weld @ np.linalg.inv(raw[weld_link]["X_ML"])
     for L in raw.values():
         L["X_WL"] = X_WM @ L["X_ML"]
@@ -189,11 +194,12 @@ def read_sdf(path, weld_link, X_W_weld):
         xe = je.find("axis").find("xyz")
         a = np.array(floats(xe.text, 3))
         child = je.find("child").text
+        # a joint's <pose> is in its child link's frame, and its axis in the joint frame (SDFormat 1.7)
+        X_WJ = raw[child]["X_WL"] @ sdf_pose(je.find("pose"))
         if xe.get("expressed_in") == "__model__":
             aW = X_WM[:3, :3] @ a
         else:
-            aW = raw[child]["X_WL"][:3, :3] @ a
-        X_WJ = raw[child]["X_WL"] @ sdf_pose(je.find("pose"))
+            aW = X_WJ[:3, :3] @ a
         jout.append(dict(name=je.get("name"), type=je.get("type"), child=child, parent=je.find("parent").text,
                          axis_W=aW.tolist(), anchor_W=X_WJ[:3, 3].tolist()))
     return record_links(raw), jout
@@ -231,6 +237,16 @@ def main():
         with open(os.path.join(OUT, "examples", f"world_{name}.json"), "w") as f:
             json.dump(d, f, indent=1)
         print(name, len(d["links"]), "links,", len(d["joints"]), "movable joints")
+    # punyo (examples/punyo/punyo.cc:46-90): `base` welded to the world at the origin, a free ball m = 1, r = 0.2
+    links, joints = read_sdf(f"{REF}/models/punyoid.sdf", "base", T())
+    r, m = 0.2, 1.0
+    links["ball"] = dict(X_WL=T().tolist(), mass=m, com_W=[0, 0, 0], I_W=(np.eye(3) * 0.4 * m * r * r).tolist(),
+                         welded_to=None, geoms=[dict(type="sphere", size=[r], X_WG=T().tolist())])
+    d = dict(source="reference models/punyoid.sdf + examples/punyo/punyo.cc:46-90", links=links, joints=joints,
+             world_geoms=[ground()], generator="tools/make_model_fixture.py")
+    with open(os.path.join(OUT, "examples", "world_punyo.json"), "w") as f:
+        json.dump(d, f, indent=1)
+    print("punyo", len(d["links"]), "links,", len(d["joints"]), "movable joints")
 
 
 if __name__ == "__main__":

@@ -255,21 +255,11 @@ __host__ __device__ inline int asm_terms_stride(int nq) { return 6 * nq * nq + 3
 // dtau_k/dq_k | dtau_k/dq_{k+1} | tau_k] plus v_{k+1}, a_k, N+_{k+1}.
 // mode 0: tau only (one evaluation); mode 1: forward differences (TO.cc:426-563).
 // Dynamic LDS layout (doubles): see the carve-up below.
-// the instantiated tree shapes of id_fast.h (DevModel::fast_shape; 0 = any model: id_eval<MAXC>)
-// GS: bodies whose weight is switched off are allowed (id_fast.h); the other shapes are chosen only when every body has it
-template <int SHAPE> struct FastShape { static constexpr int MAXC = 0, NP = 1, CJ = -1, J0 = 0, K0 = 0, W2 = -1, GS = 0; };
-template <> struct FastShape<1> { static constexpr int MAXC = 2, NP = 1, CJ = -1, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_WORLD, W2 = -1, GS = 0; };             // acrobot
-template <> struct FastShape<2> { static constexpr int MAXC = 3, NP = 1, CJ = -1, J0 = IDTO_JOINT_PLANAR, K0 = PK_WORLD, W2 = -1, GS = 0; };               // hopper
-template <> struct FastShape<3> { static constexpr int MAXC = 3, NP = 4, CJ = IDTO_JOINT_FLOATING, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_COMMON, W2 = -1, GS = 0; };  // mini_cheetah
-template <> struct FastShape<4> { static constexpr int MAXC = 4, NP = 4, CJ = IDTO_JOINT_FLOATING, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_WORLD, W2 = -1, GS = 0; };   // allegro_hand + ball
-template <> struct FastShape<5> { static constexpr int MAXC = 3, NP = 1, CJ = -1, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_WORLD, W2 = 2, GS = 0; };              // spinner: two-link finger + the spinner, off the world
-template <> struct FastShape<6> { static constexpr int MAXC = 7, NP = 1, CJ = IDTO_JOINT_FLOATING, J0 = IDTO_JOINT_REVOLUTE, K0 = PK_WORLD, W2 = -1, GS = 1; };   // a free object + an arm of seven revolute bodies off the world (jaco, jaco_ball)
-// Not a tree shape: SHAPE_XCH selects the generic evaluation with the exchange area of shared pairs (id_eval<MAXC, true>,
-// models with DevModel::nxb > 0; DevModel::fast_shape stays 0 for them)
-constexpr int SHAPE_XCH = 7;
-// ... and SHAPE_STEM the one that also walks a stem below the common body (id_eval<MAXC, true, true>, DevModel::nstem > 1): its
-// exchange area has the stem's blocks behind the records (id_eval.h xch_eval_doubles)
-constexpr int SHAPE_STEM = 8;
+// the instantiated tree shapes of id_fast.h (DevModel::fast_shape; 0 = any model: id_eval<MAXC>): model_layout.h's table
+template <int SHAPE> struct FastShape {
+  static constexpr TreeShape T = tree_shape(SHAPE);
+  static constexpr int MAXC = T.MAXC, NP = T.NP, CJ = T.CJ, J0 = T.J0, K0 = T.K0, W2 = T.W2, GS = T.GS;
+};
 // the part of fd_body's LDS that id_eval<MAXC, true> exchanges the chain states through: a record per chain body that a
 // pair touches, for each of the block's concurrent evaluations
 __host__ __device__ inline int fd_xch_doubles(int nxb, int threads, int npaths, int nstem = 0) {

@@ -1,33 +1,42 @@
 // fd_launch.hip — the instantiations of fd_kernel (fd_kernel.h) and their launch.
 #include "fd_launch.h"
 
+#include <utility>
+
 namespace idto_dev {
 
-#define FD_ARGS a.M, a.cp, a.P, a.q, a.slab, a.slab_stride, a.v, a.a, a.nplus, a.k_begin, a.mode, a.stop_after, a.echunk, \
-                a.pstride, a.terms, a.alt
-#define FD_GO(MC, SH) hipLaunchKernelGGL((fd_kernel<MC, SH>), a.grid, a.block, a.lds, a.stream, FD_ARGS)
+// The instantiations: the generic evaluation for chains of up to 2, 3, 4 and 8 bodies, and one kernel per row of
+// model_layout.h's shapes - the tree shapes, SHAPE_XCH, SHAPE_STEM - with the chain bound the table gives it.
+template <int MC, int SH>
+static void go(const FdLaunch& a) {
+  hipLaunchKernelGGL((fd_kernel<MC, SH>), a.grid, a.block, a.lds, a.stream, a.M, a.cp, a.P, a.q, a.slab, a.slab_stride, a.v,
+                     a.a, a.nplus, a.k_begin, a.mode, a.stop_after, a.echunk, a.pstride, a.terms, a.alt);
+}
+template <int MC, int SH>
+static void allow(int max_lds) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fd_kernel<MC, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+}
+using Shapes = std::make_integer_sequence<int, SHAPE_STEM>;   // (shape = 1 + the index)
 
+template <int... I>
+static void go_shape(const FdLaunch& a, std::integer_sequence<int, I...>) {
+  ((a.shape == I + 1 ? go<tree_shape(I + 1).KC, I + 1>(a) : void()), ...);
+}
 void fd_launch(const FdLaunch& a) {
-  if (a.shape == 1) FD_GO(2, 1);
-  else if (a.shape == 2) FD_GO(3, 2);
-  else if (a.shape == 3) FD_GO(3, 3);
-  else if (a.shape == 4) FD_GO(4, 4);
-  else if (a.shape == 5) FD_GO(3, 5);
-  else if (a.shape == 6) FD_GO(8, 6);
-  else if (a.shape == SHAPE_XCH) FD_GO(8, SHAPE_XCH);   // (models with shared pairs: any chain length)
-  else if (a.shape == SHAPE_STEM) FD_GO(8, SHAPE_STEM);   // (a stem below the common body; shared pairs or not)
-  else if (a.maxc <= 2) FD_GO(2, 0);
-  else if (a.maxc <= 3) FD_GO(3, 0);
-  else if (a.maxc <= 4) FD_GO(4, 0);
-  else FD_GO(8, 0);
+  if (a.shape) go_shape(a, Shapes{});
+  else if (a.maxc <= 2) go<2, 0>(a);
+  else if (a.maxc <= 3) go<3, 0>(a);
+  else if (a.maxc <= 4) go<4, 0>(a);
+  else go<8, 0>(a);
 }
 
-#define FD_ATTR(MC, SH) \
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fd_kernel<MC, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)
-
+template <int... I>
+static void allow_shapes(int max_lds, std::integer_sequence<int, I...>) {
+  (allow<tree_shape(I + 1).KC, I + 1>(max_lds), ...);
+}
 void fd_set_max_lds(int max_lds) {
-  FD_ATTR(2, 0); FD_ATTR(3, 0); FD_ATTR(4, 0); FD_ATTR(8, 0);
-  FD_ATTR(2, 1); FD_ATTR(3, 2); FD_ATTR(3, 3); FD_ATTR(4, 4); FD_ATTR(3, 5); FD_ATTR(8, 6); FD_ATTR(8, SHAPE_XCH); FD_ATTR(8, SHAPE_STEM);
+  allow<2, 0>(max_lds); allow<3, 0>(max_lds); allow<4, 0>(max_lds); allow<8, 0>(max_lds);
+  allow_shapes(max_lds, Shapes{});
 }
 
 }  // namespace idto_dev

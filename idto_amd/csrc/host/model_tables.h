@@ -1,0 +1,43 @@
+// model_tables.h — everything idto_hip_create derives from an idto_model_t before it touches a device: the checks of
+// the model and the tables DevModel (id_eval.h) points at, packed as the one blob the kernels stage.  Plain C++: the
+// unit builds, runs and is sanitized without HIP.
+#pragma once
+
+#include <cstddef>
+#include <string>
+#include <vector>
+
+#include "idto_model.h"
+
+namespace idto_host {
+
+// DevModel's table pointers, by member name
+#define IDTO_MODEL_DOUBLE_TABLES(X) \
+  X(X_PF) X(axis) X(mass) X(com) X(inertia) X(damping) X(geom_X) X(geom_size) X(nplus_const) X(f_body) X(f_cbody) X(f_pairs)
+#define IDTO_MODEL_INT_TABLES(X)                                                                                      \
+  X(parent) X(jtype) X(qstart) X(vstart) X(geom_type) X(chain) X(nchain) X(pkind) X(path_npairs) X(path_pairs) X(pair_ga) \
+  X(pair_gb) X(pair_sa) X(pair_sb) X(colinfo) X(rowinfo) X(f_seg) X(xrec) X(pair_xa) X(pair_xb) X(stem)
+
+struct ModelTables {
+  // the double tables, then the int tables (two per double slot) and a trailing pad
+  std::vector<double> blob;
+  // where each table starts: a double table as an index into blob, an int table as an index into the blob read as int[]
+  struct Offsets {
+#define X(name) size_t name = 0;
+    IDTO_MODEL_DOUBLE_TABLES(X) IDTO_MODEL_INT_TABLES(X)
+#undef X
+  } at;
+  // DevModel's scalars of the same names
+  int maxpp = 1, nfloat = 0, float_qs[4] = {0, 0, 0, 0}, float_vs[4] = {0, 0, 0, 0};
+  int fast_shape = 0, fast_lo = 0, fast_n = 0, f_maxpp = 1, nxb = 0, nstem = 0, gcommon = 1, gstem = 0;
+  unsigned long long gslots = 0;
+  // the context's: the longest chain, and whether the model has a capsule
+  int maxc = 1;
+  bool capsules = false;
+};
+
+// 0, or -1 with the refusal in *err.  The checks run in a fixed order - geometry, stem, then paths, joints, gravity
+// switches, chains and pairs - and the first one that fails is reported.
+int BuildModelTables(const idto_model_t* m, ModelTables* out, std::string* err);
+
+}  // namespace idto_host

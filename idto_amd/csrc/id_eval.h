@@ -20,6 +20,7 @@
 
 #include "dev_math.h"
 #include "idto_model.h"
+#include "model_layout.h"
 
 namespace idto_dev {
 
@@ -118,8 +119,6 @@ IDTO_DEV DevModel rebase_model(const DevModel& M, const double* dst) {
 struct DevContact {
   double k, vd, vs, mu, sigma, threshold;
 };
-
-enum { PK_WORLD = 0, PK_COMMON = 1, PK_PREV = 2 };
 
 struct BodyState {  // what later stages need of a body
   M3 R;

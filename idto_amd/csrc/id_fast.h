@@ -10,8 +10,8 @@
 //   CJ   joint of the common root body: -1 (none) or IDTO_JOINT_FLOATING, attached to the world
 //   J0   joint of chain slot 0: revolute or planar;  K0: its parent, PK_WORLD or PK_COMMON
 //   slots 1 .. MAXC-1: revolute, parent = the previous slot; every path has exactly MAXC bodies
-// and every contact pair touches at most one chain body.  BuildModel (idto_hip.hip) checks a
-// model against the instantiated shapes and gathers, on the host, one record of constants per
+// and every contact pair touches at most one chain body.  host/model_tables.cc checks a
+// model against the instantiated shapes (model_layout.h) and gathers, on the host, one record of constants per
 // (path, slot) and per contact pair in the order this file walks them, so that every table read
 // is `base(path) + immediate` and nothing on the recursion's chain waits for an index.
 // The contact pairs of a slot are evaluated right after the slot's kinematics: a finished slot
@@ -39,14 +39,6 @@
 #endif
 
 namespace idto_dev {
-
-// record of one body (doubles); FB_IDX holds {qstart, vstart} as two ints
-enum { FB_XPF = 0, FB_AXIS = 12, FB_MASS = 15, FB_COM = 16, FB_INERTIA = 19, FB_DAMP = 25, FB_IDX = 31, FB_STRIDE = 34 };
-// record of one contact pair; FP_INFO holds {type on C, type on the other body, C is the pair's A, the other body is
-// the common one} as four ints.
-// XC, SC: geometry frame and size on C (the chain slot of the pair's group; the common body for a pair without a
-// chain body); XO, SO: on the other body - for the world [I R | 0 + I p], formed on the host
-enum { FP_INFO = 0, FP_XC = 2, FP_SC = 14, FP_XO = 17, FP_SO = 29, FP_STRIDE = 34 };
 
 // x + (x of the lane whose index differs in bit 0 / bit 1): the butterfly of dev_math.h tree_sum
 // as DPP quad permutations (no LDS round trip); lanes of one evaluation are adjacent and aligned
@@ -200,7 +192,7 @@ IDTO_DEV bool pair_eval(const double* pr, const DevContact& cp, const BodyState&
       else { n1 = gW; Cc = boxW; Co = sphW; }
       hit = true;
     }
-  } else {  // box A on a moving body (always C: BuildModel) vs world-fixed axis-aligned box B: A's lowest vertex against B's top face
+  } else {  // box A on a moving body (always C: host/model_tables.cc) vs world-fixed axis-aligned box B: A's lowest vertex against B's top face
     const M3 RgA = C.R * ldm3(pr + FP_XC);
     const double ztop = pgO.z + sO.z;
     double zmin = 0;
@@ -347,7 +339,7 @@ struct InFwd {
 // tau = ID(q, v, a) for the lane's path: id_eval<MAXC> for a model of shape (CJ, J0, K0).
 // W2 >= 1 (the spinner: finger of two links + the spinner itself in ONE path): slot W2 hangs off the world again, and the
 // pairs of its group touch slot W2 - 1 as their other body (pair_eval's "common" argument is that slot's state; the
-// force on it is taken out of its wrench after the group - the slot has no pairs of its own, BuildModel checks, so the
+// force on it is taken out of its wrench after the group - the slot has no pairs of its own, host/model_tables.cc checks, so the
 // order of the generic sum, fin - (0 + f), is kept).
 template <int MAXC, int NP, int CJ, int J0, int K0, int W2, int GS = 0, class In>
 IDTO_DEV void id_eval_fast(const FastTab& T, const double* gravity, const DevContact& cp, int path, bool full,

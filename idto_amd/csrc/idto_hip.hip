@@ -37,6 +37,7 @@
 #include "dense_ldl.h"
 #include "trust_region.h"
 #include "kkt.h"
+#include "host/model_tables.h"
 
 using namespace idto_dev;
 
@@ -494,438 +495,28 @@ int UploadProblemArrays(idto_hip_ctx* c, const idto_problem_t* p, int pb = 0) {
   return 0;
 }
 
-// The geometry types and the pairs a capsule may take part in (include/idto_model.h).  Host tables only: it runs before
-// any device is touched, so a refused model fails the same way with or without a GPU.
-static bool IdentityRotation(const double* X) {
-  bool ident = true;
-  for (int e = 0; e < 9; ++e) ident &= (X[e] == ((e % 4 == 0) ? 1.0 : 0.0));
-  return ident;
-}
-static int CheckGeometry(const idto_model_t* m) {
-  for (int g = 0; g < m->ngeoms; ++g) {
-    const int t = m->geom_type[g];
-    if (t != IDTO_GEOM_SPHERE && t != IDTO_GEOM_BOX && t != IDTO_GEOM_CAPSULE) {
-      g_err = "unknown geometry type (0 sphere, 1 box, 2 capsule)";
-      return -1;
-    }
-    const double* s = m->geom_size + (size_t)3 * g;
-    if (t == IDTO_GEOM_CAPSULE &&
-        !(std::isfinite(s[0]) && std::isfinite(s[1]) && std::isfinite(s[2]) && s[0] > 0 && s[1] >= 0)) {
-      g_err = "capsule size must be finite with radius > 0 and h >= 0";
-      return -1;
-    }
-  }
-  for (int i = 0; i < m->npairs; ++i) {
-    const int ga = m->pair_a[i], gb = m->pair_b[i];
-    if (ga < 0 || ga >= m->ngeoms || gb < 0 || gb >= m->ngeoms) { g_err = "pair geometry index out of range"; return -1; }
-    const int ta = m->geom_type[ga], tb = m->geom_type[gb];
-    if ((ta == IDTO_GEOM_CAPSULE && tb == IDTO_GEOM_BOX) || (ta == IDTO_GEOM_BOX && tb == IDTO_GEOM_CAPSULE)) {
-      const int box = (ta == IDTO_GEOM_BOX) ? ga : gb;
-      if (m->geom_body[box] >= 0 || !IdentityRotation(m->geom_X + (size_t)12 * box)) {
-        g_err = "capsule-box contact pairs need a world-fixed box with identity rotation";
-        return -1;
-      }
-    }
-  }
-  return 0;
-}
-
-// The stem (include/idto_model.h): the common body and its ancestors.  Host tables only, as CheckGeometry.
-static int CheckStem(const idto_model_t* m) {
-  const int nb = m->nbodies;
-  if (m->common_body >= nb) { g_err = "common body out of range"; return -1; }
-  std::vector<int> stem, stem_idx(nb, -1);   // (common body first here)
-  for (int b = m->common_body; b >= 0; b = m->parent[b]) {
-    if (m->parent[b] >= b) { g_err = "bodies must be numbered so that parent[i] < i"; return -1; }
-    if ((int)stem.size() == IDTO_MAX_STEM) {
-      g_err = "the stem (the common body and its ancestors) is longer than IDTO_MAX_STEM bodies";
-      return -1;
-    }
-    stem_idx[b] = (int)stem.size();
-    stem.push_back(b);
-  }
-  if (stem.size() < 2) return 0;
-  for (size_t k = 1; k < stem.size(); ++k) {
-    int children = 0;
-    for (int i = 0; i < nb; ++i) children += m->parent[i] == stem[k];
-    if (children != 1) {
-      g_err = "a stem body below the common body has a second child (chains hang off the common body or the world)";
-      return -1;
-    }
-    if (m->body_path[stem[k]] != -1) { g_err = "a stem body must have body_path -1"; return -1; }
-  }
-  std::vector<int> stem_path(nb, -1);
-  for (int i = 0; i < m->npairs; ++i) {
-    const int ga = m->pair_a[i], gb = m->pair_b[i];
-    if (ga < 0 || ga >= m->ngeoms || gb < 0 || gb >= m->ngeoms) { g_err = "pair geometry index out of range"; return -1; }
-    const int ba = m->geom_body[ga], bb = m->geom_body[gb];
-    if (ba >= nb || bb >= nb) { g_err = "geometry body out of range"; return -1; }
-    if (ba >= 0 && bb >= 0 && stem_idx[ba] >= 0 && stem_idx[bb] >= 0) {
-      g_err = "contact pair between two stem bodies (the common body included)";
-      return -1;
-    }
-    for (int b : {ba, bb})
-      if (b >= 0 && stem_idx[b] > 0) {
-        if (stem_path[b] >= 0 && stem_path[b] != m->pair_path[i]) {
-          g_err = "the pairs of one stem body name different paths (pair_path)";
-          return -1;
-        }
-        stem_path[b] = m->pair_path[i];
-      }
-  }
-  return 0;
-}
-
-int BuildModel(idto_hip_ctx* c, const idto_model_t* m) {
-  const int nb = m->nbodies, K = m->npaths;
-  if (K < 1 || K > IDTO_MAX_PATHS || (K & (K - 1))) { g_err = "npaths must be a power of two <= 8"; return -1; }
-  // star decomposition tables
-  std::vector<int> chain((size_t)K * IDTO_MAX_CHAIN, -1), nchain(K, 0), pkind((size_t)K * IDTO_MAX_CHAIN, 0);
-  std::vector<int> slot_of(nb, -3);
-  for (int i = 0; i < nb; ++i)
-    if ((m->jtype[i] == IDTO_JOINT_PLANAR || m->jtype[i] == IDTO_JOINT_FLOATING) && m->parent[i] >= 0) {
-      g_err = "planar and floating joints must be attached to the world";
-      return -1;
-    }
-  // the stem: the common body and its ancestors, world side first (stem_idx: a body's place in it, -1 for every other body).
-  // A body below the common one carries nothing but the next stem body, and has no path of its own.
-  // (CheckStem has seen the tables)
-  std::vector<int> stem, stem_idx(nb, -1);
-  for (int b = m->common_body; b >= 0; b = m->parent[b]) stem.push_back(b);
-  std::reverse(stem.begin(), stem.end());
-  const int nstem = (int)stem.size();
-  for (int k = 0; k < nstem; ++k) stem_idx[stem[k]] = k;
-  // per-body gravity switch: 0 or 1 per body, NULL = every body
-  bool all_gravity = true;
-  if (m->gravity_enabled)
-    for (int i = 0; i < nb; ++i) {
-      if (m->gravity_enabled[i] != 0 && m->gravity_enabled[i] != 1) {
-        g_err = "gravity_enabled entries must be 0 or 1";
-        return -1;
-      }
-      all_gravity = all_gravity && m->gravity_enabled[i] == 1;
-    }
-  for (int i = 0; i < nb; ++i) {
-    if (i == m->common_body) { slot_of[i] = -1; continue; }
-    if (stem_idx[i] >= 0) { slot_of[i] = -4 - stem_idx[i]; continue; }   // (a stem body below the common one: id_eval.h)
-    const int p = m->body_path[i];
-    if (p < 0 || p >= K) { g_err = "body without a valid path"; return -1; }
-    const int s = nchain[p]++;
-    if (s >= IDTO_MAX_CHAIN) { g_err = "chain longer than IDTO_MAX_CHAIN"; return -1; }
-    chain[(size_t)p * IDTO_MAX_CHAIN + s] = i;
-    slot_of[i] = s;
-    const int par = m->parent[i];
-    int kind;
-    if (par < 0) kind = PK_WORLD;
-    else if (par == m->common_body) kind = PK_COMMON;
-    else if (s > 0 && chain[(size_t)p * IDTO_MAX_CHAIN + s - 1] == par) kind = PK_PREV;
-    else { g_err = "model is not a star decomposition (body parent is neither world, common nor previous in path)"; return -1; }
-    pkind[(size_t)p * IDTO_MAX_CHAIN + s] = kind;
-  }
-  int maxc = 1;
-  for (int p = 0; p < K; ++p) maxc = std::max(maxc, nchain[p]);
-  c->maxc = maxc;
-  bool capsules = false;
-  for (int g = 0; g < m->ngeoms; ++g) capsules = capsules || m->geom_type[g] == IDTO_GEOM_CAPSULE;
-  c->capsules = capsules;
-  // a pair stays inside one path (with the common body / the world), or joins chain bodies of two paths: a shared pair,
-  // which both paths evaluate (pair_path must name one of the two) - it goes into both pair lists, in index order
-  // A stem body below the common one: all its pairs are in ONE path's list, so that one lane forms its contact sum in
-  // index order; its partner in a pair is the world or a chain body.
-  std::vector<int> path_npairs(K, 0), pair_other(m->npairs, -1);   // pair_other: the second path of a shared pair
-  std::vector<int> stem_path(IDTO_MAX_STEM, -1);
-  for (int i = 0; i < m->npairs; ++i) {
-    const int p = m->pair_path[i];
-    if (p < 0 || p >= K) { g_err = "pair without a valid path"; return -1; }
-    const int ba = m->geom_body[m->pair_a[i]], bb = m->geom_body[m->pair_b[i]];
-    const bool chain_a = ba >= 0 && stem_idx[ba] < 0, chain_b = bb >= 0 && stem_idx[bb] < 0;
-    for (int b : {ba, bb})
-      if (b >= 0 && stem_idx[b] >= 0 && b != m->common_body) stem_path[stem_idx[b]] = p;
-    if (chain_a && chain_b && m->body_path[ba] != m->body_path[bb] && (m->body_path[ba] == p || m->body_path[bb] == p))
-      pair_other[i] = m->body_path[ba] == p ? m->body_path[bb] : m->body_path[ba];
-    path_npairs[p]++;
-    if (pair_other[i] >= 0) path_npairs[pair_other[i]]++;
-  }
-  int maxpp = 1;
-  for (int p = 0; p < K; ++p) maxpp = std::max(maxpp, path_npairs[p]);
-  std::vector<int> path_pairs((size_t)K * maxpp, 0), fill(K, 0), sa(m->npairs), sb(m->npairs);
-  for (int i = 0; i < m->npairs; ++i) {
-    const int p = m->pair_path[i];
-    path_pairs[(size_t)p * maxpp + fill[p]++] = i;
-    if (pair_other[i] >= 0) path_pairs[(size_t)pair_other[i] * maxpp + fill[pair_other[i]]++] = i;
-    const int ba = m->geom_body[m->pair_a[i]], bb = m->geom_body[m->pair_b[i]];
-    sa[i] = ba < 0 ? -2 : slot_of[ba];
-    sb[i] = bb < 0 ? -2 : slot_of[bb];
-    for (int b : {ba, bb})
-      if (pair_other[i] < 0 && b >= 0 && stem_idx[b] < 0 && m->body_path[b] != p) {
-        g_err = "pair touches a body outside its path";
-        return -1;
-      }
-    // box-box is implemented for ONE configuration only (id_eval.h signed_distance): A = a box on a
-    // moving body, B = a world-fixed, axis-aligned box whose top face acts as the half-space
-    // z <= top (the ground boxes of the reference's examples).  Anything else would silently get
-    // wrong witness points, so it is refused here.
-    if (m->geom_type[m->pair_a[i]] == IDTO_GEOM_BOX && m->geom_type[m->pair_b[i]] == IDTO_GEOM_BOX) {
-      const double* XB = m->geom_X + (size_t)12 * m->pair_b[i];
-      bool ident = true;
-      for (int e = 0; e < 9; ++e) ident &= (XB[e] == ((e % 4 == 0) ? 1.0 : 0.0));
-      if (ba < 0 || bb >= 0 || !ident) {
-        g_err = "box-box contact pairs must be (box on a moving body, world-fixed axis-aligned box), in this order";
-        return -1;
-      }
-    }
-  }
-  // shared pairs: the exchange records of id_eval<MAXC, true> - one per chain body that some pair touches, numbered
-  // path by path, slot by slot - and each pair's two records
-  bool shared = false;
-  for (int i = 0; i < m->npairs; ++i) shared = shared || pair_other[i] >= 0;
-  // (a model with a stem has the same records, shared pairs or not, and behind them one for each stem body below the
-  // common one that a pair touches: stem_tab[IDTO_MAX_STEM + k])
-  int nxb = 0;
-  std::vector<int> xrec((size_t)K * IDTO_MAX_CHAIN, -1), pair_xa(m->npairs, -1), pair_xb(m->npairs, -1);
-  std::vector<int> stem_tab(2 * IDTO_MAX_STEM, -1);
-  for (int k = 0; k < nstem; ++k) stem_tab[k] = stem[k];
-  const bool xtab = shared || nstem > 1;
-  if (xtab) {
-    for (int i = 0; i < m->npairs; ++i)
-      for (int b : {m->geom_body[m->pair_a[i]], m->geom_body[m->pair_b[i]]})
-        if (b >= 0 && stem_idx[b] < 0) xrec[(size_t)m->body_path[b] * IDTO_MAX_CHAIN + slot_of[b]] = 0;
-    for (int& x : xrec)
-      if (x == 0) x = nxb++;
-    for (int k = 0; k + 1 < nstem; ++k)
-      if (stem_path[k] >= 0) stem_tab[IDTO_MAX_STEM + k] = nxb++;
-    for (int i = 0; i < m->npairs; ++i) {
-      const int ba = m->geom_body[m->pair_a[i]], bb = m->geom_body[m->pair_b[i]];
-      pair_xa[i] = sa[i] >= 0 ? xrec[(size_t)m->body_path[ba] * IDTO_MAX_CHAIN + sa[i]] : (sa[i] <= -4 ? stem_tab[IDTO_MAX_STEM - 4 - sa[i]] : sa[i]);
-      pair_xb[i] = sb[i] >= 0 ? xrec[(size_t)m->body_path[bb] * IDTO_MAX_CHAIN + sb[i]] : (sb[i] <= -4 ? stem_tab[IDTO_MAX_STEM - 4 - sb[i]] : sb[i]);
-    }
-  }
-  DevModel& M = c->M;
-  M.nb = nb; M.nq = m->nq; M.nv = m->nv; M.npaths = K; M.common_body = m->common_body;
-  M.ngeoms = m->ngeoms; M.npairs = m->npairs; M.maxpp = maxpp;
-  for (int i = 0; i < 3; ++i) M.gravity[i] = m->gravity[i];
-  M.gslots = 0; M.gcommon = 1; M.gstem = 0; M.nstem = nstem;
-  for (int i = 0; i < nb; ++i) {
-    const bool on = !m->gravity_enabled || m->gravity_enabled[i] == 1;
-    if (i == m->common_body) M.gcommon = on ? 1 : 0;
-    else if (stem_idx[i] >= 0) M.gstem |= (on ? 1 : 0) << stem_idx[i];
-    else if (on) M.gslots |= 1ull << (m->body_path[i] * IDTO_MAX_CHAIN + slot_of[i]);
-  }
-  // one blob: double tables, then int tables (two per double slot)
-  std::vector<double> dbl;
-  std::vector<int> ints;
-  auto addd = [&](const double* src, size_t n) { const size_t o = dbl.size(); dbl.insert(dbl.end(), src, src + n); return o; };
-  auto addi = [&](const int* src, size_t n) { const size_t o = ints.size(); ints.insert(ints.end(), src, src + n); return o; };
-  const size_t o_XPF = addd(m->X_PF, (size_t)12 * nb), o_axis = addd(m->axis, (size_t)3 * nb), o_mass = addd(m->mass, nb),
-               o_com = addd(m->com, (size_t)3 * nb), o_in = addd(m->inertia, (size_t)6 * nb),
-               o_damp = addd(m->damping, m->nv), o_gX = addd(m->geom_X, (size_t)12 * m->ngeoms),
-               o_gs = addd(m->geom_size, (size_t)3 * m->ngeoms);
-  // N+ (TO.cc:1633-1647): its constant entries, and the non-zero range of every column and row
-  const int nqm = m->nq, nvm = m->nv;
-  std::vector<double> npc((size_t)nvm * nqm, 0.0);
-  std::vector<int> colinfo(nqm, 0), rowinfo(nvm, 0);
-  int nfloat = 0, float_qs[4] = {0, 0, 0, 0}, float_vs[4] = {0, 0, 0, 0};
-  for (int b = 0; b < nb; ++b) {
-    const int qs = m->qstart[b], vs = m->vstart[b], jt = m->jtype[b];
-    if (jt == IDTO_JOINT_REVOLUTE || jt == IDTO_JOINT_PRISMATIC) {
-      npc[(size_t)qs * nvm + vs] = 1.0; colinfo[qs] = vs | 1 << 16; rowinfo[vs] = qs | 1 << 16;
-    } else if (jt == IDTO_JOINT_PLANAR) {
-      for (int kq = 0; kq < 3; ++kq) {
-        npc[(size_t)(qs + kq) * nvm + vs + kq] = 1.0; colinfo[qs + kq] = (vs + kq) | 1 << 16; rowinfo[vs + kq] = (qs + kq) | 1 << 16;
-      }
-    } else {
-      for (int r = 0; r < 3; ++r)
-        for (int cq = 0; cq < 4; ++cq) npc[(size_t)(qs + cq) * nvm + vs + r] = std::numeric_limits<double>::quiet_NaN();
-      for (int kq = 0; kq < 4; ++kq) colinfo[qs + kq] = vs | 3 << 16;
-      for (int r = 0; r < 3; ++r) rowinfo[vs + r] = qs | 4 << 16;
-      for (int kq = 0; kq < 3; ++kq) {
-        npc[(size_t)(qs + 4 + kq) * nvm + vs + 3 + kq] = 1.0;
-        colinfo[qs + 4 + kq] = (vs + 3 + kq) | 1 << 16; rowinfo[vs + 3 + kq] = (qs + 4 + kq) | 1 << 16;
-      }
-      if (nfloat >= 0 && nfloat < 4) { float_qs[nfloat] = qs; float_vs[nfloat] = vs; ++nfloat; }
-      else nfloat = -1;
-    }
-  }
-  const size_t o_npc = addd(npc.data(), npc.size());
-  // ---- id_fast.h: does the model have one of the instantiated tree shapes?  If so, gather one record of
-  // constants per (path, slot) and per contact pair in the order id_eval_fast walks them.
-  int fast_shape = 0, f_maxpp = 1;
-  size_t o_fbody = 0, o_fcbody = 0, o_fpairs = 0, fast_lo = 0;
-  std::vector<int> fseg(1, 0);
-  {
-    const int cbody = m->common_body;
-    bool ok = true;
-    for (int p = 0; p < K; ++p) ok = ok && nchain[p] == maxc;
-    const int cj = cbody >= 0 ? m->jtype[cbody] : -1;
-    if (cbody >= 0 && cj != IDTO_JOINT_FLOATING) ok = false;
-    if (shared) ok = false;   // (every shape's pair records are per path: a model with shared pairs has none of them)
-    if (nstem > 1) ok = false;   // (... and no shape has a stem below its common body)
-    int j0 = -1, k0 = -1, w2 = -1;   // w2: a later slot of the (single) path that hangs off the world again (the spinner)
-    for (int p = 0; p < K && ok; ++p)
-      for (int s = 0; s < maxc; ++s) {
-        const int b = chain[(size_t)p * IDTO_MAX_CHAIN + s], jt = m->jtype[b], kd = pkind[(size_t)p * IDTO_MAX_CHAIN + s];
-        if (s == 0) {
-          if (p == 0) { j0 = jt; k0 = kd; }
-          if (jt != j0 || kd != k0) ok = false;
-        } else if (jt == IDTO_JOINT_REVOLUTE && kd == PK_WORLD && K == 1 && w2 < 0) {
-          w2 = s;
-        } else if (jt != IDTO_JOINT_REVOLUTE || kd != PK_PREV) {
-          ok = false;
-        }
-      }
-    if (ok) {
-      if (w2 >= 0) { if (w2 == 2 && maxc == 3 && K == 1 && cj == -1 && j0 == IDTO_JOINT_REVOLUTE && k0 == PK_WORLD) fast_shape = 5; }   // spinner
-      else if (maxc == 2 && K == 1 && cj == -1 && j0 == IDTO_JOINT_REVOLUTE && k0 == PK_WORLD) fast_shape = 1;   // acrobot
-      else if (maxc == 3 && K == 1 && cj == -1 && j0 == IDTO_JOINT_PLANAR && k0 == PK_WORLD) fast_shape = 2;     // hopper
-      else if (maxc == 3 && K == 4 && cj == IDTO_JOINT_FLOATING && j0 == IDTO_JOINT_REVOLUTE && k0 == PK_COMMON) fast_shape = 3;   // mini_cheetah
-      else if (maxc == 4 && K == 4 && cj == IDTO_JOINT_FLOATING && j0 == IDTO_JOINT_REVOLUTE && k0 == PK_WORLD) fast_shape = 4;    // allegro_hand + ball
-      // (shapes 1 - 5 apply gravity to every body: a model with a body switched off is theirs only through id_eval)
-      if (!all_gravity) fast_shape = 0;
-      // a free object + one arm of seven revolute bodies off the world, any gravity switches (the Jaco examples)
-      if (maxc == 7 && K == 1 && cj == IDTO_JOINT_FLOATING && j0 == IDTO_JOINT_REVOLUTE && k0 == PK_WORLD && w2 < 0)
-        fast_shape = 6;
-      // (id_fast.h's pair code has no capsule reduction: a model with a capsule is id_eval's)
-      if (capsules) fast_shape = 0;
-    }
-    // processing order of a path's pairs: [pairs without a chain body that come first | slot 0 | ... | slot maxc-1 |
-    // the other pairs without a chain body].  The sums that have an order are those onto one chain body (its pairs stay
-    // in list order) and the path's partial sum onto the common body: its pairs must keep their list order too.
-    std::vector<std::vector<int>> order(K);
-    std::vector<int>& segw = fseg;
-    segw.assign((size_t)K * (maxc + 2), 0);
-    for (int p = 0; p < K && fast_shape; ++p) {
-      std::vector<int> mine;
-      for (int j = 0; j < path_npairs[p]; ++j) mine.push_back(path_pairs[(size_t)p * maxpp + j]);
-      int lo_chain_common = 1 << 30, hi_chain_common = -1, last_slot = -1;
-      for (int pi : mine) {
-        const int nchainb = (sa[pi] >= 0) + (sb[pi] >= 0);
-        if (nchainb > 1) {
-          // two chain bodies: slots (w2 - 1, w2) of the spinner's shape only, and slot w2 - 1 has no other pair (the
-          // force on it is taken out of its wrench in one subtraction, as the generic sum fin - (0 + f) is)
-          bool fine = fast_shape == 5 && std::min(sa[pi], sb[pi]) == w2 - 1 && std::max(sa[pi], sb[pi]) == w2;
-          for (int pj : mine) fine = fine && (pj == pi || (sa[pj] != w2 - 1 && sb[pj] != w2 - 1));
-          if (!fine) { fast_shape = 0; break; }
-          continue;
-        }
-        if (nchainb == 1 && (sa[pi] == -1 || sb[pi] == -1)) {
-          const int sl = std::max(sa[pi], sb[pi]);
-          if (sl < last_slot) { fast_shape = 0; break; }   // (slot, index) order != index order on the common body's sum
-          last_slot = sl;
-          lo_chain_common = std::min(lo_chain_common, pi);
-          hi_chain_common = std::max(hi_chain_common, pi);
-        }
-      }
-      if (!fast_shape) break;
-      std::vector<std::vector<int>> groups(maxc + 2);
-      for (int pi : mine) {
-        const int sl = std::max(sa[pi], sb[pi]);
-        if (sl >= 0) { groups[1 + sl].push_back(pi); continue; }
-        const bool touches_common = sa[pi] == -1 || sb[pi] == -1;
-        if (!touches_common || (sa[pi] == -1 && sb[pi] == -1)) { fast_shape = 0; break; }   // (world, world) / (common, common)
-        if (pi < lo_chain_common) groups[0].push_back(pi);
-        else if (pi > hi_chain_common) groups[maxc + 1].push_back(pi);
-        else { fast_shape = 0; break; }
-      }
-      if (!fast_shape) break;
-      for (int gi = 0; gi < maxc + 2; ++gi) {
-        segw[(size_t)p * (maxc + 2) + gi] = (int)order[p].size() | ((int)groups[gi].size() << 16);
-        for (int pi : groups[gi]) order[p].push_back(pi);
-      }
-    }
-    if (fast_shape) {
-      auto ident_mul = [](const double* X, double* out) {   // [I * R | I * p] with the fused forms of dev_math.h
-        static const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        for (int r = 0; r < 3; ++r) {
-          for (int cc = 0; cc < 3; ++cc)
-            out[3 * r + cc] = std::fma(I[3 * r + 2], X[6 + cc], std::fma(I[3 * r + 1], X[3 + cc], I[3 * r] * X[cc]));
-          out[9 + r] = std::fma(I[3 * r + 2], X[11], std::fma(I[3 * r + 1], X[10], I[3 * r] * X[9]));
-        }
-      };
-      auto body_record = [&](int b, bool world, double* rec) {
-        if (world) ident_mul(m->X_PF + (size_t)12 * b, rec + FB_XPF);
-        else std::memcpy(rec + FB_XPF, m->X_PF + (size_t)12 * b, 12 * sizeof(double));
-        std::memcpy(rec + FB_AXIS, m->axis + (size_t)3 * b, 3 * sizeof(double));
-        rec[FB_MASS] = m->mass[b];
-        std::memcpy(rec + FB_COM, m->com + (size_t)3 * b, 3 * sizeof(double));
-        std::memcpy(rec + FB_INERTIA, m->inertia + (size_t)6 * b, 6 * sizeof(double));
-        const int ndof = m->jtype[b] == IDTO_JOINT_FLOATING ? 6 : (m->jtype[b] == IDTO_JOINT_PLANAR ? 3 : 1);
-        for (int d = 0; d < ndof; ++d) rec[FB_DAMP + d] = m->damping[m->vstart[b] + d];
-        const int ix[2] = {m->qstart[b], m->vstart[b]};
-        std::memcpy(rec + FB_IDX, ix, sizeof(ix));
-      };
-      std::vector<double> fb((size_t)K * maxc * FB_STRIDE, 0.0), fc(FB_STRIDE, 0.0);
-      for (int p = 0; p < K; ++p)
-        for (int s = 0; s < maxc; ++s)
-          body_record(chain[(size_t)p * IDTO_MAX_CHAIN + s], pkind[(size_t)p * IDTO_MAX_CHAIN + s] == PK_WORLD,
-                      fb.data() + ((size_t)p * maxc + s) * FB_STRIDE);
-      if (cbody >= 0) body_record(cbody, true, fc.data());
-      for (int p = 0; p < K; ++p) f_maxpp = std::max(f_maxpp, (int)order[p].size());
-      std::vector<double> fp((size_t)K * f_maxpp * FP_STRIDE, 0.0);
-      for (int p = 0; p < K; ++p)
-        for (size_t j = 0; j < order[p].size(); ++j) {
-          const int pi = order[p][j], ga = m->pair_a[pi], gb = m->pair_b[pi];
-          double* rec = fp.data() + ((size_t)p * f_maxpp + j) * FP_STRIDE;
-          // C: the chain body of the pair's group, or the common body for a pair without one; the other body is
-          // the common one or the world
-          const bool a_chain = sa[pi] >= 0, b_chain = sb[pi] >= 0;
-          // (two chain bodies - the spinner's shape: C is the body of the later slot, the other one is handed to
-          // pair_eval where the common body goes)
-          const bool cia = (a_chain && b_chain) ? sa[pi] > sb[pi] : (a_chain || (!b_chain && sa[pi] == -1));
-          const int gc = cia ? ga : gb, go = cia ? gb : ga, so = cia ? sb[pi] : sa[pi];
-          const int info[4] = {m->geom_type[gc], m->geom_type[go], cia ? 1 : 0, (so == -1 || so >= 0) ? 1 : 0};
-          std::memcpy(rec + FP_INFO, info, sizeof(info));
-          std::memcpy(rec + FP_XC, m->geom_X + (size_t)12 * gc, 12 * sizeof(double));
-          std::memcpy(rec + FP_SC, m->geom_size + (size_t)3 * gc, 3 * sizeof(double));
-          if (so == -2) {   // world: [I R | 0 + I p], the expressions id_eval.h evaluates for a world-fixed geometry
-            ident_mul(m->geom_X + (size_t)12 * go, rec + FP_XO);
-            for (int e = 0; e < 3; ++e) rec[FP_XO + 9 + e] = 0.0 + rec[FP_XO + 9 + e];
-          } else {
-            std::memcpy(rec + FP_XO, m->geom_X + (size_t)12 * go, 12 * sizeof(double));
-          }
-          std::memcpy(rec + FP_SO, m->geom_size + (size_t)3 * go, 3 * sizeof(double));
-        }
-      o_fbody = addd(fb.data(), fb.size());
-      o_fcbody = addd(fc.data(), fc.size());
-      o_fpairs = addd(fp.data(), fp.size());
-    }
-    // the int tables, those fd_kernel needs beside the gathered records first: with a fast shape it stages only
-    // [fast_lo, fast_lo + fast_n) of the blob in LDS
-    fast_lo = fast_shape ? o_fbody : 0;
-  }
-  const size_t i_jt = addi(m->jtype, nb), i_qs = addi(m->qstart, nb), i_vs = addi(m->vstart, nb);
-  const size_t i_colinfo = addi(colinfo.data(), colinfo.size()), i_rowinfo = addi(rowinfo.data(), rowinfo.size());
-  const size_t i_fseg = addi(fseg.data(), fseg.size());
-  const size_t i_fast_end = ints.size();
-  const size_t i_par = addi(m->parent, nb), i_gt = addi(m->geom_type, m->ngeoms), i_ch = addi(chain.data(), chain.size()),
-               i_nch = addi(nchain.data(), nchain.size()), i_pk = addi(pkind.data(), pkind.size()),
-               i_pnp = addi(path_npairs.data(), path_npairs.size()), i_pp = addi(path_pairs.data(), path_pairs.size()),
-               i_ga = addi(m->pair_a, m->npairs), i_gb = addi(m->pair_b, m->npairs), i_sa = addi(sa.data(), sa.size()),
-               i_sb = addi(sb.data(), sb.size());
-  // (the exchange tables only where there are shared pairs: other models stage the blob they staged before)
-  const size_t i_xrec = xtab ? addi(xrec.data(), xrec.size()) : i_par, i_xa = xtab ? addi(pair_xa.data(), pair_xa.size()) : i_par,
-               i_xb = xtab ? addi(pair_xb.data(), pair_xb.size()) : i_par;
-  const size_t i_stem = nstem > 1 ? addi(stem_tab.data(), stem_tab.size()) : i_par;
-  const size_t nd = dbl.size(), ni = ints.size();
-  std::vector<double> blob(nd + (ni + 1) / 2 + 1, 0.0);
-  std::memcpy(blob.data(), dbl.data(), nd * sizeof(double));
-  std::memcpy(blob.data() + nd, ints.data(), ni * sizeof(int));
+// The model tables as the device sees them: the blob that host/model_tables.cc built, uploaded, and DevModel's pointers
+// into it.  (Every check of the model has been made by then, on the host's tables.)
+int UploadModel(idto_hip_ctx* c, const idto_model_t* m, const idto_host::ModelTables& t) {
   double* bd = nullptr;
-  if (Upload(c, blob.data(), blob.size(), &bd)) return -2;
-  const int* bi = reinterpret_cast<const int*>(bd + nd);
-  M.blob = bd; M.blob_n = (int)blob.size();
-  M.X_PF = bd + o_XPF; M.axis = bd + o_axis; M.mass = bd + o_mass; M.com = bd + o_com; M.inertia = bd + o_in;
-  M.damping = bd + o_damp; M.geom_X = bd + o_gX; M.geom_size = bd + o_gs;
-  M.parent = bi + i_par; M.jtype = bi + i_jt; M.qstart = bi + i_qs; M.vstart = bi + i_vs; M.geom_type = bi + i_gt;
-  M.chain = bi + i_ch; M.nchain = bi + i_nch; M.pkind = bi + i_pk; M.path_npairs = bi + i_pnp; M.path_pairs = bi + i_pp;
-  M.pair_ga = bi + i_ga; M.pair_gb = bi + i_gb; M.pair_sa = bi + i_sa; M.pair_sb = bi + i_sb;
-  M.nfloat = nfloat;
-  for (int i = 0; i < 4; ++i) { M.float_qs[i] = float_qs[i]; M.float_vs[i] = float_vs[i]; }
-  M.nplus_const = bd + o_npc; M.colinfo = bi + i_colinfo; M.rowinfo = bi + i_rowinfo;
-  M.fast_shape = fast_shape; M.f_maxpp = f_maxpp;
-  M.fast_lo = (int)fast_lo; M.fast_n = (int)(nd + (i_fast_end + 1) / 2 - fast_lo);
-  M.f_body = bd + o_fbody; M.f_cbody = bd + o_fcbody; M.f_pairs = bd + o_fpairs; M.f_seg = bi + i_fseg;
-  M.nxb = nxb; M.xrec = bi + i_xrec; M.pair_xa = bi + i_xa; M.pair_xb = bi + i_xb;
-  M.stem = bi + i_stem;
+  if (Upload(c, t.blob.data(), t.blob.size(), &bd)) return -2;
+  const int* bi = reinterpret_cast<const int*>(bd);
+  DevModel& M = c->M;
+  M.blob = bd; M.blob_n = (int)t.blob.size();
+#define X(name) M.name = bd + t.at.name;
+  IDTO_MODEL_DOUBLE_TABLES(X)
+#undef X
+#define X(name) M.name = bi + t.at.name;
+  IDTO_MODEL_INT_TABLES(X)
+#undef X
+  M.nb = m->nbodies; M.nq = m->nq; M.nv = m->nv; M.npaths = m->npaths; M.common_body = m->common_body;
+  M.ngeoms = m->ngeoms; M.npairs = m->npairs; M.maxpp = t.maxpp;
+  for (int i = 0; i < 3; ++i) M.gravity[i] = m->gravity[i];
+  M.nfloat = t.nfloat;
+  for (int i = 0; i < 4; ++i) { M.float_qs[i] = t.float_qs[i]; M.float_vs[i] = t.float_vs[i]; }
+  M.fast_shape = t.fast_shape; M.fast_lo = t.fast_lo; M.fast_n = t.fast_n; M.f_maxpp = t.f_maxpp;
+  M.gslots = t.gslots; M.gcommon = t.gcommon; M.gstem = t.gstem; M.nxb = t.nxb; M.nstem = t.nstem;
+  c->maxc = t.maxc; c->capsules = t.capsules;
   return 0;
 }
 
@@ -1107,8 +698,8 @@ int idto_hip_create(const idto_model_t* model, const idto_problem_t* problem, co
 int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* problems, const idto_contact_params_t* contact,
                           int device, int batch, idto_hip_ctx** out) {
   *out = nullptr;
-  if (int rc = CheckGeometry(model)) return rc;
-  if (int rc = CheckStem(model)) return rc;
+  idto_host::ModelTables tables;   // (every refusal of a model is made here: the same with or without a GPU)
+  if (int rc = idto_host::BuildModelTables(model, &tables, &g_err)) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
     g_err = "no HIP device available (the product path has no CPU fallback)";
@@ -1130,7 +721,7 @@ int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* probl
   c->nb = model->nbodies; c->nq = model->nq; c->nv = model->nv; c->N = problem->num_steps;
   c->dt = problem->time_step; c->npaths = model->npaths;
   const int nq = c->nq, nv = c->nv, N = c->N;
-  int rc = BuildModel(c, model);
+  int rc = UploadModel(c, model, tables);
   if (rc) { idto_hip_destroy(c); return rc; }
   if (batch > 1) {
     c->host_model = std::make_unique<HostModelCopy>();

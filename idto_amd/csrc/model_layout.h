@@ -1,0 +1,49 @@
+// model_layout.h — what the host's table builder (host/model_tables.cc) and the kernels agree on: the codes in the model
+// tables, the layout of id_fast.h's gathered records, and the instantiated tree shapes.  Constants only: no device code.
+#pragma once
+
+#include "idto_model.h"
+
+namespace idto_dev {
+
+// DevModel::pkind: what a chain slot's body hangs off
+enum { PK_WORLD = 0, PK_COMMON = 1, PK_PREV = 2 };
+
+// id_fast.h's record of one body (doubles); FB_IDX holds {qstart, vstart} as two ints
+enum { FB_XPF = 0, FB_AXIS = 12, FB_MASS = 15, FB_COM = 16, FB_INERTIA = 19, FB_DAMP = 25, FB_IDX = 31, FB_STRIDE = 34 };
+// record of one contact pair; FP_INFO holds {type on C, type on the other body, C is the pair's A, the other body is
+// the common one} as four ints.
+// XC, SC: geometry frame and size on C (the chain slot of the pair's group; the common body for a pair without a
+// chain body); XO, SO: on the other body - for the world [I R | 0 + I p], formed on the host
+enum { FP_INFO = 0, FP_XC = 2, FP_SC = 14, FP_XO = 17, FP_SO = 29, FP_STRIDE = 34 };
+
+// The instantiated tree shapes of id_fast.h (DevModel::fast_shape = 1 + the row; 0 = any model: id_eval<MAXC>).  A model
+// has a shape when every path has MAXC bodies, there are NP paths, the common body's joint is CJ (-1: no common body),
+// slot 0 of every path has joint J0 and parent kind K0, and the later slots are revolute on the previous one - but for
+// slot W2 (-1: none) of a single path, which hangs off the world again.  On top of the tuple:
+//   - GS: bodies whose weight is switched off are allowed; a shape without it is chosen only when every body has gravity
+//   - a capsule clears the shape (id_fast.h's pair code has no capsule reduction)
+//   - shared pairs or a stem below the common body clear it (the pair records are per path; no shape has a stem)
+// KC: the chain bound fd_kernel<KC, shape> is instantiated with (fd_launch.hip).
+struct TreeShape { int MAXC, NP, CJ, J0, K0, W2, GS, KC; };
+constexpr TreeShape kTreeShapes[] = {
+    {2, 1, -1, IDTO_JOINT_REVOLUTE, PK_WORLD, -1, 0, 2},                     // 1 acrobot
+    {3, 1, -1, IDTO_JOINT_PLANAR, PK_WORLD, -1, 0, 3},                       // 2 hopper
+    {3, 4, IDTO_JOINT_FLOATING, IDTO_JOINT_REVOLUTE, PK_COMMON, -1, 0, 3},   // 3 mini_cheetah
+    {4, 4, IDTO_JOINT_FLOATING, IDTO_JOINT_REVOLUTE, PK_WORLD, -1, 0, 4},    // 4 allegro_hand + ball
+    {3, 1, -1, IDTO_JOINT_REVOLUTE, PK_WORLD, 2, 0, 3},                      // 5 spinner: two-link finger + the spinner, off the world
+    {7, 1, IDTO_JOINT_FLOATING, IDTO_JOINT_REVOLUTE, PK_WORLD, -1, 1, 8},    // 6 a free object + an arm of seven revolute bodies off the world (jaco, jaco_ball)
+};
+constexpr int kNumTreeShapes = sizeof(kTreeShapes) / sizeof(kTreeShapes[0]);
+// Not tree shapes: SHAPE_XCH selects the generic evaluation with the exchange area of shared pairs (id_eval<MAXC, true>,
+// models with DevModel::nxb > 0; DevModel::fast_shape stays 0 for them)
+constexpr int SHAPE_XCH = kNumTreeShapes + 1;
+// ... and SHAPE_STEM the one that also walks a stem below the common body (id_eval<MAXC, true, true>, DevModel::nstem > 1): its
+// exchange area has the stem's blocks behind the records (id_eval.h xch_eval_doubles)
+constexpr int SHAPE_STEM = kNumTreeShapes + 2;
+// (both serve any chain length: KC = 8)
+constexpr TreeShape tree_shape(int shape) {
+  return shape >= 1 && shape <= kNumTreeShapes ? kTreeShapes[shape - 1] : TreeShape{0, 1, -1, 0, 0, -1, 0, 8};
+}
+
+}  // namespace idto_dev

@@ -1,6 +1,6 @@
 """The straight-line inverse-dynamics evaluation of csrc/id_fast.h against the generic id_eval<MAXC> it specialises.
 
-BuildModel (idto_hip.hip) recognises the tree shapes that are instantiated - acrobot, hopper, mini_cheetah, allegro_hand
+BuildModelTables (host/model_tables.cc) recognises the tree shapes that are instantiated - acrobot, hopper, mini_cheetah, allegro_hand
 (+ ball), spinner (its third body hangs off the world again and its pair touches two chain bodies: shape 5) - and
 fd_kernel<MAXC, SHAPE> then evaluates with compile-time joint types, host-gathered records, contact pairs inside the
 forward recursion, inputs formed by the consuming lane.  Same operations in the same order: every output of the
@@ -82,7 +82,7 @@ def test_a_pair_order_the_fast_walk_cannot_keep_falls_back_to_the_generic_evalua
     the list's order (id_fast.h).  A cheetah whose body-ground pair is listed BETWEEN two pairs that touch the body through
     different feet of one path cannot be walked that way - here: all feet assigned to path 0's list is not possible, so the
     model is altered the other way: the pair list is reversed, which puts (foot, ground) pairs before (body, foot) pairs of
-    a path and the body-ground pair first; BuildModel must either keep a valid walk or fall back, and the results must be
+    a path and the body-ground pair first; BuildModelTables must either keep a valid walk or fall back, and the results must be
     those of the generic evaluation."""
     cfg, model = load_config("mini_cheetah"), load_model("mini_cheetah")
     import copy

@@ -8,6 +8,7 @@ import copy
 import numpy as np
 
 from idto_amd.model import GEOM_TYPES
+from oracle_lib import Oracle
 
 SPHERE, BOX, CAPSULE = GEOM_TYPES["sphere"], GEOM_TYPES["box"], GEOM_TYPES["capsule"]
 PARALLEL = 1e-10   # 1 - dot(u1, u2)^2 at or below which two segments count as parallel
@@ -104,3 +105,39 @@ def without_geometry(model):
     m.geom_body, m.geom_type, m.geom_size, m.geom_X = [], [], np.zeros((0, 3)), np.zeros((0, 12))
     m.pair_a, m.pair_b, m.pair_path = [], [], []
     return m.normalize()
+
+
+def frozen_expectation(model, prob, sp, q):
+    """v, a, tau and the three dtau/dq blocks of forward differences (oracle/traj_opt.h, TO.cc:504-561) with every
+    inverse dynamics evaluated by the oracle on the sphere model frozen at that evaluation's configuration"""
+    N, nq, dt = prob.num_steps, model.nq, prob.time_step
+    base = Oracle(without_geometry(model), prob, sp)
+    v, a, tau_free, _ = base.eval_traj(q)
+    frozen = {}
+
+    def tau_at(qc, vc, ac):
+        key = qc.tobytes()
+        if key not in frozen:
+            frozen[key] = Oracle(frozen_sphere_model(model, base.body_poses(qc)), prob, sp)
+        return frozen[key].inverse_dynamics(qc, vc, ac)
+
+    tau = np.array([tau_at(q[t + 1], v[t + 1], a[t]) for t in range(N)])
+    P = base.eval_partials(q)   # (dtau_dqm: the mass matrix, no contact)
+    dqp, dqt = np.zeros_like(P["dtau_dqp"]), np.zeros_like(P["dtau_dqt"])
+    Np = [base.nplus(q[t]) for t in range(N + 1)]
+    eps = np.sqrt(np.finfo(float).eps)
+    for t in range(1, N + 1):
+        for i in range(nq):
+            qi = q[t, i]
+            dq = eps * max(1.0, abs(qi))
+            dq = (qi + dq) - qi
+            dv = dq / dt
+            da = dv / dt
+            qe = q[t].copy()
+            qe[i] = qi + dq
+            dqp[t - 1][:, i] = (tau_at(qe, v[t] + dv * Np[t][:, i], a[t - 1] + da * Np[t][:, i]) - tau[t - 1]) / dq
+            if t < N:
+                vp = v[t + 1] - dv * Np[t + 1][:, i]
+                ap = a[t] - da * (Np[t + 1][:, i] + Np[t][:, i])
+                dqt[t][:, i] = (tau_at(q[t + 1], vp, ap) - tau[t]) / dq
+    return v, a, tau, tau_free, dict(dtau_dqp=dqp, dtau_dqt=dqt, dtau_dqm=P["dtau_dqm"])

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import capsule_ref as cr
+from capsule_ref import frozen_expectation  # noqa: F401  (test_gpu_stem.py imports it from here)
 from idto_amd import hip
 from idto_amd.model import load_model
 from idto_amd.optimizer import TrajectoryOptimizer, TrajectoryOptimizerSolution, TrajectoryOptimizerStats
@@ -115,42 +116,6 @@ def test_zero_length_capsules_are_spheres(name, method):
 
 
 # ---- capsules with length, against the oracle on frozen sphere models
-def frozen_expectation(model, prob, sp, q):
-    """v, a, tau and the three dtau/dq blocks of forward differences (oracle/traj_opt.h, TO.cc:504-561) with every
-    inverse dynamics evaluated by the oracle on the sphere model frozen at that evaluation's configuration"""
-    N, nq, dt = prob.num_steps, model.nq, prob.time_step
-    base = Oracle(cr.without_geometry(model), prob, sp)
-    v, a, tau_free, _ = base.eval_traj(q)
-    frozen = {}
-
-    def tau_at(qc, vc, ac):
-        key = qc.tobytes()
-        if key not in frozen:
-            frozen[key] = Oracle(cr.frozen_sphere_model(model, base.body_poses(qc)), prob, sp)
-        return frozen[key].inverse_dynamics(qc, vc, ac)
-
-    tau = np.array([tau_at(q[t + 1], v[t + 1], a[t]) for t in range(N)])
-    P = base.eval_partials(q)   # (dtau_dqm: the mass matrix, no contact)
-    dqp, dqt = np.zeros_like(P["dtau_dqp"]), np.zeros_like(P["dtau_dqt"])
-    Np = [base.nplus(q[t]) for t in range(N + 1)]
-    eps = np.sqrt(np.finfo(float).eps)
-    for t in range(1, N + 1):
-        for i in range(nq):
-            qi = q[t, i]
-            dq = eps * max(1.0, abs(qi))
-            dq = (qi + dq) - qi
-            dv = dq / dt
-            da = dv / dt
-            qe = q[t].copy()
-            qe[i] = qi + dq
-            dqp[t - 1][:, i] = (tau_at(qe, v[t] + dv * Np[t][:, i], a[t - 1] + da * Np[t][:, i]) - tau[t - 1]) / dq
-            if t < N:
-                vp = v[t + 1] - dv * Np[t + 1][:, i]
-                ap = a[t] - da * (Np[t + 1][:, i] + Np[t][:, i])
-                dqt[t][:, i] = (tau_at(q[t + 1], vp, ap) - tau[t]) / dq
-    return v, a, tau, tau_free, dict(dtau_dqp=dqp, dtau_dqt=dqt, dtau_dqm=P["dtau_dqm"])
-
-
 def hopper_capsule_foot():
     """the hopper with its two foot spheres replaced by one capsule between their centres (axis = the segment, the frame
     turned about it)"""

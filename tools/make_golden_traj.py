@@ -30,6 +30,12 @@ truncation error ~dq |tau''| of the reference's forward differences on the stiff
 dtau_dqm, which is analytic in the reference, agrees to 1e-14).
 
 Run from the repo root:  python tools/make_golden_traj.py   (a few minutes)
+                         python tools/make_golden_traj.py <name> ...   only these; besides the three BASELINE models
+                             <name> may be dual_jaco, spinner_capsule or punyo: the example model as it is (capsules with
+                             length by tools/golden_examples.py, per-body gravity switch, shared pairs, stem)
+                             -> tests/golden/examples/traj_<name>.json, then run tools/measure_golden_examples.py
+
+Nothing here assumes that the common body hangs off the world or that a pair's two bodies lie on one path.
 """
 import json
 import os
@@ -41,9 +47,11 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 from idto_amd.model import load_model  # noqa: E402
 from idto_amd.problem import load_config, make_problem, synthetic_trajectory  # noqa: E402
 
+import golden_examples as ge  # noqa: E402
+
 LD = np.longdouble
 REV, PRI, PLA, FLO = 0, 1, 2, 3
-SPHERE, BOX = 0, 1
+SPHERE, BOX, CAPSULE = 0, 1, 2
 
 
 def rot_axis(axis, ang):
@@ -85,6 +93,7 @@ class Mech:
         eps = np.sqrt(LD(np.finfo(float).eps))
         s, k = LD(contact["smoothing_factor"]), LD(contact["contact_stiffness"])
         self.threshold = -s * np.log(np.exp(eps / (s * k)) - 1)   # TO.cc:266-269
+        self.margins = None   # a golden_examples.Margins while the trajectory's own configurations are looked at
 
     def fk(self, q):
         m, X = self.m, []
@@ -181,6 +190,11 @@ class Mech:
         XA, XB = pose(ga), pose(gb)
         tA, tB = int(m.geom_type[ga]), int(m.geom_type[gb])
         sA, sB = np.asarray(m.geom_size[ga], LD), np.asarray(m.geom_size[gb], LD)
+        if CAPSULE in (tA, tB):   # a capsule side: the sphere of its radius at the substitute centre (include/idto_model.h)
+            cA, cB = ge.reduce_capsules(tA, XA, sA, int(m.geom_body[ga]), tB, XB, sB, int(m.geom_body[gb]),
+                                        self.threshold, self.margins)
+            XA, XB = hom(XA[:3, :3], cA), hom(XB[:3, :3], cB)
+            tA, tB = (SPHERE if tA == CAPSULE else tA), (SPHERE if tB == CAPSULE else tB)
         if tA == SPHERE and tB == SPHERE:
             d = XB[:3, 3] - XA[:3, 3]
             dist = np.sqrt(d @ d)
@@ -249,7 +263,8 @@ class Mech:
         return self.jacobians(np.asarray(q, LD))
 
     def inverse_dynamics(self, q, v, a, prep=None):
-        """tau = sum_i J_i^T (inertial wrench - gravity) + damping v - contact  (Kane)"""
+        """tau = sum_i J_i^T (inertial wrench - gravity) + damping v - contact  (Kane); a body whose gravity_enabled
+        entry is 0 contributes m a_cm without the - m g (include/idto_model.h)"""
         m = self.m
         q, v, a = np.asarray(q, LD), np.asarray(v, LD), np.asarray(a, LD)
         X, Jo, Jw = prep if prep is not None else self.jacobians(q)
@@ -267,7 +282,7 @@ class Mech:
             a_c = a_o + np.cross(alp, c) + np.cross(w, np.cross(w, c))
             K = np.array([[0, -c[2], c[1]], [c[2], 0, -c[0]], [-c[1], c[0], 0]], LD)
             Jc = Jo[i] - K @ Jw[i]
-            tau += Jc.T @ (LD(m.mass[i]) * (a_c - g)) + Jw[i].T @ (IW @ alp + np.cross(w, IW @ w))
+            tau += Jc.T @ (LD(m.mass[i]) * (a_c - (g if int(m.gravity_enabled[i]) else 0 * g))) + Jw[i].T @ (IW @ alp + np.cross(w, IW @ w))
         tau += np.asarray(m.damping, LD) * v
         if m.npairs:
             tau -= self.contact_tau(q, v, X, Jo, Jw)
@@ -297,13 +312,15 @@ def richardson(f, h):
     return (4 * d2 - d1) / 3
 
 
-def trajectory_golden(name, N, seed, lower, step):
-    cfg, model = load_config(name), load_model(name)
+def trajectory_golden(name, N, seed, lower, step, example=None):
+    """example: (model, cfg, q[N + 1]) of an example model instead of the BASELINE model `name` on its synthetic
+    trajectory"""
+    cfg, model = (load_config(name), load_model(name)) if example is None else (example[1], example[0])
     prob, sp, _ = make_problem(cfg, model, num_steps=N)
     contact = {k: float(getattr(sp, k)) for k in ("contact_stiffness", "dissipation_velocity", "stiction_velocity",
                                                   "friction_coefficient", "smoothing_factor")}
     mech = Mech(model, contact)
-    q = np.asarray(synthetic_trajectory(cfg, model, N, seed=seed, lower=lower), LD)
+    q = np.asarray(synthetic_trajectory(cfg, model, N, seed=seed, lower=lower) if example is None else example[2], LD)
     nq, nv, dt = model.nq, model.nv, LD(prob.time_step)
     Np = [nplus(model, q[t]) for t in range(N + 1)]
     v = [np.asarray(prob.v_init, LD)] + [Np[t] @ (q[t] - q[t - 1]) / dt for t in range(1, N + 1)]
@@ -361,12 +378,53 @@ def trajectory_golden(name, N, seed, lower, step):
                 dtau_dqm=f(M), gradient=f(g), H_A=f(A), H_B=f(B), H_C=f(C))
 
 
+def example_golden(name, step):
+    """tests/golden/examples/traj_<name>.json, N = 3: the example model as it is on a trajectory of the tests' helpers
+    with pairs in penetration; the margins of golden_examples hold at every time step"""
+    from make_golden import Kane   # (double precision: only for the scan that finds dual_jaco's touching hands)
+    model, cfg = ge.example(name)
+    contact = ge.contact_parameters(cfg, model)
+    shared = set(ge.shared_pairs(model))
+    kane = Kane(model, contact)
+    source, q = ge.traj_states(name, model, cfg, lambda qt, vt: np.abs(kane.contact_tau(qt, vt, only=shared)).max())
+    N = 3
+    assert q.shape == (N + 1, model.nq)
+    mech = Mech(model, contact)
+    mech.margins = ge.Margins()
+    inside = set()   # pairs in penetration at a time step whose tau is evaluated
+    for t in range(1, N + 1):
+        X = mech.fk(np.asarray(q[t], LD))
+        inside |= {k for k in range(model.npairs)
+                   if mech.signed_distance(int(model.pair_a[k]), int(model.pair_b[k]), X)[0] < 0}
+    margins = mech.margins.as_dict()
+    assert inside, "no pair in penetration"
+    if name == "dual_jaco":
+        assert inside & shared, "no shared pair in penetration"
+    if name == "punyo":
+        assert any(ge.punyo_class(model, k) == "arm-ball" for k in inside), "no arm-ball pair in penetration"
+        assert inside & set(ge.stem_pairs(model)), "no pair on a stem body in penetration"
+    fix = trajectory_golden(name, N, None, None, step, example=(model, cfg, q))
+    del fix["seed"], fix["lower"]
+    # the tolerance of the derivatives is not fixed in advance: tools/measure_golden_examples.py measures the
+    # disagreement with the oracle's forward differences on the CPU and stores both numbers
+    fix.update(model_file=name + ".model", source=source, margins=margins, penetrating_pairs=sorted(inside),
+               generator="tools/make_golden_traj.py " + name, observed_derivatives=None, tolerance_derivatives=None)
+    return fix
+
+
+EXAMPLE_CASES = {"dual_jaco": 1e-6, "spinner_capsule": 1e-6, "punyo": 1e-6}
 CASES = [("hopper", 3, 21, 0.02, 1e-5), ("mini_cheetah", 3, 22, 0.02, 1e-5), ("allegro_hand", 3, 23, 0.0, 1e-6)]
 
 
 def main():
     outdir = os.path.join(os.path.dirname(__file__), "..", "tests", "golden")
     only = sys.argv[1:]
+    for name in only:
+        if name in EXAMPLE_CASES:
+            fix = example_golden(name, EXAMPLE_CASES[name])
+            with open(os.path.join(ge.EXAMPLES, f"traj_{name}.json"), "w") as f:
+                json.dump(fix, f)
+            print(name, "written: |tau|", np.abs(fix["tau"]).max(), "|P|", np.abs(fix["dtau_dqp"]).max(), fix["margins"])
     for name, N, seed, lower, step in CASES:
         if only and name not in only:
             continue

@@ -23,6 +23,7 @@
 
 #include "kernels.h"
 #include "penta_band.h"
+#include "solver_layout.h"
 
 namespace idto_dev {
 
@@ -58,17 +59,7 @@ struct SmallArgs {
   // The whole iteration is ONE launch.
   TrIterArgs I;
 };
-// LDS of the folded iteration (doubles); it has to fit the band solver's carve-up (the host checks)
-__host__ __device__ constexpr int gn_small_fold_doubles(int N, int K) { return 26 * (N + 1) * K + 18 * (N + 1) + 32; }
-
-// doubles of dynamic LDS behind the band solver's carve-up (gn_small_kernel's own arrays, in its order)
-__host__ __device__ inline int gn_small_doubles(int N, int K, int fast_n, int KK = 0) {
-  const int E = 1 + 3 * K;
-  if (KK > K) return gn_small_doubles(N, K, fast_n) + 3 * (N + 1) * KK * KK + (N + 1) * KK;
-  return 2 * (N + 1) * K + N * K + 3 * N * E + N * E * K + K * K + 3 * N * K * K + 5 * K + (K & 1) + fast_n + (fast_n & 1) +
-         3 * (N + 1) * K * K + 3 * (N + 1) * K + 2 * K * K + (K * K & 1) + K + 2 +
-         5 * K + (K & 1) + (3 * N + 2) * (K + 1) + 2 * (N + 1) + 2 + 24;   // (the trust-region loop's cost and decision)
-}
+// (gn_small_doubles, gn_small_fold_doubles: solver_layout.h)
 
 // TR: the instantiation that serves the trust-region loop (T / I / tau_only are looked at); the plain step's has none of that
 // code - with it in, the plain step lost 1.2 us to the register allocation alone (acrobot 20.9 -> 22.2 us).

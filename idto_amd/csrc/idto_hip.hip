@@ -38,6 +38,7 @@
 #include "trust_region.h"
 #include "kkt.h"
 #include "host/model_tables.h"
+#include "host/solver_plan.h"
 
 using namespace idto_dev;
 
@@ -252,14 +253,12 @@ struct idto_hip_ctx {
   bool solver_pipe = true;                // ... with pipelined chains (penta_pipe.h: 5 workgroups) when the block size allows
   BandStageItem* small_stage = nullptr; int small_stage_n = 0, small_stage_N = -1;   // gn_small.h: the solver's staging table for horizon small_stage_N
   int gn_small = 1;                       // option "gn_small": the whole step of a small model in one workgroup (gn_small.h; see SmallEligible)
-  int solver_band = 1;                    // small blocks: the scalar band factorisation in one workgroup (penta_band.h; see BandEligible)
+  int solver_band = 1;                    // small blocks: the scalar band factorisation in one workgroup (penta_band.h; host/solver_plan.cc BandEligible)
   unsigned long long* nd_rowcnt = nullptr; // its per-row release counters, buffers and launch count
   unsigned* asm_ready = nullptr;               // penta_pipe.h PipeAsm: [N + 1][4] epoch words of the assembly inside the solver's launch
   bool tr_conv_on = false;                 // idto_hip_tr_set_convergence
   double tr_conv_tol[6] = {0, 0, 0, 0, 0, 0};
   bool asm_in_solver = true;                  // option "asm_in_solver": idto_hip_gn_step assembles g and H inside the pipelined solver's launch
-  const double* fuse_gate = nullptr;          // ... gated: problems whose word is 0 keep their g and H (idto_hip_tr_solve)
-  bool fuse_asm_next = false;                 // (set by idto_hip_gn_step for the FactorSolve that follows)
   unsigned long long* pipe_rowcnt = nullptr;   // the same for the pipelined variant (its own launch count: the two
   unsigned long long pipe_launches = 0;        // variants release a row with different increments)
   int solver_timeouts = 0;                // launches whose waits between workgroups ran out (FactorStatus)
@@ -366,7 +365,6 @@ struct idto_hip_ctx {
   bool tr_fold = true;                     // option "tr_fold" (0: tr_iter_kernel stays a launch of its own in front of the small models' launch)
   bool kkt_in_asm = true;                  // option "kkt_in_asm" (0: kkt_build_kernel stays a launch of its own behind the assembly)
   bool decide_in_solver = true;            // option "decide_in_solver" (0: cost_kernel stays a launch of its own in front of the pipelined solver's)
-  const TrDecideArgs* fuse_decide = nullptr;   // (during idto_hip_tr_solve's call of the solver) the decision the launch is to make
   double* decide_word = nullptr; unsigned decide_epoch = 0;   // ... and the word it publishes it in (per problem, epoch in every word)
   bool tr_resident_ok = true;              // false once tr_iter_kernel's wait between its workgroups ran out (FactorStatus): idto_hip_tr_solve then refuses
   int ldl_npos = 0;                        // (a KKT context) the solver expects the pivots [ldl_npos, nq) of a block negative
@@ -773,18 +771,19 @@ int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* probl
   const size_t o_K = carve((size_t)(N + 1) * qq, D), o_LU = carve((size_t)(N + 1) * qq, D);
   const size_t o_Y = carve((size_t)(N + 1) * qq, D), o_Z = carve((size_t)(N + 1) * qq, D);
   const size_t o_piv = carve((size_t)(N + 1) * nq, sizeof(int));
-  const size_t o_dbg = carve((size_t)(N + 4) * 8 * 32, D);
-  const size_t o_U = carve((size_t)(N + 1) * 32 * 36, D), o_Hs = carve((size_t)(N + 1) * 32 * 36, D);
-  const size_t o_E = carve((size_t)(N + 1) * 32 * 36, D), o_Ds = carve((size_t)(N + 1) * 32, D);
-  // exchange buffer of the two-sided solver (one right-hand side): 2 augmented blocks + [2][K]
-  c->xch_count = 2 * (size_t)(3 * 32 + 1) * ldl_ks(32) + 2 * 32;
-  const size_t o_xch = carve(2 * c->xch_count, D);   // (two producer / joiner pairs in the nested-dissection kernel)
-  const size_t o_ndcnt = carve(4 * ND_MAXROWS, sizeof(unsigned long long)), o_ndbuf = carve((size_t)nd_layout(32).end, D);
-  const size_t o_pipecnt = carve(4 * ND_MAXROWS, sizeof(unsigned long long));
-  const bool nd_wst_on = nq > 20 && nq <= 32;
-  const size_t o_ndwst = carve(nd_wst_on ? 2 * (size_t)ND_MAXROWS * nd_layout(nq).frow : 1, D);
+  // the solvers' own arrays (host/solver_plan.cc SolverBufferCounts)
+  const idto_host::SolverBuffers sb = idto_host::SolverBufferCounts(nq, N);
+  const size_t o_dbg = carve(sb.dbg, D);
+  const size_t o_U = carve(sb.factors, D), o_Hs = carve(sb.factors, D);
+  const size_t o_E = carve(sb.factors, D), o_Ds = carve(sb.dinv, D);
+  c->xch_count = sb.xch_count;
+  const size_t o_xch = carve(sb.xch, D);
+  const size_t o_ndcnt = carve(sb.rowcnt, sizeof(unsigned long long)), o_ndbuf = carve(sb.nd_buf, D);
+  const size_t o_pipecnt = carve(sb.rowcnt, sizeof(unsigned long long));
+  const bool nd_wst_on = sb.has_wst;
+  const size_t o_ndwst = carve(sb.nd_wst, D);
   const size_t o_asmready = carve(4 * (size_t)(N + 1), sizeof(unsigned));
-  c->flag_count = 16;
+  c->flag_count = sb.flags;
   const size_t o_flags = carve(c->flag_count, sizeof(unsigned)), o_sync = carve(2, sizeof(unsigned long long));
   const size_t nvars = (size_t)(N + 1) * nq;
   const size_t o_trD = carve(nvars, D), o_trg = carve(nvars, D), o_trw = carve(nvars, D), o_trdq = carve(nvars, D),
@@ -889,8 +888,7 @@ int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* probl
   const int max_lds = 160 * 1024;
   // (cost_kernel is a single block holding one column of every cost term; penta_apply_kernel keeps
   // the right-hand side of each of its four wavefronts: both bound the horizon as well)
-  const int Kpad = (nq == 2 || nq == 3 || nq == 5 || nq == 19 || nq == 23) ? nq : (nq <= 8 ? 8 : nq <= 16 ? 16 : nq <= 24 ? 24 : 32);
-  const int apply_lds = 4 * (n * Kpad + 4 * 64 + 2) * (int)sizeof(double);
+  const int apply_lds = idto_host::ApplyLds(n, idto_host::SolverBlockSize(nq));
   if (c->fd_lds > max_lds || c->asm_lds > max_lds || c->penta_lds > max_lds || c->cost_lds > max_lds ||
       apply_lds > max_lds) {
     g_err = "problem too large for the 160 KiB LDS carve-up of the v1 kernels (fd / assemble / solver / cost / "
@@ -901,43 +899,38 @@ int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* probl
   // kernels that need more than the default 64 KiB of dynamic LDS must opt in
   fd_set_max_lds(max_lds);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&assemble_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-#define BAND_ATTR(WM) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&penta_band_kernel<WM>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  BAND_ATTR(6) BAND_ATTR(9) BAND_ATTR(12) BAND_ATTR(15)
+#define MAX_LDS(KERNEL) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+  // (every instantiation of the solver families: solver_layout.h)
+#define BAND_ATTR(WM) MAX_LDS(penta_band_kernel<WM>)
+  IDTO_BAND_KERNELS(BAND_ATTR)
 #undef BAND_ATTR
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_small_kernel<1, 6, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_small_kernel<5, 9, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_small_kernel<1, 6, 256, 6, true>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_small_kernel<5, 9, 256, 9, true>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_small_kernel<1, 6, 256, 9, true>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_small_kernel<5, 9, 256, 12, true>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+#define SMALL_ATTR(SH, WM, WSM, TR) MAX_LDS((gn_small_kernel<SH, WM, 256, WSM, TR>))
+  IDTO_SMALL_KERNELS(SMALL_ATTR)
+#undef SMALL_ATTR
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&penta_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&assemble_diag_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cost_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&assemble_terms_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&constraint_lambda_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-#define APPLY_ATTR(KM) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&penta_apply_kernel<KM, (KM <= 8)>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  APPLY_ATTR(2) APPLY_ATTR(3) APPLY_ATTR(5) APPLY_ATTR(8) APPLY_ATTR(16) APPLY_ATTR(19) APPLY_ATTR(23) APPLY_ATTR(24) APPLY_ATTR(32)
+#define APPLY_ATTR(KM) MAX_LDS((penta_apply_kernel<KM, (KM <= 8)>))
+  IDTO_APPLY_KERNELS(APPLY_ATTR)
 #undef APPLY_ATTR
-#define LDL_ATTR(KM, PD, GW)                                                                   \
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&penta_ldl_kernel<KM, 256, PD, GW>), \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  LDL_ATTR(2, false, 1) LDL_ATTR(3, false, 1) LDL_ATTR(5, false, 1) LDL_ATTR(19, false, 1) LDL_ATTR(23, false, 2)
-  LDL_ATTR(8, true, 1) LDL_ATTR(16, true, 1) LDL_ATTR(24, true, 2) LDL_ATTR(30, true, 2) LDL_ATTR(29, false, 2) LDL_ATTR(4, false, 1) LDL_ATTR(32, true, 3)
+#define LDL_ATTR(KM, PD, GW) MAX_LDS((penta_ldl_kernel<KM, 256, PD, GW>))
+  IDTO_LDL_KERNELS(LDL_ATTR)
 #undef LDL_ATTR
-#define ND_ATTR(KM, PD) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&penta_nd_kernel<KM, PD>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  ND_ATTR(2, false) ND_ATTR(3, false) ND_ATTR(5, false) ND_ATTR(19, false) ND_ATTR(23, false) ND_ATTR(29, false) ND_ATTR(8, false)
+#define ND_ATTR(KM) MAX_LDS((penta_nd_kernel<KM, false>))
+  IDTO_ND_KERNELS(ND_ATTR)
 #undef ND_ATTR
-#define PIPE_ATTR(KM) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&penta_pipe_kernel<KM>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&penta_pipe_kernel<5, true>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&penta_pipe_kernel<19, true>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  PIPE_ATTR(2) PIPE_ATTR(3) PIPE_ATTR(5) PIPE_ATTR(19)
+#define PIPE_ATTR(KM) MAX_LDS(penta_pipe_kernel<KM>)
+#define PIPE_DEC_ATTR(KM) MAX_LDS((penta_pipe_kernel<KM, true>))
+  IDTO_PIPE_DEC_KERNELS(PIPE_DEC_ATTR)
+  IDTO_PIPE_KERNELS(PIPE_ATTR)
 #undef PIPE_ATTR
-#define FUSED_ATTR(MC, KM, PD, GW)                                                                 \
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gn_fused_kernel<MC, KM, PD, GW>),       \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-  FUSED_ATTR(2, 2, false, 1) FUSED_ATTR(3, 3, false, 1) FUSED_ATTR(3, 5, false, 1) FUSED_ATTR(3, 19, false, 1)
-  FUSED_ATTR(4, 23, false, 2)
+#undef PIPE_DEC_ATTR
+#define FUSED_ATTR(MC, KM, PD, GW) MAX_LDS((gn_fused_kernel<MC, KM, PD, GW>))
+  IDTO_FUSED_KERNELS(FUSED_ATTR)
 #undef FUSED_ATTR
+#undef MAX_LDS
   if (const char* e = getenv("IDTO_SOLVER_REFERENCE")) c->reference_solver = (e[0] == '1');
   if (const char* e = getenv("IDTO_TWO_SIDED")) c->two_sided = (e[0] == '1');   // (debugging aids: option defaults)
   if (const char* e = getenv("IDTO_FUSED")) c->fused = (e[0] == '1');
@@ -1185,150 +1178,68 @@ int idto_hip_grad_hess(idto_hip_ctx* c) {
   return TimeEnd(c);
 }
 
-// Rows the fast solver works on.  The assembled Gauss-Newton Hessian has C_0 = I, B_1 = A_2 = 0
-// and g_0 = 0 (q_0 is not a decision variable, TO.cc:1093-1165): block row 0 is decoupled, so the
-// factorisation starts at row 1 (one block row less on the serial chain of the top workgroup)
-// and x_0 = rhs_0.  Bands written into the context behind the API's back get the full system.
-static int SolverFirstRow(const idto_hip_ctx* c) { return (c->h_assembled && c->N >= 2) ? 1 : 0; }
-
-// Geometry of one launch of the banded block LDL^T solver (one right-hand side in the kernel; more
-// go through penta_apply_kernel).
-struct LdlPlan {
-  int r0, n, k, K, gj_waves, lds, m_split;
-  int lds_full;   // the chain code's carve-up with every row of the system (nested dissection, fused launch: their own row counts)
-  size_t qq0;
-};
-static int SolverBlockSize(int k, bool single_rhs_only = false) {
-  // block sizes of the reference's example models are instantiated exactly, others are padded
-  // (30: the factorisation alone - no penta_apply_kernel of that size -, for the KKT systems of kkt.h: allegro's 23 + 6.
-  // The 32 x 32 instantiation needs three elimination wavefronts and spills 378 registers.)
-  if (single_rhs_only && (k == 29 || k == 4)) return k;   // (exact instantiations for the KKT systems of allegro and spinner)
-  if (single_rhs_only && k > 24 && k <= 30) return 30;
-  return (k == 2 || k == 3 || k == 5 || k == 19 || k == 23) ? k : (k <= 8 ? 8 : k <= 16 ? 16 : k <= 24 ? 24 : 32);
+// ---- the banded solvers.  Which kernel serves a system, with which block size, split, grid and LDS, is decided in
+// host/solver_plan.cc (PlanSolve, host-only); the launch functions below fill arguments and launch what the plan names.
+using idto_host::SolverPlan;
+using idto_host::SolveRequest;
+static idto_host::SolverShape ShapeOf(const idto_hip_ctx* c, bool assembled) {
+  idto_host::SolverShape s;
+  s.k = c->nq; s.N = c->N; s.batch = c->batch; s.npos = c->ldl_npos; s.h_assembled = assembled;
+  s.two_sided = c->two_sided; s.solver_nd = c->solver_nd; s.solver_pipe = c->solver_pipe;
+  s.solver_band = c->solver_band; s.nd_min_rows = c->nd_min_rows; s.nd_recursion = c->nd_recursion;
+  s.has_wst = c->nd_wst != nullptr;
+  s.asm_terms_lds = c->asm_terms_lds; s.cost_lds = c->cost_lds;
+  return s;
 }
-static int PlanLdl(idto_hip_ctx* c, bool one_sided, LdlPlan* p) {
-  p->r0 = SolverFirstRow(c);
-  p->n = c->N + 1 - p->r0;
-  p->k = c->nq;
-  p->qq0 = (size_t)p->r0 * p->k * p->k;
-  if (p->k > 32) { g_err = "fast solver supports nq <= 32"; return -1; }
-  p->K = SolverBlockSize(p->k, c->ldl_npos > 0);
-  const int per_wave = 64 - p->K, ncr = 2 * p->K + 1;
-  p->gj_waves = (ncr + per_wave - 1) / per_wave;
-  // two-sided elimination (two workgroups meeting at block rows m, m+1) once the horizon is long
-  // enough to pay for the hand-over
-  p->m_split = (c->two_sided && !one_sided && p->n >= 10) ? (p->n - 1) / 2 : 0;
-  // (a workgroup of the two-sided elimination keeps the right-hand side and rt / x of its own rows only)
-  p->lds = penta_ldl_layout(p->n, p->K, 1, ldl_two_sided_rows(p->n, p->m_split, 1)).end * (int)sizeof(double);
-  p->lds_full = penta_ldl_layout(p->n, p->K, 1).end * (int)sizeof(double);
-  if (p->lds > 160 * 1024) { g_err = "right-hand sides do not fit the LDS carve-up"; return -1; }
-  // the two workgroups must not share a CU (each is one wavefront per SIMD, issue-bound): ask for
-  // more than half of the 160 KB LDS so that the dispatcher cannot co-locate them
-  if (p->m_split > 0) p->lds = std::max(p->lds, 84 * 1024);
-  if (p->lds > 160 * 1024) { g_err = "LDS carve-up too large"; return -1; }
+// assembled: plan for the system as it is once the bands count as assembled (block row 0 the identity), whatever
+// c->h_assembled says now - the launches that assemble H themselves
+static int Plan(const idto_hip_ctx* c, bool assembled, const SolveRequest& rq, SolverPlan* p) {
+  std::string err;
+  if (idto_host::PlanSolve(ShapeOf(c, assembled), rq, p, &err)) { g_err = err; return -1; }
   return 0;
 }
+static SolveRequest WholeStep(const idto_hip_ctx* c) {   // (c: the context of the model, also where a KKT context's system is solved)
+  SolveRequest rq;
+  rq.kind = SolveRequest::WHOLE_STEP; rq.step_nq = c->nq; rq.step_fast_n = c->M.fast_n;
+  return rq;
+}
+static int NoKernel(const char* family, int size) {   // (PlanSolve names instantiated sizes only: tests/cpp/solver_plan_check.cc)
+  g_err = std::string("no ") + family + " instantiation of size " + std::to_string(size);
+  return -1;
+}
 
-// Nested dissection (penta_nd.h): seven workgroups - two producer / joiner pairs, two spike
-// workgroups, the separator.  Its factors are not what penta_apply_kernel walks, so it serves the
-// single-right-hand-side solves only (the Gauss-Newton step).
-// separator in the middle; in each half the joiner chain (next to the separator) gets the extra row
-struct NdSplit { int s, j1, j2; };
-// Pipelined chains (penta_pipe.h): a joiner's block row costs ~1.35x a producer's (its spike wavefronts share the
-// SIMDs) and its two join rows come after the producer's hand-over, so the producers take ~57% of the rows that are
-// not join rows: both sides then reach the join together (measured at K = 19: 2.56 / 3.45 us per row).
-static NdSplit nd_split(int n, bool pipe, int K) {
-  NdSplit sp;
-  sp.s = (n - 2) / 2;
-  const int htop = sp.s, hbot = n - sp.s - 2;
-  auto producer_rows = [&](int half) {
-    if (!pipe) {
-      // (seven workgroups.  Measured: producer done at 0.6 + (np + 2) t, joiner at the join at 0.6 + d + (half - np - 2) t'
-      // with t = 4.2, t' = 4.53, d = 6.3 us at K = 23 (the joiner publishes every row and starts later) and t = 6.2,
-      // t' = 6.3, d = 8.5 at K = 29: both sides meet at np = (half - 2) / 2 + 0.27 resp. - 0.24 rows.  An odd
-      // half - 2 (every even n) therefore rounds UP at K = 23 - allegro N = 60: 67.7 / 66.6 us instead of 63.6 / 70.3 -
-      // and down at K = 29 - N = 40: 62 / 66 instead of 68 / 59.5.)
-      static const int extra = [] { const char* e = std::getenv("IDTO_ND_PRODUCER_EXTRA"); return e ? std::atoi(e) : -1; }();   // (measurement aid)
-      const int np = extra >= 0 ? (half - 2) / 2 + extra : (half - 2 + (K > 20 && K <= 24 ? 1 : 0)) / 2;
-      return std::max(1, std::min(np, half - 3));
-    }
-    static const double share = [] { const char* e = std::getenv("IDTO_PIPE_SPLIT"); return e ? std::atof(e) : 0.52; }();   // (measurement aid)
-    int np = (int)(share * (half - 2) + 0.6);
-    return std::max(1, std::min(np, half - 3));
-  };
-  sp.j1 = producer_rows(htop);                     // producer P0: rows 0 .. j1-1
-  sp.j2 = n - producer_rows(hbot) - 2;             // producer P3: rows j2+2 .. n-1
-  return sp;
-}
-static int NdLds(const idto_hip_ctx* c, const LdlPlan& p, int nloc_max);
-static bool NdEligible(const idto_hip_ctx* c, const LdlPlan& p) {
-  const bool inst = (p.K == 2 || p.K == 3 || p.K == 5 || p.K == 19 || p.K == 23 || p.K == 29 || (p.K == 8 && c->ldl_npos > 0)) && p.K == p.k;
-  // (seven workgroups per problem, one per CU: a batch that would not fit the 256 CUs at once is
-  // better served by the two-workgroup form - same work per problem on fewer CUs)
-  // (horizons from nd_min_rows block rows on - option "nd_min_rows", 16: the MPC examples plan over 20 steps, and the
-  // one-launch iteration that serves shorter systems takes 99 us for the cheetah there against 21 + ~40 of fd_kernel and
-  // the pipelined solver.  The seven-workgroup kernel keeps 24: its chains of 4 - 5 rows buy nothing below that.)
-  const bool pipe_kernel = c->solver_pipe && p.K <= 20;
-  if (!(c->solver_nd && c->two_sided && inst && p.n >= (pipe_kernel ? c->nd_min_rows : std::max(24, c->nd_min_rows)) && 7 * c->batch <= 256)) return false;
-  // the joiner chains' per-row tables hold ND_MAXROWS local rows: longer horizons (n >= 127) take the
-  // two-workgroup factorisation
-  NdSplit sp = nd_split(p.n, c->solver_pipe && p.K <= 20, p.K);
-  const int nloc_max = std::max(std::max(sp.s - sp.j1, sp.j2 - sp.s), std::max(sp.j1, p.n - sp.j2 - 2));
-  return nloc_max <= ND_MAXROWS && NdLds(c, p, nloc_max) <= 160 * 1024;
-}
-// (the chains keep the right-hand side and rt / x of their own rows: joiner nloc, producer nloc + 2 pseudo-rows, + 2 spare)
-static int NdChainRows(int nloc_max) { return nloc_max + 4; }
-static int NdLds(const idto_hip_ctx* c, const LdlPlan& p, int nloc_max) {
-  const int ks = ldl_ks(p.K), NF = 2 * p.K, KP = 4 * ((p.K + 3) / 4);
-  const int chain = penta_ldl_layout(p.n, p.K, 1, NdChainRows(nloc_max)).end * (int)sizeof(double);
-  const int spike = (3 * NF * ks + 3 * KP * ks + 3 * p.K * p.K + 2 * ks + 4) * (int)sizeof(double);
-  const int sep = nd_sep_lds_doubles(p.K) * (int)sizeof(double);
-  return std::max(std::max(spike, sep), chain);
-}
-// idto_hip_gn_step / idto_hip_tr_solve asked the solver's launch to assemble g and the bands itself (AsmInSolver): the
-// 4 (N + 1) workgroups behind the solver's own run assemble_terms_kernel's rows (penta_pipe.h PipeAsm)
-static PipeAsm TakeAsm(idto_hip_ctx* c, const LdlPlan& p) {
+// What a solver's launch is to do besides solving (SolverPlan::can_assemble / can_decide; penta_pipe.h PipeAsm):
+// assemble g and the bands itself - 4 (N + 1) workgroups behind the solver's own run assemble_terms_kernel's rows,
+// gated: problems whose word is 0 keep their g and H (idto_hip_tr_solve) - and decide on the trial point first
+struct SolverExtras {
+  bool assemble = false;
+  const double* gate = nullptr;
+  const TrDecideArgs* decide = nullptr;
+};
+static PipeAsm MakeAsm(idto_hip_ctx* c, const SolverPlan& p, const SolverExtras& ex) {
   PipeAsm F{};
-  F.on = c->fuse_asm_next ? 1 : 0;
-  c->fuse_asm_next = false;
+  F.on = ex.assemble ? 1 : 0;
   if (F.on) {
     F.nq = c->nq; F.nv = c->nv; F.rows = c->N + 1; F.first = p.r0;
     F.P = c->P; F.q = c->q; F.terms = c->terms; F.v_res = c->v; F.nplus = c->nplus;
-    F.g = c->g; F.HA = c->HA; F.HB = c->HB; F.HC = c->HC; F.alt = c->alt_r; F.ready = c->asm_ready; F.gate = c->fuse_gate;
+    F.g = c->g; F.HA = c->HA; F.HB = c->HB; F.HC = c->HC; F.alt = c->alt_r; F.ready = c->asm_ready; F.gate = ex.gate;
     c->last_assembly = 4;
   }
+  if (!(F.on && ex.decide)) return F;
+  F.decide = 1;
+  F.dq = c->q_trial; F.dv = c->v; F.dslab = c->slab; F.dslab_stride = (int)c->slab_stride; F.dcost = c->cost;
+  F.ddiag = c->weights_diagonal ? 1 : 0;
+  F.dT = *ex.decide; F.dalt = c->alt_w;
+  F.dword = c->decide_word;
+  F.g2 = c->g2; F.HA2 = c->HA2; F.HB2 = c->HB2; F.HC2 = c->HC2;
+  F.curpre = c->decide_word + 2;
+  if (++c->decide_epoch == 0u) c->decide_epoch = 1u;
+  F.depoch = c->decide_epoch;
   return F;
 }
-// ... and (the pipelined chains' launch inside idto_hip_tr_solve) to decide on the trial point first
-static void TakeDecide(idto_hip_ctx* c, PipeAsm* F) {
-  if (!(F->on && c->fuse_decide)) return;
-  F->decide = 1;
-  F->dq = c->q_trial; F->dv = c->v; F->dslab = c->slab; F->dslab_stride = (int)c->slab_stride; F->dcost = c->cost;
-  F->ddiag = c->weights_diagonal ? 1 : 0;
-  F->dT = *c->fuse_decide; F->dalt = c->alt_w;
-  F->dword = c->decide_word;
-  F->g2 = c->g2; F->HA2 = c->HA2; F->HB2 = c->HB2; F->HC2 = c->HC2;
-  F->curpre = c->decide_word + 2;
-  if (++c->decide_epoch == 0u) c->decide_epoch = 1u;
-  F->depoch = c->decide_epoch;
-  c->fuse_decide = nullptr;
-}
 
-// The scalar band factorisation (penta_band.h): blocks up to 5 (half width 3 k - 1 <= 14: a lane per diagonal in a row
-// of 16), one workgroup per problem, single right-hand side.
-static bool BandEligible(const idto_hip_ctx* c, const LdlPlan& p, bool whole_step = false) {
-  // (option solver_band: 0 off, 1 blocks up to 4 - at 5 the pipelined kernel is faster, 41 against 47 us for hopper -, 2 up to 5)
-  if (!(c->solver_band > 0 && c->two_sided && p.K == p.k && p.k >= 2 && p.k <= (c->solver_band > 1 ? 5 : 4))) return false;
-  const int M = p.n * p.k, W = 3 * p.k;
-  // (a batch: two wavefronts per problem shorten ONE problem's solve; with many in flight the five workgroups' work per
-  // problem is what counts - 64 spinner problems 554k against 567k it/s, 256: 747k / 782k; acrobot 649k / 619k)
-  // (gn_small.h - `whole_step` - is one workgroup per problem for EVERYTHING: there the batch argument points the other
-  // way, 64 acrobot problems 650k -> 2.89M it/s)
-  if (c->batch > 1 && c->solver_band < 2 && p.k > 2 && !whole_step) return false;
-  // (horizons the pipelined kernel would take: shorter ones keep the fused launch / the two-workgroup factorisation)
-  return p.n >= c->nd_min_rows && M >= 4 * W && band_layout(M, W).end * (int)sizeof(double) <= 160 * 1024;
-}
-static int LaunchBand(idto_hip_ctx* c, const LdlPlan& p, const double* b, double sign, double* xo) {
+// The scalar band factorisation (penta_band.h)
+static int LaunchBand(idto_hip_ctx* c, const SolverPlan& p, const double* b, double sign, double* xo, const SolverExtras& ex) {
   BandArgs A;
   A.n = p.n; A.k = p.k;
   A.HA = c->HA + p.qq0; A.HB = c->HB + p.qq0; A.HC = c->HC + p.qq0;
@@ -1339,23 +1250,20 @@ static int LaunchBand(idto_hip_ctx* c, const LdlPlan& p, const double* b, double
   A.npos = c->ldl_npos;
   A.ts = c->solver_debug ? c->dbg : nullptr;
   c->last_solver = 6;
-  const PipeAsm F = TakeAsm(c, p);
-  const int W = 3 * p.k;
-  int lds = band_layout(p.n * p.k, W).end * (int)sizeof(double);
-  if (F.on) lds = std::max(lds, c->asm_terms_lds);
-  const dim3 grid(1 + (F.on ? 4 * (c->N + 1) : 0), c->batch);
-#define BAND_LAUNCH(WM) hipLaunchKernelGGL((penta_band_kernel<WM>), grid, dim3(256), lds, c->stream, A, F)
-  switch (W) {
-    case 6: BAND_LAUNCH(6); break;
-    case 9: BAND_LAUNCH(9); break;
-    case 12: BAND_LAUNCH(12); break;
-    default: BAND_LAUNCH(15); break;
+  const PipeAsm F = MakeAsm(c, p, ex);
+  const int lds = F.on ? p.lds_assemble : p.lds;
+  const dim3 grid(p.grid + (F.on ? 4 * (c->N + 1) : 0), c->batch);
+  switch (3 * p.k) {
+#define BAND_CASE(WM) case WM: hipLaunchKernelGGL((penta_band_kernel<WM>), grid, dim3(p.threads), lds, c->stream, A, F); break;
+    IDTO_BAND_KERNELS(BAND_CASE)
+#undef BAND_CASE
+    default: return NoKernel("penta_band_kernel", 3 * p.k);
   }
-#undef BAND_LAUNCH
   HIP_OK(hipGetLastError());
   return 0;
 }
-static int LaunchNd(idto_hip_ctx* c, const LdlPlan& p, const double* b, double sign, double* xo) {
+// Nested dissection: the pipelined chains (penta_pipe.h, five workgroups) or the seven-workgroup kernel (penta_nd.h)
+static int LaunchNd(idto_hip_ctx* c, const SolverPlan& p, const double* b, double sign, double* xo, const SolverExtras& ex) {
   NdArgs A;
   A.debug_skip_role = c->debug_skip_role;
   A.debug_pipe_tail = c->debug_pipe_tail;
@@ -1366,25 +1274,10 @@ static int LaunchNd(idto_hip_ctx* c, const LdlPlan& p, const double* b, double s
   A.HA = c->HA + p.qq0; A.HB = c->HB + p.qq0; A.HC = c->HC + p.qq0;
   A.b = b + (size_t)p.r0 * p.k; A.rhs_sign = sign; A.x = xo + (size_t)p.r0 * p.k;
   A.Ust = c->Ust; A.Hst = c->Hst; A.Est = c->Est; A.Dst = c->Dst;
-  { const NdSplit sp = nd_split(p.n, c->solver_pipe && p.K <= 20, p.K); A.s = sp.s; A.j1 = sp.j1; A.j2 = sp.j2; }
-  const int nloc_max = std::max(std::max(A.s - A.j1, A.j2 - A.s), std::max(A.j1, A.n - A.j2 - 2));
-  if (nloc_max > ND_MAXROWS) { g_err = "horizon too long for the nested-dissection solver's row tables"; return -1; }
-  const int lds = NdLds(c, p, nloc_max);
-  if (lds > 160 * 1024) { g_err = "nested-dissection solver: LDS carve-up too large"; return -1; }
-  A.npos = c->ldl_npos; A.lds_rows = NdChainRows(nloc_max);
+  A.s = p.s; A.j1 = p.j1; A.j2 = p.j2;
+  A.npos = c->ldl_npos; A.lds_rows = p.lds_rows;
   A.xch = c->xch; A.xch_pair = (int)c->xch_count; A.flags = c->flags;
-  if (c->solver_pipe && p.K <= 20) {
-    // pipelined chains (penta_pipe.h): five workgroups of eight wavefronts, the joiners carry their spike columns
-    int plds = 0;
-    switch (p.K) {
-      case 2: plds = pipe_layout<2>(p.n, true).end; break;
-      case 3: plds = pipe_layout<3>(p.n, true).end; break;
-      case 5: plds = pipe_layout<5>(p.n, true).end; break;
-      default: plds = pipe_layout<19>(p.n, true).end; break;
-    }
-    const int sep = nd_sep_lds_doubles(p.K) * (int)sizeof(double);
-    plds = std::max(plds * (int)sizeof(double), sep);
-    if (plds > 160 * 1024) { g_err = "pipelined solver: LDS carve-up too large"; return -1; }
+  if (p.kind == idto_host::SOLVER_PIPE) {
     A.rowcnt = c->pipe_rowcnt; A.ndbuf = c->nd_buf;
     ++c->pipe_launches;
     c->last_solver = 4;
@@ -1394,25 +1287,24 @@ static int LaunchNd(idto_hip_ctx* c, const LdlPlan& p, const double* b, double s
     A.epoch = c->epoch; A.status = c->status_dev; A.fact_id = c->fact_id; A.pstride = c->pstride;
     A.ts = c->solver_debug ? c->dbg : nullptr;
     // (idto_hip_gn_step: g and the bands are assembled by 4 (N + 1) more workgroups of this launch, penta_pipe.h PipeAsm)
-    PipeAsm F = TakeAsm(c, p);
-    if (p.K == 5 || p.K == 19) TakeDecide(c, &F);
-    if (F.on) plds = std::max(plds, c->asm_terms_lds);
-    if (F.decide) plds = std::max(plds, c->cost_lds);
-    A.asm_ready = nullptr; A.asm_first = 0;
-    const dim3 pgrid(5 + (F.on ? 4 * (c->N + 1) : 0) + (F.decide ? 1 : 0), c->batch);
-#define PIPE_LAUNCH(KM) hipLaunchKernelGGL((penta_pipe_kernel<KM>), pgrid, dim3(512), plds, c->stream, A, F)
-#define PIPE_LAUNCH_DEC(KM) hipLaunchKernelGGL((penta_pipe_kernel<KM, true>), pgrid, dim3(512), plds, c->stream, A, F)
+    const PipeAsm F = MakeAsm(c, p, ex);
+    const int plds = F.decide ? p.lds_decide : (F.on ? p.lds_assemble : p.lds);
+    const dim3 pgrid(p.grid + (F.on ? 4 * (c->N + 1) : 0) + (F.decide ? 1 : 0), c->batch);
+#define PIPE_CASE(KM) case KM: hipLaunchKernelGGL((penta_pipe_kernel<KM>), pgrid, dim3(p.threads), plds, c->stream, A, F); break;
+#define PIPE_DEC_CASE(KM) case KM: hipLaunchKernelGGL((penta_pipe_kernel<KM, true>), pgrid, dim3(p.threads), plds, c->stream, A, F); break;
     if (F.decide) {
-      if (p.K == 5) PIPE_LAUNCH_DEC(5); else PIPE_LAUNCH_DEC(19);
-    } else
-    switch (p.K) {
-      case 2: PIPE_LAUNCH(2); break;
-      case 3: PIPE_LAUNCH(3); break;
-      case 5: PIPE_LAUNCH(5); break;
-      default: PIPE_LAUNCH(19); break;
+      switch (p.K) {
+        IDTO_PIPE_DEC_KERNELS(PIPE_DEC_CASE)
+        default: return NoKernel("deciding penta_pipe_kernel", p.K);
+      }
+    } else {
+      switch (p.K) {
+        IDTO_PIPE_KERNELS(PIPE_CASE)
+        default: return NoKernel("penta_pipe_kernel", p.K);
+      }
     }
-#undef PIPE_LAUNCH
-#undef PIPE_LAUNCH_DEC
+#undef PIPE_CASE
+#undef PIPE_DEC_CASE
     HIP_OK(hipGetLastError());
     return 0;
   }
@@ -1429,91 +1321,67 @@ static int LaunchNd(idto_hip_ctx* c, const LdlPlan& p, const double* b, double s
   if (++c->fact_id == 0) c->fact_id = 1;
   A.epoch = c->epoch; A.status = c->status_dev; A.fact_id = c->fact_id; A.pstride = c->pstride;
   A.ts = c->solver_debug ? c->dbg : nullptr;
-  // back substitution in recursion form (penta_pipe.h chain_recursion_tail) where every row's [Y | Z | c] fits the
-  // 160 KB: allegro's 23 x 23 blocks up to N = 60, its 29 x 29 KKT blocks up to N = 40
-  int nd_lds = lds;
-  if (c->nd_recursion && c->nd_wst && p.K == p.k && (p.K == 23 || p.K == 29)) {
-    const int nj = std::max(A.s - A.j1, A.j2 - A.s), np = std::max(A.j1, A.n - A.j2 - 2), all = 160 * 1024 / (int)sizeof(double);
-    if (const int ww = p.K == 23 ? pipe_recursion_tail_fits<23>(all, nj, np) : pipe_recursion_tail_fits<29>(all, nj, np)) {
-      A.rec_tail = ww; A.lds_doubles = all; A.wst = c->nd_wst;
-      nd_lds = 160 * 1024;
-    }
-  }
-  const dim3 grid(7, c->batch);
-#define ND_LAUNCH(KM, PD) hipLaunchKernelGGL((penta_nd_kernel<KM, PD>), grid, dim3(256), nd_lds, c->stream, A)
+  // (back substitution in recursion form, penta_pipe.h chain_recursion_tail: the plan then asks for the whole LDS)
+  if (p.rec_tail) { A.rec_tail = p.rec_tail; A.lds_doubles = p.lds / (int)sizeof(double); A.wst = c->nd_wst; }
+  const dim3 grid(p.grid, c->batch);
   switch (p.K) {
-    case 2: ND_LAUNCH(2, false); break;
-    case 3: ND_LAUNCH(3, false); break;
-    case 5: ND_LAUNCH(5, false); break;
-    case 23: ND_LAUNCH(23, false); break;
-    case 29: ND_LAUNCH(29, false); break;
-    case 8: ND_LAUNCH(8, false); break;
-    default: ND_LAUNCH(19, false); break;
+#define ND_CASE(KM) case KM: hipLaunchKernelGGL((penta_nd_kernel<KM, false>), grid, dim3(p.threads), p.lds, c->stream, A); break;
+    IDTO_ND_KERNELS(ND_CASE)
+#undef ND_CASE
+    default: return NoKernel("penta_nd_kernel", p.K);
   }
-#undef ND_LAUNCH
   HIP_OK(hipGetLastError());
   return 0;
 }
 
-static int LaunchLdl(idto_hip_ctx* c, const double* b, double sign, double* xo, bool one_sided = false, bool allow_nd = false,
-                     bool factor_only = false) {
-  LdlPlan p;
-  if (int rc = PlanLdl(c, one_sided, &p)) return rc;
-  if (allow_nd && !one_sided && BandEligible(c, p)) return LaunchBand(c, p, b, sign, xo);
-  if (allow_nd && !one_sided && NdEligible(c, p)) return LaunchNd(c, p, b, sign, xo);
+// the launch the plan names; penta_ldl_kernel (one or two workgroups) here
+static int LaunchLdl(idto_hip_ctx* c, const SolverPlan& p, const double* b, double sign, double* xo, bool factor_only, const SolverExtras& ex) {
+  if (ex.assemble && !(p.can_assemble && (!ex.decide || p.can_decide))) { g_err = "the planned solver launch cannot carry the assembly / the decision"; return -1; }
+  if (p.kind == idto_host::SOLVER_BAND) return LaunchBand(c, p, b, sign, xo, ex);
+  if (p.kind == idto_host::SOLVER_ND || p.kind == idto_host::SOLVER_PIPE) return LaunchNd(c, p, b, sign, xo, ex);
   const int n = p.n, k = p.k, m_split = p.m_split, lds = p.lds, nrhs = 1;
   const size_t qq0 = p.qq0;
   b += (size_t)p.r0 * k;
   xo += (size_t)p.r0 * k;
   double* dbg = c->solver_debug ? c->dbg : nullptr;
-  const dim3 grid(m_split > 0 ? 2 : 1, c->batch);
+  const dim3 grid(p.grid, c->batch);
   c->last_solver = 1;
   if (m_split > 0) ++c->epoch;  // (exchange buffer and flags live in the problem's arena)
   if (++c->fact_id == 0) c->fact_id = 1;  // (0 is the initial value of the status word)
 #define LDL_ARGS n, k, c->HA + qq0, c->HB + qq0, c->HC + qq0, b, sign, nrhs, xo, c->Ust, c->Hst, c->Est, c->Dst, dbg, \
                  m_split, c->xch, c->flags, c->epoch, c->status_dev, c->fact_id, c->pstride, factor_only ? 1 : 0, c->ldl_npos
-#define LDL_LAUNCH(KM, PD, GW) \
-  hipLaunchKernelGGL((penta_ldl_kernel<KM, 256, PD, GW>), grid, dim3(256), lds, c->stream, LDL_ARGS)
+#define LDL_CASE(KM, PD, GW) \
+  case KM: hipLaunchKernelGGL((penta_ldl_kernel<KM, 256, PD, GW>), grid, dim3(p.threads), lds, c->stream, LDL_ARGS); break;
   switch (p.K) {
-    case 2: LDL_LAUNCH(2, false, 1); break;
-    case 3: LDL_LAUNCH(3, false, 1); break;
-    case 5: LDL_LAUNCH(5, false, 1); break;
-    case 8: LDL_LAUNCH(8, true, 1); break;
-    case 16: LDL_LAUNCH(16, true, 1); break;
-    case 19: LDL_LAUNCH(19, false, 1); break;
-    case 23: LDL_LAUNCH(23, false, 2); break;
-    case 24: LDL_LAUNCH(24, true, 2); break;
-    case 30: LDL_LAUNCH(30, true, 2); break;
-    case 29: LDL_LAUNCH(29, false, 2); break;
-    case 4: LDL_LAUNCH(4, false, 1); break;
-    default: LDL_LAUNCH(32, true, 3); break;
+    IDTO_LDL_KERNELS(LDL_CASE)
+    default: return NoKernel("penta_ldl_kernel", p.K);
   }
-#undef LDL_LAUNCH
+#undef LDL_CASE
 #undef LDL_ARGS
   HIP_OK(hipGetLastError());
   return 0;
 }
 
 // ---- one persistent launch for the whole Gauss-Newton iteration (fused.h)
+static int FusedMaxc(const idto_hip_ctx* c) { return c->maxc <= 2 ? 2 : (c->maxc <= 3 ? 3 : (c->maxc <= 4 ? 4 : 8)); }
 static int FusedVariant(const idto_hip_ctx* c) {  // instantiated (MAXC, K) combinations: the reference's example models
   if (c->M.nxb || c->M.nstem > 1) return 0;   // (gn_fused_kernel embeds id_eval without the exchange of shared pairs / the stem)
   if (c->capsules) return 0;   // (capsule models: the three-launch path only)
-  const int mc = c->maxc <= 2 ? 2 : (c->maxc <= 3 ? 3 : (c->maxc <= 4 ? 4 : 8));
-  if (mc == 2 && c->nq == 2) return 1;
-  if (mc == 3 && c->nq == 3) return 2;
-  if (mc == 3 && c->nq == 5) return 3;
-  if (mc == 3 && c->nq == 19) return 4;
-  if (mc == 4 && c->nq == 23) return 5;
-  return 0;
+  const int mc = FusedMaxc(c);
+  int variant = 0, i = 0;
+#define FUSED_IS(MC, KM, PD, GW) ++i; if (mc == MC && c->nq == KM) variant = i;
+  IDTO_FUSED_KERNELS(FUSED_IS)
+#undef FUSED_IS
+  return variant;
 }
 static bool FusedEligible(const idto_hip_ctx* c) {
-  {  // the nested-dissection solver is its own launch (seven workgroups): the three-launch path takes it
-    LdlPlan p;
-    idto_hip_ctx* cc = const_cast<idto_hip_ctx*>(c);
-    if (PlanLdl(cc, false, &p) == 0 && (NdEligible(c, p) || BandEligible(c, p))) return false;   // (likewise the scalar band factorisation's)
-  }
-  return c->fused && c->batch == 1 && c->weights_diagonal && !c->reference_solver && !c->solver_debug && c->fd_stop == 0 &&
-         c->asm_stop == 0 && c->k_begin == 0 && c->k_end == c->N && c->N >= 2 && FusedVariant(c) != 0;
+  if (!(c->fused && c->batch == 1 && c->weights_diagonal && !c->reference_solver && !c->solver_debug && c->fd_stop == 0 &&
+        c->asm_stop == 0 && c->k_begin == 0 && c->k_end == c->N && c->N >= 2 && FusedVariant(c) != 0))
+    return false;
+  // the nested-dissection solvers and the scalar band factorisation are launches of their own: the three-launch path
+  // takes them (the system as it stands - a context's first step still counts block row 0)
+  SolverPlan p;
+  return Plan(c, c->h_assembled, SolveRequest{}, &p) == 0 && p.kind == idto_host::SOLVER_LDL;
 }
 static int LaunchFused(idto_hip_ctx* c) {
   DropPrefetch(c, {IDTO_ARR_V, IDTO_ARR_A, IDTO_ARR_NPLUS, IDTO_ARR_SLAB, IDTO_ARR_GRADIENT, IDTO_ARR_H_A, IDTO_ARR_H_B,
@@ -1523,8 +1391,8 @@ static int LaunchFused(idto_hip_ctx* c) {
     HIP_OK(hipMemsetAsync(c->step, 0, (size_t)c->nq * sizeof(double), c->stream));
     c->h_assembled = true;
   }
-  LdlPlan p;
-  if (int rc = PlanLdl(c, false, &p)) return rc;
+  SolverPlan p;   // (the chains' geometry: r0, n, m_split and lds_full are the same whichever kernel the plan names)
+  if (int rc = Plan(c, true, SolveRequest{}, &p)) return rc;
   const int mode = 1 + c->gradients_method;
   const int E = FdEvals(c, mode), groups = 256 / c->npaths;
   int ec = E;
@@ -1555,13 +1423,12 @@ static int LaunchFused(idto_hip_ctx* c) {
   c->last_step_kind = 2;
   if (TimeBegin(c, 3)) return -2;
 #define FUSED_LAUNCH(MC, KM, PD, GW) \
-  hipLaunchKernelGGL((gn_fused_kernel<MC, KM, PD, GW>), grid, dim3(256), lds, c->stream, A)
-  switch (FusedVariant(c)) {
-    case 1: FUSED_LAUNCH(2, 2, false, 1); break;
-    case 2: FUSED_LAUNCH(3, 3, false, 1); break;
-    case 3: FUSED_LAUNCH(3, 5, false, 1); break;
-    case 4: FUSED_LAUNCH(3, 19, false, 1); break;
-    default: FUSED_LAUNCH(4, 23, false, 2); break;
+  if (mc == MC && c->nq == KM) { hipLaunchKernelGGL((gn_fused_kernel<MC, KM, PD, GW>), grid, dim3(256), lds, c->stream, A); launched = true; }
+  {
+    const int mc = FusedMaxc(c);
+    bool launched = false;
+    IDTO_FUSED_KERNELS(FUSED_LAUNCH)
+    if (!launched) return NoKernel("gn_fused_kernel", c->nq);
   }
 #undef FUSED_LAUNCH
   HIP_OK(hipGetLastError());
@@ -1573,33 +1440,22 @@ static int LaunchFused(idto_hip_ctx* c) {
 // gn_small.h: fd + assembly + band solve of a small all-revolute model in ONE workgroup per problem.  What it stands in
 // for must be what the two launches would have run: forward differences from the straight-line evaluation, diagonal
 // weights, the whole horizon, the scalar band factorisation (BandEligible), nothing switched to a measurement mode.
-// (p: the plan of the system the launch solves - H's, or the KKT context's with blocks of nq + nu)
-static int SmallLds(const idto_hip_ctx* c, const LdlPlan& p, int* lds_small) {
-  int band = band_layout(p.n * p.k, 3 * p.k).end;
-  band += band & 1;
-  if (lds_small) *lds_small = band;
-  return (band + gn_small_doubles(c->N, c->nq, c->M.fast_n, p.k)) * (int)sizeof(double);
-}
-static bool SmallEligible(const idto_hip_ctx* c) {
+// p: the plan of the system the launch solves - H's, or the KKT context's with blocks of nq + nu
+static bool SmallEligible(const idto_hip_ctx* c, SolverPlan* p) {
   if (!c->gn_small || !c->fd_fast || c->gradients_method != 0 || !c->weights_diagonal || c->reference_solver) return false;
   if (c->M.nxb || c->M.nstem > 1) return false;   // (id_eval_fast has no shared pairs and no stem)
   if (!(c->M.fast_shape == 1 || c->M.fast_shape == 5) || c->M.nfloat != 0 || c->nq != c->nv || c->npaths != 1) return false;
   if (!((c->M.fast_shape == 1 && c->nq == 2) || (c->M.fast_shape == 5 && c->nq == 3))) return false;   // (the instantiations)
   if (c->k_begin != 0 || c->k_end != c->N || c->fd_stop || c->asm_stop || c->solver_debug || c->ldl_npos > 0) return false;
-  LdlPlan p;
-  idto_hip_ctx* cc = const_cast<idto_hip_ctx*>(c);
-  const bool assembled = c->h_assembled;
-  cc->h_assembled = true;   // (the kernel assembles H itself: block row 0 is the identity, the solver starts at row 1)
-  const bool ok = c->N >= 2 && PlanLdl(cc, false, &p) == 0 && BandEligible(c, p, true) && p.r0 == 1 && SmallLds(c, p, nullptr) <= 160 * 1024;
-  cc->h_assembled = assembled;
-  return ok;
+  // (the kernel assembles H itself: block row 0 is the identity, the solver starts at row 1)
+  return Plan(c, true, WholeStep(c), p) == 0;
 }
 // tr: inside idto_hip_tr_solve - the launch evaluates the trial point c->q_trial into the output set `alt`, decides, and
 // goes on to g, H and the step only for an accepted step (gn_small.h SmallArgs::T); last: tau, cost and decision only
 // kkt: with enforced constraints - the step is the banded KKT solve, z into c->kkt's step (gn_small.h SmallArgs::kkt_r0)
 // iter: ... and tr_iter_kernel's part for the iterate in front (SmallArgs::I; a second workgroup reads the status words)
-static int LaunchSmall(idto_hip_ctx* c, const TrDecideArgs* tr = nullptr, bool last = false, AltSel alt = AltSel{nullptr, 0, 0},
-                       bool kkt = false, const TrIterArgs* iter = nullptr) {
+static int LaunchSmall(idto_hip_ctx* c, const SolverPlan& p, const TrDecideArgs* tr = nullptr, bool last = false,
+                       AltSel alt = AltSel{nullptr, 0, 0}, bool kkt = false, const TrIterArgs* iter = nullptr) {
   DropPrefetch(c, {IDTO_ARR_V, IDTO_ARR_A, IDTO_ARR_NPLUS, IDTO_ARR_SLAB, IDTO_ARR_GRADIENT, IDTO_ARR_H_A, IDTO_ARR_H_B,
                    IDTO_ARR_H_C, IDTO_ARR_HBANDS, IDTO_ARR_STEP, IDTO_ARR_COST});
   c->con_ready = false; c->con_begun = false;
@@ -1607,9 +1463,7 @@ static int LaunchSmall(idto_hip_ctx* c, const TrDecideArgs* tr = nullptr, bool l
     HIP_OK(hipMemset2DAsync(c->step, c->pstride, 0, (size_t)c->nq * sizeof(double), (size_t)c->batch, c->stream));
     c->h_assembled = true;
   }
-  LdlPlan p;
   idto_hip_ctx* sc = kkt ? c->kkt : c;   // whose system the launch solves
-  if (int rc = PlanLdl(sc, false, &p)) return rc;
   SmallArgs A;
   A.kkt_r0 = p.r0; A.kstride = sc->pstride;
   A.M = c->M; A.cp = c->cp; A.P = c->P; A.q = c->q; A.slab = c->slab; A.slab_stride = c->slab_stride;
@@ -1628,7 +1482,7 @@ static int LaunchSmall(idto_hip_ctx* c, const TrDecideArgs* tr = nullptr, bool l
   B.status = sc->status_dev; B.fact_id = sc->fact_id; B.epoch = sc->epoch; B.pstride = sc->pstride;
   B.npos = sc->ldl_npos; B.ts = nullptr;
   A.ts = std::getenv("IDTO_SMALL_STAMPS") ? c->dbg : nullptr;
-  const int lds = SmallLds(c, p, &A.lds_small);
+  A.lds_small = p.lds_small;
   if (sc->small_stage_N != c->N) {   // (once per horizon; the KKT system's table lives in its own context)
     const int qq = p.k * p.k, nb = c->N + 1;
     std::vector<BandStageItem> tab((size_t)band_stage_table(p.n, p.k, 0, 0, 0, 0, nullptr));
@@ -1645,25 +1499,33 @@ static int LaunchSmall(idto_hip_ctx* c, const TrDecideArgs* tr = nullptr, bool l
   if (!tr && TimeBegin(c, 3)) return -2;
   // (256 threads, one wavefront per SIMD: the evaluation needs more than the 256 registers a lane has at two per SIMD -
   // 512 threads spilled 19 / 67 registers to scratch inside it and the step was slower than the two launches)
-  if (kkt && c->nq == 2) hipLaunchKernelGGL((gn_small_kernel<1, 6, 256, 9, true>), dim3(gx, c->batch), dim3(256), lds, c->stream, A);
-  else if (kkt) hipLaunchKernelGGL((gn_small_kernel<5, 9, 256, 12, true>), dim3(gx, c->batch), dim3(256), lds, c->stream, A);
-  else if (tr && c->nq == 2) hipLaunchKernelGGL((gn_small_kernel<1, 6, 256, 6, true>), dim3(gx, c->batch), dim3(256), lds, c->stream, A);
-  else if (tr) hipLaunchKernelGGL((gn_small_kernel<5, 9, 256, 9, true>), dim3(gx, c->batch), dim3(256), lds, c->stream, A);
-  else if (c->nq == 2) hipLaunchKernelGGL((gn_small_kernel<1, 6, 256>), dim3(gx, c->batch), dim3(256), lds, c->stream, A);
-  else hipLaunchKernelGGL((gn_small_kernel<5, 9, 256>), dim3(gx, c->batch), dim3(256), lds, c->stream, A);
+  {  // the model's shape and band width, the solved system's band width (a KKT context's is wider), the loop's instantiation or the plain step's
+    const int shape = c->M.fast_shape, w = 3 * c->nq, ws = 3 * p.k;
+    const bool trk = tr || kkt;
+    bool launched = false;
+#define SMALL_LAUNCH(SH, WM, WSM, TR) \
+    if (shape == SH && w == WM && ws == WSM && trk == TR) { hipLaunchKernelGGL((gn_small_kernel<SH, WM, 256, WSM, TR>), dim3(gx * p.grid, c->batch), dim3(p.threads), p.lds, c->stream, A); launched = true; }
+    IDTO_SMALL_KERNELS(SMALL_LAUNCH)
+#undef SMALL_LAUNCH
+    if (!launched) return NoKernel("gn_small_kernel", ws);
+  }
   HIP_OK(hipGetLastError());
   c->fd_full = !last; c->partials_ahead = false;
   c->terms_valid = false;   // (no single-record products: a later idto_hip_grad_hess assembles from the slab)
   return tr ? 0 : TimeEnd(c);
 }
 
-static int FactorSolve(idto_hip_ctx* c, const double* rhs, int nrhs, double* x, const RhsSource* src);
+static int FactorSolve(idto_hip_ctx* c, const double* rhs, int nrhs, double* x, const RhsSource* src,
+                       const SolverPlan* planned = nullptr, const SolverExtras& ex = SolverExtras{});
 int idto_hip_factor_solve(idto_hip_ctx* c, const double* rhs, int nrhs, double* x) {
   return FactorSolve(c, rhs, nrhs, x, nullptr);
 }
 // src: the right-hand sides are [g | J^T] read in place (penta_apply.h RhsSource; nrhs > 1), `rhs` is then any valid
 // pointer to (N + 1) nq doubles for the factorisation kernel's unused first column
-static int FactorSolve(idto_hip_ctx* c, const double* rhs, int nrhs, double* x, const RhsSource* src) {
+// planned, ex: (idto_hip_gn_step, idto_hip_tr_solve; the solve of -g) the plan the caller has made for this solve and
+// what it found the plan's launch can do besides
+static int FactorSolve(idto_hip_ctx* c, const double* rhs, int nrhs, double* x, const RhsSource* src, const SolverPlan* planned,
+                       const SolverExtras& ex) {
   const bool x0_written = src != nullptr;   // (the substitution kernel zeroes x_0 itself)
   HIP_OK(hipSetDevice(c->device));
   if (!rhs) DropPrefetch(c, {IDTO_ARR_STEP});
@@ -1692,12 +1554,18 @@ static int FactorSolve(idto_hip_ctx* c, const double* rhs, int nrhs, double* x, 
   }
   // block LDL^T: factorise once with the first right-hand side (two-sided when the horizon is
   // long enough; the substitution kernel walks both chains of factors) ...
-  const int K = (k == 2 || k == 3 || k == 5 || k == 19 || k == 23) ? k : (k <= 8 ? 8 : k <= 16 ? 16 : k <= 24 ? 24 : 32);
   // (several right-hand sides: the factorisation stops after its forward pass, every column incl. the first is
   // substituted by penta_apply_kernel - the chains' own back substitution would only delay the others)
-  int rc = LaunchLdl(c, b, rhs ? 1.0 : -1.0, xo, false, /*allow_nd=*/nrhs == 1, /*factor_only=*/nrhs > 1);
-  const int r0 = SolverFirstRow(c), ns = n - r0;                      // the sub-system LaunchLdl factorised
-  const int m_split = (c->two_sided && ns >= 10) ? (ns - 1) / 2 : 0;  // as LaunchLdl chose
+  SolverPlan own;
+  if (!planned) {
+    SolveRequest rq;
+    rq.nrhs = nrhs;
+    if (int rp = Plan(c, c->h_assembled, rq, &own)) return rp;
+    planned = &own;
+  }
+  const SolverPlan& p = *planned;
+  int rc = LaunchLdl(c, p, b, rhs ? 1.0 : -1.0, xo, /*factor_only=*/nrhs > 1, ex);
+  const int r0 = p.r0, ns = p.n, K = p.apply_K, m_split = p.m_split;   // the sub-system the launch factorised
   if (r0 && rhs && !x0_written)  // x_0 = rhs_0 for every column (row 0 of H is the identity); the default rhs has g_0 = 0 = x_0
     HIP_OK(hipMemcpy2DAsync(x, (size_t)n * k * sizeof(double), rhs, (size_t)n * k * sizeof(double), (size_t)k * sizeof(double),
                             (size_t)nrhs, hipMemcpyDeviceToDevice, c->stream));
@@ -1706,10 +1574,10 @@ static int FactorSolve(idto_hip_ctx* c, const double* rhs, int nrhs, double* x, 
     // ... then substitute the other right-hand sides in parallel: one wavefront each (two, one per chain, when the
     // factorisation was two-sided)
     const int waves = 4, cols = m_split > 0 ? waves / 2 : waves, blocks = (nrhs + cols - 1) / cols;
-    const int lds = waves * (ns * K + 4 * 64 + 2) * (int)sizeof(double);   // (per column: rt of every row, the chains' exchange)
+    const int lds = p.apply_lds;
     const double* b1 = b + (size_t)r0 * k;
     double* x1 = xo + (size_t)r0 * k;
-    if (!c->Tst && Alloc(c, (size_t)3 * (c->N + 1) * 32 * 36, &c->Tst)) return -2;
+    if (!c->Tst && Alloc(c, idto_host::SolverBufferCounts(k, c->N).apply_t, &c->Tst)) return -2;
     RhsSource RS{};
     if (src) { RS = *src; RS.r0 = r0; }
 #define APPLY_LAUNCH(KM)                                                                                          \
@@ -1722,17 +1590,12 @@ static int FactorSolve(idto_hip_ctx* c, const double* rhs, int nrhs, double* x, 
       hipLaunchKernelGGL((penta_apply_kernel<KM, false>), dim3(blocks), dim3(64 * waves), lds, c->stream, ns, k, c->Ust, \
                          c->Hst, c->Est, c->Dst, c->Tst, b1, rhs ? 1.0 : -1.0, nrhs, x1, m_split, (size_t)n * k, RS); \
     }
+#define APPLY_CASE(KM) case KM: APPLY_LAUNCH(KM); break;
     switch (K) {
-      case 2: APPLY_LAUNCH(2); break;
-      case 3: APPLY_LAUNCH(3); break;
-      case 5: APPLY_LAUNCH(5); break;
-      case 8: APPLY_LAUNCH(8); break;
-      case 16: APPLY_LAUNCH(16); break;
-      case 19: APPLY_LAUNCH(19); break;
-      case 23: APPLY_LAUNCH(23); break;
-      case 24: APPLY_LAUNCH(24); break;
-      default: APPLY_LAUNCH(32); break;
+      IDTO_APPLY_KERNELS(APPLY_CASE)
+      default: return NoKernel("penta_apply_kernel", K);
     }
+#undef APPLY_CASE
 #undef APPLY_LAUNCH
     HIP_OK(hipGetLastError());
   }
@@ -2167,7 +2030,7 @@ static int MakeKkt(idto_hip_ctx* c, int nu) {
   const size_t kk = (size_t)K * K;
   idto_hip_ctx* kc = k.get();
   auto fail = [&](const char* what) { g_err = what; idto_hip_destroy(k.release()); return -2; };
-  // one arena per problem, as in idto_hip_create_batch: the solver kernels take the problem from blockIdx.y
+  // one arena per problem, as in idto_hip_create_batch (the same SolverBufferCounts): the solver kernels take the problem from blockIdx.y
   size_t top = 0;
   auto carve = [&](size_t count, size_t elem) {
     const size_t o = (top + 63) & ~(size_t)63;
@@ -2175,16 +2038,17 @@ static int MakeKkt(idto_hip_ctx* c, int nu) {
     return o;
   };
   const size_t D = sizeof(double);
-  kc->xch_count = 2 * (size_t)(3 * 32 + 1) * ldl_ks(32) + 2 * 32;
-  kc->flag_count = 16;
-  const size_t o_H = carve((size_t)3 * (N + 6) * kk, D), o_g = carve((size_t)(N + 1) * K, D), o_step = carve((size_t)(N + 1) * K, D);
-  const size_t o_U = carve((size_t)(N + 1) * 32 * 36, D), o_Hs = carve((size_t)(N + 1) * 32 * 36, D), o_E = carve((size_t)(N + 1) * 32 * 36, D);
-  const size_t o_Ds = carve((size_t)(N + 1) * 32, D), o_dbg = carve((size_t)(N + 4) * 8 * 32, D);
-  const size_t o_xch = carve(2 * kc->xch_count, D), o_flags = carve(kc->flag_count, sizeof(unsigned));
-  const size_t o_ndcnt = carve(4 * ND_MAXROWS, sizeof(unsigned long long)), o_pipecnt = carve(4 * ND_MAXROWS, sizeof(unsigned long long));
-  const size_t o_ndbuf = carve((size_t)nd_layout(32).end, D);
-  const bool nd_wst_on = K > 20 && K <= 32;
-  const size_t o_ndwst = carve(nd_wst_on ? 2 * (size_t)ND_MAXROWS * nd_layout(K).frow : 1, D);
+  const idto_host::SolverBuffers sb = idto_host::SolverBufferCounts(K, N);
+  kc->xch_count = sb.xch_count;
+  kc->flag_count = sb.flags;
+  const size_t o_H = carve(sb.bands, D), o_g = carve((size_t)(N + 1) * K, D), o_step = carve((size_t)(N + 1) * K, D);
+  const size_t o_U = carve(sb.factors, D), o_Hs = carve(sb.factors, D), o_E = carve(sb.factors, D);
+  const size_t o_Ds = carve(sb.dinv, D), o_dbg = carve(sb.dbg, D);
+  const size_t o_xch = carve(sb.xch, D), o_flags = carve(kc->flag_count, sizeof(unsigned));
+  const size_t o_ndcnt = carve(sb.rowcnt, sizeof(unsigned long long)), o_pipecnt = carve(sb.rowcnt, sizeof(unsigned long long));
+  const size_t o_ndbuf = carve(sb.nd_buf, D);
+  const bool nd_wst_on = sb.has_wst;
+  const size_t o_ndwst = carve(sb.nd_wst, D);
   kc->pstride = (top + 255) & ~(size_t)255;
   {
     void* p = nullptr;
@@ -2213,8 +2077,7 @@ static int MakeKkt(idto_hip_ctx* c, int nu) {
   return 0;
 }
 
-static bool AsmInSolver(idto_hip_ctx* c);
-static bool DecideInSolver(idto_hip_ctx* c);
+static bool AsmInSolver(const idto_hip_ctx* c, SolverPlan* p);
 // Delta0s / Delta_out: one radius per problem of the context; rows_host: [batch][iterations][TRR_COUNT]
 static int TrSolve(idto_hip_ctx* c, int iterations, int scaling_method, int scaling, int normalize_quaternions,
                    const double* Delta0s, double Delta_max, double eta, const int* constrained_dofs, int nu,
@@ -2283,7 +2146,7 @@ static int TrSolve(idto_hip_ctx* c, int iterations, int scaling_method, int scal
   // (blocks of nq + nu up to the 30 x 30 instantiation of the two-workgroup factorisation: allegro's 23 + 6, N = 60,
   // 0.523 against 0.665 ms per iteration with the Schur-complement chain; the 32 x 32 one needs a third elimination
   // wavefront and spills: 442 against 245 us at N = 20)
-  const bool use_kkt = nu > 0 && c->con_kkt && SolverBlockSize(c->nq + nu, true) <= 30;
+  const bool use_kkt = nu > 0 && c->con_kkt && idto_host::SolverBlockSize(c->nq + nu, true) <= 30;
   if (B != 1 && nu > 0 && !use_kkt) { g_err = "tr_solve: enforced constraints on a batch need the banded KKT step (nq + nu <= 30, option con_kkt)"; return -1; }
   if (use_kkt) {
     if ((rc = ConstraintDofs(c, constrained_dofs, nu)) != 0) return rc;
@@ -2304,19 +2167,13 @@ static int TrSolve(idto_hip_ctx* c, int iterations, int scaling_method, int scal
   }
   // (the small models' one-workgroup launch, gn_small.h: unconstrained, or with ONE enforced constraint through the banded
   // KKT step - the instantiations: acrobot 2 + 1, spinner 3 + 1 - whose context the scalar band solver takes)
-  bool tr_small = c->tr_small && lookahead && SmallEligible(c) && c->h_assembled;
-  if (tr_small && nu > 0) {
-    LdlPlan kp;
-    tr_small = use_kkt && nu == 1 && c->kkt->batch == c->batch && PlanLdl(c->kkt, false, &kp) == 0 && BandEligible(c->kkt, kp, true) &&
-               kp.k == c->nq + 1 && SmallLds(c, kp, nullptr) <= 160 * 1024;
-  }
+  SolverPlan small_plan;   // of the system the launch solves: H's, or the KKT context's
+  bool tr_small = c->tr_small && lookahead && SmallEligible(c, &small_plan) && c->h_assembled;
+  if (tr_small && nu > 0)
+    tr_small = use_kkt && nu == 1 && c->kkt->batch == c->batch && Plan(c->kkt, true, WholeStep(c), &small_plan) == 0 && small_plan.k == c->nq + 1;
   bool kkt_built = false;
-  bool tr_fold_fits = false;
-  if (tr_small) {   // (the folded iteration's arrays live in the band solver's carve-up)
-    LdlPlan sp;
-    int band = 0;
-    if (PlanLdl(nu > 0 ? c->kkt : c, false, &sp) == 0) { (void)SmallLds(c, sp, &band); tr_fold_fits = gn_small_fold_doubles(c->N, c->nq) <= band; }
-  }
+  // (the folded iteration's arrays live in the band solver's carve-up)
+  const bool tr_fold_fits = tr_small && gn_small_fold_doubles(c->N, c->nq) <= small_plan.lds_small;
   TrConvergence conv{};
   conv.on = c->tr_conv_on ? 1 : 0;
   conv.rel_cost = c->tr_conv_tol[0]; conv.abs_cost = c->tr_conv_tol[1]; conv.rel_grad = c->tr_conv_tol[2];
@@ -2368,7 +2225,7 @@ static int TrSolve(idto_hip_ctx* c, int iterations, int scaling_method, int scal
       Ke.N = c->N; Ke.nq = c->nq; Ke.nv = c->nv; Ke.nu = nu;
       Ke.z = kc->step; Ke.slab = c->slab; Ke.slab_stride = c->slab_stride; Ke.dofs = c->con_dofs;
       Ke.w = c->con_out; Ke.jtl = c->con_out + n; Ke.lambda = c->con_lambda;
-      Ke.Dinv = kc->Dst; Ke.dstride = SolverBlockSize(kc->nq, true); Ke.first_row = SolverFirstRow(kc);
+      Ke.Dinv = kc->Dst; Ke.dstride = idto_host::SolverBlockSize(kc->nq, true); Ke.first_row = idto_host::SolverFirstRow(kc->h_assembled, kc->N);
       Ke.state = c->tr_state; Ke.alt = c->alt_r;
       Ke.pstride = c->pstride; Ke.kstride = kc->pstride;
       kkt_fold = c->kkt_fold;
@@ -2450,7 +2307,7 @@ static int TrSolve(idto_hip_ctx* c, int iterations, int scaling_method, int scal
     if (tr_small) {
       // a small all-revolute model: the trial point's evaluation, its cost, the decision and - accepted - g, H and the next
       // step in ONE workgroup of ONE launch (gn_small.h), the bits of the three launches below
-      rc = LaunchSmall(c, &Dc, !more, c->alt_w, nu > 0, fold ? &T : nullptr);
+      rc = LaunchSmall(c, small_plan, &Dc, !more, c->alt_w, nu > 0, fold ? &T : nullptr);
       if (rc) return rc;
       if (!more) break;
       continue;
@@ -2460,7 +2317,9 @@ static int TrSolve(idto_hip_ctx* c, int iterations, int scaling_method, int scal
     c->fd_full = lookahead && more;   // (v, N+ of the trial point = of the iterate the gated assembly runs for)
     // the cost of the trial point and the decision: a launch of their own (cost_kernel), or one more workgroup of the
     // pipelined solver's launch that follows (penta_pipe.h PipeAsm::decide, option "decide_in_solver")
-    const bool decide_in_solver = !rc && more && lookahead && nu == 0 && c->decide_in_solver && AsmInSolver(c) && DecideInSolver(c);
+    SolverPlan sp;   // the next solve's, when its launch is to carry the gated assembly
+    const bool asm_in_solver = !rc && more && lookahead && nu == 0 && c->h_assembled && AsmInSolver(c, &sp);
+    const bool decide_in_solver = asm_in_solver && c->decide_in_solver && sp.can_decide;
     if (!rc && !decide_in_solver)
       hipLaunchKernelGGL(cost_kernel, dim3(1, B), dim3(1024), c->cost_lds, c->stream, c->M, c->P, c->q, c->v, c->slab,
                          c->slab_stride, c->cost, c->weights_diagonal ? 1 : 0, (double*)nullptr, c->pstride,
@@ -2469,24 +2328,14 @@ static int TrSolve(idto_hip_ctx* c, int iterations, int scaling_method, int scal
     if (rc) return rc;
     HIP_OK(hipGetLastError());
     if (!more) break;
-    if (lookahead && nu == 0 && AsmInSolver(c)) {
+    if (asm_in_solver) {
       // the gated assembly inside the pipelined solver's launch (penta_pipe.h PipeAsm): a problem whose step was
       // rejected keeps g and H and the solver reads them where they are -> the same step
       DropPrefetch(c, {IDTO_ARR_GRADIENT, IDTO_ARR_H_A, IDTO_ARR_H_B, IDTO_ARR_H_C, IDTO_ARR_HBANDS});
       c->con_ready = false; c->con_begun = false;
-      c->fuse_asm_next = true;
-      c->fuse_gate = c->tr_state + TRS_ACCEPTED;
-      c->fuse_decide = decide_in_solver ? &Dc : nullptr;
-      rc = idto_hip_factor_solve(c, nullptr, 1, nullptr);
-      c->fuse_gate = nullptr;
-      if (c->fuse_decide) {
-        c->fuse_decide = nullptr;
-        if (!rc) { g_err = "tr_solve: the solver's launch that was to decide on the trial point did not run"; rc = -1; }
-      }
-      if (c->fuse_asm_next) {
-        c->fuse_asm_next = false;
-        if (!rc) { g_err = "tr_solve: the solver that was to assemble g and H did not run"; rc = -1; }
-      }
+      SolverExtras ex;
+      ex.assemble = true; ex.gate = c->tr_state + TRS_ACCEPTED; ex.decide = decide_in_solver ? &Dc : nullptr;
+      rc = FactorSolve(c, nullptr, 1, nullptr, nullptr, &sp, ex);
     } else if (lookahead) {
       if (nu > 0 && use_kkt && c->kkt_in_asm) {
         // (the next iteration's KKT system written by this assembly: a rejected step keeps g, H - and the system, which the
@@ -2636,7 +2485,7 @@ int idto_hip_tr_solve_batch_constrained(idto_hip_ctx* c, int iterations, int sca
   // the banded KKT step (kkt.h) is a sequence of launches with grid.y = problem like everything else of the loop: one
   // launch set per iteration for the whole batch.  The Schur-complement route (option con_kkt = 0, or nq + nu > 30) is
   // single-problem launches: a child context, stream and host thread per problem.
-  if (c->con_kkt && SolverBlockSize(c->nq + nu, true) <= 30 && c->weights_diagonal) {
+  if (c->con_kkt && idto_host::SolverBlockSize(c->nq + nu, true) <= 30 && c->weights_diagonal) {
     if (int rc = idto_hip_eval_tau(c)) return rc;   // (the loop starts from the cost of the resident q; the other route evaluates it per problem)
     return TrSolve(c, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu, rows_host, Delta_out);
   }
@@ -2905,40 +2754,25 @@ int idto_hip_set_option(idto_hip_ctx* c, const char* name, int value) {
   return -1;
 }
 
-// Does idto_hip_gn_step's solve take the pipelined kernel with the assembly inside (the conditions of LaunchAssemble's
-// products path and of LaunchNd's pipelined branch, evaluated as they will be once the bands count as assembled)?
-static bool AsmInSolver(idto_hip_ctx* c) {
+// Can idto_hip_gn_step's solve carry the assembly (the conditions of LaunchAssemble's products path; *p: the plan of
+// that solve, made for the bands as they will be once they count as assembled)?  p->can_decide: ... and the decision on
+// the trust-region loop's trial point
+static bool AsmInSolver(const idto_hip_ctx* c, SolverPlan* p) {
   if (!(c->asm_in_solver && c->solver_pipe && !c->reference_solver)) return false;
   if (!(c->weights_diagonal && c->terms_valid && c->fd_full && c->asm_stop == 0)) return false;
-  const bool was = c->h_assembled;
-  c->h_assembled = true;   // (the plan's first row depends on it)
-  LdlPlan p;
-  const bool ok = PlanLdl(c, false, &p) == 0 && (BandEligible(c, p) || (p.K <= 20 && NdEligible(c, p) && 5 * c->batch <= 64));
-  c->h_assembled = was;
-  return ok;
-}
-
-// (AsmInSolver holds) is the launch the pipelined chains' - the kernel that can also decide on the trial point - and one
-// of its DEC instantiations?
-static bool DecideInSolver(idto_hip_ctx* c) {
-  const bool was = c->h_assembled;
-  c->h_assembled = true;
-  LdlPlan p;
-  const bool ok = PlanLdl(c, false, &p) == 0 && !BandEligible(c, p) && NdEligible(c, p) && c->solver_pipe && (p.K == 5 || p.K == 19) &&
-                  c->cost_lds <= 160 * 1024;
-  c->h_assembled = was;
-  return ok;
+  return Plan(c, true, SolveRequest{}, p) == 0 && p->can_assemble;
 }
 
 int idto_hip_gn_step(idto_hip_ctx* c) {
   HIP_OK(hipSetDevice(c->device));
   if (c->spec_ready) return 0;   // already enqueued for this q by idto_hip_tr_trial (speculation)
   c->spec_pending = false;
+  SolverPlan p;
   if (FusedEligible(c)) return LaunchFused(c);
-  if (SmallEligible(c)) return LaunchSmall(c);
+  if (SmallEligible(c, &p)) return LaunchSmall(c, p);
   int rc = idto_hip_eval_partials(c);
   if (rc) return rc;
-  if (AsmInSolver(c)) {
+  if (AsmInSolver(c, &p)) {
     // two launches: the pipelined solver's grid carries the assembly (LaunchNd).  LaunchAssemble's bookkeeping:
     DropPrefetch(c, {IDTO_ARR_GRADIENT, IDTO_ARR_H_A, IDTO_ARR_H_B, IDTO_ARR_H_C, IDTO_ARR_HBANDS});
     if (!c->h_assembled) {
@@ -2946,13 +2780,9 @@ int idto_hip_gn_step(idto_hip_ctx* c) {
       c->h_assembled = true;
     }
     c->con_ready = false; c->con_begun = false;
-    c->fuse_asm_next = true;
-    rc = idto_hip_factor_solve(c, nullptr, 1, nullptr);
-    if (c->fuse_asm_next) {   // (nobody took it: the solve went another way than AsmInSolver foresaw)
-      c->fuse_asm_next = false;
-      if (!rc) { g_err = "gn_step: the solver that was to assemble g and H did not run"; rc = -1; }
-    }
-    return rc;
+    SolverExtras ex;
+    ex.assemble = true;
+    return FactorSolve(c, nullptr, 1, nullptr, nullptr, &p, ex);
   }
   rc = idto_hip_grad_hess(c);
   if (rc) return rc;

@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "penta_pipe.h"
+#include "solver_layout.h"
 
 namespace idto_dev {
 
@@ -50,31 +51,7 @@ struct BandArgs {
   double* ts;                            // debug stamps or nullptr
 };
 
-// The split and the LDS carve-up (doubles).  First chain: pivots 0 .. m - 1 (m a multiple of W), then the W middle rows
-// m .. lim - 1 (three whole blocks; w would do); mirrored chain: the nb rows behind them in the order band_mirror
-// gives them, `pad` identity pivots in front.  Columns of a copy: FRONT zero columns (the back substitution's reads
-// above row 0 and its blocks of four steps run into them), the chain's own, 2 W + 1 padding columns (identity behind the first chain's, zero behind
-// the mirrored chain's: those only collect its Schur complement).
-struct BandLds { int m, lim, nb, pad, tcols, bcols, T, Bm, Dt, Db, D0, J, end; };
-constexpr int BAND_FRONT = 32;
-__host__ __device__ inline BandLds band_layout(int M, int W) {
-  BandLds L;
-  L.m = ((M - W) / 2 + W / 2) / W * W;
-  L.lim = L.m + W;
-  L.nb = M - W - L.m;
-  L.pad = (W - L.nb % W) % W;
-  L.tcols = BAND_FRONT + L.lim + 2 * W + 1;
-  L.bcols = BAND_FRONT + L.pad + L.nb + 2 * W + 1;
-  int o = 0;
-  L.T = o; o += L.tcols * 16;
-  L.Bm = o; o += L.bcols * 16;
-  L.Dt = o; o += L.tcols;
-  L.Db = o; o += L.bcols;
-  L.D0 = o; o += M + (M & 1);   // the diagonal entries as assembled (pivot test)
-  L.J = o; o += W * 16;   // the mirrored chain's window at the join, [slot][lane]
-  L.end = o;
-  return L;
-}
+// (BandLds / band_layout: solver_layout.h)
 
 template <int I, int N, class Fn>
 __device__ __forceinline__ void band_static_for(Fn&& f) {

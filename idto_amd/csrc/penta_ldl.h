@@ -40,6 +40,7 @@
 #include <hip/hip_runtime.h>
 
 #include "batch.h"
+#include "solver_layout.h"
 
 namespace idto_dev {
 
@@ -164,49 +165,7 @@ __device__ __forceinline__ double ldl_eliminate_wave(double (&xr)[K], int lane, 
   return fast_rcp(__hiloint2double(dhi, dlo));
 }
 
-// Column stride (in doubles) of every K-row block kept in LDS and of the row-major factor blocks:
-// even (16-byte aligned columns for ds_read_b128), = 2 mod 4, i.e. an odd number of 16-byte
-// units, so that consecutive columns start in different LDS bank groups, and >= 4 ceil(K/4): the
-// MFMA k-steps read rows up to 4 ceil(K/4) - 1 of a column (zero pad rows).
-__host__ __device__ constexpr int ldl_ks(int K) { return 4 * ((K + 3) / 4) + 2; }
-
-struct PentaLdlLds {  // offsets in doubles
-  int W, Ht, Et, Iv, rt, U, G, in, dump, yh, ye, Eb, bl, bl_size, xall, end;
-  int kks, rts;
-};
-// `rows` (> 0, single right-hand side): the chain's local rows incl. pseudo-rows - the right-hand side and rt / x of
-// every row are indexed by LOCAL row, so a workgroup of the two-sided elimination needs its own half only
-__host__ __device__ inline PentaLdlLds penta_ldl_layout(int n, int K, int nrhs, int rows = 0) {
-  PentaLdlLds L;
-  const int ks = ldl_ks(K), ncr = 2 * K + nrhs;
-  L.kks = K * ks;
-  L.rts = nrhs * ks;
-  int o = 0;
-  L.W = o; o += (K + ncr) * ks;   // augmented block [S | H | E | y], column-major, stride ks
-  L.Ht = o; o += 2 * L.kks;       // ring: Ht_i, Ht_{i-1}
-  L.Et = o; o += 3 * L.kks;       // ring: Et_i, Et_{i-1}, Et_{i-2}
-  L.Iv = o; o += 3 * ks;          // ring: 1/diag(U) (padded to ks)
-  L.rt = o; o += 3 * L.rts;       // ring: rt_i (forward) / x_i (backward)
-  L.U = o; o += 2 * L.kks;        // ring: U_i, U_{i-1} (write-back staging)
-  L.G = o; o += (K * K + 1) & ~1; // Et_{i-1}^T Dn Et_{i-1} for the next row (even size: what follows is read as double2;
-                                  // b128 reads off a 16-byte boundary halve the LDS throughput)
-  {                               // staged A_i, B_{i+1}, C_i, A_{i+2}; reused by the backward pass
-    const int fwd = 4 * K * K, bwd = 3 * K * ks + ks;
-    L.in = o; o += ((fwd > bwd ? fwd : bwd) + 1) & ~1;
-  }
-  L.dump = o; o += 2;             // write target of staging lanes without a slot
-  L.yh = o; o += 2 * ks;          // y-push rings: (Ht_i^T Dn rt_i) of the last two rows ...
-  L.ye = o; o += 3 * ks;          // ... and (Et_i^T Dn rt_i) of the last three
-  L.Eb = o; o += 2 * L.kks;       // E_i = A_{i+2}^T staged straight in column layout (row parity)
-  L.bl = o;
-  const int nr = (rows > 0 && nrhs == 1 && rows < n) ? rows : n;
-  L.bl_size = (nrhs * n * K <= 4096) ? nrhs * nr * K : 0;
-  o += (L.bl_size + 1) & ~1;      // right-hand sides staged in LDS when small ...
-  L.xall = o;                     // ... and rt_i / x_i of every row: [j][n + 2][ks], two leading zero rows
-  o += L.bl_size ? nrhs * (nr + 2) * ks : 0;
-  L.end = o;
-  return L;
-}
+// (ldl_ks, PentaLdlLds / penta_ldl_layout, ldl_two_sided_rows: solver_layout.h)
 
 // Role of one workgroup of the factorisation.  The two-workgroup ("twisted") kernel uses two of
 // them: the top one eliminates rows 0 .. m-1 top-down and then the two join rows m, m+1 (joiner),
@@ -1108,12 +1067,6 @@ penta_ldl_body(int n, int k, const double* __restrict__ HA, const double* __rest
   penta_ldl_tail<K, NT>(n, k, nrhs, x, Ust, Hst, Est, Dst, dbg, cfg, xch, flags, epoch, L.xall, L.bl_size, L.W, nfwd);
 }
 
-// local rows (incl. the producer's two pseudo-rows, + 2 spare) either workgroup of the two-sided kernel touches
-__host__ __device__ inline int ldl_two_sided_rows(int n, int m_split, int nrhs) {
-  if (m_split <= 0 || nrhs != 1) return 0;
-  const int top = m_split + 2, bottom = n - m_split;
-  return (top > bottom ? top : bottom) + 2;
-}
 // the two roles of the two-workgroup kernel (m_split = 0: one workgroup, the whole system)
 __host__ __device__ inline ChainCfg two_sided_cfg(int n, int m_split, int side) {
   ChainCfg c = {};

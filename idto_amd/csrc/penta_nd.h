@@ -31,10 +31,9 @@
 
 #include <type_traits>
 #include "penta_ldl.h"
+#include "solver_layout.h"
 
 namespace idto_dev {
-
-enum { ND_MAXROWS = 32 };  // local rows of a joiner chain (incl. its two join rows)
 
 struct NdArgs {
   int n, k;
@@ -71,22 +70,7 @@ __device__ __forceinline__ void nd_ts(const NdArgs& A, int role, int slot) {
   if (A.ts && threadIdx.x == 0) A.ts[role * 64 + slot] = (double)wall_clock64();
 }
 
-struct NdBuf { int rtpub, fst, frow, xsep, ll, joinll, joinll_pair, end; };  // offsets in doubles; rtpub / fst are [2][...]
-__host__ __device__ inline NdBuf nd_layout(int K) {
-  NdBuf L;
-  const int ks = ldl_ks(K), ct2 = (2 * K + 1 + 15) / 16;   // columns [Ft | rt], in tiles of 16
-  int o = 0;
-  L.rtpub = o; o += 2 * ND_MAXROWS * K;
-  L.frow = 16 * ct2 * ks;                // doubles per published row (whole 16-column tiles: the separator's MFMA loads)
-  L.fst = o; o += 2 * ND_MAXROWS * L.frow + 16 * ks;
-  L.xsep = o; o += 2 * K;
-  o += o & 1;
-  L.ll = o; o += 3 * 4 * K;              // flagged copies (ll_store): x_sep, and the two join rows of each producer / joiner pair
-  L.joinll = o; L.joinll_pair = 2 * 2 * K * 64;            // [pseudo row][r][column: 64 lanes] of 16-byte slots   // penta_pipe.h: a producer's Schur-complement contributions to the join rows, flagged
-  o += 2 * L.joinll_pair;
-  L.end = o;
-  return L;
-}
+// (ND_MAXROWS, NdBuf / nd_layout, nd_sep_lds_doubles: solver_layout.h)
 
 // tile t of the lower triangle of a tile grid, row by row: (0,0) (1,0) (1,1) (2,0) (2,1) (2,2) ...
 __host__ __device__ constexpr int nd_tile_row(int t) { int tr = 0; while (t > tr) { t -= tr + 1; ++tr; } return tr; }
@@ -396,15 +380,6 @@ __device__ __forceinline__ void nd_spike(const NdArgs& A, const int w) {
   nd_ts(A, 4 + w, 1);
 }
 
-// doubles of the separator's Q: per spike workgroup the lower-triangle tiles of Q as the matrix cores leave them
-// ([tile][register][lane]: stored and summed without a condition or a transposed copy)
-__host__ __device__ constexpr int nd_sep_q_tiles(int K) { return ((2 * K + 1 + 15) / 16) * ((2 * K + 1 + 15) / 16 + 1) / 2; }
-__host__ __device__ constexpr int nd_sep_q_doubles(int K) { return 2 * nd_sep_q_tiles(K) * 256; }
-// (the whole carve-up of nd_separator)
-__host__ __device__ inline int nd_sep_lds_doubles(int K) {
-  const int ks = ldl_ks(K);
-  return nd_sep_q_doubles(K) + (2 * K + 1) * ks + (K + 1) * ks + 2 * K * ks + K * ks + 4 * ks + 2;
-}
 
 // ---- separator workgroup
 // While the chains run: wavefronts 0, 1 accumulate Q of spike workgroup 0, wavefronts 2, 3 of spike

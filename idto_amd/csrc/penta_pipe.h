@@ -30,76 +30,11 @@
 
 #include "kernels.h"
 #include "penta_nd.h"
+#include "solver_layout.h"
 
 namespace idto_dev {
 
-// positions (in doubles) inside one published row; every part starts at an even position so that pairs are
-// 16-byte aligned for ds_read_b128
-template <int K>
-struct PipeGeo {
-  static constexpr int KE = K + (K & 1);
-  static constexpr int KR = 4 * ((K + 3) / 4);        // rows of a ring slot (pad rows stay zero: MFMA k-steps)
-  static constexpr int oS = 0, oH = KE, oE = 2 * KE, oy = 3 * KE, oF = 3 * KE + 2;
-  static constexpr int od = oF + 2 * K;               // the main wavefront's "row published" word (NaN until then)
-  static constexpr int og = od + 1;                   // the spike wavefront's
-  static constexpr int oi = og + 1;                   // 1 / d_j
-  static constexpr int odump = oi + 1;                // 8 positions written by lanes that hold no column
-  static constexpr int oz = odump + 8;                // a position that stays zero
-  // the parts the follower multiplies with, once more UNscaled: W_{i+1}[r][c] -= (Ht[j][r] / d_j) * Ht[j][c] with the
-  // second factor as it sits in the eliminating wavefront's registers (recomputing it as scaled * d costs two more
-  // roundings per term: measurably less accurate at cond(H) ~ 1e12)
-  static constexpr int oRH = oz + 1 + ((oz + 1) & 1), oRE = oRH + KE, oRy = oRE + KE;
-  static constexpr int used = oRy + 1;
-  static constexpr int RS = ((used + 15) / 32) * 32 + 16;   // = 16 mod 32: the four k-rows of an MFMA operand read hit different banks
-  static constexpr int SLOT = KR * RS;
-  static constexpr int GS = ldl_ks(K);                // column stride of the staged inputs and of G
-  static constexpr int NCX = 3 * K + 1;               // columns [S | H | E | y] of the main wavefront
-  static constexpr int NGC = KE + 2 + 2 * K;          // columns of G: [S-part (K, padded to KE) | y | . | F (2K)]
-  static_assert(3 * K <= 61, "main wavefront: 3K + 1 columns and the lane that publishes d");
-  static_assert(RS >= used && RS % 32 == 16, "row stride");
-};
-
-// The follower that eliminates next ("low" follower) takes rows 0 .. RLO-1 of the next block row, the wavefront that
-// has just eliminated takes the rest and hands them over through LDS (PipeRows below).  K >= 17: RLO = 16, ONE row tile
-// of the matrix cores - the low follower forms Ht^T Dn [Ht | Et | rt] (spike wavefronts: Ht^T Dn Ft) for its 16 rows
-// with v_mfma_f64_16x16x4, a k-step per four published pivots (pipe_follow_mfma), instead of K rank-one updates
-// with broadcast multipliers.
-template <int K>
-constexpr int pipe_rlo() { return K >= 17 ? 16 : (K >= 3 ? (((K + 1) / 2 + 1) & ~1) : K); }
-template <int K>
-constexpr bool pipe_mfma_follow() { return K >= 17; }
-// the low follower's products leave the matrix cores as tiles (lane = (k-row, column), register = row); the wavefront
-// turns them into its own layout (lane = column, register = row) through a scratch of its own: PIPE_HPC product columns
-// (three column tiles) + one column that stays zero (lanes whose column takes no update), column stride PIPE_HS (16 rows;
-// 36 dwords: eight lanes' 16-byte reads cover the 32 banks once)
-constexpr int PIPE_HPC = 48, PIPE_HS = 18, PIPE_HPN = (PIPE_HPC + 1) * PIPE_HS;
-
-struct PipeLds {   // offsets in doubles
-  int ring, stage, gbuf, xhi, hp, jbuf, xall, W, flags, end;
-};
-template <int K>
-__host__ __device__ inline PipeLds pipe_layout(int n, bool spike) {
-  using G = PipeGeo<K>;
-  PipeLds L;
-  int o = 0;
-  L.ring = o; o += 3 * G::SLOT;
-  // (the main columns only: the spike wavefronts take their first two rows' inputs straight from the band arrays.
-  // Rounds 3-5 reserved 2 x 2K more columns here that nothing wrote or read: 12 KB at K = 19)
-  L.stage = o; o += 2 * G::NCX * G::GS + 2;   // (+ a dump double)
-  L.gbuf = o; o += 2 * G::NGC * G::GS;
-  {   // the second follower's rows of the next block row, [column][row] (+ a dump column)
-    constexpr int NHI = K - pipe_rlo<K>();
-    L.xhi = o; o += (G::NCX + (spike ? 2 * K : 0) + 1) * (NHI + (NHI & 1)) + 2;
-  }
-  L.hp = o; o += pipe_mfma_follow<K>() ? (spike ? 2 : 1) * PIPE_HPN : 0;   // pipe_follow_mfma's scratch: main wavefronts, spike wavefronts
-  (void)n;
-  L.jbuf = o; o += spike ? (3 * K + 2) * G::KE : 0;   // a joiner: the producer's contributions to its two join rows, columns [S | H | y], [S | y]
-  L.xall = o; o += (ND_MAXROWS + 2) * G::GS;   // rt of the chain's local rows (two leading zero rows)
-  L.W = o; o += 2 * G::KE + 2;
-  L.flags = o; o += 32;            // 64 ints
-  L.end = o;
-  return L;
-}
+// (PipeGeo, pipe_rlo, pipe_mfma_follow, PIPE_HPC / HS / HPN, PipeLds / pipe_layout<K>: solver_layout.h)
 
 // flag words (ints, values = local row + 1)
 enum {
@@ -1223,15 +1158,7 @@ __device__ __forceinline__ void pipe_forward(const PipeArgs& A, const ChainCfg& 
 //   x_i = c_i - Y_i x_{i+1} - Z_i x_{i+2},
 // two dense K x K mat-vecs per row with x passed through LDS: ~0.12 us per row.
 // LDS (everything the forward pass used is free): per local row [Y | Z] row-major (stride 2 KE), W likewise, c.
-template <int K, bool SPK>
-struct PipeBack {
-  // (a row-major block also stages D^-1 U, stride ks.  Row stride: not a multiple of 16 dwords, or the rows that the
-  // lanes of the recursion read - one row per lane, ds_read_b128 - start in 2 (K = 23: 96 dwords) or 4 (K = 19: 80) of the
-  // 16 bank groups; K = 29: 120 dwords, 8 groups, left alone - two more doubles per row and 11 rows of the KKT system
-  // at N = 40 no longer fit)
-  static constexpr int KE = K + (K & 1), YS0 = 2 * KE > ldl_ks(K) ? 2 * KE : ldl_ks(K), YS = YS0 + (YS0 % 8 == 0 ? 2 : 0);
-  static constexpr int oYZ = 0, oW = K * YS, oC = oW + (SPK ? K * YS : 0), BS = oC + KE;
-};
+// (PipeBack: solver_layout.h)
 
 // v[lane] + v[lane ^ 32] in every lane: one v_permlane32_swap per 32-bit half (a ds_bpermute round trip costs ~100 cycles)
 __device__ __forceinline__ double pipe_half_sum(double v) {
@@ -1525,19 +1452,7 @@ __device__ __forceinline__ void pipe_backward(const PipeArgs& A, const ChainCfg&
 // ---- the seven-workgroup kernel's chains (penta_nd.h, K = 23 / 29) take their back substitution in the same form.
 // Their forward pass (penta_ldl_body) leaves rt of the local rows at xall_off, in the middle of what the recursion
 // matrices will occupy: the rows move to the top of the launch's LDS first.
-// -> the number of the producer's wavefronts that work on the partner's rows (each stages a block D^-1 U of its own), 0: does not fit
-template <int K>
-__host__ __device__ inline int pipe_recursion_tail_fits(int lds_doubles, int nloc_joiner, int nloc_producer) {
-  using B = PipeBack<K, false>;
-  constexpr int ks = ldl_ks(K);
-  const int nloc = nloc_joiner > nloc_producer ? nloc_joiner : nloc_producer;
-  if (!(nloc_joiner * B::BS + 6 * B::KE + 4 <= lds_doubles - (nloc_joiner + 2) * ks && (nloc + 2) * ks <= 4 * 256 &&
-        nloc_joiner * K <= 2 * 256))
-    return 0;
-  for (int w = 4; w >= 1; w >>= 1)
-    if (nloc_producer * B::BS + 6 * B::KE + 4 + w * K * ks <= lds_doubles - (nloc_producer + 2) * ks) return w;
-  return 0;
-}
+// (pipe_recursion_tail_fits: solver_layout.h)
 template <int K>
 __device__ void chain_recursion_tail(int n, int k, double* x, double* Ust, double* Hst, double* Est, double* Dst,
                                      const ChainCfg& cfg, unsigned epoch, int xall_off) {

@@ -292,3 +292,45 @@ def test_pipelined_solver_takes_mpc_horizons(name, N):
     assert err(p_nd) <= 4 * err(p_lu) + 16 * unc + 1e-12, (err(p_nd), err(p_before), err(p_lu))
     assert bwd(p_nd) <= 16 * bwd(p_lu) + 2e-13, (bwd(p_nd), bwd(p_lu))
     dev.close()
+
+
+@pytest.mark.parametrize("name,N,B,kind,assembly_in_solver", [
+    ("mini_cheetah", 15, 1, 1, False), ("mini_cheetah", 16, 1, 4, True),     # option nd_min_rows: 16 block rows
+    ("allegro_hand", 23, 1, 1, False), ("allegro_hand", 24, 1, 2, False),    # the seven-workgroup kernel's own minimum: 24
+    ("hopper", 9, 1, 1, False), ("hopper", 10, 1, 1, False),                 # two workgroups from 10 block rows on
+    ("hopper", 16, 12, 4, True), ("hopper", 16, 13, 4, False),               # the assembly rides along while 5 B <= 64
+    ("allegro_hand", 24, 36, 2, False), ("allegro_hand", 24, 37, 1, False),  # seven workgroups per problem while 7 B <= 256
+])
+def test_kernel_choice_on_either_side_of_a_threshold(name, N, B, kind, assembly_in_solver):
+    """host/solver_plan.cc PlanSolve at the thresholds the tests above do not straddle, at the smallest horizon that sits
+    on each: the kernel tests/golden/solver_plan.txt names for the size runs (rows `k 0 N B 1 0 1`; 4 with
+    IDTO_SOLVER_BAND = 0 for the hopper), reports a clean status, and its step agrees with the two-workgroup
+    factorisation's - for the sizes that take that one anyway, the one-workgroup factorisation's."""
+    cfg, model = load_config(name), load_model(name)
+    probs, qs = [], []
+    for b in range(B):
+        prob, sp, _ = make_problem(cfg, model, num_steps=N)
+        sp.scaling = False
+        sp.equality_constraints = False
+        prob.q_nom = prob.q_nom + 0.01 * b
+        probs.append(prob)
+        qs.append(synthetic_trajectory(cfg, model, N, seed=b, lower=0.01))
+    dev = hip.HipPath(model, probs if B > 1 else probs[0], sp)
+    dev.set_option("fused", 0)   # (the single-launch iteration has its own tests: this one is about the solver's launch)
+    step = (lambda: np.array([dev.get("step", b) for b in range(B)])) if B > 1 else (lambda: dev.get("step"))
+    if B > 1:
+        dev.set_q_batch(np.array(qs))
+    else:
+        dev.set_q(qs[0])
+    for _ in range(2):   # (a context's first step still counts block row 0; from the second on the system is rows 1 .. N)
+        dev.gn_step()
+    assert dev.get_option("last_solver") == kind
+    assert (dev.get_option("last_assembly") == 4) == assembly_in_solver
+    assert (dev.solver_status_batch() == [False] * B) if B > 1 else (dev.solver_status() == (False, 0))
+    p = step()
+    dev.set_option("solver_nd" if kind != 1 else "two_sided", 0)
+    dev.gn_step()
+    assert dev.get_option("last_solver") == 1
+    ref = step()
+    assert np.abs(p - ref).max() <= 1e-3 * np.abs(ref).max()   # (two factorisations of the same system differ ~cond * eps)
+    dev.close()

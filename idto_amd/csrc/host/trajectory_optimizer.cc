@@ -1120,6 +1120,13 @@ bool TO::DeviceLoopEligible() const {
   // enforced constraints and the convergence criteria: only the resident loop (idto_hip_tr_solve) has them on the
   // device (multipliers by a single-workgroup LDL^T of S for n_eq <= 128, by the blocked one above; the criteria
   // by the iteration kernel that follows an accepted step)
+  if (constrained) {
+    // ... and it forms the multipliers on the two-set evaluation, which serves diagonal cost weights: with dense ones
+    // idto_hip_tr_solve declines (nu > 0), so the host loop takes the solve, as it does for the adaptive scalings
+    int weights_diagonal = 0;
+    Check(idto_hip_get_option(dev(), "weights_diagonal", &weights_diagonal));
+    if (!weights_diagonal) return false;
+  }
   return ResidentLoopEligible();
 }
 

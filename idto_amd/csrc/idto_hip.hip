@@ -230,7 +230,8 @@ struct idto_hip_ctx {
   double* terms = nullptr;                // per-record assembly products written by fd_kernel (asm_terms_stride)
   bool asm_fold = true;                   // option "asm_fold": fd_kernel forms them, assemble_terms_kernel combines
   bool terms_valid = false;               // ... and they belong to the resident slab, for every k
-  int last_assembly = 0;                  // 1 assemble_terms_kernel, 2 assemble_diag_kernel, 3 assemble_kernel
+  int last_assembly = 0;                  // 1 assemble_terms_kernel, 2 assemble_diag_kernel (also inside the fused launch), 3 assemble_kernel,
+                                          // 4 inside the solver's launch, 5 inside gn_small_kernel
   // launch geometry
   int fd_threads = 256, fd_lds = 0, asm_lds = 0, penta_lds = 0, solve_lds = 0, cost_lds = 0;
   // timing
@@ -1421,6 +1422,7 @@ static int LaunchFused(idto_hip_ctx* c) {
   const dim3 grid(A.nfd + 4 * A.nrows + (p.m_split > 0 ? 2 : 1));
   c->last_solver = 5;
   c->last_step_kind = 2;
+  c->last_assembly = 2;   // (assemble_diag_kernel's rows, run by the launch's assembly workgroups: not what an earlier path left)
   if (TimeBegin(c, 3)) return -2;
 #define FUSED_LAUNCH(MC, KM, PD, GW) \
   if (mc == MC && c->nq == KM) { hipLaunchKernelGGL((gn_fused_kernel<MC, KM, PD, GW>), grid, dim3(256), lds, c->stream, A); launched = true; }

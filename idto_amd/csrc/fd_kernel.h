@@ -189,8 +189,56 @@ IDTO_DEV void asm_dot_n(const double* const (&A)[U], const double* const (&B)[U]
 // TB x TB asm_dot values acc[ur][uc] = asm_dot(A[ur], B[uc]) from 2 TB operand reads per step instead
 // of 2 TB^2: the products are bound by LDS bandwidth (two 16-byte reads per two multiply-adds), a
 // register tile reads each operand once for TB results.  Same operations per entry: same bits.
-template <int TB>
-IDTO_DEV void asm_dot_tile(const double* const (&A)[TB], const double* const (&B)[TB], int nv, double (&acc)[TB][TB]) {
+// NV: nv where the kernel knows it at compile time (a tree shape, model_layout.h tree_shape_nv; 0: the run-time loop).  The
+// loop's prefetch of depth one is 36 multiply-adds against an LDS round trip on one wavefront per SIMD; with the trip count
+// a constant every operand read stands in front of the first product, and the products wait for their own reads only.
+// Register budget: 2 TB (NV / 2) double2 operands live at once - 216 vector registers at NV = 18, 264 at NV = 22 - beside the 18
+// of the accumulators.  That fits only because fd_kernel's block is one wavefront per SIMD (__launch_bounds__(256): 256 VGPRs and
+// 256 AGPRs a lane; what does not fit the VGPRs is moved through AGPRs, no scratch: tools/check_resources.py holds fd_kernel<4, 4>
+// at 0 spilled vector registers).  With more wavefronts per SIMD, or a larger NV, read the operands in halves.
+template <int TB, int NV = 0>
+IDTO_DEV void asm_dot_tile(const double* const (&A)[TB], const double* const (&B)[TB], int nv, double (&acc)[TB][TB]
+#ifdef IDTO_FD_STAMPS
+                           , long long* idto_fd_st = nullptr
+#endif
+) {
+  if constexpr (NV > 1) {
+    constexpr int NP = NV >> 1;
+    double2 a[NP][TB], b[NP][TB];
+#pragma unroll
+    for (int m = 0; m < NP; ++m)
+#pragma unroll
+      for (int u = 0; u < TB; ++u) {
+        a[m][u] = reinterpret_cast<const double2*>(A[u])[m];
+        b[m][u] = reinterpret_cast<const double2*>(B[u])[m];
+      }
+#pragma unroll
+    for (int m = 0; m < NP; ++m) {
+#pragma unroll
+      for (int ur = 0; ur < TB; ++ur)
+#pragma unroll
+        for (int uc = 0; uc < TB; ++uc) {
+          if (m == 0) acc[ur][uc] = a[m][ur].x * b[m][uc].x;
+          else acc[ur][uc] = acc[ur][uc] + a[m][ur].x * b[m][uc].x;
+          acc[ur][uc] = acc[ur][uc] + a[m][ur].y * b[m][uc].y;
+        }
+      // (the TB^2 chains stay in lockstep: left alone the compiler sinks each entry's whole chain into the branch of its
+      // store, one dependent chain after the other)
+#pragma unroll
+      for (int ur = 0; ur < TB; ++ur)
+#pragma unroll
+        for (int uc = 0; uc < TB; ++uc) asm volatile("" : "+v"(acc[ur][uc]));
+      if (m == 0) FD_STAMP(18);
+    }
+    if (NV & 1) {
+#pragma unroll
+      for (int ur = 0; ur < TB; ++ur)
+#pragma unroll
+        for (int uc = 0; uc < TB; ++uc) acc[ur][uc] = acc[ur][uc] + A[ur][NV - 1] * B[uc][NV - 1];
+    }
+    FD_STAMP(19);
+    return;
+  }
   const int np = nv >> 1;
   double2 a[TB], b[TB];
 #pragma unroll
@@ -205,6 +253,7 @@ IDTO_DEV void asm_dot_tile(const double* const (&A)[TB], const double* const (&B
       acc[ur][uc] = a[ur].x * b[uc].x;
       if (nv > 1) acc[ur][uc] = acc[ur][uc] + a[ur].y * b[uc].y;
     }
+  FD_STAMP(18);
   // (the operands of step m + 1 are read while step m is being accumulated: one wavefront per SIMD, nothing else
   // covers the LDS round trip)
   double2 an[TB], bn[TB];
@@ -238,6 +287,7 @@ IDTO_DEV void asm_dot_tile(const double* const (&A)[TB], const double* const (&B
 #pragma unroll
       for (int uc = 0; uc < TB; ++uc) acc[ur][uc] = acc[ur][uc] + A[ur][nv - 1] * B[uc][nv - 1];
   }
+  FD_STAMP(19);
 }
 
 // Per tau-index k, the products of the Gauss-Newton assembly that involve record k ONLY
@@ -276,7 +326,7 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
   const int tid = threadIdx.x, nt = blockDim.x;
   if (stop_after == 10) return;   // (profiling aid: the launch alone)
 #ifdef IDTO_FD_STAMPS
-  long long st_arr[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  long long st_arr[IDTO_FD_NSTAMPS] = {};
   long long* idto_fd_st = (tid == 0 || tid == IDTO_FD_STAMP_TID) ? st_arr : nullptr;
 #endif
   FD_STAMP(0);
@@ -319,13 +369,13 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
   const int blob_lo = FAST ? M.fast_lo : 0, blob_n = FAST ? M.fast_n : M.blob_n;
   int* colinfo = reinterpret_cast<int*>(mblob + blob_n + (blob_n & 1));  // [nq] non-zero rows of N+ column c
   // (terms != nullptr) the record and its weighted copy for the assembly products: 6 blocks of nq
-  // columns, column stride nvp (16-byte aligned columns), + tau_k R' and the diagonal of R'
+  // columns, column stride nvp (16-byte aligned columns), + the diagonal of R' and tau_k R'
   const int nvp = (nv + 1) & ~1, psz = nvp * nq;
   // (16-byte aligned: asm_dot reads double2; 8 bytes off, the products below took twice as long)
-  double* rec = reinterpret_cast<double*>(colinfo + nq + (nq & 1));   // [P | T | M | P R' | T R' | M R'] then diag R'
+  double* rec = reinterpret_cast<double*>(colinfo + nq + (nq & 1));   // [P | T | M | P R' | T R' | M R'] then diag R', tau R'
   rec += (rec - lds) & 1;
   // (SHAPE_XCH) the exchange area of the concurrent evaluations (fd_xch_doubles), behind the record and diag R'
-  double* xch = rec + (terms ? 6 * psz + nvp : 0);
+  double* xch = rec + (terms ? 6 * psz + 2 * nvp : 0);
 
   // N+_k and N+_{k+1} (TO.cc:1633-1647).  The model's table holds the constant entries (NaN where a quaternion block
   // goes); the 3 x 4 block of a floating joint is formed here, entry by entry, by twelve lanes of wavefront 0 (q_k) and of
@@ -345,6 +395,7 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
   // first of them is used: a loop `lds[i] = global[i]` waits for each of its loads in turn, and after a kernel
   // boundary none of them is an L2 hit - ten such round trips in a row were 7k of the kernel's 48k cycles.
   double* wr = rec + 6 * psz;      // [nv] diagonal of R' (fetched now: an HBM round trip off the tail's critical path)
+  double* tw = wr + nvp;           // [nvp] tau_k R', rounded: the A operand of the g rows of the products (16-byte aligned)
   constexpr int BU = 8;            // model words per thread in the batched part (the rest, if any, in a loop)
   double breg[BU];
 #pragma unroll
@@ -624,79 +675,100 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
 
   FD_STAMP(12);
   if (stop_after == 3) return;  // after the inverse-dynamics evaluations
-  // ---- outputs
+  // ---- outputs.  From here on a tree shape's kernel has its sizes as constants (model_layout.h tree_shape_nq / _nv; the host
+  // gives a model the shape only if they are its nq and nv): the divisions by nv and nb, the trip counts and the tile grid fold.
+  // GROWS: gP, gT, gM as row nq of the lower-triangle tiles (below).  The tree shapes' kernels; the generic evaluation's
+  // kernels (shape 0, SHAPE_XCH, SHAPE_STEM) keep the loop behind the tiles: fd_kernel<8, 0>, which spills vector registers
+  // to scratch, returned a wrong tau_k for the Jaco models with the rows in its tail.
+  constexpr bool GROWS = FAST;
+  constexpr bool CSIZES = FAST && SHAPE <= kNumSizedShapes;   // (model_layout.h: the example configurations' shapes)
+  constexpr int CNQ = CSIZES ? tree_shape_nq(SHAPE) : 0, CNV = CSIZES ? tree_shape_nv(SHAPE) : 0, CNVP = (CNV + 1) & ~1;
+  // t...: the tail's sizes - constants in a kernel of a sized shape, the run-time values in any other
+  const int tnq = CNQ ? CNQ : nq, tnv = CNQ ? CNV : nv, tbsz = CNQ ? CNV * CNQ : bsz, tnvp = CNQ ? CNVP : nvp, tpsz = CNQ ? CNVP * CNQ : psz;
   double* sl = slab + (size_t)k * slab_stride;
   double* Mk = sl;
-  double* Tk = sl + bsz;
-  double* Pk = sl + 2 * bsz;
-  double* tauk = sl + 3 * bsz;
-  for (int r = tid; r < nv; r += nt) tauk[r] = etau[r];
+  double* Tk = sl + tbsz;
+  double* Pk = sl + 2 * tbsz;
+  double* tauk = sl + 3 * tbsz;
+  for (int r = tid; r < tnv; r += nt) tauk[r] = etau[r];
+  if constexpr (GROWS)
+    if (terms && mode != 0)   // (the last threads: wavefront 0 is the one the record phase waits for)
+      for (int r = nt - 1 - tid; r < tnvp; r += nt) tw[r] = (r < tnv) ? etau[r] * wr[r] : 0.0;
   if (mode == 1) {
     // Two entries of each of the three blocks per thread and pass, every LDS read of the pass before the first division:
     // one wavefront per SIMD has nothing else to cover the reads' and the divisions' latencies with.
     //   dtau_k/dq_{k+1} (TO.cc:531), dtau_k/dq_k (:539), dtau_k/dq_{k-1} = (1/dt^2) M(q_{k+1}) N+_k (:556-561): the sum over j
     //   in the reference's order; the terms outside [j0, j0 + cnt) are exact zeros
     const double sc = 1 / dt / dt;
-    const double* Mcols = etau + (1 + nP + nT) * nv;  // column j = tau of mass evaluation j
+    const double* Mcols = etau + (1 + tnq + tnq) * tnv;  // column j = tau of mass evaluation j
     const double fillM = (k == 0) ? __builtin_nan("") : 0.0;
     constexpr int RU = 2;
-    for (int base = tid; base < bsz; base += RU * nt) {
+    for (int base = tid; base < tbsz; base += RU * nt) {
       int ii[RU], rr[RU], j0[RU], cnt[RU];
       bool ok[RU];
       double tp[RU], tt[RU], t0[RU], dqp[RU], dqt[RU], w[RU], mc[RU][3], n0[RU][3];
 #pragma unroll
       for (int u = 0; u < RU; ++u) {
         const int idx = base + u * nt;
-        ok[u] = idx < bsz;
+        ok[u] = idx < tbsz;
         const int id = ok[u] ? idx : 0;
-        ii[u] = id / nv; rr[u] = id - ii[u] * nv;
+        ii[u] = id / tnv; rr[u] = id - ii[u] * tnv;
         const int ci = colinfo[ii[u]];
         j0[u] = ci & 0xffff; cnt[u] = ci >> 16;
-        tp[u] = etau[(1 + ii[u]) * nv + rr[u]]; tt[u] = etau[(1 + nP + ii[u]) * nv + rr[u]]; t0[u] = etau[rr[u]];
-        dqp[u] = edq[1 + ii[u]]; dqt[u] = edq[1 + nP + ii[u]];
+        tp[u] = etau[(1 + ii[u]) * tnv + rr[u]]; tt[u] = etau[(1 + tnq + ii[u]) * tnv + rr[u]]; t0[u] = etau[rr[u]];
+        dqp[u] = edq[1 + ii[u]]; dqt[u] = edq[1 + tnq + ii[u]];
         w[u] = terms ? wr[rr[u]] : 0.0;
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
           const int j = (t < cnt[u]) ? j0[u] + t : j0[u];
-          mc[u][t] = Mcols[j * nv + rr[u]];
-          n0[u][t] = N0[ii[u] * nv + j];
+          mc[u][t] = Mcols[j * tnv + rr[u]];
+          n0[u][t] = N0[ii[u] * tnv + j];
         }
       }
+      FD_STAMP(13);
+      double pvs[RU], tvs[RU], accs[RU];
+#pragma unroll
+      for (int u = 0; u < RU; ++u) {
+        if (!ok[u]) continue;
+        pvs[u] = (tp[u] - t0[u]) / dqp[u];
+        tvs[u] = (k >= 1) ? (tt[u] - t0[u]) / dqt[u] : 0.0;
+        double acc = (sc * mc[u][0]) * n0[u][0];
+        if (cnt[u] > 1) acc += (sc * mc[u][1]) * n0[u][1];
+        if (cnt[u] > 2) acc += (sc * mc[u][2]) * n0[u][2];
+        accs[u] = acc;
+      }
+      FD_STAMP(14);
 #pragma unroll
       for (int u = 0; u < RU; ++u) {
         if (!ok[u]) continue;
         const int idx = base + u * nt, i = ii[u], r = rr[u];
-        const double pv = (tp[u] - t0[u]) / dqp[u];
-        const double tv = (k >= 1) ? (tt[u] - t0[u]) / dqt[u] : 0.0;
-        double acc = (sc * mc[u][0]) * n0[u][0];
-        if (cnt[u] > 1) acc += (sc * mc[u][1]) * n0[u][1];
-        if (cnt[u] > 2) acc += (sc * mc[u][2]) * n0[u][2];
+        const double pv = pvs[u], tv = tvs[u], acc = accs[u];
         const double mv = (k >= 2) ? acc : fillM;
         Pk[idx] = pv;
         Tk[idx] = tv;
         Mk[idx] = mv;
         if (terms) {   // ... and (A^T W)(r, l) = A(l, r) w_l, as assemble_diag_kernel forms it, by the thread that holds A(l, r)
           const double mr = (k >= 2) ? acc : 0.0;   // (never used by the assembly for k < 2)
-          rec[i * nvp + r] = pv; rec[psz + i * nvp + r] = tv; rec[2 * psz + i * nvp + r] = mr;
-          rec[3 * psz + i * nvp + r] = pv * w[u]; rec[4 * psz + i * nvp + r] = tv * w[u]; rec[5 * psz + i * nvp + r] = mr * w[u];
-          if (r == nv - 1 && nvp > nv) {
-            rec[3 * psz + i * nvp + nv] = 0.0; rec[4 * psz + i * nvp + nv] = 0.0; rec[5 * psz + i * nvp + nv] = 0.0;
+          rec[i * tnvp + r] = pv; rec[tpsz + i * tnvp + r] = tv; rec[2 * tpsz + i * tnvp + r] = mr;
+          rec[3 * tpsz + i * tnvp + r] = pv * w[u]; rec[4 * tpsz + i * tnvp + r] = tv * w[u]; rec[5 * tpsz + i * tnvp + r] = mr * w[u];
+          if (r == tnv - 1 && tnvp > tnv) {
+            rec[3 * tpsz + i * tnvp + tnv] = 0.0; rec[4 * tpsz + i * tnvp + tnv] = 0.0; rec[5 * tpsz + i * tnvp + tnv] = 0.0;
           }
         }
       }
     }
   } else if (central) {
     // (tau(+) - tau(-)) / (2 dq), or the five-point formula, in the reference's expression order
-    for (int idx = tid; idx < 3 * bsz; idx += nt) {
-      const int g = idx / bsz, rem = idx - g * bsz, i = rem / nv, r = rem - i * nv;
-      const int e0 = 1 + (g * NM) * nq + i;  // multiplier 0 (+1); +nq per multiplier index
+    for (int idx = tid; idx < 3 * tbsz; idx += nt) {
+      const int g = idx / tbsz, rem = idx - g * tbsz, i = rem / tnv, r = rem - i * tnv;
+      const int e0 = 1 + (g * NM) * tnq + i;  // multiplier 0 (+1); +nq per multiplier index
       const double dq = edq[e0];
-      const double tp = etau[e0 * nv + r], tm = etau[(e0 + nq) * nv + r];
+      const double tp = etau[e0 * tnv + r], tm = etau[(e0 + tnq) * tnv + r];
       double d;
       if (mode == 2) {
         d = 0.5 * (tp - tm) / dq;
       } else {
-        const double tpp = etau[(e0 + 2 * nq) * nv + r], tmm = etau[(e0 + 3 * nq) * nv + r];
+        const double tpp = etau[(e0 + 2 * tnq) * tnv + r], tmm = etau[(e0 + 3 * tnq) * tnv + r];
         d = 2.0 / 3.0 * (tp - tm) / dq - 1.0 / 12.0 * (tpp - tmm) / dq;
       }
       const double val = (g == 0) ? d : ((g == 1) ? ((k >= 1) ? d : 0.0) : ((k >= 2) ? d : ((k == 0) ? __builtin_nan("") : 0.0)));
@@ -705,25 +777,30 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
       else Mk[rem] = val;
       if (terms) {
         const double rv = (g == 2 && k < 2) ? 0.0 : val;
-        rec[g * psz + i * nvp + r] = rv;
-        rec[(3 + g) * psz + i * nvp + r] = rv * wr[r];
-        if (r == nv - 1 && nvp > nv) rec[(3 + g) * psz + i * nvp + nv] = 0.0;
+        rec[g * tpsz + i * tnvp + r] = rv;
+        rec[(3 + g) * tpsz + i * tnvp + r] = rv * wr[r];
+        if (r == tnv - 1 && tnvp > tnv) rec[(3 + g) * tpsz + i * tnvp + tnv] = 0.0;
       }
     }
   }
   if (!terms || mode == 0 || stop_after == 4) return;
   // ---- the assembly products of this record (see asm_terms_stride); the weighted copy was formed with the record
-  FD_STAMP(13);
+  FD_STAMP(15);
   __syncthreads();
+  FD_STAMP(16);
   if (stop_after == 5) return;
-  const int qq = nq * nq, ts = asm_terms_stride(nq);
+  const int qq = tnq * tnq, ts = asm_terms_stride(tnq);
   // (each product goes straight to its place in HBM: stores do not stall the lane, and a staging pass through LDS
   // behind one more barrier was 2.9k of the kernel's 48k cycles)
   double* stage = terms + (size_t)k * ts;
   // 3 x 3 register tiles: the lower-triangle tiles of CP, CT, CM, then all tiles of
   // BPT = (P R')^T T, BTM = (T R')^T M, APM = (P R')^T M  (one round of 231 tiles at nq = 19)
+  // gP, gT, gM ride along as ROW nq of the lower-triangle tiles: its A operand is tau R' (tw) in place of a weighted
+  // column, so entry (nq, c) of CP / CT / CM's grid is asm_dot(tau R', column c of P / T / M).  Where nq is no multiple of
+  // TB the last tile row has that row to spare (it was a clamped recomputation, thrown away); where it is one
+  // (the spinner), the lower triangles get one more tile row: nbr tile rows over nb tile columns.
   constexpr int TB = 3;
-  const int nb = (nq + TB - 1) / TB, ntt = nb * (nb + 1) / 2, nbb = nb * nb, ntiles = 3 * ntt + 3 * nbb;
+  const int nb = (tnq + TB - 1) / TB, nbr = GROWS ? tnq / TB + 1 : nb, ntt = nb * nbr - nb * (nb - 1) / 2, nbb = nb * nb, ntiles = 3 * ntt + 3 * nbb;
   const float inb = 1.0f / (float)nb;
   for (int tile = tid; tile < ntiles; tile += nt) {
     if (stop_after == 6 && tile >= 3 * ntt) break;
@@ -733,46 +810,71 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
       const int which = (tile >= ntt) + (tile >= 2 * ntt);
       int rem = tile - which * ntt;
       tc = 0;
-      while (rem >= nb - tc) { rem -= nb - tc; ++tc; }
+      if constexpr (CNQ != 0) {   // tc = how many of the columns' running tile counts S_t rem has reached: independent compares
+        constexpr int NB = (CNQ + TB - 1) / TB, NBR = CNQ / TB + 1;
+        int off = 0;
+#pragma unroll
+        for (int t = 0, S = 0; t < NB - 1; ++t) {
+          S += NBR - t;
+          const bool ge = rem >= S;
+          tc += ge; off = ge ? S : off;
+        }
+        rem -= off;
+      } else {
+        while (rem >= nbr - tc) { rem -= nbr - tc; ++tc; }
+      }
       tr = tc + rem;
       xa = which; sb = which; ob = which * qq;
     } else {
       const int it = tile - 3 * ntt, which = (it >= nbb) + (it >= 2 * nbb), e = it - which * nbb;
-      tc = (int)(((float)e + 0.5f) * inb);   // e / nb (exact: e < 2^12)
+      if constexpr (CNQ != 0) tc = e / nb;   // (a constant divisor)
+      else tc = (int)(((float)e + 0.5f) * inb);   // e / nb (exact: e < 2^12)
       tr = e - tc * nb;
       xa = (which == 1) ? 1 : 0; sb = (which == 0) ? 1 : 2; ob = (3 + which) * qq;
     }
     const double* A[TB];
     const double* B[TB];
 #pragma unroll
-    for (int u = 0; u < TB; ++u) {   // (rows / columns past the edge: recompute the last one, not stored)
+    for (int u = 0; u < TB; ++u) {   // (rows past the edge: tau R', stored from row nq of a lower tile only; columns: the last one again, not stored)
       const int r = tr * TB + u, c = tc * TB + u;
-      A[u] = rec + (3 + xa) * psz + (r < nq ? r : nq - 1) * nvp;
-      B[u] = rec + sb * psz + (c < nq ? c : nq - 1) * nvp;
+      if constexpr (GROWS) A[u] = r < tnq ? rec + (3 + xa) * tpsz + r * tnvp : tw;
+      else A[u] = rec + (3 + xa) * tpsz + (r < tnq ? r : tnq - 1) * tnvp;
+      B[u] = rec + sb * tpsz + (c < tnq ? c : tnq - 1) * tnvp;
     }
     double acc[TB][TB];
-    asm_dot_tile<TB>(A, B, nv, acc);
+    FD_STAMP(17);
+#ifdef IDTO_FD_STAMPS
+    asm_dot_tile<TB, CNV>(A, B, tnv, acc, idto_fd_st);
+#else
+    asm_dot_tile<TB, CNV>(A, B, tnv, acc);
+#endif
 #pragma unroll
     for (int ur = 0; ur < TB; ++ur)
 #pragma unroll
       for (int uc = 0; uc < TB; ++uc) {
         const int r = tr * TB + ur, c = tc * TB + uc;
-        if (r < nq && c < nq && (!lower || r >= c)) stage[ob + c * nq + r] = acc[ur][uc];
+        if (r < tnq && c < tnq && (!lower || r >= c)) stage[ob + c * tnq + r] = acc[ur][uc];
+        // gP, gT, gM: sum_l (tau_l w_l) J[l][c]  (xa = 0, 1, 2 on the lower tiles)
+        if constexpr (GROWS)
+          if (lower && r == tnq && c < tnq && stop_after != 7) stage[6 * qq + xa * tnq + c] = acc[ur][uc];
       }
+    FD_STAMP(20);
   }
-  if (stop_after != 7)
-    for (int it = nt - 1 - tid; it < 3 * nq; it += nt) {   // gP, gT, gM: sum_r (tau_r w_r) J[r][j]  (threads without a tile first)
-      const int which = (it >= nq) + (it >= 2 * nq), j = it - which * nq;
-      const double* J = rec + which * psz + j * nvp;
-      double acc = (etau[0] * wr[0]) * J[0];
-      for (int r = 1; r < nv; ++r) acc += (etau[r] * wr[r]) * J[r];
-      stage[6 * qq + which * nq + j] = acc;
-    }
-  FD_STAMP(14);
-  FD_STAMP(15);
+  FD_STAMP(21);
+  if constexpr (!GROWS)
+    if (stop_after != 7)
+      for (int it = nt - 1 - tid; it < 3 * tnq; it += nt) {   // gP, gT, gM: sum_r (tau_r w_r) J[r][j]  (threads without a tile first)
+        const int which = (it >= tnq) + (it >= 2 * tnq), j = it - which * tnq;
+        const double* J = rec + which * tpsz + j * tnvp;
+        double acc = (etau[0] * wr[0]) * J[0];
+        for (int r = 1; r < tnv; ++r) acc += (etau[r] * wr[r]) * J[r];
+        stage[6 * qq + which * tnq + j] = acc;
+      }
+  FD_STAMP(22);
 #ifdef IDTO_FD_STAMPS
-  if (idto_fd_st && k == 1)
-    for (int i = 0; i < 16; ++i) nplus_out[(size_t)(k + 1) * bsz + (tid == 0 ? 0 : 16) + i] = (double)(st_arr[i] - st_arr[0]);   // (over N+_2: a profiling build)
+  if (idto_fd_st && k == 1 && 2 * IDTO_FD_NSTAMPS <= tbsz)
+    for (int i = 0; i < IDTO_FD_NSTAMPS; ++i)   // (over N+_2: a profiling build)
+      nplus_out[(size_t)(k + 1) * tbsz + (tid == 0 ? 0 : IDTO_FD_NSTAMPS) + i] = (double)(st_arr[i] - st_arr[0]);
 #endif
 }
 

@@ -287,7 +287,9 @@ FastShapeOf RecogniseShape(const idto_model_t* m, const Stem& stem, const Star& 
     }
   for (int s = 1; s <= kNumTreeShapes && ok; ++s) {
     const TreeShape& t = kTreeShapes[s - 1];
-    if (star.maxc == t.MAXC && K == t.NP && cj == t.CJ && j0 == t.J0 && k0 == t.K0 && f.w2 == t.W2 && (t.GS || star.all_gravity))
+    // (nq, nv: the shape's kernel has them as constants, model_layout.h tree_shape_nq / _nv)
+    if (star.maxc == t.MAXC && K == t.NP && cj == t.CJ && j0 == t.J0 && k0 == t.K0 && f.w2 == t.W2 && (t.GS || star.all_gravity) &&
+        m->nq == tree_shape_nq(s) && m->nv == tree_shape_nv(s))
       f.shape = s;
   }
   return f;

@@ -33,6 +33,7 @@
 #ifndef IDTO_FD_STAMP_TID
 #define IDTO_FD_STAMP_TID 192
 #endif
+#define IDTO_FD_NSTAMPS 24   // slots per stamping lane (tools/fd_stamps.py names them)
 #define FD_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); asm volatile("" ::: "memory"); if (idto_fd_st) idto_fd_st[i] = (long long)__builtin_readcyclecounter(); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
 #define FD_STAMP(i) do { } while (0)

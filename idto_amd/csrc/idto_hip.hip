@@ -530,7 +530,7 @@ int FdEvals(const idto_hip_ctx* c, int mode) {
 // threads: of the block (0: the context's fd_threads, 64 for a launch of tau alone)
 int FdLds(const idto_hip_ctx* c, int mode, int ec, bool with_terms = false, bool fast = true, int threads = 0) {
   const int nq = c->nq, nv = c->nv, E = FdEvals(c, mode), nvp = (nv + 1) & ~1;
-  const int rec = with_terms ? 6 * nvp * nq + nvp + 1 : 0;   // the record, its weighted copy, diag R' (+1: 16-byte alignment)
+  const int rec = with_terms ? 6 * nvp * nq + 2 * nvp + 1 : 0;   // the record, its weighted copy, diag R', tau R' (+1: 16-byte alignment)
   const int blob_n = (fast && c->fd_fast && c->M.fast_shape) ? c->M.fast_n : c->M.blob_n;   // what fd_body stages of the model
   // (the exchange of shared pairs and of a stem, per concurrent evaluation: id_eval.h xch_eval_doubles)
   if (!threads) threads = mode >= 1 ? c->fd_threads : 64;

@@ -45,5 +45,31 @@ constexpr int SHAPE_STEM = kNumTreeShapes + 2;
 constexpr TreeShape tree_shape(int shape) {
   return shape >= 1 && shape <= kNumTreeShapes ? kTreeShapes[shape - 1] : TreeShape{0, 1, -1, 0, 0, -1, 0, 8};
 }
+// Shapes 1 ... kNumSizedShapes - the five example configurations - have the constants compiled into fd_kernel's tail.  The Jaco
+// shape (6) takes the g rows but keeps the run-time loops: no benchmark configuration has it, and the constants were never
+// measured on it.
+constexpr int kNumSizedShapes = 5;
+// nq and nv of a model of a tree shape (0: not a tree shape): the common body's joint, then NP chains of slot 0's joint and
+// MAXC - 1 revolute ones.  The host gives a model the shape only if its nq and nv are these (model_tables.cc), so the tail of
+// fd_kernel<KC, shape> takes its sizes from here at compile time.
+constexpr int joint_nq(int jt) { return jt == IDTO_JOINT_FLOATING ? 7 : (jt == IDTO_JOINT_PLANAR ? 3 : (jt < 0 ? 0 : 1)); }
+constexpr int joint_nv(int jt) { return jt == IDTO_JOINT_FLOATING ? 6 : (jt == IDTO_JOINT_PLANAR ? 3 : (jt < 0 ? 0 : 1)); }
+constexpr int tree_shape_nq(int shape) {
+  return shape >= 1 && shape <= kNumTreeShapes
+             ? joint_nq(kTreeShapes[shape - 1].CJ) + kTreeShapes[shape - 1].NP * (joint_nq(kTreeShapes[shape - 1].J0) + kTreeShapes[shape - 1].MAXC - 1)
+             : 0;
+}
+constexpr int tree_shape_nv(int shape) {
+  return shape >= 1 && shape <= kNumTreeShapes
+             ? joint_nv(kTreeShapes[shape - 1].CJ) + kTreeShapes[shape - 1].NP * (joint_nv(kTreeShapes[shape - 1].J0) + kTreeShapes[shape - 1].MAXC - 1)
+             : 0;
+}
+// (a wrong size here would not fail loudly: the host would refuse the shape and the generic kernel would run)
+static_assert(tree_shape_nq(1) == 2 && tree_shape_nv(1) == 2, "acrobot");
+static_assert(tree_shape_nq(2) == 5 && tree_shape_nv(2) == 5, "hopper");
+static_assert(tree_shape_nq(3) == 19 && tree_shape_nv(3) == 18, "mini_cheetah");
+static_assert(tree_shape_nq(4) == 23 && tree_shape_nv(4) == 22, "allegro_hand");
+static_assert(tree_shape_nq(5) == 3 && tree_shape_nv(5) == 3, "spinner");
+static_assert(tree_shape_nq(6) == 14 && tree_shape_nv(6) == 13, "jaco, jaco_ball");
 
 }  // namespace idto_dev

@@ -84,6 +84,55 @@ punyo = open(os.path.join(ROOT, "profiles", "punyo_kernel_stats.txt")).read()
 pm_ = lambda pat: re.search(pat, punyo).group(1)
 vals.update({"PUNYO_FD": pm_(r"fd_kernel<8, 8>.*?median\s+([\d.]+) us"), "PUNYO_CUT": pm_(r"fd_kernel<8, 7>.*?median\s+([\d.]+) us"),
              "PUNYO_ITER": pm_(r"punyo solve:.*?median ([\d.]+) ms"), "PUNYO_LDL": pm_(r"penta_ldl_kernel<30.*?median\s+([\d.]+) us")})
+# the tail of fd_kernel since round 6: profiles/fd_tail_* (parent and tree through one job; §3.3, the headline table)
+import statistics
+
+
+def tail_stamps(path):
+    t, cur = {}, None
+    for l in open(path):
+        if l.startswith(("mini_cheetah", "allegro_hand")):
+            cur = l.split()[0]; t[cur] = {}
+        mm = re.match(r"\s+(\d+) .*?tid0\s+(\d+) \(.*?tid192\s+(\d+)", l)
+        if mm and cur:
+            t[cur][int(mm.group(1))] = (int(mm.group(2)), int(mm.group(3)))
+    return {k: [tuple(s[x][i] - s[y][i] for i in (0, 1)) for x, y in ((22, 12), (16, 12), (22, 16))] for k, s in t.items()}
+
+
+FT = lambda f: os.path.join(ROOT, "profiles", "fd_tail_" + f)
+tb, ta = tail_stamps(FT("stamps_before.txt")), tail_stamps(FT("stamps_after.txt"))
+kc = lambda x: "%.1f k" % (x / 1e3)
+cb, ca = tb["mini_cheetah"], ta["mini_cheetah"]
+# (a line is `parent` or `new` and what bench.py printed; metric and value by pattern, so that a line cut short still counts)
+runs = [(l.split()[0], {"metric": re.search(r'"metric": "([^"]*)"', l).group(1), "value": float(re.search(r'"value": ([\d.]+)', l).group(1))})
+        for l in open(FT("bench.txt")) if re.match(r"(parent|new)\s+\{", l)]
+head = {t: [d["value"] for tt, d in runs if tt == t and "mini_cheetah" in d["metric"]] for t in ("parent", "new")}
+med = {t: statistics.median(x) for t, x in head.items()}
+spr = {t: (max(x) - min(x)) / med[t] for t, x in head.items()}
+gain, bar = med["new"] / med["parent"] - 1, 3 * max(spr.values())
+others = {}
+for tt, d in runs:
+    if "mini_cheetah" not in d["metric"]:
+        others.setdefault(d["metric"].split(", ")[-1], {})[tt] = d["value"]
+have_stats = os.path.exists(FT("kernel_stats_before.csv")) and os.path.exists(FT("kernel_stats_after.csv"))
+fd_b, fd_a = (avg_us(FT("kernel_stats_before.csv"), "fd_kernel"), avg_us(FT("kernel_stats_after.csv"), "fd_kernel")) if have_stats else (None, None)
+fd_ba = f"{fd_b:.2f} → {fd_a:.2f} µs (`profiles/fd_tail_kernel_stats_before.csv` / `_after.csv`)" if have_stats else "not measured on this tree (no kernel statistics of the two trees)"
+numbers += f"""
+| since round 6: the tail of `fd_kernel` (`profiles/fd_tail_*`, parent and tree through one job) | `fd_kernel<3,3>` {fd_ba}; step {1e6 / med['parent']:.1f} → {1e6 / med['new']:.1f} µs, **{med['new']:.0f}** it/s (median of {len(head['new'])}) |"""
+vals.update({
+    "R6_NUMBERS": numbers,
+    "FD_TAIL_STAMPS": f"tid 0 {kc(cb[0][0])} → {kc(ca[0][0])}, tid 192 (the lane that ended the kernel) {kc(cb[0][1])} → {kc(ca[0][1])}; of it the record with its barrier "
+                      f"{kc(cb[1][0])} → {kc(ca[1][0])} / {kc(cb[1][1])} → {kc(ca[1][1])} and the products {kc(cb[2][0])} → {kc(ca[2][0])} / {kc(cb[2][1])} → {kc(ca[2][1])} "
+                      f"(allegro N = 60: products {kc(tb['allegro_hand'][2][0])} → {kc(ta['allegro_hand'][2][0])} on tid 0, two rounds); `fd_kernel<3,3>` by rocprofv3 {fd_ba}",
+    "FD_TAIL_BENCH": f"parent median {med['parent']:.0f} it/s (spread {100 * spr['parent']:.2f} %), this tree {med['new']:.0f} it/s (spread {100 * spr['new']:.2f} %): "
+                     f"+{100 * gain:.2f} %, {1e6 / med['parent'] - 1e6 / med['new']:.2f} µs a step, against a bar of three times the larger spread, {100 * bar:.2f} % — "
+                     + ("a gain" if gain > bar else "below the bar: not claimed as a gain") + f" (medians of {len(head['parent'])} and {len(head['new'])} runs); "
+                     + ("one run each of the other configurations, parent → tree: " + ", ".join(f"{k} {v['parent']:.0f} → {v['new']:.0f} it/s" for k, v in others.items())
+                        if others else "allegro_hand and hopper: not measured"),
+    "FD_TAIL_END": kc(max(ca[0])),
+    "FD_TAIL_FD_US": f"{fd_a:.1f} µs (`profiles/fd_tail_kernel_stats_after.csv`; round 6: {fd_us:.1f})" if have_stats else f"{fd_us:.1f} µs (round 6; the tail since: §3.3)",
+    "FD_TAIL_STEP": f"{1e6 / med['new']:.1f} µs = {med['new']:.0f} it/s (`profiles/fd_tail_bench.txt`, median of {len(head['new'])}; round 6: {1e3 * b['ms_per_step']:.1f} µs = {b['value']:.0f} it/s)",
+})
 src = os.path.join(ROOT, "tools", "design", "DESIGN.in.md")
 text = open(src).read()
 subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_design.py")])

@@ -32,7 +32,7 @@ for old, new in [
     ("ONE banded solve of the KKT system with blocks of nq + nu (`csrc/kkt.h`, HISTORY §13.1; blocks ≤ 24); the reference's route over S = J H⁻¹ Jᵀ (`csrc/constraints.h`, `dense_ldl.h`) for allegro and behind the stepwise API",
      "ONE banded solve of the KKT system with blocks of nq + nu (`csrc/kkt.h`, §5.5, HISTORY §13.1; blocks ≤ 30: every example, allegro's 23 + 6 included); the reference's route over S = J H⁻¹ Jᵀ (`csrc/constraints.h`, `dense_ldl.h`) behind the stepwise API and for a singular S"),
     ("solve with H run on the device.  Without convergence checks and with the non-adaptive scalings\n  — all five example configurations — the whole trust-region loop incl. the multipliers of enforced\n  equality constraints runs on the device and the host waits once per `Solve` (§13); with\n  convergence checks, the adaptive scalings or `IDTO_OPT_HOST_LOOP=1` the O(num_vars) bookkeeping",
-     "solve with H run on the device.  The whole trust-region loop - the multipliers of enforced equality\n  constraints, the convergence criteria and (with diagonal cost weights) the adaptive scalings included - runs on the\n  device and the host waits once per `Solve` (§13: all five example configurations); with dense cost weights under\n  an adaptive scaling, `linear_solver = kDenseLdlt`, the debug switches or `IDTO_OPT_HOST_LOOP=1` the O(num_vars) bookkeeping"),
+     "solve with H run on the device.  The whole trust-region loop - the multipliers of enforced equality\n  constraints, the convergence criteria and (with diagonal cost weights) the adaptive scalings included - runs on the\n  device and the host waits once per `Solve` (§13: all five example configurations).  Dense cost weights without\n  constraints and with a non-adaptive scaling run the same device loop without its two-set evaluation (`idto_hip_gn_step`\n  again at the iterate every iteration; `tests/test_gpu_dense_weights.py` holds it to the stepwise loop bit for bit, a run\n  with rejected steps included, and to the oracle's iterates); with dense cost weights under\n  an adaptive scaling or with enforced constraints (`idto_hip_tr_solve` declines both, and `DeviceLoopEligible` asks\n  `weights_diagonal` before it chooses), `linear_solver = kDenseLdlt`, the debug switches or `IDTO_OPT_HOST_LOOP=1` the O(num_vars) bookkeeping"),
     ("`tr_iter_kernel`, `tr_decide` in `cost_kernel` (`csrc/trust_region.h`, §13)",
      "`tr_iter_kernel`, `tr_decide` in `cost_kernel` (`csrc/trust_region.h`, §13); acrobot and the spinner: the whole iteration in `gn_small_kernel` (§5.4)"),
 ]:

@@ -4,6 +4,7 @@
 
 #include <cstring>
 #include <memory>
+#include <stdexcept>
 #include <string>
 
 #include "idto/examples/mpc_controller.h"
@@ -14,6 +15,7 @@ using namespace idto::optimizer;
 struct idto_opt {
   std::unique_ptr<TrajectoryOptimizer<double>> to;
   int nq = 0, nv = 0, N = 0;
+  TrajectoryOptimizer<double>::BatchSolveResult batch;   // of the last idto_opt_solve_batch (kept: its storage is reused)
 };
 struct idto_opt_warm_start {
   std::unique_ptr<WarmStart> ws;
@@ -171,6 +173,54 @@ int idto_opt_solve(idto_opt* o, const double* q_guess, double* sol_q, double* so
     if (reason) *reason = (int)r;
   });
 }
+
+int idto_opt_solve_batch(idto_opt* o, int B, const idto_problem_t* problems, const double* q_guesses, int only_best,
+                         double* sol_q, double* sol_v, double* sol_tau, idto_stats_t* stats, int* flags, int* reasons,
+                         double* final_costs, int* best) {
+  return Guard([&] {
+    if (B < 1 || !q_guesses) throw std::runtime_error("solve_batch: B >= 1 problems and their q_guesses are required");
+    const int nq = o->nq, nv = o->nv;
+    std::vector<ProblemDefinition> probs;
+    if (problems) {
+      probs.resize((size_t)B);
+      for (int b = 0; b < B; ++b) {
+        const idto_problem_t& p = problems[b];
+        if (p.num_steps < 0) throw std::runtime_error("solve_batch: problem " + std::to_string(b) + " has a negative num_steps");
+        if (p.time_step != o->to->time_step())
+          throw std::runtime_error("solve_batch: problem " + std::to_string(b) + " has another time_step than the optimizer's");
+        ProblemDefinition& prob = probs[b];
+        prob.num_steps = p.num_steps;
+        prob.q_init.assign(p.q_init, p.q_init + nq);
+        prob.v_init.assign(p.v_init, p.v_init + nv);
+        prob.Qq = Mat(p.Qq, nq); prob.Qv = Mat(p.Qv, nv); prob.Qf_q = Mat(p.Qf_q, nq); prob.Qf_v = Mat(p.Qf_v, nv);
+        prob.R = Mat(p.R, nv);
+        prob.q_nom = Rows(p.q_nom, p.num_steps + 1, nq);
+        prob.v_nom = Rows(p.v_nom, p.num_steps + 1, nv);
+      }
+    }
+    std::vector<std::vector<VectorXd>> guesses((size_t)B);
+    const size_t nqa = (size_t)(o->N + 1) * nq, nva = (size_t)(o->N + 1) * nv, nta = (size_t)o->N * nv;
+    for (int b = 0; b < B; ++b) guesses[b] = Rows(q_guesses + b * nqa, o->N + 1, nq);
+    auto& R = o->batch;
+    o->to->SolveBatch(guesses, problems ? &probs : nullptr, &R, only_best != 0);
+    for (int b = 0; b < B; ++b) {
+      if (!R.solutions[b].q.empty()) {   // (only_best: the best entry's alone; an entry that failed has none)
+        Flat(R.solutions[b].q, sol_q ? sol_q + b * nqa : nullptr);
+        Flat(R.solutions[b].v, sol_v ? sol_v + b * nva : nullptr);
+        Flat(R.solutions[b].tau, sol_tau ? sol_tau + b * nta : nullptr);
+      }
+      if (stats) FillStats(R.stats[b], &stats[b]);
+      if (flags) flags[b] = (int)R.flags[b];
+      if (reasons) reasons[b] = (int)R.stats[b].convergence_reason;
+      if (final_costs) final_costs[b] = R.final_costs[b];
+    }
+    if (best) *best = R.best;
+  });
+}
+const char* idto_opt_batch_error(const idto_opt* o, int b) {
+  return (b >= 0 && b < (int)o->batch.errors.size()) ? o->batch.errors[b].c_str() : "";
+}
+int idto_opt_last_batch_route(const idto_opt* o) { return o->to->last_batch_route(); }
 
 int idto_opt_ws_create(idto_opt* o, const double* q_guess, idto_opt_warm_start** out) {
   return Guard([&] {

@@ -12,13 +12,18 @@
 // constructor throws.
 #include "idto/optimizer/trajectory_optimizer.h"
 
+#include "host/batch_rows.h"
+
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <string>
+
+static_assert(idto::optimizer::internal::kTrRow == IDTO_TR_ROW, "batch_rows.h and idto_hip.h disagree about a row's width");
 
 namespace idto {
 namespace optimizer {
@@ -311,18 +316,22 @@ TO::TrajectoryOptimizer(const idto_model_t& model, double time_step, const Probl
 }
 
 TO::~TrajectoryOptimizer() {
+  for (auto& kv : batch_ctx_)
+    if (kv.second.ctx) idto_hip_destroy(kv.second.ctx);
   for (std::size_t i = 1; i < shard_ctx_.size(); ++i) idto_hip_destroy(shard_ctx_[i]);
   idto_hip_destroy(hip_);
 }
 
-void TO::UploadProblem() const {
+void TO::UploadProblem() const { UploadProblemDefinition(prob_); }
+
+void TO::UploadProblemDefinition(const ProblemDefinition& prob) const {
   problem_dirty_ = false;
-  const Vec qn = Flatten(prob_.q_nom), vn = Flatten(prob_.v_nom);
+  const Vec qn = Flatten(prob.q_nom), vn = Flatten(prob.v_nom);
   idto_problem_t p = {};
   p.num_steps = num_steps(); p.time_step = time_step_;
-  p.q_init = prob_.q_init.data(); p.v_init = prob_.v_init.data();
-  p.Qq = prob_.Qq.data(); p.Qv = prob_.Qv.data(); p.Qf_q = prob_.Qf_q.data(); p.Qf_v = prob_.Qf_v.data();
-  p.R = prob_.R.data(); p.q_nom = qn.data(); p.v_nom = vn.data();
+  p.q_init = prob.q_init.data(); p.v_init = prob.v_init.data();
+  p.Qq = prob.Qq.data(); p.Qv = prob.Qv.data(); p.Qf_q = prob.Qf_q.data(); p.Qf_v = prob.Qf_v.data();
+  p.R = prob.R.data(); p.q_nom = qn.data(); p.v_nom = vn.data();
   Check(idto_hip_set_problem(hip_, &p));
   for (std::size_t i = 1; i < shard_ctx_.size(); ++i) Check(idto_hip_set_problem(shard_ctx_[i], &p));
   resident_ = nullptr;  // every cached device result depends on the problem data
@@ -1362,6 +1371,217 @@ SolverFlag TO::SolveOnDevice(WarmStart* ws, TrajectoryOptimizerSolution<T>* solu
   stats->solve_time = std::chrono::duration<double>(clock::now() - start_time).count();
   if (k == params_.max_iterations) return SolverFlag::kMaxIterationsReached;
   return SolverFlag::kSuccess;
+}
+
+// ---- SolveBatch (trajectory_optimizer.h): B problems through the device's batch loop, or one after another
+
+void TO::CheckBatchProblem(const ProblemDefinition& p, int b) const {
+  auto square = [](const MatrixXd& m, int n) { return m.rows() == n && m.cols() == n; };
+  bool ok = p.num_steps == num_steps() && (int)p.q_init.size() == nq_ && (int)p.v_init.size() == nv_ &&
+            (int)p.q_nom.size() == num_steps() + 1 && (int)p.v_nom.size() == num_steps() + 1 && square(p.Qq, nq_) &&
+            square(p.Qv, nv_) && square(p.Qf_q, nq_) && square(p.Qf_v, nv_) && square(p.R, nv_);
+  for (std::size_t t = 0; ok && t < p.q_nom.size(); ++t) ok = (int)p.q_nom[t].size() == nq_ && (int)p.v_nom[t].size() == nv_;
+  if (!ok)
+    throw std::runtime_error("SolveBatch: problem " + std::to_string(b) + " has another num_steps or other sizes than the optimizer's");
+}
+
+namespace {
+bool IsDiagonal(const MatrixXd& W) {
+  for (int c = 0; c < W.cols(); ++c)
+    for (int r = 0; r < W.rows(); ++r)
+      if (r != c && W(r, c) != 0.0) return false;
+  return true;
+}
+bool DiagonalWeights(const ProblemDefinition& p) {
+  return IsDiagonal(p.Qq) && IsDiagonal(p.Qv) && IsDiagonal(p.R) && IsDiagonal(p.Qf_q) && IsDiagonal(p.Qf_v);
+}
+bool Usable(SolverFlag f) { return f == SolverFlag::kSuccess || f == SolverFlag::kMaxIterationsReached; }
+void ClearStats(TrajectoryOptimizerStats<double>* s) {
+  s->convergence_reason = kNoConvergenceCriteriaSatisfied;
+  s->solve_time = 0;
+  s->iteration_times.clear(); s->iteration_costs.clear(); s->linesearch_iterations.clear(); s->linesearch_alphas.clear();
+  s->trust_region_radii.clear(); s->gradient_norms.clear(); s->q_norms.clear(); s->dq_norms.clear(); s->dqH_norms.clear();
+  s->trust_ratios.clear(); s->dL_dqs.clear(); s->h_norms.clear(); s->merits.clear();
+}
+void ClearSolution(TrajectoryOptimizerSolution<double>* s) { s->q.clear(); s->v.clear(); s->tau.clear(); }
+}  // namespace
+
+TO::BatchContext* TO::GetBatchContext(int B, const std::vector<const ProblemDefinition*>& probs) const {
+  BatchContext& bc = batch_ctx_[B];
+  const std::size_t nqa = (std::size_t)num_vars(), nva = (std::size_t)(num_steps() + 1) * nv_, nta = (std::size_t)num_steps() * nv_;
+  if (!bc.ctx) {
+    bc.q.resize(B * nqa); bc.q_nom.resize(nqa); bc.v_nom.resize(nva);
+    bc.Delta0.resize(B); bc.Delta_out.resize(B); bc.final_cost.resize(B); bc.status.resize(B);
+    bc.sol_q.resize(B * nqa); bc.sol_v.resize(B * nva); bc.sol_tau.resize(B * nta);
+    // (created from the optimizer's own problem in every slot: each call uploads its problems anyway)
+    const Vec qn = Flatten(prob_.q_nom), vn = Flatten(prob_.v_nom);
+    idto_problem_t p = {};
+    p.num_steps = num_steps(); p.time_step = time_step_;
+    p.q_init = prob_.q_init.data(); p.v_init = prob_.v_init.data();
+    p.Qq = prob_.Qq.data(); p.Qv = prob_.Qv.data(); p.Qf_q = prob_.Qf_q.data(); p.Qf_v = prob_.Qf_v.data();
+    p.R = prob_.R.data(); p.q_nom = qn.data(); p.v_nom = vn.data();
+    std::vector<idto_problem_t> ps((std::size_t)B, p);
+    Check(idto_hip_create_batch_like(hip_, ps.data(), B, &bc.ctx));
+    if (!std::getenv("IDTO_OPT_BLOCKING_UPLOADS")) Check(idto_hip_set_option(bc.ctx, "async_uploads", 1));
+  }
+  if ((int)bc.rows.size() < B * params_.max_iterations * IDTO_TR_ROW) bc.rows.resize((std::size_t)B * params_.max_iterations * IDTO_TR_ROW);
+  for (int b = 0; b < B; ++b) {
+    const ProblemDefinition& pd = *probs[b];
+    for (int t = 0; t <= num_steps(); ++t) {
+      std::copy(pd.q_nom[t].begin(), pd.q_nom[t].end(), bc.q_nom.begin() + (std::size_t)t * nq_);
+      std::copy(pd.v_nom[t].begin(), pd.v_nom[t].end(), bc.v_nom.begin() + (std::size_t)t * nv_);
+    }
+    idto_problem_t p = {};
+    p.num_steps = num_steps(); p.time_step = time_step_;
+    p.q_init = pd.q_init.data(); p.v_init = pd.v_init.data();
+    p.Qq = pd.Qq.data(); p.Qv = pd.Qv.data(); p.Qf_q = pd.Qf_q.data(); p.Qf_v = pd.Qf_v.data();
+    p.R = pd.R.data(); p.q_nom = bc.q_nom.data(); p.v_nom = bc.v_nom.data();
+    Check(idto_hip_set_problem_batch(bc.ctx, b, &p));
+  }
+  return &bc;
+}
+
+void TO::SolveBatchEntryAlone(const ProblemDefinition* prob, const std::vector<VectorXd>& q_guess, int b,
+                              BatchSolveResult* out) const {
+  ClearStats(&out->stats[b]);
+  ClearSolution(&out->solutions[b]);
+  out->errors[b].clear();
+  out->final_costs[b] = std::numeric_limits<double>::quiet_NaN();
+  out->flags[b] = SolverFlag::kFactorizationFailed;
+  try {
+    if (prob) {
+      UploadProblemDefinition(*prob);
+      resident_ = nullptr;
+      device_level_ = 0;
+    }
+    out->flags[b] = Solve(q_guess, &out->solutions[b], &out->stats[b]);
+    if (Usable(out->flags[b])) {
+      TrajectoryOptimizerState<T> state = CreateState();
+      state.set_q(out->solutions[b].q);
+      out->final_costs[b] = EvalCost(state);
+      resident_ = nullptr;   // (`state` goes out of scope)
+      device_level_ = 0;
+    } else if (out->flags[b] == SolverFlag::kFactorizationFailed) {
+      out->errors[b] = "idto_hip: factorisation failed";
+      ClearSolution(&out->solutions[b]);
+    }
+  } catch (const std::exception& e) {
+    out->errors[b] = e.what();
+    ClearSolution(&out->solutions[b]);
+  }
+  // (this optimizer's own problem returns to its context with the next device call: dev())
+  if (prob) problem_dirty_ = true;
+}
+
+void TO::SolveBatch(const std::vector<std::vector<VectorXd>>& q_guesses, const std::vector<ProblemDefinition>* problems,
+                    BatchSolveResult* out, bool only_best) const {
+  using clock = std::chrono::high_resolution_clock;
+  const int B = (int)q_guesses.size();
+  if (B < 1) throw std::runtime_error("SolveBatch: no q_guesses");
+  if (problems && (int)problems->size() != B)
+    throw std::runtime_error("SolveBatch: q_guesses and problems disagree in length (" + std::to_string(B) + " and " +
+                             std::to_string(problems->size()) + ")");
+  std::vector<const ProblemDefinition*> probs((std::size_t)B, &prob_);
+  for (int b = 0; b < B; ++b) {
+    if (problems) { probs[b] = &(*problems)[b]; CheckBatchProblem(*probs[b], b); }
+    bool ok = (int)q_guesses[b].size() == num_steps() + 1;
+    for (std::size_t t = 0; ok && t < q_guesses[b].size(); ++t) ok = (int)q_guesses[b][t].size() == nq_;
+    if (!ok) throw std::runtime_error("SolveBatch: q_guesses[" + std::to_string(b) + "] has the wrong size");
+  }
+  out->solutions.resize(B); out->stats.resize(B); out->flags.resize(B); out->errors.resize(B); out->final_costs.resize(B);
+  out->best = -1;
+  const auto start_time = clock::now();
+
+  // which route: the device's batch loop serves what the resident single-problem loop serves, except ...
+  const bool constrained = params_.equality_constraints && num_equality_constraints() > 0;
+  const int scal = params_.scaling ? static_cast<int>(params_.scaling_method) : -1;
+  // ... the adaptive scalings (a batch context's memory of D cannot be set: idto_hip_tr_set_scale_memory serves
+  // single-problem contexts, and a context kept per B would start from the previous call's D instead of ones),
+  const bool adaptive = scal == static_cast<int>(kAdaptiveSqrt) || scal == static_cast<int>(kAdaptiveDoubleSqrt);
+  // ... dense cost weights (the batch loop runs on the two-set evaluation), several devices, and the per-iteration table
+  bool batch_route = B >= 2 && params_.method == kTrustRegion && shard_ctx_.empty() && !adaptive && !params_.verbose &&
+                     DeviceLoopEligible() && ResidentLoopEligible();
+  for (int b = 0; batch_route && b < B; ++b) batch_route = DiagonalWeights(*probs[b]);
+
+  std::vector<char> alone((std::size_t)B, batch_route ? 0 : 1);
+  if (batch_route) {
+    BatchContext* bc = GetBatchContext(B, probs);
+    int resident_ok = 1;
+    Check(idto_hip_get_option(bc->ctx, "tr_resident_ok", &resident_ok));
+    const std::size_t nqa = (std::size_t)num_vars(), nva = (std::size_t)(num_steps() + 1) * nv_, nta = (std::size_t)num_steps() * nv_;
+    const int iters = params_.max_iterations;
+    int rc = -1, best_dev = -1;
+    if (resident_ok) {
+      for (int b = 0; b < B; ++b)
+        for (int t = 0; t <= num_steps(); ++t)
+          std::copy(q_guesses[b][t].begin(), q_guesses[b][t].end(), bc->q.begin() + b * nqa + (std::size_t)t * nq_);
+      Check(idto_hip_set_q_batch(bc->ctx, bc->q.data()));
+      Check(idto_hip_set_unactuated_dofs(bc->ctx, unactuated_dofs_.data(), (int)unactuated_dofs_.size()));
+      Check(idto_hip_eval_tau(bc->ctx));
+      if (params_.check_convergence) {
+        const auto& t = params_.convergence_tolerances;
+        const double tol[6] = {t.rel_cost_reduction, t.abs_cost_reduction, t.rel_gradient_along_dq, t.abs_gradient_along_dq,
+                               t.rel_state_change, t.abs_state_change};
+        Check(idto_hip_tr_set_convergence(bc->ctx, tol));
+      } else {
+        Check(idto_hip_tr_set_convergence(bc->ctx, nullptr));
+      }
+      std::fill(bc->Delta0.begin(), bc->Delta0.end(), params_.Delta0);
+      rc = idto_hip_tr_solve_batch_fetch(bc->ctx, iters, scal, params_.scaling ? 1 : 0, params_.normalize_quaternions ? 1 : 0,
+                                         bc->Delta0.data(), params_.Delta_max, 0.0, constrained ? unactuated_dofs_.data() : nullptr,
+                                         constrained ? (int)unactuated_dofs_.size() : 0, bc->rows.data(), bc->Delta_out.data(),
+                                         only_best ? 1 : 0, bc->sol_q.data(), bc->sol_v.data(), bc->sol_tau.data(), nullptr, nullptr,
+                                         bc->final_cost.data(), bc->status.data(), &best_dev);
+    }
+    if (rc == 0 || rc == IDTO_HIP_FACTORIZATION_FAILED) {
+      const double total = std::chrono::duration<double>(clock::now() - start_time).count();
+      for (int b = 0; b < B; ++b) {
+        ClearStats(&out->stats[b]);
+        ClearSolution(&out->solutions[b]);
+        out->errors[b].clear();
+        internal::BatchRowsResult r;
+        internal::RowsToStats(bc->rows.data() + (std::size_t)b * iters * IDTO_TR_ROW, iters, bc->Delta_out[b], total, params_,
+                              &out->stats[b], &r);
+        out->flags[b] = r.flag;
+        out->final_costs[b] = bc->final_cost[b];
+        if (r.outcome == internal::RowsOutcome::kNeedsHostLoop) { alone[b] = 1; continue; }
+        if (r.outcome != internal::RowsOutcome::kDone) {
+          out->flags[b] = SolverFlag::kFactorizationFailed;
+          out->errors[b] = r.error;
+          out->final_costs[b] = std::numeric_limits<double>::quiet_NaN();
+          continue;
+        }
+        const int slot = only_best ? (b == best_dev ? 0 : -1) : b;
+        if (slot < 0) continue;
+        Vec tmp;
+        tmp.assign(bc->sol_q.begin() + slot * nqa, bc->sol_q.begin() + (slot + 1) * nqa);
+        UnflattenInto(tmp, num_steps() + 1, nq_, &out->solutions[b].q);
+        tmp.assign(bc->sol_v.begin() + slot * nva, bc->sol_v.begin() + (slot + 1) * nva);
+        UnflattenInto(tmp, num_steps() + 1, nv_, &out->solutions[b].v);
+        tmp.assign(bc->sol_tau.begin() + slot * nta, bc->sol_tau.begin() + (slot + 1) * nta);
+        UnflattenInto(tmp, num_steps(), nv_, &out->solutions[b].tau);
+      }
+    } else if (!resident_ok || rc == IDTO_HIP_SOLVER_TIMEOUT ||
+               (rc == -1 && std::strstr(idto_hip_last_error(), "child-context route"))) {
+      // the loop's workgroups timed out on a shared device, or these constraints take the child-context route: entry by entry
+      batch_route = false;
+      std::fill(alone.begin(), alone.end(), 1);
+    } else {
+      Check(rc);
+    }
+  }
+  last_batch_route_ = batch_route ? 1 : 0;
+  for (int b = 0; b < B; ++b)
+    if (alone[b]) SolveBatchEntryAlone(problems ? probs[b] : nullptr, q_guesses[b], b, out);
+
+  // the best entry, by one rule for both routes (it is the device's choice when every entry came from the batch loop)
+  for (int b = 0; b < B; ++b) {
+    if (!out->errors[b].empty() || !Usable(out->flags[b]) || !std::isfinite(out->final_costs[b])) continue;
+    if (out->best < 0 || out->final_costs[b] < out->final_costs[out->best]) out->best = b;
+  }
+  if (only_best)
+    for (int b = 0; b < B; ++b)
+      if (b != out->best) ClearSolution(&out->solutions[b]);
 }
 
 SolverFlag TO::SolveFromWarmStartImpl(WarmStart* ws, TrajectoryOptimizerSolution<T>* solution,

@@ -299,7 +299,8 @@ struct idto_hip_ctx {
   bool con_S_factored = false;                                         // con_S holds the LDL^T factors, not S
   // SolverParameters::linear_solver = kDenseLdlt (idto_hip_solve_dense_ldlt): [H dense | L], pivots, [min, max], [r | y]
   double *dn_S = nullptr, *dn_d = nullptr, *dn_stat = nullptr, *dn_rv = nullptr; int dn_n = 0;
-  double* fetch_dev = nullptr; double* fetch_pin = nullptr; size_t fetch_cap = 0;   // idto_hip_tr_solve_fetch's staging
+  double* fetch_dev = nullptr; double* fetch_pin = nullptr; size_t fetch_cap = 0;   // idto_hip_tr_solve_fetch's staging (and the batch form's)
+  double* bstate_pin = nullptr;   // idto_hip_tr_solve_batch_fetch: the initial state words of every problem, pinned ([batch][TRS_COUNT])
   // option "async_uploads": idto_hip_set_q / idto_hip_set_problem copy from pinned staging of the context - two buffers
   // taken in turn, an event each - and return without waiting (everything else the context does is ordered behind them on
   // its stream); a caller that reads device memory on ANOTHER stream keeps the default, the blocking copies
@@ -722,14 +723,16 @@ int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* probl
   const int nq = c->nq, nv = c->nv, N = c->N;
   int rc = UploadModel(c, model, tables);
   if (rc) { idto_hip_destroy(c); return rc; }
+  // (host copies: of the model and the contact parameters always - idto_hip_create_batch_like builds a batch context from
+  // them -, of the problems for a batch, whose constrained loop may build child contexts)
+  c->host_model = std::make_unique<HostModelCopy>();
+  c->host_model->Set(*model);
+  c->host_contact = *contact;
   if (batch > 1) {
-    c->host_model = std::make_unique<HostModelCopy>();
-    c->host_model->Set(*model);
     for (int b = 0; b < batch; ++b) {
       c->host_problems.push_back(std::make_unique<HostProblemCopy>());
       c->host_problems.back()->Set(problems[b], model->nq, model->nv);
     }
-    c->host_contact = *contact;
   }
   c->cp.k = contact->contact_stiffness; c->cp.vd = contact->dissipation_velocity;
   c->cp.vs = contact->stiction_velocity; c->cp.mu = contact->friction_coefficient;
@@ -973,6 +976,7 @@ void idto_hip_destroy(idto_hip_ctx* c) {
   if (c->spec_ev) (void)hipEventDestroy(c->spec_ev);
   if (c->con_pin) (void)hipHostFree(c->con_pin);
   if (c->fetch_pin) (void)hipHostFree(c->fetch_pin);
+  if (c->bstate_pin) (void)hipHostFree(c->bstate_pin);
   for (int i = 0; i < 2; ++i) {
     if (c->up_pin[i]) (void)hipHostFree(c->up_pin[i]);
     if (c->up_ev[i]) (void)hipEventDestroy(c->up_ev[i]);
@@ -1003,6 +1007,15 @@ int idto_hip_set_problem_batch(idto_hip_ctx* c, int b, const idto_problem_t* p) 
 }
 
 int idto_hip_batch_size(idto_hip_ctx* c) { return c->batch; }
+
+int idto_hip_create_batch_like(idto_hip_ctx* like, const idto_problem_t* problems, int batch, idto_hip_ctx** out) {
+  *out = nullptr;
+  if (!like || !like->host_model) { g_err = "create_batch_like: the context keeps no host copy of its model"; return -1; }
+  const int rc = idto_hip_create_batch(&like->host_model->m, problems, &like->host_contact, like->device, batch, out);
+  if (rc) return rc;
+  (*out)->gradients_method = like->gradients_method;
+  return 0;
+}
 
 int idto_hip_set_stream(idto_hip_ctx* c, void* s) {
   if (c->own_stream && c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
@@ -2080,12 +2093,19 @@ static int MakeKkt(idto_hip_ctx* c, int nu) {
 }
 
 static bool AsmInSolver(const idto_hip_ctx* c, SolverPlan* p);
+// idto_hip_tr_solve_batch_fetch's outputs beyond rows and radii (a batch of more than one problem)
+struct TrBatchFetch {
+  int only_best;
+  double* out[5];   // q, v, tau, dq, w: [batch][...] or - only_best - [1][...]; any may be null
+  double* final_cost; int* status; int* best;
+};
 // Delta0s / Delta_out: one radius per problem of the context; rows_host: [batch][iterations][TRR_COUNT]
 static int TrSolve(idto_hip_ctx* c, int iterations, int scaling_method, int scaling, int normalize_quaternions,
                    const double* Delta0s, double Delta_max, double eta, const int* constrained_dofs, int nu,
-                   double* rows_host, double* Delta_out, double* const* fetch = nullptr) {
+                   double* rows_host, double* Delta_out, double* const* fetch = nullptr, const TrBatchFetch* bfetch = nullptr) {
   HIP_OK(hipSetDevice(c->device));
   const int B = c->batch;
+  if (bfetch && B == 1) { g_err = "tr_solve: the batch fetch serves batches of more than one problem"; return -1; }
   TRACE("hip: tr_solve begins");
   if (iterations <= 0) { g_err = "tr_solve: iterations must be positive"; return -1; }
   if (!c->tr_resident_ok) {
@@ -2125,11 +2145,20 @@ static int TrSolve(idto_hip_ctx* c, int iterations, int scaling_method, int scal
     HIP_OK(hipGetLastError());
   } else {
     HIP_OK(hipMemset2DAsync(c->tr_cnt, c->pstride, 0, sizeof(unsigned long long), (size_t)B, c->stream));
-    std::vector<double> st((size_t)B * TRS_COUNT, 0.0);
+    std::vector<double> tmp;
+    double* st = nullptr;
+    if (bfetch) {   // (pinned words of the context: no wait here - the call's one wait is behind the loop, and every return in between waits too)
+      if (!c->bstate_pin) HIP_OK(hipHostMalloc((void**)&c->bstate_pin, (size_t)B * TRS_COUNT * sizeof(double), hipHostMallocDefault));
+      st = c->bstate_pin;
+      std::fill(st, st + (size_t)B * TRS_COUNT, 0.0);
+    } else {
+      tmp.assign((size_t)B * TRS_COUNT, 0.0);
+      st = tmp.data();
+    }
     for (int b = 0; b < B; ++b) { st[(size_t)b * TRS_COUNT + TRS_DELTA] = Delta0s[b]; st[(size_t)b * TRS_COUNT + TRS_ACCEPTED] = 1.0; }
-    HIP_OK(hipMemcpy2DAsync(c->tr_state, c->pstride, st.data(), TRS_COUNT * sizeof(double), TRS_COUNT * sizeof(double), (size_t)B,
+    HIP_OK(hipMemcpy2DAsync(c->tr_state, c->pstride, st, TRS_COUNT * sizeof(double), TRS_COUNT * sizeof(double), (size_t)B,
                             hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));   // (the host buffer is a temporary)
+    if (!bfetch) HIP_OK(hipStreamSynchronize(c->stream));   // (the host buffer is a temporary)
   }
   if (B != 1)
     HIP_OK(hipMemcpy2DAsync(c->tr_state + TRS_COST, c->pstride, c->cost, c->pstride, sizeof(double), (size_t)B,
@@ -2362,6 +2391,65 @@ static int TrSolve(idto_hip_ctx* c, int iterations, int scaling_method, int scal
     // every problem has its own current set: the ones whose iterate ended up in the other set get it copied over
     // (a single-problem context swaps its pointers instead, below)
     if (c->alt_off <= 0) { g_err = "tr_solve: batch contexts keep their primary output set"; return -1; }
+    if (bfetch) {
+      // idto_hip_tr_solve_batch_fetch: state words, rows and the iterates of every problem (only_best: of the best one) packed
+      // by ONE launch, which also chooses the best problem; one copy, one wait (trust_region.h tr_gather_batch_kernel)
+      const size_t nrow = rows_stride;
+      const size_t nqa = (size_t)(c->N + 1) * c->nq, nva = (size_t)(c->N + 1) * c->nv, nta = (size_t)c->N * c->nv;
+      const size_t ntraj = 3 * nqa + nva + nta, head = tr_gather_batch_header(B);
+      const size_t total = head + (size_t)B * (TRS_COUNT + nrow) + (bfetch->only_best ? 1 : (size_t)B) * ntraj;
+      const size_t lds = (size_t)B * (sizeof(double) + sizeof(int));
+      if (lds > 60 * 1024) { g_err = "tr_solve_batch_fetch: the batch is too large for the selecting workgroup's LDS"; return -1; }
+      if (c->fetch_cap < total) {
+        Release(c, &c->fetch_dev);
+        if (c->fetch_pin) (void)hipHostFree(c->fetch_pin);
+        c->fetch_pin = nullptr; c->fetch_cap = 0;
+        if (Alloc(c, total, &c->fetch_dev)) return -2;
+        HIP_OK(hipHostMalloc((void**)&c->fetch_pin, total * sizeof(double), hipHostMallocDefault));
+        c->fetch_cap = total;
+      }
+      TrGatherBatchArgs G;
+      G.state = c->tr_state; G.rows = c->tr_rows; G.B = B; G.iterations = iterations; G.nrows = (int)nrow;
+      G.only_best = bfetch->only_best ? 1 : 0;
+      G.q = c->q; G.v = c->v; G.slab = c->slab; G.dq = c->tr_dq; G.w = c->tr_w;
+      G.N = c->N; G.nq = c->nq; G.nv = c->nv; G.slab_stride = (int)c->slab_stride;
+      G.alt_off = (long long)c->alt_off; G.pstride = c->pstride;
+      G.out = c->fetch_dev;
+      hipLaunchKernelGGL(tr_gather_batch_kernel, dim3(TR_GATHER_BATCH_GX + 1, B), dim3(256), lds, c->stream, G);
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipMemcpyAsync(c->fetch_pin, c->fetch_dev, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      // (behind the copy: the fold only makes the context's first set the iterate's for the calls that follow)
+      hipLaunchKernelGGL(tr_fold_sets_kernel, dim3(64, B), dim3(256), 0, c->stream, c->v, (size_t)c->alt_off / sizeof(double),
+                         c->tr_state, c->pstride);
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipStreamSynchronize(c->stream));
+      TRACE("hip: tr_solve: waited for the device (every problem's state words, rows and solution back)");
+      const double* p = c->fetch_pin;
+      const int best = (int)p[0];
+      *bfetch->best = best;
+      for (int b = 0; b < B; ++b) { bfetch->final_cost[b] = p[1 + b]; bfetch->status[b] = (int)p[1 + B + b]; }
+      p += head;
+      const double* states = p;
+      for (int b = 0; b < B; ++b, p += TRS_COUNT + nrow) {
+        if (Delta_out) Delta_out[b] = p[TRS_DELTA];
+        std::memcpy(rows_host + (size_t)b * nrow, p + TRS_COUNT, nrow * sizeof(double));
+      }
+      const size_t cnt[5] = {nqa, nva, nta, nqa, nqa};
+      if (!bfetch->only_best || best >= 0) {
+        const size_t T = bfetch->only_best ? 1 : (size_t)B;
+        for (size_t t = 0; t < T; ++t)
+          for (int i = 0; i < 5; ++i) { if (bfetch->out[i]) std::memcpy(bfetch->out[i] + t * cnt[i], p, cnt[i] * sizeof(double)); p += cnt[i]; }
+      }
+      // every problem's outputs are filled; the return value: a time-out first, else whether any factorisation failed
+      int failed = 0;
+      for (int b = 0; b < B; ++b) {
+        const bool singular = ((int)states[(size_t)b * (TRS_COUNT + nrow) + TRS_FLAGS] & TRF_SINGULAR_S) != 0;
+        const int fk = use_kkt ? FactorStatus(c->kkt, b) : 0, fh = FactorStatus(c, b);
+        if (fk == IDTO_HIP_SOLVER_TIMEOUT || fh == IDTO_HIP_SOLVER_TIMEOUT) return IDTO_HIP_SOLVER_TIMEOUT;
+        if ((fk && !singular) || fh || (bfetch->status[b] & TRF_FACTORIZATION)) failed = IDTO_HIP_FACTORIZATION_FAILED;
+      }
+      return failed;
+    }
     hipLaunchKernelGGL(tr_fold_sets_kernel, dim3(64, B), dim3(256), 0, c->stream, c->v, (size_t)c->alt_off / sizeof(double),
                        c->tr_state, c->pstride);
     HIP_OK(hipGetLastError());
@@ -2539,6 +2627,50 @@ int idto_hip_tr_solve_batch_constrained(idto_hip_ctx* c, int iterations, int sca
   for (int b = 0; b < B; ++b)
     if (rcs[b]) { g_err = "problem " + std::to_string(b) + ": " + errs[b]; return rcs[b]; }
   return 0;
+}
+
+// The batch loop with everything a caller reads afterwards brought back under the loop's one wait, and the best problem
+// chosen on the device (trust_region.h tr_gather_batch_kernel).
+int idto_hip_tr_solve_batch_fetch(idto_hip_ctx* c, int iterations, int scaling_method, int scaling, int normalize_quaternions,
+                                  const double* Delta0, double Delta_max, double eta, const int* constrained_dofs, int nu,
+                                  double* rows_host, double* Delta_out, int only_best, double* q_out, double* v_out,
+                                  double* tau_out, double* dq_out, double* w_out, double* final_cost, int* status, int* best) {
+  if (!Delta0 || !rows_host || !final_cost || !status || !best) {
+    g_err = "tr_solve_batch_fetch: Delta0[batch], rows_host[batch][iterations][IDTO_TR_ROW], final_cost[batch], status[batch] and best are required";
+    return -1;
+  }
+  if (nu < 0 || (nu > 0 && !constrained_dofs)) { g_err = "tr_solve_batch_fetch: bad constraint arguments"; return -1; }
+  if (iterations <= 0) { g_err = "tr_solve_batch_fetch: iterations must be positive"; return -1; }
+  const int B = c->batch;
+  if (B == 1) {
+    // one problem: idto_hip_tr_solve_fetch, and the choice among one made here from what it returned
+    double* const fetch[5] = {q_out, v_out, tau_out, dq_out, w_out};
+    const int rc = TrSolve(c, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu,
+                           rows_host, Delta_out, fetch);
+    if (rc < 0 || rc == IDTO_HIP_SOLVER_TIMEOUT) return rc;
+    int f = 0;
+    for (int k = 0; k < iterations; ++k) f |= (int)rows_host[(size_t)k * TRR_COUNT + TRR_FLAGS];
+    final_cost[0] = c->tr_pin[TRS_COST];
+    status[0] = f;
+    *best = ((f & TR_ELIGIBLE_MASK) == 0 && std::isfinite(final_cost[0])) ? 0 : -1;
+    return rc;
+  }
+  if (nu > 0 && !(c->con_kkt && idto_host::SolverBlockSize(c->nq + nu, true) <= 30 && c->weights_diagonal)) {
+    g_err = "tr_solve_batch_fetch: these enforced constraints take the child-context route of idto_hip_tr_solve_batch_constrained "
+            "(option con_kkt = 0, nq + nu > 30 or dense cost weights: every problem advanced in a single-problem context of "
+            "its own), which has no gathered fetch: use idto_hip_tr_solve_batch_constrained + idto_hip_get_batch";
+    return -1;
+  }
+  HIP_OK(hipSetDevice(c->device));
+  if (nu > 0)
+    if (int rc = idto_hip_eval_tau(c)) return rc;   // (as idto_hip_tr_solve_batch_constrained: the loop starts from the cost of the resident q)
+  TrBatchFetch bf{only_best ? 1 : 0, {q_out, v_out, tau_out, dq_out, w_out}, final_cost, status, best};
+  const int rc = TrSolve(c, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu,
+                         rows_host, Delta_out, nullptr, &bf);
+  // (a return from inside the loop's enqueueing: the initial state words travel from pinned memory of the context, which the
+  // next call rewrites - wait for what is enqueued)
+  if (rc < 0) (void)hipStreamSynchronize(c->stream);
+  return rc;
 }
 
 #define NCCL_OK(expr)                                                                 \

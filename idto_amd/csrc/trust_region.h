@@ -847,6 +847,98 @@ __global__ void tr_gather_kernel(TrGatherArgs A) {
   for (int i = tid; i < nqa; i += nt) o[i] = A.w[i];
 }
 
+// The same for a batch (idto_hip_tr_solve_batch_fetch), grid (TR_GATHER_BATCH_GX + 1, problem), together with the choice of
+// the best problem.  Layout of `out`:
+//   [best | final_cost[B] | status[B]]   (doubles; tr_gather_batch_header)
+//   B x [state TRS_COUNT | rows nrows]
+//   T x [q | v | tau | dq | w]            T = B, or - only_best - 1: the best problem's
+// v and tau of a problem come from the set its own TRS_CUR names.  final_cost = TRS_COST, status = the OR of the rows' flags;
+// eligible: none of TRF_DOGLEG / NONFINITE / NOT_DESCENT / SINGULAR_S / FACTORIZATION and a finite cost; best = the eligible
+// problem of the lowest cost, the lowest index among equals, -1: none.  The choice reads state words and rows only - inputs
+// of this launch - and is made in a fixed order: every thread fills the entries b = tid, tid + blockDim, ... of two LDS
+// arrays, thread 0 scans them from 0 to B - 1.  The workgroup (GX, 0) writes the header; with only_best the packing
+// workgroups make the same choice themselves (B state words and B x iterations flag words: nothing to wait for).
+constexpr int TR_GATHER_BATCH_GX = 16;
+constexpr int TR_ELIGIBLE_MASK = TRF_DOGLEG | TRF_NONFINITE | TRF_NOT_DESCENT | TRF_SINGULAR_S | TRF_FACTORIZATION;
+__host__ __device__ inline size_t tr_gather_batch_header(int B) { return 1 + 2 * (size_t)B; }
+struct TrGatherBatchArgs {
+  const double* state; const double* rows;   // state: problem 0's (arenas pstride bytes apart); rows: [B][nrows]
+  int B, iterations, nrows, only_best;
+  const double* q; const double* v; const double* slab; const double* dq; const double* w;   // problem 0's
+  int N, nq, nv, slab_stride;
+  long long alt_off;
+  size_t pstride;
+  double* out;
+};
+// (LDS: B doubles + B ints)
+__device__ inline int tr_select_best(const TrGatherBatchArgs& A, double* cost, int* status) {
+  __shared__ int best_s;
+  for (int b = threadIdx.x; b < A.B; b += blockDim.x) {
+    cost[b] = at_problem(A.state, (size_t)b * A.pstride)[TRS_COST];
+    const double* r = A.rows + (size_t)b * A.nrows;
+    int f = 0;
+    for (int k = 0; k < A.iterations; ++k) f |= (int)r[(size_t)k * TRR_COUNT + TRR_FLAGS];
+    status[b] = f;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int best = -1;
+    for (int b = 0; b < A.B; ++b) {
+      const double cb = cost[b];
+      const bool finite = cb - cb == 0.0;   // (neither NaN nor an infinity)
+      if ((status[b] & TR_ELIGIBLE_MASK) == 0 && finite && (best < 0 || cb < cost[best])) best = b;
+    }
+    best_s = best;
+  }
+  __syncthreads();
+  return best_s;
+}
+__global__ void tr_gather_batch_kernel(TrGatherBatchArgs A) {
+  extern __shared__ double gb_lds[];
+  double* cost = gb_lds;
+  int* status = reinterpret_cast<int*>(gb_lds + A.B);
+  const int b = blockIdx.y;
+  const size_t head = tr_gather_batch_header(A.B), nblk = (size_t)TRS_COUNT + A.nrows;
+  if (blockIdx.x == TR_GATHER_BATCH_GX) {   // the selecting workgroup
+    if (b != 0) return;
+    const int best = tr_select_best(A, cost, status);
+    if (threadIdx.x == 0) A.out[0] = (double)best;
+    for (int i = threadIdx.x; i < A.B; i += blockDim.x) { A.out[1 + i] = cost[i]; A.out[1 + A.B + i] = (double)status[i]; }
+    return;
+  }
+  int slot = b;
+  if (A.only_best) {
+    const int best = tr_select_best(A, cost, status);
+    slot = (b == best) ? 0 : -1;
+  }
+  const int tid = blockIdx.x * blockDim.x + threadIdx.x, nt = TR_GATHER_BATCH_GX * blockDim.x;
+  const size_t po = (size_t)b * A.pstride;
+  const double* st = at_problem(A.state, po);
+  const double* rows = A.rows + (size_t)b * A.nrows;
+  double* o = A.out + head + (size_t)b * nblk;
+  for (int i = tid; i < TRS_COUNT; i += nt) o[i] = st[i];
+  o += TRS_COUNT;
+  for (int i = tid; i < A.nrows; i += nt) o[i] = rows[i];
+  if (slot < 0) return;
+  const size_t off = po + (size_t)((A.alt_off != 0 && st[IDTO_TRS_CUR] != 0.0) ? A.alt_off : 0);
+  const double* v = at_problem(A.v, off);
+  const double* slab = at_problem(A.slab, off);
+  const double* q = at_problem(A.q, po);
+  const double* dq = at_problem(A.dq, po);
+  const double* w = at_problem(A.w, po);
+  const int nqa = (A.N + 1) * A.nq, nva = (A.N + 1) * A.nv, nta = A.N * A.nv;
+  o = A.out + head + (size_t)A.B * nblk + (size_t)slot * (3 * (size_t)nqa + nva + nta);
+  for (int i = tid; i < nqa; i += nt) o[i] = q[i];
+  o += nqa;
+  for (int i = tid; i < nva; i += nt) o[i] = v[i];
+  o += nva;
+  for (int i = tid; i < nta; i += nt) { const int t = i / A.nv, r = i - t * A.nv; o[i] = slab[(size_t)t * A.slab_stride + 3 * A.nv * A.nq + r]; }
+  o += nta;
+  for (int i = tid; i < nqa; i += nt) o[i] = dq[i];
+  o += nqa;
+  for (int i = tid; i < nqa; i += nt) o[i] = w[i];
+}
+
 // batch contexts after idto_hip_tr_solve_batch: a problem whose iterate's v, a, N+, slab and products ended up in the
 // second set of fd_kernel outputs (batch.h AltSel) gets them copied into the first (grid (x, problem))
 __global__ void tr_fold_sets_kernel(double* set_a, size_t count, const double* state, size_t pstride) {

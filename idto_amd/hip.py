@@ -67,6 +67,11 @@ def lib():
         L.idto_hip_tr_solve_batch_constrained.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
                                                           C.c_double, C.c_double, C.POINTER(C.c_int), C.c_int,
                                                           C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.idto_hip_tr_solve_fetch.argtypes = L.idto_hip_tr_solve.argtypes + [C.POINTER(C.c_double)] * 5
+        L.idto_hip_tr_solve_batch_fetch.argtypes = (
+            [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double,
+             C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
+            + [C.POINTER(C.c_double)] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int)])
         L.idto_hip_tr_reject.argtypes = [C.c_void_p]
         L.idto_hip_tr_set_scale_memory.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.idto_hip_tr_set_convergence.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -118,9 +123,9 @@ EXPORTED_SYMBOLS = [
     "idto_hip_set_option", "idto_hip_get_option",
     "idto_hip_timing_enable", "idto_hip_timing_reset", "idto_hip_timing_get", "idto_hip_sync", "idto_hip_get",
     "idto_hip_device_ptr", "idto_hip_array_size", "idto_hip_slab_stride", "idto_hip_math_probe",
-    "idto_hip_solver_status", "idto_hip_create_batch", "idto_hip_batch_size", "idto_hip_set_problem_batch",
+    "idto_hip_solver_status", "idto_hip_create_batch", "idto_hip_create_batch_like", "idto_hip_batch_size", "idto_hip_set_problem_batch",
     "idto_hip_set_q_batch", "idto_hip_gn_step_batch", "idto_hip_get_batch", "idto_hip_get_many", "idto_hip_solver_status_batch",
-    "idto_hip_tr_prepare", "idto_hip_tr_trial", "idto_hip_tr_accept", "idto_hip_tr_reject", "idto_hip_tr_set_scale_memory", "idto_hip_tr_set_convergence", "idto_hip_tr_solve", "idto_hip_tr_solve_fetch", "idto_hip_tr_solve_batch", "idto_hip_tr_solve_batch_constrained", "idto_hip_set_unactuated_dofs",
+    "idto_hip_tr_prepare", "idto_hip_tr_trial", "idto_hip_tr_accept", "idto_hip_tr_reject", "idto_hip_tr_set_scale_memory", "idto_hip_tr_set_convergence", "idto_hip_tr_solve", "idto_hip_tr_solve_fetch", "idto_hip_tr_solve_batch", "idto_hip_tr_solve_batch_constrained", "idto_hip_tr_solve_batch_fetch", "idto_hip_set_unactuated_dofs",
     "idto_hip_rccl_info", "idto_hip_comm_unique_id", "idto_hip_comm_init", "idto_hip_comm_init_all", "idto_hip_comm_destroy",
     "idto_hip_allgather_slab", "idto_hip_gn_step_sharded", "idto_hip_gn_step_multi", "idto_hip_eval_partials_multi",
     "idto_hip_trace_enable", "idto_hip_trace_mark", "idto_hip_trace_dump",
@@ -300,6 +305,52 @@ class HipPath:
                                                        int(normalize_quaternions), dptr(d0), float(Delta_max), float(eta),
                                                        dofs.ctypes.data_as(C.POINTER(C.c_int)), len(dofs), dptr(rows), dptr(delta)))
         return rows, delta
+
+    def _traj_buffers(self, T: int):
+        N, nq, nv = self.N, self.nq, self.nv
+        return dict(q=np.zeros((T, N + 1, nq)), v=np.zeros((T, N + 1, nv)), tau=np.zeros((T, N, nv)),
+                    dq=np.zeros((T, N + 1, nq)), w=np.zeros((T, N + 1, nq)))
+
+    def tr_solve_fetch(self, iterations: int, scaling_method: int, scaling: bool, normalize_quaternions: bool, Delta0: float,
+                       Delta_max: float, eta: float = 0.0, constrained_dofs=()):
+        """idto_hip_tr_solve_fetch: (rows [iterations, 17], final Delta, dict of q, v, tau, dq, w)"""
+        rows = np.zeros((int(iterations), 17))
+        delta = C.c_double(0.0)
+        dofs = np.ascontiguousarray(np.asarray(constrained_dofs, dtype=np.int32))
+        out = {k: a[0] for k, a in self._traj_buffers(1).items()}
+        self.last_tr_rows = rows
+        _chk(lib().idto_hip_tr_solve_fetch(self.h, int(iterations), int(scaling_method), int(scaling), int(normalize_quaternions),
+                                           float(Delta0), float(Delta_max), float(eta),
+                                           dofs.ctypes.data_as(C.POINTER(C.c_int)) if dofs.size else None, int(dofs.size),
+                                           dptr(rows), C.byref(delta), *[dptr(out[k]) for k in ("q", "v", "tau", "dq", "w")]))
+        return rows, delta.value, out
+
+    def tr_solve_batch_fetch(self, iterations: int, scaling_method: int, scaling: bool, normalize_quaternions: bool, Delta0,
+                             Delta_max: float, eta: float = 0.0, constrained_dofs=(), only_best: bool = False,
+                             check: bool = True):
+        """idto_hip_tr_solve_batch_fetch: the batch's loop, every problem's rows, radius, cost, status and trajectories
+        (only_best: the best problem's trajectories alone, leading dimension 1) and the index of the best problem, under
+        ONE wait.  Returns a dict: rows [B, iterations, 17], delta [B], q, v, tau, dq, w, final_cost [B], status [B], best,
+        rc (the call's return code; check=False hands IDTO_HIP_FACTORIZATION_FAILED back there instead of raising)."""
+        B = self.batch
+        rows = np.zeros((B, int(iterations), 17))
+        d0 = np.ascontiguousarray(np.broadcast_to(np.asarray(Delta0, dtype=np.float64), (B,)))
+        delta = np.zeros(B)
+        dofs = np.ascontiguousarray(np.asarray(constrained_dofs, dtype=np.int32))
+        out = self._traj_buffers(1 if only_best else B)
+        final_cost = np.zeros(B)
+        status = np.zeros(B, dtype=np.int32)
+        best = C.c_int(-2)
+        self.last_tr_rows = rows
+        rc = lib().idto_hip_tr_solve_batch_fetch(
+            self.h, int(iterations), int(scaling_method), int(scaling), int(normalize_quaternions), dptr(d0), float(Delta_max),
+            float(eta), dofs.ctypes.data_as(C.POINTER(C.c_int)) if dofs.size else None, int(dofs.size), dptr(rows), dptr(delta),
+            int(only_best), *[dptr(out[k]) for k in ("q", "v", "tau", "dq", "w")], dptr(final_cost),
+            status.ctypes.data_as(C.POINTER(C.c_int)), C.byref(best))
+        if check or rc not in (0, FACTORIZATION_FAILED):
+            _chk(rc)
+        out.update(rows=rows, delta=delta, final_cost=final_cost, status=status, best=best.value, rc=rc)
+        return out
 
     def tr_set_convergence(self, tolerances=None):
         """[rel_cost, abs_cost, rel_gradient_along_dq, abs_gradient_along_dq, rel_state, abs_state] or None (no checks)"""

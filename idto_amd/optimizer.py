@@ -43,6 +43,11 @@ def lib():
         L.idto_opt_num_equality_constraints.argtypes = [C.c_void_p]
         P = C.POINTER(C.c_double)
         L.idto_opt_solve.argtypes = [C.c_void_p, P, P, P, P, C.POINTER(CStats), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.idto_opt_solve_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(CProblem), P, C.c_int, P, P, P, C.POINTER(CStats),
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int), P, C.POINTER(C.c_int)]
+        L.idto_opt_batch_error.argtypes = [C.c_void_p, C.c_int]
+        L.idto_opt_batch_error.restype = C.c_char_p
+        L.idto_opt_last_batch_route.argtypes = [C.c_void_p]
         L.idto_opt_ws_create.argtypes = [C.c_void_p, P, C.POINTER(C.c_void_p)]
         L.idto_opt_ws_destroy.argtypes = [C.c_void_p]
         L.idto_opt_ws_set_q.argtypes = [C.c_void_p, C.c_void_p, P]
@@ -73,6 +78,7 @@ EXPORTED_SYMBOLS = [
     "idto_opt_num_equality_constraints", "idto_opt_solve", "idto_opt_ws_create", "idto_opt_ws_destroy",
     "idto_opt_ws_set_q", "idto_opt_ws_get", "idto_opt_ws_solve", "idto_opt_reset_initial_conditions",
     "idto_opt_update_nominal_trajectory", "idto_opt_eval", "idto_opt_dogleg", "idto_opt_trust_ratio",
+    "idto_opt_solve_batch", "idto_opt_batch_error", "idto_opt_last_batch_route",
 ]
 MPC_SYMBOLS = ["idto_mpc_create", "idto_mpc_destroy", "idto_mpc_num_actuators", "idto_mpc_update", "idto_mpc_state",
                "idto_mpc_control", "idto_mpc_start_time", "idto_mpc_spline_eval"]
@@ -125,6 +131,18 @@ class TrajectoryOptimizerSolution:
 
     def __init__(self):
         self.q = self.v = self.tau = None
+
+
+class BatchSolveResult:
+    """what `TrajectoryOptimizer.solve_batch` returns (TrajectoryOptimizer::BatchSolveResult of the C++ API): per entry a
+    solution (None where the entry has none: it failed, or only_best was asked and it is not the best), the statistics,
+    the SolverFlag name, the error text ("" for an entry with a solution), the convergence reason and the final cost;
+    `best`: the entry of the lowest final cost among the usable ones (-1: none); `batch_route`: True when the device's
+    batch loop ran the entries, False when they ran one after another."""
+
+    def __init__(self, solutions, stats, flags, errors, reasons, final_costs, best, batch_route):
+        self.solutions, self.stats, self.flags, self.errors = solutions, stats, flags, errors
+        self.convergence_reasons, self.final_costs, self.best, self.batch_route = reasons, final_costs, best, batch_route
 
 
 class WarmStart:
@@ -224,6 +242,48 @@ class TrajectoryOptimizer:
         solution.q, solution.v, solution.tau = q, v, tau
         self.last_convergence_reason = reason.value
         return SOLVER_FLAGS[flag.value]
+
+    def solve_batch(self, q_guesses, problems=None, only_best: bool = False) -> BatchSolveResult:
+        """TrajectoryOptimizer::SolveBatch: entry b is `Solve(q_guesses[b])` on an optimizer made with `problems[b]` (None:
+        this optimizer's own problem for every entry), all entries through ONE trust-region loop on the device where the
+        configuration allows it, one after another otherwise."""
+        q = _d(q_guesses)
+        if q.ndim != 3 or q.shape[1:] != (self.N + 1, self.nq):
+            raise RuntimeError(f"solve_batch: q_guesses must be [B, {self.N + 1}, {self.nq}]")
+        B = q.shape[0]
+        carr, keep = None, []
+        if problems is not None:
+            if len(problems) != B:
+                raise RuntimeError(f"solve_batch: q_guesses and problems disagree in length ({B} and {len(problems)})")
+            carr = (CProblem * B)()
+            for b, pr in enumerate(problems):
+                if pr.num_steps != self.N or np.shape(pr.q_nom) != (self.N + 1, self.nq) or np.shape(pr.v_nom) != (self.N + 1, self.nv) \
+                        or np.size(pr.q_init) != self.nq or np.size(pr.v_init) != self.nv:
+                    raise RuntimeError(f"solve_batch: problem {b} has another num_steps or other sizes than the optimizer's")
+                carr[b], k = pr.to_c()
+                keep.append(k)
+        sq, sv, st = np.zeros((B, self.N + 1, self.nq)), np.zeros((B, self.N + 1, self.nv)), np.zeros((B, self.N, self.nv))
+        stats = [TrajectoryOptimizerStats(max(self._params.max_iterations, 1)) for _ in range(B)]
+        cst = (CStats * B)()
+        for b in range(B):
+            cst[b] = stats[b].c
+        flags, reasons, best = (C.c_int * B)(), (C.c_int * B)(), C.c_int(-1)
+        costs = np.zeros(B)
+        self._chk(lib().idto_opt_solve_batch(self._h, B, carr, dptr(q), int(only_best), dptr(sq), dptr(sv), dptr(st), cst, flags,
+                                             reasons, dptr(costs), C.byref(best)))
+        errors = [lib().idto_opt_batch_error(self._h, b).decode() for b in range(B)]
+        sols = []
+        for b in range(B):
+            stats[b].c = cst[b]   # (count, total and solve_time were written into the array's copy; the series are shared)
+            has = not errors[b] and SOLVER_FLAGS[flags[b]] in ("kSuccess", "kMaxIterationsReached") and (not only_best or b == best.value)
+            if has:
+                sol = TrajectoryOptimizerSolution()
+                sol.q, sol.v, sol.tau = sq[b], sv[b], st[b]
+                sols.append(sol)
+            else:
+                sols.append(None)
+        return BatchSolveResult(sols, stats, [SOLVER_FLAGS[f] for f in flags], errors, list(reasons), costs, best.value,
+                                bool(lib().idto_opt_last_batch_route(self._h) == 1))
 
     def CreateWarmStart(self, q_guess):
         h = C.c_void_p()

@@ -29,8 +29,10 @@
 // the 2-DoF toy examples' figures, TO.cc:1650-1830) are not produced: the constructor throws if one is set.
 #pragma once
 
+#include <map>
 #include <memory>
 #include <stdexcept>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -95,6 +97,34 @@ class TrajectoryOptimizer<double> {
   SolverFlag SolveFromWarmStart(WarmStart* warm_start, TrajectoryOptimizerSolution<T>* solution,
                                 TrajectoryOptimizerStats<T>* stats, ConvergenceReason* reason = nullptr) const;
 
+  // Several problems of this optimizer's model, horizon, SolverParameters and contact parameters at once (no counterpart in
+  // the reference, whose caller loops over Solve): what a sampling-based planner, a multi-start on a non-convex contact
+  // problem or an MPC server with several warm-started problems per tick asks for.
+  struct BatchSolveResult {
+    std::vector<TrajectoryOptimizerSolution<T>> solutions;   // [B]; only_best: only solutions[best] is filled
+    std::vector<TrajectoryOptimizerStats<T>> stats;          // [B]
+    std::vector<SolverFlag> flags;                           // [B]; meaningful where errors[b] is empty or names a failed factorisation
+    std::vector<std::string> errors;                         // [B]; non-empty: entry b has no solution, and this says why
+    std::vector<double> final_costs;                         // [B]; the cost of entry b's final iterate (NaN: none)
+    int best = -1;   // the entry of the lowest final cost among those that ended kSuccess / kMaxIterationsReached with a
+                     // finite cost, the lowest index among equals; -1: none
+  };
+  // Entry b is Solve(q_guesses[b]) on an optimizer constructed with (*problems)[b] (null: this optimizer's own problem for
+  // every entry) from a fresh state: Delta = Delta0, the adaptive scalings' memory ones.  One entry's failure is its own
+  // flags[b] / errors[b].  Configurations the device's batch loop serves (trust region, one device, the device-resident
+  // loop, diagonal cost weights, no adaptive scaling, verbose off, enforced constraints through the banded KKT step) run as
+  // ONE loop for all entries with one wait for everything that comes back (idto_hip_tr_solve_batch_fetch) on a batch context
+  // created on first use and kept per B; every other configuration runs the entries one after another on this
+  // optimizer's own context, with the same result layout.  A batch of more than two small models (blocks up to 4) takes
+  // the block solver kernels where one problem alone takes the scalar band kernels: the entries then agree with Solve to
+  // the solver's round-off, otherwise bit for bit.
+  // Throws, before any device work, when q_guesses and problems disagree in length or a problem's num_steps / vector
+  // sizes differ from this optimizer's.
+  void SolveBatch(const std::vector<std::vector<VectorXd>>& q_guesses, const std::vector<ProblemDefinition>* problems,
+                  BatchSolveResult* out, bool only_best = false) const;
+  // how the last SolveBatch ran: 1 the batch loop, 0 entry by entry (tests and tools/solve_batch_bench.py ask)
+  int last_batch_route() const { return last_batch_route_; }
+
   const std::vector<VectorXd>& EvalV(const TrajectoryOptimizerState<T>& state) const;
   const std::vector<VectorXd>& EvalA(const TrajectoryOptimizerState<T>& state) const;
   const std::vector<VectorXd>& EvalTau(const TrajectoryOptimizerState<T>& state) const;
@@ -127,6 +157,17 @@ class TrajectoryOptimizer<double> {
  private:
   int num_vars() const { return (num_steps() + 1) * nq_; }
   void UploadProblem() const;
+  void UploadProblemDefinition(const ProblemDefinition& prob) const;   // `prob` onto this optimizer's context(s)
+  // SolveBatch: the batch context of a given B with the host buffers of its calls (allocated once per B)
+  struct BatchContext {
+    idto_hip_ctx* ctx = nullptr;
+    std::vector<double> q, rows, Delta0, Delta_out, sol_q, sol_v, sol_tau, final_cost, q_nom, v_nom;
+    std::vector<int> status;
+  };
+  BatchContext* GetBatchContext(int B, const std::vector<const ProblemDefinition*>& probs) const;
+  void CheckBatchProblem(const ProblemDefinition& p, int b) const;
+  // entry b of a batch solved alone on this optimizer's own context (the fallback of SolveBatch)
+  void SolveBatchEntryAlone(const ProblemDefinition* prob, const std::vector<VectorXd>& q_guess, int b, BatchSolveResult* out) const;
   // the context, with the problem data on the device up to date (ResetInitialConditions / UpdateNominalTrajectory only
   // mark them: an MPC re-plan calls both, examples/mpc_controller.cc:60-75, and pays for one upload)
   idto_hip_ctx* dev() const { if (problem_dirty_) UploadProblem(); return hip_; }
@@ -177,6 +218,8 @@ class TrajectoryOptimizer<double> {
   // host loop (pivoted LDL^T) finishes the solve from that iterate
   mutable bool force_host_loop_ = false;
   mutable int resume_k_ = 0;
+  mutable std::map<int, BatchContext> batch_ctx_;   // SolveBatch: per batch size
+  mutable int last_batch_route_ = -1;
   mutable double last_sparse_vs_dense_ = -1.0;   // debug_compare_against_dense: the figure CalcDoglegPoint printed last
 };
 

@@ -109,6 +109,10 @@ void idto_hip_destroy(idto_hip_ctx* ctx);
 int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* problems /* [batch] */,
                           const idto_contact_params_t* contact, int device, int batch, idto_hip_ctx** out);
 int idto_hip_batch_size(idto_hip_ctx* ctx);
+/* A batch context for the model, the contact parameters, the device and the "gradients_method" option of an existing
+ * context (which keeps host copies of the first two): how the host-side TrajectoryOptimizer, which holds a context and
+ * not the model it was made from, gets the batch behind SolveBatch. */
+int idto_hip_create_batch_like(idto_hip_ctx* like, const idto_problem_t* problems /* [batch] */, int batch, idto_hip_ctx** out);
 int idto_hip_set_problem_batch(idto_hip_ctx* ctx, int problem, const idto_problem_t* p);
 int idto_hip_set_q_batch(idto_hip_ctx* ctx, const double* q_host /* [batch][(N+1)*nq] */);
 int idto_hip_gn_step_batch(idto_hip_ctx* ctx); /* = idto_hip_gn_step: every problem of the batch */
@@ -335,6 +339,29 @@ int idto_hip_tr_solve_batch(idto_hip_ctx* ctx, int iterations, int scaling_metho
 int idto_hip_tr_solve_batch_constrained(idto_hip_ctx* ctx, int iterations, int scaling_method, int scaling,
                                         int normalize_quaternions, const double* Delta0, double Delta_max, double eta,
                                         const int* constrained_dofs, int nu, double* rows_host, double* Delta_out);
+
+/* The batch loop of idto_hip_tr_solve_batch(_constrained) that also brings back what the caller reads next, and chooses
+ * the best problem: behind the last iteration ONE launch packs every problem's state words, rows, iterate q, its v and tau
+ * (from the set of outputs the problem's own iterate ended up in), the last step dq and w into one buffer, one copy takes
+ * it to pinned memory of the context (grown on demand, kept), and the call waits for the device exactly once - where
+ * idto_hip_tr_solve_batch + idto_hip_get_batch wait about three times per problem.  The context is left as
+ * idto_hip_tr_solve_batch leaves it.
+ *   final_cost[b]: the cost of problem b's iterate as the loop's state holds it;
+ *   status[b]: the OR of column [14] over problem b's rows;
+ *   best: among the problems with status & (1|2|4|8|32) == 0 and a finite cost the one of the lowest final_cost, the
+ *     lowest index among equals (a fixed scan from 0 to batch - 1 on the device: the same answer at every launch
+ *     geometry), -1 when there is none;
+ *   only_best != 0: q_out ... w_out receive the best problem's arrays alone ([1][...]; untouched when best is -1), and
+ *     only those are packed and copied; rows, radii, costs and statuses come back for every problem.
+ * Every problem's outputs are filled even when a factorisation failed (status bit 32 names the problem); the return value
+ * is then IDTO_HIP_FACTORIZATION_FAILED, or IDTO_HIP_SOLVER_TIMEOUT as for the other loops.  On a context of one problem
+ * the call is idto_hip_tr_solve_fetch.  Enforced constraints that idto_hip_tr_solve_batch_constrained would advance in
+ * child contexts (option con_kkt = 0, nq + nu > 30, dense cost weights) are refused with -1 before any device work.
+ * Residency as for idto_hip_tr_solve_batch: idto_hip_set_q_batch + idto_hip_eval_tau. */
+int idto_hip_tr_solve_batch_fetch(idto_hip_ctx* ctx, int iterations, int scaling_method, int scaling, int normalize_quaternions,
+                                  const double* Delta0, double Delta_max, double eta, const int* constrained_dofs, int nu,
+                                  double* rows_host, double* Delta_out, int only_best, double* q_out, double* v_out,
+                                  double* tau_out, double* dq_out, double* w_out, double* final_cost, int* status, int* best);
 
 /* Options: "gradients_method" = 0 forward differences (default), 1 / 2 central differences of
  * 2nd / 4th order (SolverParameters::gradients_method, reference solver_parameters.h:26-50,

@@ -46,6 +46,22 @@ int idto_opt_num_equality_constraints(const idto_opt* opt);
 int idto_opt_solve(idto_opt* opt, const double* q_guess, double* sol_q, double* sol_v, double* sol_tau,
                    idto_stats_t* stats, int* flag, int* reason);
 
+/* TrajectoryOptimizer::SolveBatch (include/idto/optimizer/trajectory_optimizer.h): B problems of the optimizer's model,
+ * horizon, solver and contact parameters; entry b is idto_opt_solve of q_guesses[b] on an optimizer created with problems[b]
+ * (NULL: the optimizer's own problem for every entry).  q_guesses: [B][(N+1)*nq]; sol_q / sol_v / sol_tau: [B][...] (any may
+ * be NULL) - the block of an entry without a solution (it failed, or only_best != 0 and it is not the best) is left
+ * untouched; stats: B blocks; flags, reasons (ConvergenceReason bitmasks), final_costs: [B] (any may be NULL); *best: the
+ * entry of the lowest final cost among those that ended kSuccess / kMaxIterationsReached, -1: none.  One entry's failure is
+ * its own flag (kFactorizationFailed) and text (idto_opt_batch_error, valid until the next idto_opt_solve_batch of the
+ * optimizer; "" for an entry that has its solution); the call itself fails only for what concerns the whole batch: a
+ * problem of another num_steps / time_step, a device error. */
+int idto_opt_solve_batch(idto_opt* opt, int B, const idto_problem_t* problems, const double* q_guesses, int only_best,
+                         double* sol_q, double* sol_v, double* sol_tau, idto_stats_t* stats, int* flags, int* reasons,
+                         double* final_costs, int* best);
+const char* idto_opt_batch_error(const idto_opt* opt, int b);
+/* 1: the last idto_opt_solve_batch ran the device's batch loop, 0: entry by entry on the optimizer's own context, -1: none yet */
+int idto_opt_last_batch_route(const idto_opt* opt);
+
 /* CreateWarmStart / SolveFromWarmStart (trajectory_optimizer.h:156-211, warm_start.h:23-76) */
 int idto_opt_ws_create(idto_opt* opt, const double* q_guess, idto_opt_warm_start** out);
 void idto_opt_ws_destroy(idto_opt_warm_start* ws);

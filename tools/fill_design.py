@@ -133,6 +133,10 @@ vals.update({
     "FD_TAIL_FD_US": f"{fd_a:.1f} µs (`profiles/fd_tail_kernel_stats_after.csv`; round 6: {fd_us:.1f})" if have_stats else f"{fd_us:.1f} µs (round 6; the tail since: §3.3)",
     "FD_TAIL_STEP": f"{1e6 / med['new']:.1f} µs = {med['new']:.0f} it/s (`profiles/fd_tail_bench.txt`, median of {len(head['new'])}; round 6: {1e3 * b['ms_per_step']:.1f} µs = {b['value']:.0f} it/s)",
 })
+# §12.1: the batch at the public interface, profiles/solve_batch.txt (tools/solve_batch_bench.py; not a round's file)
+sb = [l.rstrip() for l in open(os.path.join(ROOT, "profiles", "solve_batch.txt")) if l.strip()]
+vals["SOLVE_BATCH_FIGURES"] = ("Measured (`tools/solve_batch_bench.py` → `profiles/solve_batch.txt`; " + sb[0].split(": ", 1)[1] + "):\n\n"
+                               + "\n".join("    " + l for l in sb[1:]))
 src = os.path.join(ROOT, "tools", "design", "DESIGN.in.md")
 text = open(src).read()
 subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_design.py")])

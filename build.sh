@@ -30,7 +30,7 @@ if [ -z "$IDTO_SKIP_RESOURCE_CHECK" ]; then python3 tools/check_resources.py bui
 $HIPCC --offload-arch=gfx950 -fPIC -shared build/fd_launch.o build/idto_hip.o build/model_tables.o build/solver_plan.o -o idto_amd/libidto_hip.so -ldl
 # libidto_opt.so: the host-side TrajectoryOptimizer (C++) + its C-ABI, on top of libidto_hip.so
 g++ -O3 -std=c++17 -fPIC -shared -Wall -Iinclude -Iidto_amd/csrc idto_amd/csrc/host/trajectory_optimizer.cc \
-  idto_amd/csrc/host/batch_rows.cc idto_amd/csrc/host/mpc_controller.cc idto_amd/csrc/host/idto_opt_c.cc -o idto_amd/libidto_opt.so -Lidto_amd -lidto_hip -Wl,-rpath,'$ORIGIN'
+  idto_amd/csrc/host/batch_rows.cc idto_amd/csrc/host/ls_rows.cc idto_amd/csrc/host/mpc_controller.cc idto_amd/csrc/host/idto_opt_c.cc -o idto_amd/libidto_opt.so -Lidto_amd -lidto_hip -Wl,-rpath,'$ORIGIN'
 
 # a C++ consumer of the boundary with no Python in the process (tests/test_gpu_cpp_consumer.py runs it on the GPU box)
 g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/solve_acrobot.cc -o build/solve_acrobot -Lidto_amd -lidto_opt -lidto_hip -Wl,-rpath,'$ORIGIN/../idto_amd'

@@ -890,5 +890,20 @@ __global__ void __launch_bounds__(256) fd_kernel(DevModel M, DevContact cp, DevP
                        terms ? at_problem(terms, w) : nullptr);
 }
 
+// tau only (mode 0) at candidate points of ONE problem (linesearch.h): blockIdx.y is the candidate - the problem's arrays
+// stay where they are, q and every output lie cstride bytes apart per candidate.  gate: a device word, not 0.0 = the
+// launch has nothing to do.  A kernel of its own, so that fd_kernel's own code is what it was: the same fd_body, the
+// mode a constant.
+template <int MAXC, int SHAPE = 0>
+__global__ void __launch_bounds__(256) fd_along_kernel(DevModel M, DevContact cp, DevProblem P, const double* __restrict__ q,
+                          double* __restrict__ slab, int slab_stride, double* __restrict__ v_out,
+                          double* __restrict__ a_out, double* __restrict__ nplus_out, int k_begin, int stop_after,
+                          int echunk, size_t cstride, const double* __restrict__ gate) {
+  if (gate && *gate != 0.0) return;
+  const size_t w = (size_t)blockIdx.y * cstride;
+  fd_body<MAXC, SHAPE>(M, cp, P, at_problem(q, w), at_problem(slab, w), slab_stride, at_problem(v_out, w),
+                       at_problem(a_out, w), at_problem(nplus_out, w), k_begin + (int)blockIdx.x, 0, stop_after, echunk, nullptr);
+}
+
 
 }  // namespace idto_dev

@@ -23,6 +23,8 @@ struct FdLaunch {
   size_t pstride;
   double* terms;
   AltSel alt;
+  const double* gate = nullptr;   // a device word: the launch returns at once when it is not 0.0
+  size_t cstride = 0;   // != 0: grid.y counts candidate points of one problem, cstride bytes apart: fd_along_kernel, mode 0
   int shape;   // id_fast.h: the model's instantiated tree shape, 0: id_eval<MAXC>, SHAPE_XCH: id_eval<8, true> (shared pairs), SHAPE_STEM: id_eval<8, true, true>
   int maxc;
 };

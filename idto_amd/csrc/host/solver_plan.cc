@@ -241,4 +241,19 @@ SolverBuffers SolverBufferCounts(int K, int N) {
   return b;
 }
 
+int PlanLsWaves(int N, int compute_units, int method, int max_linesearch_iterations, int override_width,
+                int widths[kLsMaxCandidates]) {
+  int total = kLsMaxCandidates;
+  if (method == 0) total = std::min(kLsMaxCandidates, std::max(1, max_linesearch_iterations));   // (Armijo's do-while: at least one)
+  int width = override_width > 0 ? override_width : std::max(1, compute_units / std::max(1, N));
+  int count = 0;
+  for (int done = 0; done < total; ++count) {
+    const int w = std::min(std::min(width, kLsMaxCandidates), total - done);
+    widths[count] = w;
+    done += w;
+    if (override_width <= 0) width *= 2;
+  }
+  return count;
+}
+
 }  // namespace idto_host

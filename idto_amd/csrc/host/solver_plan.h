@@ -90,4 +90,15 @@ struct SolverBuffers {
 };
 SolverBuffers SolverBufferCounts(int K, int N);
 
+// The linesearch loop's waves (idto_hip_ls_solve): how many candidate step lengths each launch set evaluates, a pure
+// function of (horizon, compute units, method, max_linesearch_iterations).  One candidate is N workgroups of one wavefront:
+// the first wave takes as many candidates as give every compute unit one workgroup, every further wave twice its
+// predecessor - most linesearches end within the first two waves, and a late one costs launches, not a device full of
+// evaluations nobody reads.  Armijo never looks past max_linesearch_iterations candidates; backtracking is not bounded by it
+// and gets all kLsMaxCandidates.  override_width > 0 (option "ls_waves"): that many candidates in every wave.
+// Returns the number of waves; widths[i] > 0, their sum is the number of candidates, in index order.
+constexpr int kLsMaxCandidates = 64;
+int PlanLsWaves(int N, int compute_units, int method, int max_linesearch_iterations, int override_width,
+                int widths[kLsMaxCandidates]);
+
 }  // namespace idto_host

@@ -13,6 +13,7 @@
 #include "idto/optimizer/trajectory_optimizer.h"
 
 #include "host/batch_rows.h"
+#include "host/ls_rows.h"
 
 #include <algorithm>
 #include <chrono>
@@ -24,6 +25,7 @@
 #include <string>
 
 static_assert(idto::optimizer::internal::kTrRow == IDTO_TR_ROW, "batch_rows.h and idto_hip.h disagree about a row's width");
+static_assert(idto::optimizer::internal::kLsRow == IDTO_LS_ROW, "ls_rows.h and idto_hip.h disagree about a row's width");
 
 namespace idto {
 namespace optimizer {
@@ -951,7 +953,8 @@ SolverFlag TO::Solve(const std::vector<VectorXd>& q_guess, TrajectoryOptimizerSo
   if (!stats->is_empty()) throw std::runtime_error("Solve: stats must be empty (TO.cc:2225)");
   if ((int)q_guess.size() != num_steps() + 1) throw std::runtime_error("Solve: q_guess has the wrong length");
   try {
-    if (params_.method == kLinesearch) return SolveWithLinesearch(q_guess, solution, stats);
+    if (params_.method == kLinesearch)
+      return LinesearchLoopEligible() ? SolveLinesearchOnDevice(q_guess, solution, stats) : SolveWithLinesearch(q_guess, solution, stats);
     std::unique_ptr<WarmStart> ws = CreateWarmStart(q_guess);
     return SolveFromWarmStart(ws.get(), solution, stats, reason);
   } catch (const FactorizationFailedError& e) {
@@ -1018,6 +1021,63 @@ std::pair<double, int> TO::BacktrackingLinesearch(const TrajectoryOptimizerState
     ++i;
   }
   return {alpha / rho, i};
+}
+
+// The linesearch method on the device (idto_hip_ls_solve_fetch: every iteration enqueued at once, the step lengths in
+// waves, one wait) serves what the reference's examples run it with - no scaling (with it the reference divides a scaled
+// gradient by an unscaled Hessian, TO.cc:2292-2302: that stays on the host loop), no enforced constraints, diagonal cost
+// weights, the banded solver, one device, no per-iteration output.  Everything else takes SolveWithLinesearch as it stands.
+bool TO::LinesearchLoopEligible() const {
+  if (std::getenv("IDTO_OPT_HOST_LOOP") || force_host_loop_) return false;
+  if (!shard_ctx_.empty() || params_.max_iterations < 1) return false;
+  if (params_.scaling || (params_.equality_constraints && num_equality_constraints() > 0)) return false;
+  if (DenseLinearSolver() || params_.debug_compare_against_dense || params_.print_debug_data || params_.verbose) return false;
+  if (params_.max_linesearch_iterations > IDTO_LS_MAX_CANDIDATES) return false;
+  int weights_diagonal = 0;
+  Check(idto_hip_get_option(dev(), "weights_diagonal", &weights_diagonal));
+  return weights_diagonal != 0;
+}
+
+SolverFlag TO::SolveLinesearchOnDevice(const std::vector<VectorXd>& q_guess, TrajectoryOptimizerSolution<T>* solution,
+                                       TrajectoryOptimizerStats<T>* stats) const {
+  using clock = std::chrono::high_resolution_clock;
+  const auto start_time = clock::now();
+  // (the host loop that takes over - a loop time-out, backtracking undecided within the device's candidates - starts
+  // from the guess again: the device loop has left nothing in `stats`)
+  auto on_host = [&]() {
+    force_host_loop_ = true;
+    struct Reset { const TO* t; ~Reset() { t->force_host_loop_ = false; } } reset{this};
+    resident_ = nullptr;
+    device_level_ = 0;
+    return SolveWithLinesearch(q_guess, solution, stats);
+  };
+  const int iters = params_.max_iterations, N = num_steps();
+  {
+    const Vec q0 = Flatten(q_guess);
+    Check(idto_hip_set_q(dev(), q0.data()));
+  }
+  resident_ = nullptr;
+  device_level_ = 0;
+  Check(idto_hip_set_unactuated_dofs(dev(), unactuated_dofs_.data(), (int)unactuated_dofs_.size()));
+  std::vector<double> rows((std::size_t)iters * IDTO_LS_ROW);
+  Vec fq((std::size_t)num_vars()), fv((std::size_t)(N + 1) * nv_), ft((std::size_t)N * nv_);
+  const int rc = idto_hip_ls_solve_fetch(dev(), iters, static_cast<int>(params_.linesearch_method), params_.max_linesearch_iterations,
+                                         params_.normalize_quaternions ? 1 : 0, rows.data(), fq.data(), fv.data(), ft.data());
+  idto_hip_trace_mark("opt: idto_hip_ls_solve_fetch returned");
+  if (rc == IDTO_HIP_SOLVER_TIMEOUT) return on_host();
+  if (rc != 0 && rc != IDTO_HIP_FACTORIZATION_FAILED) Check(rc);
+  const double total = std::chrono::duration<double>(clock::now() - start_time).count();
+  TrajectoryOptimizerStats<T> device_stats;
+  internal::LsRowsResult res;
+  internal::LsRowsToStats(rows.data(), iters, total, params_.linesearch_method, &device_stats, &res);
+  if (res.outcome == internal::LsRowsOutcome::kNeedsHostLoop) return on_host();
+  *stats = device_stats;
+  if (res.outcome == internal::LsRowsOutcome::kFailed) throw FactorizationFailedError(res.error);
+  if (res.outcome == internal::LsRowsOutcome::kError) throw std::runtime_error(res.error);
+  solution->q = Unflatten(fq, N + 1, nq_);
+  solution->v = Unflatten(fv, N + 1, nv_);
+  solution->tau = Unflatten(ft, N, nv_);
+  return res.flag;
 }
 
 // TO.cc:2244-2407

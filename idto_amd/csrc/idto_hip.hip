@@ -37,6 +37,7 @@
 #include "dense_ldl.h"
 #include "trust_region.h"
 #include "kkt.h"
+#include "linesearch.h"
 #include "host/model_tables.h"
 #include "host/solver_plan.h"
 
@@ -284,6 +285,13 @@ struct idto_hip_ctx {
   double *stage_rhs = nullptr, *stage_x = nullptr;  // idto_hip_solve_host
   double* pack = nullptr;                            // [tau | cost] of idto_hip_trial_cost (device)
   double* pin = nullptr;                             // pinned host staging: q in, [tau | cost] out
+  double *ls_arenas = nullptr, *ls_costs = nullptr; int ls_cap = 0;   // idto_hip_costs_along: candidate arenas (linesearch.h LsArena), their costs
+  double* ls_pin = nullptr;                          // ... and the costs' pinned staging ([IDTO_LS_MAX_CANDIDATES])
+  // idto_hip_ls_solve: the loop's state words, the scan, the statistics rows, the trust ratio's [step | H step], the
+  // pinned staging of [rows | q | v | tau]; option "ls_waves"; calls so far (the tests' proof of which loop ran)
+  double *ls_state = nullptr, *ls_rows = nullptr, *ls_work = nullptr; idto_ls::LsScan* ls_scan = nullptr; int ls_rows_cap = 0;
+  double* ls_fetch_pin = nullptr; size_t ls_fetch_cap = 0;
+  int ls_waves = 0, ls_solves = 0, compute_units = 0;
   char* prob_pin = nullptr; size_t prob_pin_bytes = 0;   // ... of the problem arrays (UploadProblemArrays)
   double* many_pin = nullptr; size_t many_cap = 0;        // ... of idto_hip_get_many
   double* rows_pin = nullptr; size_t rows_cap = 0;        // ... of idto_hip_tr_solve's statistics rows
@@ -554,11 +562,15 @@ static int FdBlock(const idto_hip_ctx* c, int mode) {
 // derivatives requested): grad_hess then only combines them
 static bool FoldTerms(const idto_hip_ctx* c, int mode) { return c->asm_fold && c->weights_diagonal && mode >= 1; }
 
-int LaunchFd(idto_hip_ctx* c, int mode, int kb, int ke, AltSel alt = AltSel{nullptr, 0, 0}) {
-  c->partials_ahead = false;   // (whatever idto_hip_eval_tau_partials left is about to be overwritten; it sets the flag after its own launch)
+// along (idto_hip_costs_along, mode 0): the launch evaluates `m` candidate points of the context's one problem instead
+// of the resident q - grid.y = candidate, q and the outputs in arenas of their own (linesearch.h LsArena), nothing of the
+// resident iterate is written
+struct FdAlong { const double* q; double *slab, *v, *a, *nplus; int slab_stride; size_t cstride; int m; const double* gate; };
+int LaunchFd(idto_hip_ctx* c, int mode, int kb, int ke, AltSel alt = AltSel{nullptr, 0, 0}, const FdAlong* along = nullptr) {
+  if (!along) c->partials_ahead = false;   // (whatever idto_hip_eval_tau_partials left is about to be overwritten; it sets the flag after its own launch)
   if (ke <= kb) return 0;
   if (mode >= 1) mode = 1 + c->gradients_method;  // 1 forward, 2 central, 3 central (4th order)
-  dim3 grid(ke - kb, c->batch), block(FdBlock(c, mode));
+  dim3 grid(ke - kb, along ? along->m : c->batch), block(FdBlock(c, mode));
   // evaluations per pass: all of them if they fit in LDS, otherwise the largest multiple of
   // the number of evaluations the block runs concurrently
   const int E = FdEvals(c, mode), groups = (int)block.x / c->npaths;
@@ -575,6 +587,10 @@ int LaunchFd(idto_hip_ctx* c, int mode, int kb, int ke, AltSel alt = AltSel{null
   fl.q = c->q; fl.slab = c->slab; fl.slab_stride = c->slab_stride; fl.v = c->v; fl.a = c->a; fl.nplus = c->nplus;
   fl.k_begin = kb; fl.mode = mode; fl.stop_after = c->fd_stop; fl.echunk = ec; fl.pstride = c->pstride; fl.terms = terms;
   fl.alt = alt;
+  if (along) {
+    fl.q = along->q; fl.slab = along->slab; fl.slab_stride = along->slab_stride; fl.v = along->v; fl.a = along->a;
+    fl.nplus = along->nplus; fl.cstride = along->cstride; fl.gate = along->gate;
+  }
   fl.shape = c->fd_fast ? c->M.fast_shape : 0;   // id_fast.h: the straight-line evaluation of the model's tree shape
   if (c->M.nxb) fl.shape = SHAPE_XCH;             // shared pairs: the generic evaluation with the exchange (whatever fd_fast says)
   if (c->M.nstem > 1) fl.shape = SHAPE_STEM;      // a stem below the common body: ... and the walk along it
@@ -914,6 +930,7 @@ int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* probl
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&penta_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&assemble_diag_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cost_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ls_cost_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&assemble_terms_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&constraint_lambda_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
 #define APPLY_ATTR(KM) MAX_LDS((penta_apply_kernel<KM, (KM <= 8)>))
@@ -968,6 +985,8 @@ void idto_hip_destroy(idto_hip_ctx* c) {
   for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
   for (void* p : c->allocs) (void)hipFree(p);
   if (c->pin) (void)hipHostFree(c->pin);
+  if (c->ls_pin) (void)hipHostFree(c->ls_pin);
+  if (c->ls_fetch_pin) (void)hipHostFree(c->ls_fetch_pin);
   if (c->prob_pin) (void)hipHostFree(c->prob_pin);
   if (c->many_pin) (void)hipHostFree(c->many_pin);
   if (c->rows_pin) (void)hipHostFree(c->rows_pin);
@@ -1137,6 +1156,186 @@ int idto_hip_trial_cost(idto_hip_ctx* c, const double* q_host, double* tau_host,
   if (tau_host) std::memcpy(tau_host, out, ntau * sizeof(double));
   *cost_host = out[ntau];
   return 0;
+}
+
+int idto_hip_ls_alphas(int linesearch_method, int m, double* alphas_host) {
+  if ((linesearch_method != idto_ls::kArmijo && linesearch_method != idto_ls::kBacktracking) || m < 0 || (m > 0 && !alphas_host)) {
+    g_err = "ls_alphas: bad arguments";
+    return -1;
+  }
+  idto_ls::ls_alpha_chain(linesearch_method, m, alphas_host);
+  return 0;
+}
+
+// the candidates' arenas for m step lengths (grown to the largest m asked for; they hold nothing between calls), their
+// costs and the costs' pinned staging
+static int LsEnsureArenas(idto_hip_ctx* c, int m) {
+  const LsArena A = ls_arena(c->N, c->nq, c->nv);
+  if (c->ls_cap < m) {
+    Release(c, &c->ls_arenas);
+    c->ls_cap = 0;
+    if (Alloc(c, A.stride * (size_t)m, &c->ls_arenas)) return -2;
+    c->ls_cap = m;
+  }
+  if (!c->ls_costs && Alloc(c, (size_t)IDTO_LS_MAX_CANDIDATES, &c->ls_costs)) return -2;
+  if (!c->ls_pin) HIP_OK(hipHostMalloc((void**)&c->ls_pin, IDTO_LS_MAX_CANDIDATES * sizeof(double), hipHostMallocDefault));
+  return 0;
+}
+
+// trial points [first, first + m) -> their tau -> their costs (alpha_dev: ONE point at a step length the device holds)
+static int LsEvaluate(idto_hip_ctx* c, const LsAlphas& al, int first, int m, int normalize_quaternions, const double* gate,
+                      const double* alpha_dev) {
+  const int N = c->N, nq = c->nq, nv = c->nv, n = (N + 1) * nq;
+  const LsArena A = ls_arena(N, nq, nv);
+  hipLaunchKernelGGL(ls_trial_kernel, dim3(m), dim3(256), 0, c->stream, n, nq, c->q, c->step, al, c->tr_quat,
+                     normalize_quaternions ? c->tr_nquat : 0, c->ls_arenas, A.stride, first, gate, alpha_dev);
+  HIP_OK(hipGetLastError());
+  double* base = c->ls_arenas + (size_t)first * A.stride;
+  FdAlong along;
+  along.q = base + A.q; along.slab = base + A.slab; along.slab_stride = nv; along.v = base + A.v; along.a = base + A.a;
+  along.nplus = base + A.nplus; along.cstride = A.stride * sizeof(double); along.m = m; along.gate = gate;
+  if (int rc = LaunchFd(c, 0, 0, N, AltSel{nullptr, 0, 0}, &along)) return rc;
+  hipLaunchKernelGGL(ls_cost_kernel, dim3(m), dim3(1024), c->cost_lds, c->stream, c->M, c->P, c->ls_arenas, A,
+                     c->weights_diagonal ? 1 : 0, c->ls_costs, first, gate);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int idto_hip_costs_along(idto_hip_ctx* c, const double* alphas_host, int m, int normalize_quaternions, double* costs_host) {
+  HIP_OK(hipSetDevice(c->device));
+  if (c->batch != 1) { g_err = "costs_along serves single-problem contexts"; return -1; }
+  if (!alphas_host || !costs_host || m < 1 || m > IDTO_LS_MAX_CANDIDATES) {
+    g_err = "costs_along: 1 .. IDTO_LS_MAX_CANDIDATES step lengths and room for their costs";
+    return -1;
+  }
+  TRACE("hip: costs_along begins");
+  if (int rc = LsEnsureArenas(c, m)) return rc;
+  LsAlphas al;
+  for (int j = 0; j < IDTO_LS_MAX_CANDIDATES; ++j) al.a[j] = j < m ? alphas_host[j] : 0.0;
+  if (int rc = LsEvaluate(c, al, 0, m, normalize_quaternions, nullptr, nullptr)) return rc;
+  HIP_OK(hipMemcpyAsync(c->ls_pin, c->ls_costs, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  TRACE("hip: costs_along: waited for the device (the candidates' costs back)");
+  std::memcpy(costs_host, c->ls_pin, (size_t)m * sizeof(double));
+  return 0;
+}
+
+static int LsSolve(idto_hip_ctx* c, int iterations, int method, int max_ls, int normalize_quaternions, double* rows_host,
+                   double* q_out, double* v_out, double* tau_out) {
+  HIP_OK(hipSetDevice(c->device));
+  if (c->batch != 1) { g_err = "ls_solve serves single-problem contexts"; return -1; }
+  if (iterations < 1 || !rows_host || (method != idto_ls::kArmijo && method != idto_ls::kBacktracking)) {
+    g_err = "ls_solve: bad arguments";
+    return -1;
+  }
+  static_assert(LSR_COUNT == IDTO_LS_ROW, "a statistics row as idto_hip.h documents it");
+  static_assert(idto_ls::kMaxCandidates == IDTO_LS_MAX_CANDIDATES && idto_host::kLsMaxCandidates == IDTO_LS_MAX_CANDIDATES, "one cap");
+  if (max_ls > IDTO_LS_MAX_CANDIDATES) { g_err = "ls_solve: max_linesearch_iterations above IDTO_LS_MAX_CANDIDATES"; return -1; }
+  if (!(c->k_begin == 0 && c->k_end == c->N)) { g_err = "ls_solve: the context evaluates a shard of the horizon"; return -1; }
+  const int N = c->N, nq = c->nq, nv = c->nv, n = (N + 1) * nq;
+  const LsArena A = ls_arena(N, nq, nv);
+  if (int rc = LsEnsureArenas(c, IDTO_LS_MAX_CANDIDATES)) return rc;
+  if (!c->ls_state) {
+    double* scan = nullptr;
+    if (Alloc(c, (size_t)LSS_COUNT, &c->ls_state) || Alloc(c, (size_t)2 * n, &c->ls_work) ||
+        Alloc(c, (sizeof(idto_ls::LsScan) + 7) / 8, &scan))
+      return -2;
+    c->ls_scan = reinterpret_cast<idto_ls::LsScan*>(scan);
+  }
+  if (c->ls_rows_cap < iterations) {
+    Release(c, &c->ls_rows);
+    c->ls_rows_cap = 0;
+    if (Alloc(c, (size_t)iterations * LSR_COUNT, &c->ls_rows)) return -2;
+    c->ls_rows_cap = iterations;
+  }
+  const size_t nrow = (size_t)iterations * LSR_COUNT, nqa = (size_t)n, nva = (size_t)(N + 1) * nv, nta = (size_t)N * nv;
+  if (c->ls_fetch_cap < nrow + nqa + nva + nta) {
+    if (c->ls_fetch_pin) (void)hipHostFree(c->ls_fetch_pin);
+    c->ls_fetch_pin = nullptr; c->ls_fetch_cap = 0;
+    HIP_OK(hipHostMalloc((void**)&c->ls_fetch_pin, (nrow + nqa + nva + nta) * sizeof(double), hipHostMallocDefault));
+    c->ls_fetch_cap = nrow + nqa + nva + nta;
+  }
+  if (!c->compute_units) {
+    HIP_OK(hipDeviceGetAttribute(&c->compute_units, hipDeviceAttributeMultiprocessorCount, c->device));
+  }
+  int widths[idto_host::kLsMaxCandidates];
+  const int nwaves = idto_host::PlanLsWaves(N, c->compute_units, method, max_ls, c->ls_waves, widths);
+  LsAlphas al;
+  idto_ls::ls_alpha_chain(method, IDTO_LS_MAX_CANDIDATES, al.a);
+  ++c->ls_solves;
+  TRACE("hip: ls_solve begins");
+  // L(q_0) and the loop's state
+  if (int rc = idto_hip_eval_tau(c)) return rc;
+  HIP_OK(hipMemsetAsync(c->ls_state, 0, LSS_COUNT * sizeof(double), c->stream));
+  HIP_OK(hipMemsetAsync(c->ls_rows, 0, nrow * sizeof(double), c->stream));
+  HIP_OK(hipMemcpyAsync(c->ls_state + LSS_COST, c->cost, sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  LsLoopArgs L;
+  L.n = n; L.nq = nq; L.nv = nv; L.N = N; L.g = c->g; L.dq = c->step; L.HA = c->HA; L.HB = c->HB; L.HC = c->HC;
+  L.slab = c->slab; L.slab_stride = c->slab_stride; L.tau_off = 3 * nv * nq; L.dofs = c->una_dofs; L.nu = c->una_nu;
+  L.q = c->q; L.cost = c->cost; L.state = c->ls_state; L.scan = c->ls_scan; L.rows = c->ls_rows; L.work = c->ls_work;
+  L.arena = c->ls_arenas; L.arena_cost = A.cost; L.status = c->status_dev; L.fact_id = 0; L.method = method;
+  L.max_iters = max_ls; L.dt = c->dt;
+  const double* gate = c->ls_state + LSS_GATE;
+  const double* stop = c->ls_state + LSS_STOP;
+  for (int it = 0; it < iterations; ++it) {
+    // the Newton step at q_k: the partials, g and H, dq = -H^-1 g - the launches of the stepwise calls, the planner's solver
+    if (int rc = idto_hip_eval_partials(c)) return rc;
+    if (int rc = idto_hip_grad_hess(c)) return rc;
+    if (int rc = idto_hip_factor_solve(c, nullptr, 1, nullptr)) return rc;
+    L.fact_id = c->fact_id;
+    hipLaunchKernelGGL(ls_prepare_kernel, dim3(1), dim3(256), 0, c->stream, L);
+    HIP_OK(hipGetLastError());
+    for (int w = 0, first = 0; w < nwaves; first += widths[w], ++w) {
+      if (int rc = LsEvaluate(c, al, first, widths[w], normalize_quaternions, gate, nullptr)) return rc;
+      hipLaunchKernelGGL(ls_scan_kernel, dim3(1), dim3(64), 0, c->stream, L, c->ls_costs, first, widths[w], w + 1 == nwaves ? 1 : 0);
+      HIP_OK(hipGetLastError());
+    }
+    // the accepted step: its trial point once more at the decided alpha (arena 0), the ratio, the row, q <- q + alpha dq
+    if (int rc = LsEvaluate(c, al, 0, 1, normalize_quaternions, stop, c->ls_state + LSS_ALPHA)) return rc;
+    hipLaunchKernelGGL(ls_finish_kernel, dim3(1), dim3(256), 0, c->stream, L);
+    HIP_OK(hipGetLastError());
+    // (what the context remembers about the resident q: it has moved on)
+    c->fd_full = false; c->partials_ahead = false; c->terms_valid = false; c->con_ready = false; c->con_begun = false;
+    c->trial_resident = false; c->spec_pending = false; c->spec_ready = false;
+  }
+  DropPrefetch(c, {IDTO_ARR_Q, IDTO_ARR_COST});
+  // v, a, tau of the final iterate, then [rows | q | v | tau] under one wait
+  if (int rc = idto_hip_eval_tau(c)) return rc;
+  double* pin = c->ls_fetch_pin;
+  HIP_OK(hipMemcpyAsync(pin, c->ls_rows, nrow * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipMemcpyAsync(pin + nrow, c->q, nqa * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipMemcpyAsync(pin + nrow + nqa, c->v, nva * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipMemcpy2DAsync(pin + nrow + nqa + nva, (size_t)nv * sizeof(double), c->slab + 3 * nv * nq,
+                          (size_t)c->slab_stride * sizeof(double), (size_t)nv * sizeof(double), (size_t)N,
+                          hipMemcpyDeviceToHost, c->stream));
+  TRACE("hip: ls_solve: every iteration and the copies enqueued");
+  HIP_OK(hipStreamSynchronize(c->stream));
+  TRACE("hip: ls_solve: waited for the device (rows and the solution back)");
+  std::memcpy(rows_host, pin, nrow * sizeof(double));
+  if (q_out) std::memcpy(q_out, pin + nrow, nqa * sizeof(double));
+  if (v_out) std::memcpy(v_out, pin + nrow + nqa, nva * sizeof(double));
+  if (tau_out) std::memcpy(tau_out, pin + nrow + nqa + nva, nta * sizeof(double));
+  // The Newton-step launches of the iterations behind a stop flag cannot be held back - the host does not know of the
+  // stop - and run at the final iterate; the ls_* kernels behind them are idle.  FactorStatus reports the LAST
+  // factorisation: when that one failed and no row carries flag 32, it belongs to such an idle iteration, which the host
+  // loop never ran, and is nobody's failure.
+  const int fs = FactorStatus(c);
+  if (fs != 0 && fs != IDTO_HIP_FACTORIZATION_FAILED) return fs;
+  bool named = false;
+  for (int k = 0; k < iterations; ++k) named = named || (((int)rows_host[(size_t)k * LSR_COUNT + LSR_FLAGS]) & LSF_BAD_PIVOT) != 0;
+  if (named && fs == 0) g_err = "factorisation failed: the Hessian is not numerically positive definite (the row with flag 32 names the iteration)";
+  return named ? IDTO_HIP_FACTORIZATION_FAILED : 0;
+}
+
+int idto_hip_ls_solve(idto_hip_ctx* c, int iterations, int linesearch_method, int max_linesearch_iterations,
+                      int normalize_quaternions, double* rows_host) {
+  return LsSolve(c, iterations, linesearch_method, max_linesearch_iterations, normalize_quaternions, rows_host, nullptr, nullptr,
+                 nullptr);
+}
+int idto_hip_ls_solve_fetch(idto_hip_ctx* c, int iterations, int linesearch_method, int max_linesearch_iterations,
+                            int normalize_quaternions, double* rows_host, double* q_out, double* v_out, double* tau_out) {
+  return LsSolve(c, iterations, linesearch_method, max_linesearch_iterations, normalize_quaternions, rows_host, q_out, v_out,
+                 tau_out);
 }
 
 int idto_hip_eval_partials(idto_hip_ctx* c) {
@@ -2832,6 +3031,8 @@ int idto_hip_get_option(idto_hip_ctx* c, const char* name, int* value) {
   if (std::strcmp(name, "asm_fold") == 0) { *value = c->asm_fold; return 0; }
   if (std::strcmp(name, "con_kkt") == 0) { *value = c->con_kkt; return 0; }
   if (std::strcmp(name, "kkt_fold") == 0) { *value = c->kkt_fold; return 0; }
+  if (std::strcmp(name, "ls_waves") == 0) { *value = c->ls_waves; return 0; }
+  if (std::strcmp(name, "ls_solves") == 0) { *value = c->ls_solves; return 0; }
   if (std::strcmp(name, "tr_small") == 0) { *value = c->tr_small; return 0; }
   if (std::strcmp(name, "tr_fold") == 0) { *value = c->tr_fold; return 0; }
   if (std::strcmp(name, "kkt_in_asm") == 0) { *value = c->kkt_in_asm; return 0; }
@@ -2871,6 +3072,11 @@ int idto_hip_set_option(idto_hip_ctx* c, const char* name, int value) {
   if (std::strcmp(name, "asm_fold") == 0) { c->asm_fold = value != 0; c->terms_valid = false; return 0; }
   if (std::strcmp(name, "con_kkt") == 0) { c->con_kkt = value != 0; return 0; }
   if (std::strcmp(name, "kkt_fold") == 0) { c->kkt_fold = value != 0; return 0; }
+  if (std::strcmp(name, "ls_waves") == 0) {
+    if (value < 0 || value > IDTO_LS_MAX_CANDIDATES) { g_err = "ls_waves: 0 (planned) .. IDTO_LS_MAX_CANDIDATES candidates per wave"; return -1; }
+    c->ls_waves = value;
+    return 0;
+  }
   if (std::strcmp(name, "tr_small") == 0) { c->tr_small = value != 0; return 0; }
   if (std::strcmp(name, "tr_fold") == 0) { c->tr_fold = value != 0; return 0; }
   if (std::strcmp(name, "kkt_in_asm") == 0) { c->kkt_in_asm = value != 0; return 0; }

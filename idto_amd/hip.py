@@ -86,6 +86,10 @@ def lib():
         L.idto_hip_set_q_device.argtypes = [C.c_void_p, C.c_void_p]
         L.idto_hip_trial_cost.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.POINTER(C.c_double)]
+        L.idto_hip_costs_along.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(C.c_double)]
+        L.idto_hip_ls_alphas.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double)]
+        L.idto_hip_ls_solve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
+        L.idto_hip_ls_solve_fetch.argtypes = L.idto_hip_ls_solve.argtypes + [C.POINTER(C.c_double)] * 3
         for f in ("eval_tau", "eval_partials", "grad_hess", "gn_step", "sync", "timing_reset"):
             getattr(L, "idto_hip_" + f).argtypes = [C.c_void_p]
         L.idto_hip_factor_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -116,7 +120,7 @@ def lib():
 
 EXPORTED_SYMBOLS = [
     "idto_hip_last_error", "idto_hip_create", "idto_hip_destroy", "idto_hip_set_problem", "idto_hip_set_stream",
-    "idto_hip_get_stream", "idto_hip_set_shard", "idto_hip_set_q", "idto_hip_set_q_device", "idto_hip_eval_tau", "idto_hip_eval_tau_partials", "idto_hip_trial_cost", "idto_hip_constraint_schur",
+    "idto_hip_get_stream", "idto_hip_set_shard", "idto_hip_set_q", "idto_hip_set_q_device", "idto_hip_eval_tau", "idto_hip_eval_tau_partials", "idto_hip_trial_cost", "idto_hip_costs_along", "idto_hip_ls_alphas", "idto_hip_ls_solve", "idto_hip_ls_solve_fetch", "idto_hip_constraint_schur",
     "idto_hip_constraint_schur_begin", "idto_hip_constraint_solve", "idto_hip_constraint_step", "idto_hip_prefetch",
     "idto_hip_eval_partials", "idto_hip_grad_hess", "idto_hip_factor_solve", "idto_hip_gn_step", "idto_hip_solve_host",
     "idto_hip_solve_dense_ldlt", "idto_hip_dense_solve_count",
@@ -130,6 +134,17 @@ EXPORTED_SYMBOLS = [
     "idto_hip_allgather_slab", "idto_hip_gn_step_sharded", "idto_hip_gn_step_multi", "idto_hip_eval_partials_multi",
     "idto_hip_trace_enable", "idto_hip_trace_mark", "idto_hip_trace_dump",
 ]
+
+
+LS_MAX_CANDIDATES = 64
+LS_ROW = 12
+
+
+def ls_alphas(linesearch_method: int, m: int):
+    """the step lengths the linesearch tries, as the host loop forms them (0 kArmijo, 1 kBacktracking; idto_hip_ls_alphas)"""
+    out = np.empty(int(m))
+    _chk(lib().idto_hip_ls_alphas(int(linesearch_method), int(m), dptr(out)))
+    return out
 
 
 class HipError(RuntimeError):
@@ -417,6 +432,28 @@ class HipPath:
         cost = C.c_double()
         _chk(lib().idto_hip_trial_cost(self.h, dptr(q), dptr(tau), C.byref(cost)))
         return tau, cost.value
+
+    def costs_along(self, alphas, normalize_quaternions: bool = False):
+        """L(q + alpha dq) for up to LS_MAX_CANDIDATES step lengths along the last solve's step dq, one launch set and one
+        wait (idto_hip_costs_along); the resident iterate is not disturbed"""
+        alphas = np.ascontiguousarray(np.asarray(alphas, dtype=np.float64).ravel())
+        costs = np.empty(alphas.size)
+        _chk(lib().idto_hip_costs_along(self.h, dptr(alphas), int(alphas.size), int(bool(normalize_quaternions)), dptr(costs)))
+        return costs
+
+    def ls_solve(self, iterations, linesearch_method=0, max_linesearch_iterations=50, normalize_quaternions=False,
+                 fetch=True):
+        """the linesearch method's loop on the device, one wait (idto_hip_ls_solve_fetch): returns a dict with rows
+        [iterations, LS_ROW] and - fetch - the final iterate's q, v, tau"""
+        rows = np.zeros((int(iterations), LS_ROW))
+        args = (self.h, int(iterations), int(linesearch_method), int(max_linesearch_iterations), int(bool(normalize_quaternions)),
+                dptr(rows))
+        if not fetch:
+            _chk(lib().idto_hip_ls_solve(*args))
+            return dict(rows=rows)
+        out = dict(rows=rows, q=np.zeros((self.N + 1, self.nq)), v=np.zeros((self.N + 1, self.nv)), tau=np.zeros((self.N, self.nv)))
+        _chk(lib().idto_hip_ls_solve_fetch(*args, dptr(out["q"]), dptr(out["v"]), dptr(out["tau"])))
+        return out
 
     def eval_partials(self):
         _chk(lib().idto_hip_eval_partials(self.h))

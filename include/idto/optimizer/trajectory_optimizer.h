@@ -194,6 +194,9 @@ class TrajectoryOptimizer<double> {
                                  TrajectoryOptimizerStats<T>* stats) const;
   SolverFlag SolveFromWarmStartImpl(WarmStart* warm_start, TrajectoryOptimizerSolution<T>* solution,
                                     TrajectoryOptimizerStats<T>* stats, ConvergenceReason* reason) const;
+  bool LinesearchLoopEligible() const;
+  SolverFlag SolveLinesearchOnDevice(const std::vector<VectorXd>& q_guess, TrajectoryOptimizerSolution<T>* solution,
+                                     TrajectoryOptimizerStats<T>* stats) const;
   bool DeviceLoopEligible() const;
   bool ResidentLoopEligible() const;
   SolverFlag SolveOnDevice(WarmStart* warm_start, TrajectoryOptimizerSolution<T>* solution,

@@ -178,6 +178,53 @@ int idto_hip_eval_tau_partials(idto_hip_ctx* ctx);
  * ((N+1)*nq, host), evaluates v, a, tau and the cost L(q) (:147-176), returns tau (N*nv, may be
  * NULL) and the cost to host memory.  Equivalent to set_q + eval_tau + get(TAU) + get(COST). */
 int idto_hip_trial_cost(idto_hip_ctx* ctx, const double* q_host, double* tau_host, double* cost_host);
+
+/* The cost along the search direction at many step lengths, one launch set and one wait: what the linesearches
+ * (ArmijoLinesearch / BacktrackingLinesearch, optimizer/trajectory_optimizer.cc:1931-1977 / :1852-1929) ask for one step
+ * length at a time - each an upload of q, an evaluation and a synchronising fetch through idto_hip_trial_cost - although
+ * the candidates alpha_j = rho^j are known in advance and independent of each other.
+ * Input: the resident q and IDTO_ARR_STEP, the dq of the last solve (idto_hip_gn_step / idto_hip_factor_solve(NULL), whose
+ * status the caller has looked at).  costs_host[j] = L(q + alphas_host[j] dq) for m <= IDTO_LS_MAX_CANDIDATES step lengths:
+ * bit for bit what idto_hip_trial_cost returns for the trial point formed as the host loop forms it - step = fl(alpha dq_i),
+ * then fl(q_i + step), then (normalize_quaternions) per quaternion n = sqrt(((w w + x x) + y y) + z z) and four divisions.
+ * Every candidate is evaluated in an arena of its own (csrc/linesearch.h): the resident iterate is not disturbed - q, its v,
+ * a, tau, cost, partials, g, H and the step are afterwards what they were.  Single-problem contexts. */
+#define IDTO_LS_MAX_CANDIDATES 64
+int idto_hip_costs_along(idto_hip_ctx* ctx, const double* alphas_host, int m, int normalize_quaternions, double* costs_host);
+/* The step lengths the two linesearches try, in the order they try them, formed as the host loops form them (repeated
+ * IEEE multiplication by rho = 0.8, never pow; csrc/ls_decide.h): linesearch_method 0 kArmijo (1/rho * rho = 1.0, 0.8,
+ * 0.6400000000000001, ...), 1 kBacktracking (1.0, then the same products).  No device involved. */
+int idto_hip_ls_alphas(int linesearch_method, int m, double* alphas_host);
+
+/* The whole linesearch method without the host (reference SolveWithLinesearch, optimizer/trajectory_optimizer.cc:2244-2407,
+ * for scaling off and no enforced constraints): `iterations` iterations are enqueued back to back and the host waits once.
+ * Per iteration: the launches of idto_hip_eval_partials, idto_hip_grad_hess and idto_hip_factor_solve(NULL) at q_k (g, H
+ * unscaled, dq = -H^-1 g by the solver the planner picks); ls_prepare_kernel (L' = g.dq, |g|, |dq|, |h| on the dofs of
+ * idto_hip_set_unactuated_dofs - the host's Dot and Norm: one thread, index order -, the throw condition, the early-outs);
+ * the candidate step lengths in waves (csrc/linesearch.h: trial points, the tau-only evaluation (fd_along_kernel) with the candidate in
+ * blockIdx.y, cost_body per candidate, then the scan of csrc/ls_decide.h over the wave's costs in index order; a wave whose
+ * iteration is decided returns at its first instruction; how many candidates a wave takes: host/solver_plan.h PlanLsWaves,
+ * option "ls_waves" = k > 0: k per wave); then the accepted step - its trial point once more at the decided alpha, the
+ * trust ratio of CalcTrustRatio (:1979-2035), the statistics row, q <- q + alpha dq on the device.
+ * linesearch_method 0 kArmijo / 1 kBacktracking; max_linesearch_iterations <= IDTO_LS_MAX_CANDIDATES.  The iterate q must
+ * be resident (idto_hip_set_q).  rows_host[iterations][IDTO_LS_ROW], a row per iteration that ran (the others are zeros):
+ *   [0] L(q_k) [1] alpha [2] ls_iters [3] the trust ratio [4] |q_{k+1}| [5] |dq| [6] |g| [7] L' = g.dq [8] |h|
+ *   [9] L(q_{k+1}) [10] device clock at the decision (100 MHz ticks) [11] flags: 2 the step is not finite, 4 it is not a
+ *   descent direction (where the reference throws), 32 the factorisation behind the step met a bad pivot, 64 ls_iters
+ *   reached max_linesearch_iterations (the step is taken, as the host takes it; the reference's linesearch_failed),
+ *   128 backtracking was undecided within IDTO_LS_MAX_CANDIDATES candidates (q stays q_k: continue on the host).  A row
+ *   with a flag is the last one: the remaining iterations are idle.
+ * On return q, v, a, tau and the cost in device memory are the final iterate's.  _fetch also brings q ((N+1) nq), v
+ * ((N+1) nv) and tau (N nv) back under the same wait (any pointer may be NULL).
+ * The Newton-step launches of the iterations behind a flagged row still run (the host enqueued them before it could know),
+ * at the final iterate, so g, H and IDTO_ARR_STEP are then those of the final iterate; their status is not reported.
+ * Returns IDTO_HIP_FACTORIZATION_FAILED when a row carries flag 32 (which names the iteration),
+ * IDTO_HIP_SOLVER_TIMEOUT as the other loops.  Option "ls_solves" (read-only) counts the calls on the context. */
+#define IDTO_LS_ROW 12
+int idto_hip_ls_solve(idto_hip_ctx* ctx, int iterations, int linesearch_method, int max_linesearch_iterations,
+                      int normalize_quaternions, double* rows_host);
+int idto_hip_ls_solve_fetch(idto_hip_ctx* ctx, int iterations, int linesearch_method, int max_linesearch_iterations,
+                            int normalize_quaternions, double* rows_host, double* q_out, double* v_out, double* tau_out);
 int idto_hip_eval_partials(idto_hip_ctx* ctx);
 int idto_hip_grad_hess(idto_hip_ctx* ctx);
 /* Factorises the resident Hessian and solves H x = rhs for `nrhs` right-hand

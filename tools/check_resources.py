@@ -69,6 +69,21 @@ LIMITS = {
     # all promoted to registers: the kernel has no scratch instruction, build/isa/main.s)
     "tr_iter_kernel": (0, 68, 73 + 24),
     "cost_kernel": (0, 0, 17 + 24),
+    # (the linesearch loop and idto_hip_costs_along, csrc/linesearch.h: no spilled register of either kind today)
+    # (fd_body with the mode fixed at tau only, the candidate in blockIdx.y: the shapes' kernels, as for fd_kernel)
+    "fd_along_kernel<2, 1>": (0, 0, 12 + 24),
+    "fd_along_kernel<3, 2>": (0, 0, 12 + 24),
+    "fd_along_kernel<3, 3>": (0, 0, 15 + 24),
+    "fd_along_kernel<3, 5>": (0, 0, 14 + 24),
+    "fd_along_kernel<4, 4>": (0, 0, 16 + 24),
+    "fd_along_kernel<8, 6>": (0, 0, 65 + 24),
+    "fd_along_kernel<8, 7>": (0, 0, 76 + 24),
+    "fd_along_kernel<8, 8>": (0, 0, 65 + 24),
+    "ls_trial_kernel": (0, 0, 0 + 24),
+    "ls_cost_kernel": (0, 0, 0 + 24),
+    "ls_prepare_kernel": (0, 0, 0 + 24),
+    "ls_scan_kernel": (0, 0, 0 + 24),
+    "ls_finish_kernel": (0, 0, 0 + 24),
 }
 
 

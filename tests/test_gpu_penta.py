@@ -21,12 +21,19 @@ MODEL_FOR_BLOCK = {2: "acrobot", 3: "spinner", 5: "hopper"}   # block size = nq 
 
 
 class DeviceSolver:
-    """a context of the right shape whose Hessian bands the test overwrites"""
+    """a context of the right shape whose Hessian bands the test overwrites: of a model, or of block size `model_or_k` - the
+    example model of that size, or solver_cases.revolute_star(k) for the sizes no example has"""
 
-    def __init__(self, bs, n):
-        name = MODEL_FOR_BLOCK[bs]
-        cfg, model = load_config(name), load_model(name)
-        prob, sp, _ = make_problem(cfg, model, num_steps=n - 1)
+    def __init__(self, model_or_k, n):
+        if isinstance(model_or_k, (int, np.integer)) and int(model_or_k) in MODEL_FOR_BLOCK:
+            name = MODEL_FOR_BLOCK[int(model_or_k)]
+            cfg, model = load_config(name), load_model(name)
+            prob, sp, _ = make_problem(cfg, model, num_steps=n - 1)
+        else:
+            import solver_cases
+            model = solver_cases.revolute_star(int(model_or_k)) if isinstance(model_or_k, (int, np.integer)) else model_or_k
+            prob, sp = solver_cases.plain_problem(model, n - 1), solver_cases.SolverParameters(verbose=False)
+        bs = model.nq
         self.dev = hip.HipPath(model, prob, sp)
         self.bs, self.n = bs, n
         span = (n + 5) * bs * bs   # (N + 6) blocks per band
@@ -45,16 +52,25 @@ class DeviceSolver:
         self.view.copy_(torch.from_numpy(host))
         torch.cuda.synchronize()
 
-    def solve(self, b, reference=False, two_sided=True):
+    def solve(self, b, reference=False, two_sided=True, **options):
         b = np.atleast_2d(np.asarray(b, dtype=np.float64))
         rhs = torch.tensor(b, dtype=torch.float64, device="cuda")
         x = torch.zeros_like(rhs)
         self.dev.set_option("reference_solver", int(reference))
         self.dev.set_option("two_sided", int(two_sided))
+        for name, value in options.items():
+            self.dev.set_option(name, value)
         self.dev.factor_solve(rhs.data_ptr(), b.shape[0], x.data_ptr())
         self.dev.sync()
         out = x.cpu().numpy()
         return out[0] if out.shape[0] == 1 else out
+
+    @property
+    def last_solver(self):
+        return self.dev.get_option("last_solver")
+
+    def close(self):
+        self.dev.close()
 
 
 def test_solve_identity():  # :109-123 (exact)

@@ -15,11 +15,44 @@ from oracle_lib import Oracle
 pytestmark = pytest.mark.gpu
 
 
-def _setup(name, N, seed=1):
+# Constrained routes on padded block sizes: solver_cases.revolute_star(nq, nu) with nu unactuated joints.  KKT blocks of
+# nq + nu: 6 + 1 in blocks of 8 (padded; hopper's 5 + 3 fills them), 13 + 2 in 16, 21 + 3 in 24, 25 + 3 in 30 - the only direct
+# test of penta_ldl_kernel<30, PADDED> - and 26 + 3 = allegro's exact 29; con_kkt = 0 sends N nu + 1 columns through
+# penta_apply_kernel<8 | 16 | 24 | 32> instead.
+STARS = {"star_6+1": (6, 1), "star_13+2": (13, 2), "star_21+3": (21, 3), "star_25+3": (25, 3), "star_26+3": (26, 3)}
+
+
+def _case(name, N, seed, lower):
+    """(cfg, model, prob, sp, q) of an example configuration or of a revolute star"""
+    if name in STARS:
+        import solver_cases
+        model = solver_cases.revolute_star(*STARS[name])
+        return (None, model) + solver_cases.star_problem(model, N, seed)
     cfg, model = load_config(name), load_model(name)
     prob, sp, _ = make_problem(cfg, model, num_steps=N)
+    return cfg, model, prob, sp, synthetic_trajectory(cfg, model, N, seed=seed, lower=lower)
+
+
+def _star_kernels_ran(name, N, dev, kkt):
+    """a star's case names the kernel it held: the two-workgroup factorisation of the KKT system in blocks of
+    SolverBlockSize(nq + nu), or - Schur-complement route - N nu + 1 columns behind the factorisation of H in blocks of
+    SolverBlockSize(nq)"""
+    if name not in STARS:
+        return
+    import solver_cases
+    nq, nu = STARS[name]
+    assert dev.get_option("kkt_last_solver") == (1 if kkt else 0)
+    if kkt:
+        assert solver_cases.solver_block_size(nq + nu, kkt=True) == {7: 8, 15: 16, 24: 24, 28: 30, 29: 29}[nq + nu]
+    else:
+        assert dev.get_option("last_solver") == 1
+        assert N * nu + 1 > 1 and solver_cases.solver_block_size(nq) == {6: 8, 13: 16, 21: 24, 25: 32, 26: 32}[nq]
+
+
+def _setup(name, N, seed=1):
+    cfg, model, prob, sp, q = _case(name, N, seed, 0.01)
     sp.equality_constraints = False
-    return cfg, model, prob, sp, synthetic_trajectory(cfg, model, N, seed=seed, lower=0.01)
+    return cfg, model, prob, sp, q
 
 
 @pytest.mark.parametrize("name,N,method", [("mini_cheetah", 40, "double_sqrt"), ("hopper", 12, "sqrt"),
@@ -272,7 +305,8 @@ def test_resident_loop_flags_a_singular_constraint_system(kkt):
 
 
 @pytest.mark.parametrize("name,N", [("hopper", 40), ("acrobot", 40), ("spinner", 30), ("allegro_hand", 21), ("hopper", 9),
-                                    ("acrobot", 3), ("spinner", 128), ("acrobot", 65), ("hopper", 42)])   # n_eq = 3, 128, 65, 126
+                                    ("acrobot", 3), ("spinner", 128), ("acrobot", 65), ("hopper", 42),   # n_eq = 3, 128, 65, 126
+                                    ("star_6+1", 12), ("star_13+2", 12), ("star_21+3", 12), ("star_25+3", 12), ("star_26+3", 12)])
 def test_single_workgroup_multiplier_solve(name, N):
     """constraint_lambda_kernel: lambda = S^-1 (h - J H^-1 g) by an unpivoted LDL^T in one workgroup, against an
     extended-precision solution of the same system (S, J H^-1 g as the device formed them).  S = J H^-1 J^T is badly
@@ -286,6 +320,7 @@ def test_single_workgroup_multiplier_solve(name, N):
     dev.eval_tau()
     h = dev.get("tau")[:, dofs].ravel()
     dev.tr_solve(1, SCALING["double_sqrt"], True, False, 1e-1, 1e5, constrained_dofs=dofs)
+    _star_kernels_ran(name, N, dev, 0)
     neq = dofs.size * N
     raw = dev.get("con_S")
     S, Jy = raw[:neq * neq].reshape(neq, neq).T, raw[neq * neq:]
@@ -335,15 +370,14 @@ def _kkt_reference(model, prob, sp, q, dev):
 
 
 @pytest.mark.parametrize("name,N,seed", [("acrobot", 40, 1), ("spinner", 40, 1), ("hopper", 40, 1), ("hopper", 40, 2), ("hopper", 50, 3),
-                                         ("hopper", 9, 1), ("acrobot", 3, 2), ("spinner", 128, 1), ("allegro_hand", 20, 1), ("allegro_hand", 60, 2)])
+                                         ("hopper", 9, 1), ("acrobot", 3, 2), ("spinner", 128, 1), ("allegro_hand", 20, 1), ("allegro_hand", 60, 2),
+                                         ("star_6+1", 12, 1), ("star_13+2", 12, 1), ("star_21+3", 12, 1), ("star_25+3", 12, 1), ("star_26+3", 12, 1)])
 def test_banded_kkt_multipliers_are_as_accurate_as_the_schur_complement_chain(name, N, seed):
     """csrc/kkt.h: the multipliers from one unpivoted banded LDL^T of the KKT system against an extended-precision
     solution of that system.  The systems are badly conditioned (1e8 .. 1e12) and BOTH device paths - this one and the
     reference's route over S = J H^-1 J^T (constraints.h) - sit at the error that conditioning allows (1e-13 ..
     2e-7 relative); the statement is that the banded solve is no worse than 4x the Schur-complement chain."""
-    cfg, model = load_config(name), load_model(name)
-    prob, sp, _ = make_problem(cfg, model, num_steps=N)
-    q = synthetic_trajectory(cfg, model, N, seed=seed, lower=0.01 if name == "hopper" else 0.0)
+    cfg, model, prob, sp, q = _case(name, N, seed, 0.01 if name == "hopper" else 0.0)
     dofs = np.asarray(model.unactuated_dofs)
     lam = {}
     for kkt in (0, 1):
@@ -354,6 +388,7 @@ def test_banded_kkt_multipliers_are_as_accurate_as_the_schur_complement_chain(na
         rows, _ = dev.tr_solve(1, SCALING["double_sqrt"], True, False, 1e-1, 1e5, constrained_dofs=dofs)
         assert rows[0, 14] == 0
         assert dev.get_option("kkt_last_solver") in ((1, 2, 6) if kkt else (0,))   # two-workgroup / seven-workgroup / scalar band factorisation
+        _star_kernels_ran(name, N, dev, kkt)
         lam[kkt] = dev.get("con_lambda")
         if kkt:
             want = _kkt_reference(model, prob, sp, q, dev)

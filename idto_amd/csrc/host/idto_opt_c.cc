@@ -3,12 +3,14 @@
 #include "idto_opt.h"
 
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
 
 #include "idto/examples/mpc_controller.h"
 #include "idto/optimizer/trajectory_optimizer.h"
+#include "mpc_spline.h"
 
 using namespace idto::optimizer;
 
@@ -22,6 +24,10 @@ struct idto_opt_warm_start {
 };
 struct idto_mpc {
   std::unique_ptr<idto::examples::mpc::ModelPredictiveController> mpc;
+  idto_opt* opt = nullptr;
+};
+struct idto_mpc_batch {
+  std::unique_ptr<idto::examples::mpc::BatchModelPredictiveController> mpc;
   idto_opt* opt = nullptr;
 };
 
@@ -45,6 +51,26 @@ MatrixXd Mat(const double* data, int n) {
   MatrixXd m(n, n);
   std::memcpy(m.data(), data, sizeof(double) * n * n);
   return m;
+}
+// B problems of the C-ABI as ProblemDefinitions (idto_opt_solve_batch, idto_mpc_batch_create)
+std::vector<ProblemDefinition> BatchProblems(const idto_opt* o, int B, const idto_problem_t* problems, const char* who) {
+  const int nq = o->nq, nv = o->nv;
+  std::vector<ProblemDefinition> probs((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    const idto_problem_t& p = problems[b];
+    if (p.num_steps < 0) throw std::runtime_error(std::string(who) + ": problem " + std::to_string(b) + " has a negative num_steps");
+    if (p.time_step != o->to->time_step())
+      throw std::runtime_error(std::string(who) + ": problem " + std::to_string(b) + " has another time_step than the optimizer's");
+    ProblemDefinition& prob = probs[b];
+    prob.num_steps = p.num_steps;
+    prob.q_init.assign(p.q_init, p.q_init + nq);
+    prob.v_init.assign(p.v_init, p.v_init + nv);
+    prob.Qq = Mat(p.Qq, nq); prob.Qv = Mat(p.Qv, nv); prob.Qf_q = Mat(p.Qf_q, nq); prob.Qf_v = Mat(p.Qf_v, nv);
+    prob.R = Mat(p.R, nv);
+    prob.q_nom = Rows(p.q_nom, p.num_steps + 1, nq);
+    prob.v_nom = Rows(p.v_nom, p.num_steps + 1, nv);
+  }
+  return probs;
 }
 void FillStats(const TrajectoryOptimizerStats<double>& s, idto_stats_t* out) {
   if (!out) return;
@@ -181,23 +207,7 @@ int idto_opt_solve_batch(idto_opt* o, int B, const idto_problem_t* problems, con
     if (B < 1 || !q_guesses) throw std::runtime_error("solve_batch: B >= 1 problems and their q_guesses are required");
     const int nq = o->nq, nv = o->nv;
     std::vector<ProblemDefinition> probs;
-    if (problems) {
-      probs.resize((size_t)B);
-      for (int b = 0; b < B; ++b) {
-        const idto_problem_t& p = problems[b];
-        if (p.num_steps < 0) throw std::runtime_error("solve_batch: problem " + std::to_string(b) + " has a negative num_steps");
-        if (p.time_step != o->to->time_step())
-          throw std::runtime_error("solve_batch: problem " + std::to_string(b) + " has another time_step than the optimizer's");
-        ProblemDefinition& prob = probs[b];
-        prob.num_steps = p.num_steps;
-        prob.q_init.assign(p.q_init, p.q_init + nq);
-        prob.v_init.assign(p.v_init, p.v_init + nv);
-        prob.Qq = Mat(p.Qq, nq); prob.Qv = Mat(p.Qv, nv); prob.Qf_q = Mat(p.Qf_q, nq); prob.Qf_v = Mat(p.Qf_v, nv);
-        prob.R = Mat(p.R, nv);
-        prob.q_nom = Rows(p.q_nom, p.num_steps + 1, nq);
-        prob.v_nom = Rows(p.v_nom, p.num_steps + 1, nv);
-      }
-    }
+    if (problems) probs = BatchProblems(o, B, problems, "solve_batch");
     std::vector<std::vector<VectorXd>> guesses((size_t)B);
     const size_t nqa = (size_t)(o->N + 1) * nq, nva = (size_t)(o->N + 1) * nv, nta = (size_t)o->N * nv;
     for (int b = 0; b < B; ++b) guesses[b] = Rows(q_guesses + b * nqa, o->N + 1, nq);
@@ -338,6 +348,103 @@ int idto_mpc_spline_eval(const double* breaks, const double* knots, int n, int d
   return Guard([&] {
     const idto::examples::mpc::PiecewiseCubic sp(std::vector<double>(breaks, breaks + n), Rows(knots, n, dim));
     for (int i = 0; i < nt; ++i) Flat(sp.value(times[i]), out + (size_t)i * dim);
+  });
+}
+int idto_mpc_stats(const idto_mpc* mpc, idto_stats_t* stats, double* radius) {
+  return Guard([&] {
+    FillStats(mpc->mpc->last_stats(), stats);
+    if (radius) *radius = mpc->mpc->trust_region_radius();
+  });
+}
+
+// ---- B controllers in one device pass per tick
+int idto_mpc_batch_create(idto_opt* opt, int B, const idto_problem_t* problems, const double* warm_q, const double* warm_v,
+                          const double* warm_tau, const int* actuated, const int* q_nom_relative_to_q_init, idto_mpc_batch** out) {
+  return Guard([&] {
+    if (B < 0 || !warm_q || !warm_v || !warm_tau) throw std::runtime_error("mpc_batch_create: B warm-start solutions are required");
+    const size_t nqa = (size_t)(opt->N + 1) * opt->nq, nva = (size_t)(opt->N + 1) * opt->nv, nta = (size_t)opt->N * opt->nv;
+    std::vector<TrajectoryOptimizerSolution<double>> warm((size_t)B);
+    for (int b = 0; b < B; ++b) {
+      warm[b].q = Rows(warm_q + b * nqa, opt->N + 1, opt->nq);
+      warm[b].v = Rows(warm_v + b * nva, opt->N + 1, opt->nv);
+      warm[b].tau = Rows(warm_tau + b * nta, opt->N, opt->nv);
+    }
+    std::vector<ProblemDefinition> probs;
+    if (problems) probs = BatchProblems(opt, B, problems, "mpc_batch_create");
+    std::vector<int> act;
+    if (actuated) act.assign(actuated, actuated + opt->nv);
+    std::vector<bool> sel((size_t)opt->nq, false);
+    if (q_nom_relative_to_q_init)
+      for (int i = 0; i < opt->nq; ++i) sel[i] = q_nom_relative_to_q_init[i] != 0;
+    auto m = std::make_unique<idto_mpc_batch>();
+    m->opt = opt;
+    m->mpc = std::make_unique<idto::examples::mpc::BatchModelPredictiveController>(opt->to.get(), warm, act, sel, problems ? &probs : nullptr);
+    *out = m.release();
+  });
+}
+void idto_mpc_batch_destroy(idto_mpc_batch* mpc) { delete mpc; }
+int idto_mpc_batch_num_actuators(const idto_mpc_batch* mpc) { return mpc->mpc->num_actuators(); }
+int idto_mpc_batch_update(idto_mpc_batch* mpc, const double* times, const double* x0, double* q_guess, double* sol_q, double* sol_v,
+                          double* sol_tau, idto_stats_t* stats, int* flags, double* radii, int* tick_ok) {
+  return Guard([&] {
+    if (!times || !x0) throw std::runtime_error("mpc_batch_update: times[B] and x0[B][nq + nv] are required");
+    const idto_opt* o = mpc->opt;
+    const int B = mpc->mpc->num_controllers();
+    const size_t nqa = (size_t)(o->N + 1) * o->nq, nva = (size_t)(o->N + 1) * o->nv, nta = (size_t)o->N * o->nv;
+    const bool ok = mpc->mpc->UpdateAll(times, x0);
+    if (tick_ok) *tick_ok = ok ? 1 : 0;
+    for (int b = 0; b < B; ++b) {
+      if (q_guess) Flat(mpc->mpc->last_guess(b), q_guess + b * nqa);
+      const auto& sol = mpc->mpc->last_solution(b);   // (a controller that failed: its previous re-plan's)
+      Flat(sol.q, sol_q ? sol_q + b * nqa : nullptr);
+      Flat(sol.v, sol_v ? sol_v + b * nva : nullptr);
+      Flat(sol.tau, sol_tau ? sol_tau + b * nta : nullptr);
+      if (stats) FillStats(mpc->mpc->last_stats(b), &stats[b]);
+      if (flags) flags[b] = (int)mpc->mpc->last_flag(b);
+      if (radii) radii[b] = mpc->mpc->trust_region_radius(b);
+    }
+  });
+}
+static void CheckController(const idto_mpc_batch* mpc, int b) {
+  if (b < 0 || b >= mpc->mpc->num_controllers()) throw std::runtime_error("mpc_batch: controller index outside the batch");
+}
+int idto_mpc_batch_state(const idto_mpc_batch* mpc, int b, double time, double* x) {
+  return Guard([&] { CheckController(mpc, b); Flat(idto::examples::mpc::Interpolator::State(mpc->mpc->stored_trajectory(b), time), x); });
+}
+int idto_mpc_batch_control(const idto_mpc_batch* mpc, int b, double time, double* u) {
+  return Guard([&] { CheckController(mpc, b); Flat(idto::examples::mpc::Interpolator::Control(mpc->mpc->stored_trajectory(b), time), u); });
+}
+double idto_mpc_batch_start_time(const idto_mpc_batch* mpc, int b) {
+  return (b >= 0 && b < mpc->mpc->num_controllers()) ? mpc->mpc->stored_trajectory(b).start_time : std::numeric_limits<double>::quiet_NaN();
+}
+int idto_mpc_batch_flag(const idto_mpc_batch* mpc, int b) {
+  return (b >= 0 && b < mpc->mpc->num_controllers()) ? (int)mpc->mpc->last_flag(b) : -1;
+}
+const char* idto_mpc_batch_error(const idto_mpc_batch* mpc, int b) {
+  if (b < 0) return mpc->mpc->last_tick_error().c_str();
+  return b < mpc->mpc->num_controllers() ? mpc->mpc->last_error(b).c_str() : "";
+}
+
+// ---- csrc/mpc_spline.h on the host, for the tests that hold the device's kernels to it
+int idto_mpc_spline_fit(const double* breaks, const double* knots, int n, int dim, double* m_out) {
+  return Guard([&] {
+    if (n < 2 || dim < 0) throw std::runtime_error("mpc_spline_fit: at least two knots");
+    std::vector<double> w((size_t)n * dim, 0.0);
+    for (int c = 0; c < dim; ++c)
+      if (idto_spline::spline_fit(breaks, n, knots + c, m_out + c, w.data() + c, dim)) throw std::runtime_error("mpc_spline_fit: singular system");
+  });
+}
+int idto_mpc_shift_reference(const double* breaks, const double* y_q, const double* m_q, int n, int nq, double start_time, double time,
+                             double time_step, const double* q0, const int* selector, double* q_nom, double* guess_out) {
+  return Guard([&] {
+    const double start = time - start_time;
+    for (int i = 0; i < n; ++i)
+      for (int c = 0; c < nq; ++c)
+        guess_out[(size_t)i * nq + c] = i == 0 ? q0[c] : idto_spline::spline_value(breaks, n, y_q + c, m_q + c, nq, idto_spline::guess_time(start, i, time_step));
+    const std::vector<double> old0(q_nom, q_nom + nq);
+    for (int i = 0; i < n; ++i)
+      for (int c = 0; c < nq; ++c)
+        q_nom[(size_t)i * nq + c] = idto_spline::nominal_shift(q_nom[(size_t)i * nq + c], selector[c] != 0, q0[c], old0[(size_t)c]);
   });
 }
 }  // extern "C"

@@ -2,8 +2,14 @@
 #include "idto/examples/mpc_controller.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <stdexcept>
+#include <string>
+
+#include "host/batch_rows.h"
+
+#include "mpc_spline.h"
 
 namespace idto {
 namespace examples {
@@ -41,54 +47,20 @@ void PiecewiseCubic::Fit(const std::vector<double>& breaks) {
     if (!(breaks[i + 1] > breaks[i])) throw std::invalid_argument("PiecewiseCubic: breaks must increase");
   t_ = breaks;
   m_.assign((size_t)n * dim_, 0.0);
-  std::vector<double>& h = h_;
-  h.resize(n - 1);
-  for (int i = 0; i + 1 < n; ++i) h[i] = breaks[i + 1] - breaks[i];
-  auto slope = [&](int i, int c) { return (y_[(size_t)(i + 1) * dim_ + c] - y_[(size_t)i * dim_ + c]) / h[i]; };
-  if (n == 2) {   // the line
-    for (int c = 0; c < dim_; ++c) m_[c] = m_[dim_ + c] = slope(0, c);
-    return;
-  }
-  if (n == 3) {   // the parabola through the three points
-    for (int c = 0; c < dim_; ++c) {
-      const double d0 = slope(0, c), d1 = slope(1, c), a2 = (d1 - d0) / (h[0] + h[1]);
-      m_[c] = d0 - a2 * h[0];
-      m_[dim_ + c] = d0 + a2 * h[0];
-      m_[2 * dim_ + c] = d1 + a2 * h[1];
-    }
-    return;
-  }
-  // The not-a-knot system for the knot derivatives is TRIDIAGONAL as it stands - row 0 = [h1, h0 + h1], rows i =
-  // [h_i, 2 (h_{i-1} + h_i), h_{i-1}], row n - 1 = [h_{n-2} + h_{n-3}, h_{n-3}] - and one elimination without pivoting
-  // is stable on it: after row 0 (multiplier 1) row 1's diagonal is h0 + h1 > h0 and the interior rows are diagonally
-  // dominant.  O(n dim) instead of the dense LU's O(n^3) that ran three times per re-plan.
-  std::vector<double>&lo = lo_, &di = di_, &up = up_, &B = B_;
-  lo.assign(n, 0.0); di.assign(n, 0.0); up.assign(n, 0.0); B.assign((size_t)n * dim_, 0.0);
-  for (int i = 1; i + 1 < n; ++i) {
-    lo[i] = h[i]; di[i] = 2 * (h[i - 1] + h[i]); up[i] = h[i - 1];
-    for (int c = 0; c < dim_; ++c) B[(size_t)i * dim_ + c] = 3 * (h[i] * slope(i - 1, c) + h[i - 1] * slope(i, c));
-  }
-  {
-    const double d = h[0] + h[1];
-    di[0] = h[1]; up[0] = d;
-    for (int c = 0; c < dim_; ++c) B[c] = ((h[0] + 2 * d) * h[1] * slope(0, c) + h[0] * h[0] * slope(1, c)) / d;
-    const double e = h[n - 2] + h[n - 3];
-    di[n - 1] = h[n - 3]; lo[n - 1] = e;
-    for (int c = 0; c < dim_; ++c)
-      B[(size_t)(n - 1) * dim_ + c] = (h[n - 2] * h[n - 2] * slope(n - 3, c) + (2 * e + h[n - 2]) * h[n - 3] * slope(n - 2, c)) / e;
-  }
-  for (int i = 1; i < n; ++i) {
-    if (di[i - 1] == 0.0) throw std::runtime_error("PiecewiseCubic: singular system");
-    const double f = lo[i] / di[i - 1];
-    di[i] -= f * up[i - 1];
-    for (int c = 0; c < dim_; ++c) B[(size_t)i * dim_ + c] -= f * B[(size_t)(i - 1) * dim_ + c];
-  }
-  if (di[n - 1] == 0.0) throw std::runtime_error("PiecewiseCubic: singular system");
-  for (int i = n - 1; i >= 0; --i)
-    for (int c = 0; c < dim_; ++c) {
-      const double s = B[(size_t)i * dim_ + c] - (i + 1 < n ? up[i] * m_[(size_t)(i + 1) * dim_ + c] : 0.0);
-      m_[(size_t)i * dim_ + c] = s / di[i];
-    }
+  // the fit itself, per component: csrc/mpc_spline.h (the device fits the same text, mpc_batch.h); B_ is its work space
+  B_.assign((size_t)n * dim_, 0.0);
+  for (int c = 0; c < dim_; ++c)
+    if (idto_spline::spline_fit(t_.data(), n, y_.data() + c, m_.data() + c, B_.data() + c, dim_))
+      throw std::runtime_error("PiecewiseCubic: singular system");
+}
+
+void PiecewiseCubic::AssignFitted(const std::vector<double>& breaks, const double* y, const double* m, int dim) {
+  const int n = (int)breaks.size();
+  if (n < 2 || dim < 0) throw std::invalid_argument("PiecewiseCubic: at least two knots, one value per break");
+  dim_ = dim;
+  t_ = breaks;
+  y_.assign(y, y + (size_t)n * dim_);
+  m_.assign(m, m + (size_t)n * dim_);
 }
 
 VectorXd PiecewiseCubic::value(double t) const {
@@ -99,19 +71,12 @@ VectorXd PiecewiseCubic::value(double t) const {
 void PiecewiseCubic::value(double t, VectorXd* out_ptr) const {
   if (t_.empty()) throw std::runtime_error("PiecewiseCubic: empty trajectory");
   const int n = (int)t_.size();
-  t = std::min(std::max(t, t_.front()), t_.back());
-  int i = (int)(std::upper_bound(t_.begin(), t_.end(), t) - t_.begin()) - 1;
-  i = std::min(std::max(i, 0), n - 2);
-  const double h = t_[i + 1] - t_[i], s = t - t_[i];
+  const int i = idto_spline::spline_interval(t_.data(), n, &t);   // (t clamped to the breaks' range)
   VectorXd& out = *out_ptr;
   out.resize((size_t)dim_);
-  for (int c = 0; c < dim_; ++c) {
-    const double y0 = y_[(size_t)i * dim_ + c], y1 = y_[(size_t)(i + 1) * dim_ + c];
-    const double m0 = m_[(size_t)i * dim_ + c], m1 = m_[(size_t)(i + 1) * dim_ + c];
-    const double d = (y1 - y0) / h;
-    const double c2 = (3 * d - 2 * m0 - m1) / h, c3 = (m0 + m1 - 2 * d) / (h * h);
-    out[c] = y0 + s * (m0 + s * (c2 + s * c3));
-  }
+  for (int c = 0; c < dim_; ++c)
+    out[c] = idto_spline::spline_piece(t_[i], t_[i + 1], y_[(size_t)i * dim_ + c], y_[(size_t)(i + 1) * dim_ + c],
+                                    m_[(size_t)i * dim_ + c], m_[(size_t)(i + 1) * dim_ + c], t);
 }
 
 // ---- ModelPredictiveController (mpc_controller.cc:13-41)
@@ -161,7 +126,7 @@ const StoredTrajectory& ModelPredictiveController::UpdateAbstractState(double ti
   std::vector<VectorXd>& q_nom_new = q_nom_scratch_;
   q_nom_new = prob.q_nom;
   for (VectorXd& qt_nom : q_nom_new)
-    for (int i = 0; i < nq_; ++i) qt_nom[i] += (selector[i] ? 1.0 : 0.0) * (q0[i] - q0_nom_old[i]);
+    for (int i = 0; i < nq_; ++i) qt_nom[i] = idto_spline::nominal_shift(qt_nom[i], selector[i], q0[i], q0_nom_old[i]);
   std::vector<VectorXd>& v_nom = v_nom_scratch_;
   v_nom = prob.v_nom;
   optimizer_->UpdateNominalTrajectory(q_nom_new, v_nom);
@@ -188,7 +153,7 @@ void ModelPredictiveController::UpdateInitialGuess(const StoredTrajectory& store
                                                    std::vector<VectorXd>* q_guess) const {
   if ((int)q_guess->size() != num_steps_) throw std::invalid_argument("UpdateInitialGuess: q_guess must have num_steps + 1 entries");
   const double start_time = current_time - stored_trajectory.start_time;
-  for (int i = 0; i < num_steps_; ++i) stored_trajectory.q.value(start_time + i * time_step_, &(*q_guess)[i]);   // (in place: no temporary per step)
+  for (int i = 0; i < num_steps_; ++i) stored_trajectory.q.value(idto_spline::guess_time(start_time, i, time_step_), &(*q_guess)[i]);   // (in place: no temporary per step)
 }
 
 // StoreOptimizerSolution (:99-138)
@@ -202,13 +167,171 @@ void ModelPredictiveController::StoreOptimizerSolution(const TrajectoryOptimizer
   // control inputs, which are undefined at the last time step (:122-126): u = B^T tau
   u_flat_.resize((size_t)num_steps_ * nu_);
   for (int i = 0; i < num_steps_; ++i) {
-    const VectorXd& tau = solution.tau[i == num_steps_ - 1 ? i - 1 : i];
+    const VectorXd& tau = solution.tau[idto_spline::control_row(i, num_steps_)];
     for (int j = 0; j < nu_; ++j) u_flat_[(size_t)i * nu_ + j] = tau[actuated_dofs_[j]];
   }
   stored_trajectory->start_time = start_time;
   stored_trajectory->q.Assign(time_steps, solution.q, num_steps_);
   stored_trajectory->v.Assign(time_steps, solution.v, num_steps_);
   stored_trajectory->u.AssignFlat(time_steps, u_flat_.data(), nu_);
+}
+
+// ---- BatchModelPredictiveController: B controllers, one device pass per tick (include/idto_hip.h idto_hip_mpc_batch_*)
+namespace {
+void HipCheck(int rc, const char* what) {
+  if (rc != 0) throw std::runtime_error(std::string(what) + ": " + idto_hip_last_error());
+}
+void RowsFromFlat(const double* flat, int count, int width, std::vector<VectorXd>* out) {
+  out->resize((size_t)count);
+  for (int t = 0; t < count; ++t) (*out)[(size_t)t].assign(flat + (size_t)t * width, flat + (size_t)(t + 1) * width);
+}
+}  // namespace
+
+BatchModelPredictiveController::BatchModelPredictiveController(TrajectoryOptimizer<double>* optimizer,
+                                                               const std::vector<TrajectoryOptimizerSolution<double>>& warm,
+                                                               const std::vector<int>& actuated,
+                                                               const std::vector<bool>& q_nom_relative_to_q_init,
+                                                               const std::vector<ProblemDefinition>* problems)
+    : optimizer_(optimizer),
+      B_((int)warm.size()),
+      N_(optimizer->num_steps()),
+      nq_(optimizer->num_positions()),
+      nv_(optimizer->num_velocities()) {
+  if (problems && (int)problems->size() != B_)
+    throw std::invalid_argument("BatchModelPredictiveController: one problem per warm-start solution (or none)");
+  std::vector<const ProblemDefinition*> probs((size_t)B_, &optimizer->prob());
+  for (int b = 0; problems && b < B_; ++b) probs[(size_t)b] = &(*problems)[(size_t)b];
+  const std::string why = optimizer->BatchLoopRefusal(B_, probs);
+  if (!why.empty())
+    throw std::invalid_argument("BatchModelPredictiveController: the device's batch loop does not serve " + why +
+                                " - use B ModelPredictiveControllers, each on an optimizer of its own");
+  const std::vector<bool>& selector = q_nom_relative_to_q_init.empty() ? optimizer->params().q_nom_relative_to_q_init : q_nom_relative_to_q_init;
+  if ((int)selector.size() != nq_)
+    throw std::invalid_argument("q_nom_relative_to_q_init must have one entry per position (mpc_controller.cc:45)");
+  std::vector<int> sel((size_t)nq_), dofs;
+  for (int i = 0; i < nq_; ++i) sel[(size_t)i] = selector[(size_t)i] ? 1 : 0;
+  for (int j = 0; j < (int)actuated.size() && j < nv_; ++j)
+    if (actuated[(size_t)j]) dofs.push_back(j);
+  if (dofs.empty())
+    for (int j = 0; j < nv_; ++j) dofs.push_back(j);
+  nu_ = (int)dofs.size();
+  const int n = N_ + 1;
+  const size_t nqa = (size_t)n * nq_, nva = (size_t)n * nv_, nta = (size_t)N_ * nv_, len = IDTO_MPC_PLAN_LEN(n, nq_, nv_, nu_);
+  q_.resize(B_ * nqa); v_.resize(B_ * nva); tau_.resize(B_ * nta); guess_.resize(B_ * nqa); plans_.resize(B_ * len);
+  for (int b = 0; b < B_; ++b) {
+    const TrajectoryOptimizerSolution<double>& w = warm[(size_t)b];
+    bool ok = (int)w.q.size() >= n && (int)w.v.size() >= n && (int)w.tau.size() >= N_;
+    for (int t = 0; ok && t < n; ++t) ok = (int)w.q[(size_t)t].size() == nq_ && (int)w.v[(size_t)t].size() == nv_;
+    for (int t = 0; ok && t < N_; ++t) ok = (int)w.tau[(size_t)t].size() == nv_;
+    if (!ok) throw std::invalid_argument("BatchModelPredictiveController: warm-start solution " + std::to_string(b) + " is shorter than the horizon");
+    for (int t = 0; t < n; ++t) {
+      std::copy(w.q[(size_t)t].begin(), w.q[(size_t)t].end(), q_.begin() + b * nqa + (size_t)t * nq_);
+      std::copy(w.v[(size_t)t].begin(), w.v[(size_t)t].end(), v_.begin() + b * nva + (size_t)t * nv_);
+    }
+    for (int t = 0; t < N_; ++t) std::copy(w.tau[(size_t)t].begin(), w.tau[(size_t)t].end(), tau_.begin() + b * nta + (size_t)t * nv_);
+  }
+  breaks_.resize((size_t)n);
+  for (int i = 0; i < n; ++i) breaks_[(size_t)i] = i * optimizer->time_step();
+  stored_.resize((size_t)B_); flags_.assign((size_t)B_, optimizer::SolverFlag::kSuccess); errors_.resize((size_t)B_);
+  stats_.resize((size_t)B_); solutions_ = warm; guesses_.resize((size_t)B_);
+  Delta_.assign((size_t)B_, optimizer->params().Delta0); Delta_out_.resize((size_t)B_);
+  final_cost_.resize((size_t)B_); status_.resize((size_t)B_); x0_.resize((size_t)B_ * (nq_ + nv_));
+  rows_.resize((size_t)B_ * std::max(1, optimizer->params().max_iterations) * IDTO_TR_ROW);
+  // ---- the first device work
+  ctx_ = optimizer->CreateBatchContext(probs);
+  try {
+    HipCheck(idto_hip_mpc_batch_begin(ctx_, sel.data(), dofs.data(), nu_), "idto_hip_mpc_batch_begin");
+    const std::vector<double> t0((size_t)B_, 0.0);   // (the constructor's StoreOptimizerSolution(warm_start_solution, 0.0))
+    HipCheck(idto_hip_mpc_batch_store(ctx_, q_.data(), v_.data(), tau_.data(), t0.data(), plans_.data()), "idto_hip_mpc_batch_store");
+    loop_ = optimizer->PrepareBatchLoop(ctx_);
+    if (loop_.nu > 0) {   // (the context's own word on the constraint route, whatever set its option)
+      int con_kkt = 1;
+      HipCheck(idto_hip_get_option(ctx_, "con_kkt", &con_kkt), "idto_hip_get_option");
+      if (!con_kkt)
+        throw std::invalid_argument("BatchModelPredictiveController: the device's batch loop does not serve the child-context constraint "
+                                    "route (option con_kkt = 0) - use B ModelPredictiveControllers, each on an optimizer of its own");
+    }
+  } catch (...) {
+    idto_hip_destroy(ctx_);
+    ctx_ = nullptr;
+    throw;
+  }
+  for (int b = 0; b < B_; ++b) AdoptPlan(b, plans_.data() + b * len);
+}
+
+BatchModelPredictiveController::~BatchModelPredictiveController() {
+  if (ctx_) idto_hip_destroy(ctx_);
+}
+
+void BatchModelPredictiveController::AdoptPlan(int b, const double* plan) {
+  const size_t n = (size_t)N_ + 1;
+  StoredTrajectory& s = stored_[(size_t)b];
+  s.start_time = plan[0];
+  const double* p = plan + 1;
+  s.q.AssignFitted(breaks_, p, p + n * nq_, nq_); p += 2 * n * nq_;
+  s.v.AssignFitted(breaks_, p, p + n * nv_, nv_); p += 2 * n * nv_;
+  s.u.AssignFitted(breaks_, p, p + n * nu_, nu_);
+}
+
+bool BatchModelPredictiveController::UpdateAll(const std::vector<double>& times, const std::vector<VectorXd>& x0s) {
+  if ((int)times.size() != B_ || (int)x0s.size() != B_) throw std::invalid_argument("UpdateAll: one time and one state estimate per controller");
+  for (int b = 0; b < B_; ++b) {
+    if ((int)x0s[(size_t)b].size() != nq_ + nv_) throw std::invalid_argument("state estimate must be [q0; v0]");
+    std::copy(x0s[(size_t)b].begin(), x0s[(size_t)b].end(), x0_.begin() + (size_t)b * (nq_ + nv_));
+  }
+  return UpdateAll(times.data(), x0_.data());
+}
+
+bool BatchModelPredictiveController::UpdateAll(const double* times, const double* x0s) {
+  using clock = std::chrono::high_resolution_clock;
+  idto_hip_trace_mark("mpc batch: UpdateAll begins");
+  const auto start = clock::now();
+  const int n = N_ + 1, iters = loop_.iterations;
+  const size_t nqa = (size_t)n * nq_, nva = (size_t)n * nv_, nta = (size_t)N_ * nv_, len = IDTO_MPC_PLAN_LEN(n, nq_, nv_, nu_);
+  int best = -1;
+  const int rc = idto_hip_mpc_batch_replan(ctx_, times, x0s, iters, loop_.scaling_method, loop_.scaling, loop_.normalize_quaternions,
+                                           Delta_.data(), loop_.Delta_max, loop_.eta, loop_.constrained_dofs, loop_.nu, rows_.data(),
+                                           Delta_out_.data(), q_.data(), v_.data(), tau_.data(), final_cost_.data(), status_.data(),
+                                           &best, guess_.data(), plans_.data());
+  idto_hip_trace_mark("mpc batch: idto_hip_mpc_batch_replan returned");
+  tick_error_.clear();
+  if (rc == IDTO_HIP_SOLVER_TIMEOUT) {
+    // nothing of this tick counts: every plan, solution and radius stays (the device's plans too: include/idto_hip.h)
+    tick_error_ = std::string("the batch loop timed out on the device: ") + idto_hip_last_error();
+    for (int b = 0; b < B_; ++b) {
+      flags_[(size_t)b] = optimizer::SolverFlag::kFactorizationFailed;
+      errors_[(size_t)b] = tick_error_;
+      stats_[(size_t)b] = TrajectoryOptimizerStats<double>();
+    }
+    return false;
+  }
+  if (rc != 0 && rc != IDTO_HIP_FACTORIZATION_FAILED) throw std::runtime_error(std::string("idto_hip_mpc_batch_replan: ") + idto_hip_last_error());
+  const double total = std::chrono::duration<double>(clock::now() - start).count();
+  for (int b = 0; b < B_; ++b) {
+    RowsFromFlat(guess_.data() + b * nqa, n, nq_, &guesses_[(size_t)b]);
+    stats_[(size_t)b] = TrajectoryOptimizerStats<double>();
+    errors_[(size_t)b].clear();
+    optimizer::internal::BatchRowsResult r;
+    optimizer::internal::RowsToStats(rows_.data() + (size_t)b * iters * IDTO_TR_ROW, iters, Delta_out_[(size_t)b], total, optimizer_->params(),
+                                     &stats_[(size_t)b], &r);
+    // (the device kept this controller's plan exactly when its status carries one of these bits: mpc_store_kernel)
+    if ((status_[(size_t)b] & (1 | 2 | 4 | 8 | 32)) != 0) {
+      flags_[(size_t)b] = optimizer::SolverFlag::kFactorizationFailed;
+      errors_[(size_t)b] = !r.error.empty() ? r.error
+                           : (status_[(size_t)b] & 8) ? std::string("singular constraint Schur complement: the batch loop has no host loop to finish in")
+                                                      : std::string("idto_hip: the re-plan failed (status ") + std::to_string(status_[(size_t)b]) + ")";
+      continue;
+    }
+    flags_[(size_t)b] = r.flag;
+    Delta_[(size_t)b] = r.Delta;
+    TrajectoryOptimizerSolution<double>& sol = solutions_[(size_t)b];
+    RowsFromFlat(q_.data() + b * nqa, n, nq_, &sol.q);
+    RowsFromFlat(v_.data() + b * nva, n, nv_, &sol.v);
+    RowsFromFlat(tau_.data() + b * nta, N_, nv_, &sol.tau);
+    AdoptPlan(b, plans_.data() + b * len);
+  }
+  idto_hip_trace_mark("mpc batch: plans adopted");
+  return true;
 }
 
 // Interpolator::SendState / SendControl (:163-178)

@@ -14,6 +14,7 @@
 
 #include "host/batch_rows.h"
 #include "host/ls_rows.h"
+#include "host/solver_plan.h"
 
 #include <algorithm>
 #include <chrono>
@@ -1642,6 +1643,74 @@ void TO::SolveBatch(const std::vector<std::vector<VectorXd>>& q_guesses, const s
   if (only_best)
     for (int b = 0; b < B; ++b)
       if (b != out->best) ClearSolution(&out->solutions[b]);
+}
+
+// ---- the batch loop for a caller with a batch context of its own (examples::mpc::BatchModelPredictiveController)
+
+std::string TO::BatchLoopRefusal(int B, const std::vector<const ProblemDefinition*>& probs) const {
+  if (B < 2) return "B < 2 (a batch of fewer than two controllers)";
+  if (params_.method != kTrustRegion) return "method = kLinesearch";
+  const int scal = params_.scaling ? static_cast<int>(params_.scaling_method) : -1;
+  if (scal == static_cast<int>(kAdaptiveSqrt) || scal == static_cast<int>(kAdaptiveDoubleSqrt))
+    return "adaptive scalings (scaling_method = kAdaptiveSqrt / kAdaptiveDoubleSqrt)";
+  if (!shard_ctx_.empty()) return "several devices";
+  if (params_.verbose) return "verbose";
+  if (DenseLinearSolver()) return "linear_solver = kDenseLdlt";
+  if (params_.debug_compare_against_dense || params_.print_debug_data)
+    return "the debug switches (debug_compare_against_dense, print_debug_data)";
+  if (params_.max_iterations <= 0) return "max_iterations <= 0";
+  for (const ProblemDefinition* p : probs)
+    if (!DiagonalWeights(*p)) return "dense weights (a cost weight matrix that is not diagonal)";
+  if (params_.equality_constraints && num_equality_constraints() > 0) {
+    const char* e = std::getenv("IDTO_CON_KKT");   // (what a context reads at creation: option "con_kkt")
+    if ((e && e[0] != '1') || idto_host::SolverBlockSize(nq_ + (int)unactuated_dofs_.size(), true) > 30)
+      return "the child-context constraint route (enforced constraints with nq + nu > 30, or option con_kkt = 0)";
+  }
+  if (std::getenv("IDTO_OPT_HOST_LOOP") || std::getenv("IDTO_OPT_STEPWISE")) return "the host loop (IDTO_OPT_HOST_LOOP / IDTO_OPT_STEPWISE)";
+  return "";
+}
+
+idto_hip_ctx* TO::CreateBatchContext(const std::vector<const ProblemDefinition*>& probs) const {
+  const int B = (int)probs.size();
+  std::vector<Vec> qn((std::size_t)B), vn((std::size_t)B);
+  std::vector<idto_problem_t> ps((std::size_t)B);
+  for (int b = 0; b < B; ++b) {
+    const ProblemDefinition& pd = *probs[b];
+    CheckBatchProblem(pd, b);
+    qn[b] = Flatten(pd.q_nom); vn[b] = Flatten(pd.v_nom);
+    idto_problem_t p = {};
+    p.num_steps = num_steps(); p.time_step = time_step_;
+    p.q_init = pd.q_init.data(); p.v_init = pd.v_init.data();
+    p.Qq = pd.Qq.data(); p.Qv = pd.Qv.data(); p.Qf_q = pd.Qf_q.data(); p.Qf_v = pd.Qf_v.data();
+    p.R = pd.R.data(); p.q_nom = qn[b].data(); p.v_nom = vn[b].data();
+    ps[b] = p;
+  }
+  idto_hip_ctx* ctx = nullptr;
+  Check(idto_hip_create_batch_like(dev(), ps.data(), B, &ctx));
+  return ctx;
+}
+
+TO::BatchLoopArgs TO::PrepareBatchLoop(idto_hip_ctx* ctx) const {
+  Check(idto_hip_set_unactuated_dofs(ctx, unactuated_dofs_.data(), (int)unactuated_dofs_.size()));
+  if (params_.check_convergence) {
+    const auto& t = params_.convergence_tolerances;
+    const double tol[6] = {t.rel_cost_reduction, t.abs_cost_reduction, t.rel_gradient_along_dq, t.abs_gradient_along_dq,
+                           t.rel_state_change, t.abs_state_change};
+    Check(idto_hip_tr_set_convergence(ctx, tol));
+  } else {
+    Check(idto_hip_tr_set_convergence(ctx, nullptr));
+  }
+  const bool constrained = params_.equality_constraints && num_equality_constraints() > 0;
+  BatchLoopArgs a;
+  a.iterations = params_.max_iterations;
+  a.scaling_method = params_.scaling ? static_cast<int>(params_.scaling_method) : -1;
+  a.scaling = params_.scaling ? 1 : 0;
+  a.normalize_quaternions = params_.normalize_quaternions ? 1 : 0;
+  a.Delta_max = params_.Delta_max;
+  a.eta = 0.0;
+  a.constrained_dofs = constrained ? unactuated_dofs_.data() : nullptr;
+  a.nu = constrained ? (int)unactuated_dofs_.size() : 0;
+  return a;
 }
 
 SolverFlag TO::SolveFromWarmStartImpl(WarmStart* ws, TrajectoryOptimizerSolution<T>* solution,

@@ -38,6 +38,7 @@
 #include "trust_region.h"
 #include "kkt.h"
 #include "linesearch.h"
+#include "mpc_batch.h"
 #include "host/model_tables.h"
 #include "host/solver_plan.h"
 
@@ -187,8 +188,28 @@ static RcclApi& RcclState() {
   if (!R) { g_err = "librccl could not be loaded (set IDTO_RCCL_LIB; tried:" + RcclState().tried + ")"; return -4; }
 
 
+// idto_hip_mpc_batch_*: the stored plans of a batch of controllers (mpc_batch.h), an allocation of its own
+struct MpcBatchState {
+  MpcPlanLayout L{};
+  std::vector<int> selector;                 // host copy (the host copies of the problems are shifted with it)
+  double* breaks = nullptr; int* selector_dev = nullptr; int* actuated_dev = nullptr;
+  double* plan[2] = {nullptr, nullptr};      // two planes of [batch][L.len()]; `cur` is the one in force
+  int cur = 0;
+  double* work = nullptr;                    // spline_fit's work space, [batch][n * dims]
+  double* tick_dev = nullptr; double* tick_pin = nullptr;   // [batch][1 + nq + nv]: time, q0, v0
+  double* io_dev = nullptr; double* io_pin = nullptr; size_t io_count = 0;   // idto_hip_mpc_batch_store / _shift: plans in, plans / guesses out
+};
+// what idto_hip_mpc_batch_replan hangs behind the batch fetch's own doubles: [guess [B][(N+1) nq] | plans [B][L.len()]]
+struct MpcTickHook {
+  MpcBatchState* m;
+  const double* times; const double* x0;     // host: [B], [B][nq + nv]
+  double* guess_out; double* plans_out;      // host, may be null
+  size_t nguess, nplans;                     // doubles of the two parts
+};
+
 struct idto_hip_ctx {
   int device = 0;
+  MpcBatchState* mpc = nullptr;
   // (batch contexts) what the context was created from, and one single-problem context per problem, made on first use
   std::unique_ptr<HostModelCopy> host_model;
   std::vector<std::unique_ptr<HostProblemCopy>> host_problems;
@@ -996,6 +1017,11 @@ void idto_hip_destroy(idto_hip_ctx* c) {
   if (c->con_pin) (void)hipHostFree(c->con_pin);
   if (c->fetch_pin) (void)hipHostFree(c->fetch_pin);
   if (c->bstate_pin) (void)hipHostFree(c->bstate_pin);
+  if (c->mpc) {   // (its device buffers are in c->allocs)
+    if (c->mpc->tick_pin) (void)hipHostFree(c->mpc->tick_pin);
+    if (c->mpc->io_pin) (void)hipHostFree(c->mpc->io_pin);
+    delete c->mpc;
+  }
   for (int i = 0; i < 2; ++i) {
     if (c->up_pin[i]) (void)hipHostFree(c->up_pin[i]);
     if (c->up_ev[i]) (void)hipEventDestroy(c->up_ev[i]);
@@ -2297,7 +2323,25 @@ struct TrBatchFetch {
   int only_best;
   double* out[5];   // q, v, tau, dq, w: [batch][...] or - only_best - [1][...]; any may be null
   double* final_cost; int* status; int* best;
+  const MpcTickHook* mpc = nullptr;   // idto_hip_mpc_batch_replan: the store behind the gather, its doubles behind the fetch's
 };
+// the doubles idto_hip_tr_solve_batch_fetch packs for the host
+static size_t BatchFetchDoubles(const idto_hip_ctx* c, int iterations, bool only_best) {
+  const size_t nqa = (size_t)(c->N + 1) * c->nq, nva = (size_t)(c->N + 1) * c->nv, nta = (size_t)c->N * c->nv;
+  return tr_gather_batch_header(c->batch) + (size_t)c->batch * (TRS_COUNT + (size_t)iterations * TRR_COUNT) +
+         (only_best ? 1 : (size_t)c->batch) * (3 * nqa + nva + nta);
+}
+// the fetches' staging on the device and its pinned mirror, grown on demand
+static int EnsureFetch(idto_hip_ctx* c, size_t total) {
+  if (c->fetch_cap >= total) return 0;
+  Release(c, &c->fetch_dev);
+  if (c->fetch_pin) (void)hipHostFree(c->fetch_pin);
+  c->fetch_pin = nullptr; c->fetch_cap = 0;
+  if (Alloc(c, total, &c->fetch_dev)) return -2;
+  HIP_OK(hipHostMalloc((void**)&c->fetch_pin, total * sizeof(double), hipHostMallocDefault));
+  c->fetch_cap = total;
+  return 0;
+}
 // Delta0s / Delta_out: one radius per problem of the context; rows_host: [batch][iterations][TRR_COUNT]
 static int TrSolve(idto_hip_ctx* c, int iterations, int scaling_method, int scaling, int normalize_quaternions,
                    const double* Delta0s, double Delta_max, double eta, const int* constrained_dofs, int nu,
@@ -2596,17 +2640,12 @@ static int TrSolve(idto_hip_ctx* c, int iterations, int scaling_method, int scal
       const size_t nrow = rows_stride;
       const size_t nqa = (size_t)(c->N + 1) * c->nq, nva = (size_t)(c->N + 1) * c->nv, nta = (size_t)c->N * c->nv;
       const size_t ntraj = 3 * nqa + nva + nta, head = tr_gather_batch_header(B);
-      const size_t total = head + (size_t)B * (TRS_COUNT + nrow) + (bfetch->only_best ? 1 : (size_t)B) * ntraj;
+      const size_t base = head + (size_t)B * (TRS_COUNT + nrow) + (bfetch->only_best ? 1 : (size_t)B) * ntraj;
+      const MpcTickHook* hook = bfetch->mpc;
+      const size_t total = base + (hook ? hook->nguess + hook->nplans : 0);
       const size_t lds = (size_t)B * (sizeof(double) + sizeof(int));
       if (lds > 60 * 1024) { g_err = "tr_solve_batch_fetch: the batch is too large for the selecting workgroup's LDS"; return -1; }
-      if (c->fetch_cap < total) {
-        Release(c, &c->fetch_dev);
-        if (c->fetch_pin) (void)hipHostFree(c->fetch_pin);
-        c->fetch_pin = nullptr; c->fetch_cap = 0;
-        if (Alloc(c, total, &c->fetch_dev)) return -2;
-        HIP_OK(hipHostMalloc((void**)&c->fetch_pin, total * sizeof(double), hipHostMallocDefault));
-        c->fetch_cap = total;
-      }
+      if (int erc = EnsureFetch(c, total)) return erc;
       TrGatherBatchArgs G;
       G.state = c->tr_state; G.rows = c->tr_rows; G.B = B; G.iterations = iterations; G.nrows = (int)nrow;
       G.only_best = bfetch->only_best ? 1 : 0;
@@ -2616,6 +2655,22 @@ static int TrSolve(idto_hip_ctx* c, int iterations, int scaling_method, int scal
       G.out = c->fetch_dev;
       hipLaunchKernelGGL(tr_gather_batch_kernel, dim3(TR_GATHER_BATCH_GX + 1, B), dim3(256), lds, c->stream, G);
       HIP_OK(hipGetLastError());
+      if (hook) {
+        // the tick's new plans: fitted on the device from the loop's result, written to the plane that is not in force and
+        // behind the guesses in the same staging buffer (the shift left those there: idto_hip_mpc_batch_replan)
+        MpcBatchState* m = hook->m;
+        MpcStoreArgs S{};
+        S.L = m->L; S.breaks = m->breaks; S.actuated = m->actuated_dev;
+        S.q = c->q; S.q_stride = c->pstride; S.v = c->v; S.v_stride = c->pstride;
+        S.tau = c->slab + 3 * (size_t)c->nv * c->nq; S.tau_stride = c->pstride; S.tau_row = (int)c->slab_stride;
+        S.state = c->tr_state; S.state_stride = c->pstride; S.alt_off = (long long)c->alt_off;
+        S.rows = c->tr_rows; S.iterations = iterations; S.nrows = (int)nrow;
+        S.times = m->tick_dev; S.times_stride = 1 + c->nq + c->nv;
+        S.plan_old = m->plan[m->cur]; S.plan_new = m->plan[m->cur ^ 1]; S.work = m->work;
+        S.out = c->fetch_dev + base + hook->nguess;
+        hipLaunchKernelGGL(mpc_store_kernel, dim3((m->L.dims() + 63) / 64, B), dim3(64), 0, c->stream, S);
+        HIP_OK(hipGetLastError());
+      }
       HIP_OK(hipMemcpyAsync(c->fetch_pin, c->fetch_dev, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
       // (behind the copy: the fold only makes the context's first set the iterate's for the calls that follow)
       hipLaunchKernelGGL(tr_fold_sets_kernel, dim3(64, B), dim3(256), 0, c->stream, c->v, (size_t)c->alt_off / sizeof(double),
@@ -2627,6 +2682,10 @@ static int TrSolve(idto_hip_ctx* c, int iterations, int scaling_method, int scal
       const int best = (int)p[0];
       *bfetch->best = best;
       for (int b = 0; b < B; ++b) { bfetch->final_cost[b] = p[1 + b]; bfetch->status[b] = (int)p[1 + B + b]; }
+      if (hook) {
+        if (hook->guess_out) std::memcpy(hook->guess_out, c->fetch_pin + base, hook->nguess * sizeof(double));
+        if (hook->plans_out) std::memcpy(hook->plans_out, c->fetch_pin + base + hook->nguess, hook->nplans * sizeof(double));
+      }
       p += head;
       const double* states = p;
       for (int b = 0; b < B; ++b, p += TRS_COUNT + nrow) {
@@ -2828,6 +2887,197 @@ int idto_hip_tr_solve_batch_constrained(idto_hip_ctx* c, int iterations, int sca
   return 0;
 }
 
+// ---- B model-predictive controllers on a batch context (mpc_batch.h)
+static int MpcReady(idto_hip_ctx* c, const char* who) {
+  if (!c->mpc) { g_err = std::string(who) + ": call idto_hip_mpc_batch_begin on the context first"; return -1; }
+  for (idto_hip_ctx* ch : c->children)
+    if (ch) {
+      g_err = std::string(who) + ": this context has child contexts (the child-context route of idto_hip_tr_solve_batch_constrained "
+              "made them), which the shift on the device would leave with the old initial conditions and nominal trajectories";
+      return -1;
+    }
+  return 0;
+}
+
+int idto_hip_mpc_batch_begin(idto_hip_ctx* c, const int* selector, const int* actuated_dofs, int nu) {
+  if (!selector || !actuated_dofs || nu < 1 || nu > c->nv) { g_err = "mpc_batch_begin: selector[nq] and 1 <= nu <= nv actuated_dofs are required"; return -1; }
+  for (int j = 0; j < nu; ++j)
+    if (actuated_dofs[j] < 0 || actuated_dofs[j] >= c->nv) { g_err = "mpc_batch_begin: an actuated dof outside [0, nv)"; return -1; }
+  if (c->N < 1) { g_err = "mpc_batch_begin: a plan needs at least two knots"; return -1; }
+  HIP_OK(hipSetDevice(c->device));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  if (c->mpc) {
+    MpcBatchState* o = c->mpc;
+    Release(c, &o->breaks); Release(c, &o->selector_dev); Release(c, &o->actuated_dev); Release(c, &o->plan[0]); Release(c, &o->plan[1]);
+    Release(c, &o->work); Release(c, &o->tick_dev); Release(c, &o->io_dev);
+    if (o->tick_pin) (void)hipHostFree(o->tick_pin);
+    if (o->io_pin) (void)hipHostFree(o->io_pin);
+    delete o;
+    c->mpc = nullptr;
+  }
+  auto m = std::make_unique<MpcBatchState>();
+  const size_t B = (size_t)c->batch;
+  const int n = c->N + 1;
+  m->L = MpcPlanLayout{n, c->nq, c->nv, nu};
+  m->selector.resize((size_t)c->nq);
+  for (int i = 0; i < c->nq; ++i) m->selector[(size_t)i] = selector[i] ? 1 : 0;
+  std::vector<double> breaks((size_t)n);
+  for (int i = 0; i < n; ++i) breaks[(size_t)i] = i * c->dt;   // StoreOptimizerSolution: time_steps[i] = i * time_step
+  const size_t nqa = (size_t)n * c->nq, nva = (size_t)n * c->nv, nta = (size_t)c->N * c->nv, len = m->L.len();
+  const size_t tick = B * (size_t)(1 + c->nq + c->nv);
+  m->io_count = std::max(std::max(B * (nqa + nva + nta + 1), B * len), 2 * B * nqa);
+  if (Upload(c, breaks.data(), breaks.size(), &m->breaks) || Upload(c, m->selector.data(), m->selector.size(), &m->selector_dev) ||
+      Upload(c, actuated_dofs, (size_t)nu, &m->actuated_dev) || Alloc(c, B * len, &m->plan[0]) || Alloc(c, B * len, &m->plan[1]) ||
+      Alloc(c, B * (size_t)n * m->L.dims(), &m->work) || Alloc(c, tick, &m->tick_dev) || Alloc(c, m->io_count, &m->io_dev))
+    return -2;
+  HIP_OK(hipHostMalloc((void**)&m->tick_pin, tick * sizeof(double), hipHostMallocDefault));
+  HIP_OK(hipHostMalloc((void**)&m->io_pin, m->io_count * sizeof(double), hipHostMallocDefault));
+  c->mpc = m.release();
+  return 0;
+}
+
+int idto_hip_mpc_batch_store(idto_hip_ctx* c, const double* q, const double* v, const double* tau, const double* start_times,
+                             double* plans_out) {
+  if (int rc = MpcReady(c, "mpc_batch_store")) return rc;
+  if (!q || !v || !tau || !start_times) { g_err = "mpc_batch_store: q, v, tau and start_times are required"; return -1; }
+  HIP_OK(hipSetDevice(c->device));
+  MpcBatchState* m = c->mpc;
+  const size_t B = (size_t)c->batch, len = m->L.len();
+  const size_t nqa = (size_t)m->L.n * c->nq, nva = (size_t)m->L.n * c->nv, nta = (size_t)c->N * c->nv;
+  double* in = m->io_pin;
+  std::memcpy(in, q, B * nqa * sizeof(double));
+  std::memcpy(in + B * nqa, v, B * nva * sizeof(double));
+  std::memcpy(in + B * (nqa + nva), tau, B * nta * sizeof(double));
+  std::memcpy(in + B * (nqa + nva + nta), start_times, B * sizeof(double));
+  const size_t count = B * (nqa + nva + nta + 1);
+  HIP_OK(hipMemcpyAsync(m->io_dev, in, count * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  MpcStoreArgs S{};
+  S.L = m->L; S.breaks = m->breaks; S.actuated = m->actuated_dev;
+  S.q = m->io_dev; S.q_stride = nqa * sizeof(double);
+  S.v = m->io_dev + B * nqa; S.v_stride = nva * sizeof(double);
+  S.tau = m->io_dev + B * (nqa + nva); S.tau_stride = nta * sizeof(double); S.tau_row = c->nv;
+  S.state = nullptr; S.state_stride = 0; S.alt_off = 0;
+  S.rows = nullptr; S.iterations = 0; S.nrows = 0;
+  S.times = m->io_dev + B * (nqa + nva + nta); S.times_stride = 1;
+  S.plan_old = m->plan[m->cur]; S.plan_new = m->plan[m->cur]; S.work = m->work;
+  S.out = nullptr;
+  hipLaunchKernelGGL(mpc_store_kernel, dim3((m->L.dims() + 63) / 64, (unsigned)B), dim3(64), 0, c->stream, S);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(m->io_pin, m->plan[m->cur], B * len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  if (plans_out) std::memcpy(plans_out, m->io_pin, B * len * sizeof(double));
+  return 0;
+}
+
+// the copy of times and x0 and the shift, enqueued; guess_dev: [B][(N+1) nq] on the device, or null
+static int MpcShiftEnqueue(idto_hip_ctx* c, const double* times, const double* x0, double* guess_dev) {
+  MpcBatchState* m = c->mpc;
+  const int B = c->batch, nq = c->nq, nv = c->nv, n = m->L.n;
+  // as idto_hip_set_q_batch + idto_hip_set_problem_batch leave the context
+  c->trial_resident = false; c->spec_pending = false; c->spec_ready = false;
+  DropPrefetch(c, {IDTO_ARR_Q});
+  c->fd_full = false; c->partials_ahead = false;
+  c->con_ready = false; c->con_begun = false;
+  const size_t w = (size_t)(1 + nq + nv);
+  for (int b = 0; b < B; ++b) {
+    double* t = m->tick_pin + (size_t)b * w;
+    t[0] = times[b];
+    std::memcpy(t + 1, x0 + (size_t)b * (nq + nv), (size_t)(nq + nv) * sizeof(double));
+  }
+  HIP_OK(hipMemcpyAsync(m->tick_dev, m->tick_pin, (size_t)B * w * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  MpcShiftArgs A{};
+  A.L = m->L; A.breaks = m->breaks; A.selector = m->selector_dev; A.time_step = c->dt;
+  A.plan = m->plan[m->cur]; A.tick = m->tick_dev;
+  A.q = c->q; A.v_init = c->d_vinit; A.q_nom = c->d_qnom; A.pstride = c->pstride;
+  A.guess_out = guess_dev;
+  hipLaunchKernelGGL(mpc_shift_kernel, dim3(1, B), dim3(256), (size_t)nq * sizeof(double), c->stream, A);
+  HIP_OK(hipGetLastError());
+  // the host copies of the problems (what a child context would be made from) follow: the same arithmetic, mpc_spline.h
+  for (int b = 0; b < B && b < (int)c->host_problems.size(); ++b) {
+    HostProblemCopy& hp = *c->host_problems[(size_t)b];
+    const double* q0 = x0 + (size_t)b * (nq + nv);
+    const std::vector<double> old0(hp.q_nom.begin(), hp.q_nom.begin() + nq);
+    for (int t = 0; t < n; ++t)
+      for (int i = 0; i < nq; ++i)
+        hp.q_nom[(size_t)t * nq + i] = idto_spline::nominal_shift(hp.q_nom[(size_t)t * nq + i], m->selector[(size_t)i] != 0, q0[i], old0[(size_t)i]);
+    std::copy(q0, q0 + nq, hp.q_init.begin());
+    std::copy(q0 + nq, q0 + nq + nv, hp.v_init.begin());
+  }
+  TRACE("hip: mpc_batch: tick inputs and the shift enqueued");
+  return 0;
+}
+
+int idto_hip_mpc_batch_shift(idto_hip_ctx* c, const double* times, const double* x0, double* guess_out, double* q_nom_out) {
+  if (int rc = MpcReady(c, "mpc_batch_shift")) return rc;
+  if (!times || !x0) { g_err = "mpc_batch_shift: times[batch] and x0[batch][nq + nv] are required"; return -1; }
+  HIP_OK(hipSetDevice(c->device));
+  MpcBatchState* m = c->mpc;
+  const size_t B = (size_t)c->batch, nqa = (size_t)m->L.n * c->nq;
+  int rc = MpcShiftEnqueue(c, times, x0, m->io_dev);
+  if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+  HIP_OK(hipMemcpyAsync(m->io_pin, m->io_dev, B * nqa * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipMemcpy2DAsync(m->io_pin + B * nqa, nqa * sizeof(double), c->d_qnom, c->pstride, nqa * sizeof(double), B,
+                          hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  if (guess_out) std::memcpy(guess_out, m->io_pin, B * nqa * sizeof(double));
+  if (q_nom_out) std::memcpy(q_nom_out, m->io_pin + B * nqa, B * nqa * sizeof(double));
+  return 0;
+}
+
+// The inside of idto_hip_tr_solve_batch_fetch for a batch of more than one problem; with bf->mpc a controllers' tick
+// (idto_hip_mpc_batch_replan): the shift and idto_hip_eval_tau in front of the loop, the store behind it.
+static int TrSolveBatchFetch(idto_hip_ctx* c, int iterations, int scaling_method, int scaling, int normalize_quaternions,
+                             const double* Delta0, double Delta_max, double eta, const int* constrained_dofs, int nu,
+                             double* rows_host, double* Delta_out, const TrBatchFetch* bf) {
+  if (nu > 0 && !(c->con_kkt && idto_host::SolverBlockSize(c->nq + nu, true) <= 30 && c->weights_diagonal)) {
+    g_err = "tr_solve_batch_fetch: these enforced constraints take the child-context route of idto_hip_tr_solve_batch_constrained "
+            "(option con_kkt = 0, nq + nu > 30 or dense cost weights: every problem advanced in a single-problem context of "
+            "its own), which has no gathered fetch: use idto_hip_tr_solve_batch_constrained + idto_hip_get_batch";
+    return -1;
+  }
+  HIP_OK(hipSetDevice(c->device));
+  int rc = 0;
+  if (bf->mpc) {
+    // (the guesses go where the one copy back finds them: behind the fetch's own doubles)
+    const size_t base = BatchFetchDoubles(c, iterations, bf->only_best != 0);
+    if ((rc = EnsureFetch(c, base + bf->mpc->nguess + bf->mpc->nplans)) != 0) return rc;
+    rc = MpcShiftEnqueue(c, bf->mpc->times, bf->mpc->x0, c->fetch_dev + base);
+  }
+  if (!rc && (nu > 0 || bf->mpc))
+    rc = idto_hip_eval_tau(c);   // (as idto_hip_tr_solve_batch_constrained: the loop starts from the cost of the resident q)
+  if (!rc)
+    rc = TrSolve(c, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu,
+                 rows_host, Delta_out, nullptr, bf);
+  // (a return from inside the loop's enqueueing: the initial state words travel from pinned memory of the context, which the
+  // next call rewrites - wait for what is enqueued)
+  if (rc < 0) (void)hipStreamSynchronize(c->stream);
+  return rc;
+}
+
+int idto_hip_mpc_batch_replan(idto_hip_ctx* c, const double* times, const double* x0, int iterations, int scaling_method,
+                              int scaling, int normalize_quaternions, const double* Delta0, double Delta_max, double eta,
+                              const int* constrained_dofs, int nu, double* rows_host, double* Delta_out, double* q_out,
+                              double* v_out, double* tau_out, double* final_cost, int* status, int* best, double* guess_out,
+                              double* plans_out) {
+  if (int rc = MpcReady(c, "mpc_batch_replan")) return rc;
+  if (!times || !x0 || !Delta0 || !rows_host || !final_cost || !status || !best) {
+    g_err = "mpc_batch_replan: times[batch], x0[batch][nq + nv], Delta0[batch], rows_host[batch][iterations][IDTO_TR_ROW], "
+            "final_cost[batch], status[batch] and best are required";
+    return -1;
+  }
+  if (nu < 0 || (nu > 0 && !constrained_dofs)) { g_err = "mpc_batch_replan: bad constraint arguments"; return -1; }
+  if (iterations <= 0) { g_err = "mpc_batch_replan: iterations must be positive"; return -1; }
+  if (c->batch < 2) { g_err = "mpc_batch_replan: serves batches of more than one problem (one controller: idto_hip_tr_solve_fetch)"; return -1; }
+  MpcBatchState* m = c->mpc;
+  MpcTickHook hook{m, times, x0, guess_out, plans_out, (size_t)c->batch * m->L.n * c->nq, (size_t)c->batch * m->L.len()};
+  TrBatchFetch bf{0, {q_out, v_out, tau_out, nullptr, nullptr}, final_cost, status, best, &hook};
+  const int rc = TrSolveBatchFetch(c, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta,
+                                   constrained_dofs, nu, rows_host, Delta_out, &bf);
+  // the plane the store wrote is in force once the tick counted; a loop that timed out, or a call that failed, leaves every plan
+  if (rc == 0 || rc == IDTO_HIP_FACTORIZATION_FAILED) m->cur ^= 1;
+  return rc;
+}
+
 // The batch loop with everything a caller reads afterwards brought back under the loop's one wait, and the best problem
 // chosen on the device (trust_region.h tr_gather_batch_kernel).
 int idto_hip_tr_solve_batch_fetch(idto_hip_ctx* c, int iterations, int scaling_method, int scaling, int normalize_quaternions,
@@ -2854,22 +3104,9 @@ int idto_hip_tr_solve_batch_fetch(idto_hip_ctx* c, int iterations, int scaling_m
     *best = ((f & TR_ELIGIBLE_MASK) == 0 && std::isfinite(final_cost[0])) ? 0 : -1;
     return rc;
   }
-  if (nu > 0 && !(c->con_kkt && idto_host::SolverBlockSize(c->nq + nu, true) <= 30 && c->weights_diagonal)) {
-    g_err = "tr_solve_batch_fetch: these enforced constraints take the child-context route of idto_hip_tr_solve_batch_constrained "
-            "(option con_kkt = 0, nq + nu > 30 or dense cost weights: every problem advanced in a single-problem context of "
-            "its own), which has no gathered fetch: use idto_hip_tr_solve_batch_constrained + idto_hip_get_batch";
-    return -1;
-  }
-  HIP_OK(hipSetDevice(c->device));
-  if (nu > 0)
-    if (int rc = idto_hip_eval_tau(c)) return rc;   // (as idto_hip_tr_solve_batch_constrained: the loop starts from the cost of the resident q)
   TrBatchFetch bf{only_best ? 1 : 0, {q_out, v_out, tau_out, dq_out, w_out}, final_cost, status, best};
-  const int rc = TrSolve(c, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu,
-                         rows_host, Delta_out, nullptr, &bf);
-  // (a return from inside the loop's enqueueing: the initial state words travel from pinned memory of the context, which the
-  // next call rewrites - wait for what is enqueued)
-  if (rc < 0) (void)hipStreamSynchronize(c->stream);
-  return rc;
+  return TrSolveBatchFetch(c, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu,
+                           rows_host, Delta_out, &bf);
 }
 
 #define NCCL_OK(expr)                                                                 \

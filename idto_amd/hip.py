@@ -72,6 +72,12 @@ def lib():
             [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double,
              C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
             + [C.POINTER(C.c_double)] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int)])
+        pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        L.idto_hip_mpc_batch_begin.argtypes = [C.c_void_p, pi, pi, C.c_int]
+        L.idto_hip_mpc_batch_store.argtypes = [C.c_void_p, pd, pd, pd, pd, pd]
+        L.idto_hip_mpc_batch_shift.argtypes = [C.c_void_p, pd, pd, pd, pd]
+        L.idto_hip_mpc_batch_replan.argtypes = ([C.c_void_p, pd, pd, C.c_int, C.c_int, C.c_int, C.c_int, pd, C.c_double, C.c_double,
+                                                 pi, C.c_int, pd, pd, pd, pd, pd, pd, pi, pi, pd, pd])
         L.idto_hip_tr_reject.argtypes = [C.c_void_p]
         L.idto_hip_tr_set_scale_memory.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.idto_hip_tr_set_convergence.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -130,6 +136,7 @@ EXPORTED_SYMBOLS = [
     "idto_hip_solver_status", "idto_hip_create_batch", "idto_hip_create_batch_like", "idto_hip_batch_size", "idto_hip_set_problem_batch",
     "idto_hip_set_q_batch", "idto_hip_gn_step_batch", "idto_hip_get_batch", "idto_hip_get_many", "idto_hip_solver_status_batch",
     "idto_hip_tr_prepare", "idto_hip_tr_trial", "idto_hip_tr_accept", "idto_hip_tr_reject", "idto_hip_tr_set_scale_memory", "idto_hip_tr_set_convergence", "idto_hip_tr_solve", "idto_hip_tr_solve_fetch", "idto_hip_tr_solve_batch", "idto_hip_tr_solve_batch_constrained", "idto_hip_tr_solve_batch_fetch", "idto_hip_set_unactuated_dofs",
+    "idto_hip_mpc_batch_begin", "idto_hip_mpc_batch_store", "idto_hip_mpc_batch_shift", "idto_hip_mpc_batch_replan",
     "idto_hip_rccl_info", "idto_hip_comm_unique_id", "idto_hip_comm_init", "idto_hip_comm_init_all", "idto_hip_comm_destroy",
     "idto_hip_allgather_slab", "idto_hip_gn_step_sharded", "idto_hip_gn_step_multi", "idto_hip_eval_partials_multi",
     "idto_hip_trace_enable", "idto_hip_trace_mark", "idto_hip_trace_dump",
@@ -366,6 +373,45 @@ class HipPath:
             _chk(rc)
         out.update(rows=rows, delta=delta, final_cost=final_cost, status=status, best=best.value, rc=rc)
         return out
+
+    # ---- B model-predictive controllers on a batch context (include/idto_hip.h idto_hip_mpc_batch_*)
+    def mpc_plan_len(self):
+        return 1 + 2 * (self.N + 1) * (self.nq + self.nv + self._mpc_nu)
+
+    def mpc_split_plan(self, plan):
+        """one problem's plan [IDTO_MPC_PLAN_LEN] as a dict: start_time, and y / m [N + 1, dim] of the q, v, u splines"""
+        n, out, o = self.N + 1, dict(start_time=float(plan[0])), 1
+        for name, dim in (("q", self.nq), ("v", self.nv), ("u", self._mpc_nu)):
+            out["y_" + name] = plan[o:o + n * dim].reshape(n, dim)
+            out["m_" + name] = plan[o + n * dim:o + 2 * n * dim].reshape(n, dim)
+            o += 2 * n * dim
+        return out
+
+    def mpc_batch_begin(self, selector, actuated_dofs):
+        sel = np.ascontiguousarray(np.asarray(selector, dtype=np.int32))
+        act = np.ascontiguousarray(np.asarray(actuated_dofs, dtype=np.int32))
+        assert sel.size == self.nq
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        _chk(lib().idto_hip_mpc_batch_begin(self.h, ip(sel), ip(act), int(act.size)))
+        self._mpc_nu = int(act.size)
+
+    def mpc_batch_store(self, q, v, tau, start_times):
+        """the plans of B solutions from the host ([B, N+1, nq], [B, N+1, nv], [B, N, nv], [B]): plans [B, plan_len]"""
+        B, N = self.batch, self.N
+        q, v, tau, t0 = (np.ascontiguousarray(np.asarray(x, dtype=np.float64)) for x in (q, v, tau, start_times))
+        assert q.size == B * (N + 1) * self.nq and v.size == B * (N + 1) * self.nv and tau.size == B * N * self.nv and t0.size == B
+        plans = np.zeros((B, self.mpc_plan_len()))
+        _chk(lib().idto_hip_mpc_batch_store(self.h, dptr(q), dptr(v), dptr(tau), dptr(t0), dptr(plans)))
+        return plans
+
+    def mpc_batch_shift(self, times, x0):
+        """the front half of a tick: (guess [B, N+1, nq], q_nom [B, N+1, nq]) as the device left them"""
+        B = self.batch
+        times, x0 = (np.ascontiguousarray(np.asarray(x, dtype=np.float64)) for x in (times, x0))
+        assert times.size == B and x0.size == B * (self.nq + self.nv)
+        guess, q_nom = np.zeros((B, self.N + 1, self.nq)), np.zeros((B, self.N + 1, self.nq))
+        _chk(lib().idto_hip_mpc_batch_shift(self.h, dptr(times), dptr(x0), dptr(guess), dptr(q_nom)))
+        return guess, q_nom
 
     def tr_set_convergence(self, tolerances=None):
         """[rel_cost, abs_cost, rel_gradient_along_dq, abs_gradient_along_dq, rel_state, abs_state] or None (no checks)"""

@@ -5,6 +5,9 @@ trajectory is shifted for the DoFs marked `q_nom_relative_to_q_init`, the initia
 reset and `SolveFromWarmStart` runs `mpc_iters` iterations from the previous trust-region
 radius.  Drake's LeafSystem plumbing (ports, abstract state) is replaced by plain method calls.
 
+`BatchDeviceModelPredictiveController` is B such controllers of one model whose tick is ONE device pass, waited for once
+(idto::examples::mpc::BatchModelPredictiveController; idto_mpc_batch_* of include/idto_opt.h).
+
 Two implementations of the same shell:
   * `DeviceModelPredictiveController` - the product: the C++ class of include/idto/examples/mpc_controller.h inside
     libidto_opt.so through the C-ABI (idto_mpc_* of include/idto_opt.h);
@@ -190,6 +193,163 @@ class DeviceModelPredictiveController:
         u = np.zeros(self.nu)
         self._chk(self._O.lib().idto_mpc_control(self._h, float(t), self._O.dptr(u)))
         return u
+
+
+    def last_stats(self):
+        """(TrajectoryOptimizerStats of the last update's solve, the trust-region radius the next update starts from)"""
+        O, C = self._O, self._C
+        st = O.TrajectoryOptimizerStats(max(self.opt.params().max_iterations, 1))
+        r = C.c_double()
+        self._chk(O.lib().idto_mpc_stats(self._h, C.byref(st.c), C.byref(r)))
+        return st, r.value
+
+
+class BatchDeviceModelPredictiveController:
+    """idto::examples::mpc::BatchModelPredictiveController of libidto_opt.so (include/idto_opt.h idto_mpc_batch_*): B
+    controllers of `optimizer`'s model, horizon and parameters - controller b equals a DeviceModelPredictiveController on
+    an optimizer of its own made with problems[b] - whose tick is enqueued on the device at once and waited for once.
+    Every controller re-plans in every tick.  Configurations the device's batch loop does not serve (linesearch, adaptive
+    scalings, dense weights, several devices, verbose, the debug switches, the dense linear solver, the child-context
+    constraint route, B < 2) raise RuntimeError with the configuration's name: use B single controllers."""
+
+    def __init__(self, optimizer, warm_start_solutions, actuated=None, q_nom_relative_to_q_init=None, problems=None,
+                 strict=True):
+        """strict: update() raises when a controller's re-plan failed or the tick did not count, as
+        DeviceModelPredictiveController's does; update(strict=...) overrides it for one tick."""
+        import ctypes as C
+        from . import optimizer as O
+        from .model import CProblem
+        self.strict = bool(strict)
+        self._O, self._C = O, C
+        self.opt = optimizer
+        prob = optimizer.prob()
+        self.N, self.nq, self.nv = optimizer.num_steps(), len(prob.q_init), len(prob.v_init)
+        self.B = B = len(warm_start_solutions)
+        q = O._d(np.array([np.asarray(w.q, float)[:self.N + 1] for w in warm_start_solutions]).reshape(B, self.N + 1, self.nq))
+        v = O._d(np.array([np.asarray(w.v, float)[:self.N + 1] for w in warm_start_solutions]).reshape(B, self.N + 1, self.nv))
+        tau = O._d(np.array([np.asarray(w.tau, float)[:self.N] for w in warm_start_solutions]).reshape(B, self.N, self.nv))
+        act = None if actuated is None else np.ascontiguousarray(np.asarray(actuated, dtype=np.int32))
+        sel = q_nom_relative_to_q_init
+        if sel is None:
+            sel = optimizer.params().q_nom_relative_to_q_init
+        sel = None if sel is None or len(sel) == 0 else np.ascontiguousarray(np.asarray(sel, dtype=np.int32))
+        ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
+        carr, keep = None, []
+        if problems is not None:
+            if len(problems) != B:
+                raise RuntimeError(f"one problem per controller ({B} warm starts, {len(problems)} problems)")
+            carr = (CProblem * B)()
+            for b, pr in enumerate(problems):
+                carr[b], k = pr.to_c()
+                keep.append(k)
+        h = C.c_void_p()
+        self._chk(O.lib().idto_mpc_batch_create(optimizer._h, B, carr, O.dptr(q), O.dptr(v), O.dptr(tau), ip(act), ip(sel), C.byref(h)))
+        self._h = h
+        self.nu = O.lib().idto_mpc_batch_num_actuators(self._h)
+        self.last_flags = [0] * B
+        self.last_radii = np.full(B, float(optimizer.params().Delta0))
+        self.last_stats = None
+
+    def _chk(self, rc):
+        if rc:
+            raise RuntimeError(self._O.lib().idto_opt_last_error().decode())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._O.lib().idto_mpc_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def _buffers(self):
+        """the tick's input / output buffers and their ctypes pointers, made once (as DeviceModelPredictiveController's)"""
+        O, C = self._O, self._C
+        b = getattr(self, "_buf", None)
+        if b is None:
+            B, N, nq, nv = self.B, self.N, self.nq, self.nv
+            times, x0 = np.zeros(B), np.zeros((B, nq + nv))
+            g, q = np.zeros((B, N + 1, nq)), np.zeros((B, N + 1, nq))
+            v, tau = np.zeros((B, N + 1, nv)), np.zeros((B, N, nv))
+            stats = [O.TrajectoryOptimizerStats(max(self.opt.params().max_iterations, 1)) for _ in range(B)]
+            cst = (O.CStats * B)()
+            for i in range(B):
+                cst[i] = stats[i].c
+            flags, radii, ok = (C.c_int * B)(), np.zeros(B), C.c_int()
+            ptrs = tuple(O.dptr(a) for a in (times, x0, g, q, v, tau)) + (cst, flags, O.dptr(radii), C.byref(ok))
+            b = self._buf = (times, x0, g, q, v, tau, stats, cst, flags, radii, ok, ptrs, O.lib().idto_mpc_batch_update)
+        return b
+
+    def update(self, times, x0s, copy=True, strict=None):
+        """UpdateAll: controller b re-plans at times[b] from x0s[b] = [q0; v0].  Returns (q_guess, q, v, tau), each
+        [B, ...]; a controller whose re-plan failed keeps its previous plan and solution.  strict: raise when any
+        controller's re-plan failed or the tick did not count (strict=False: `last_flags[b] == 2` / `last_tick_ok`
+        say so, `error(b)` why).  copy=False: the controllers' own output buffers, overwritten by the next update."""
+        strict = self.strict if strict is None else bool(strict)
+        times_b, x0_b, g, q, v, tau, stats, cst, flags, radii, ok, ptrs, fn = self._buffers()
+        times_b[:] = times
+        x0_b[:] = np.asarray(x0s, float).reshape(self.B, self.nq + self.nv)
+        if fn(self._h, *ptrs):
+            raise RuntimeError(self._O.lib().idto_opt_last_error().decode())
+        for b in range(self.B):
+            stats[b].c = cst[b]
+        self.last_stats = stats
+        self.last_flags = list(flags)
+        self.last_radii = radii.copy()
+        self.last_tick_ok = bool(ok.value)
+        if strict and not self.last_tick_ok:
+            raise RuntimeError("MPC tick: " + self.error(-1) + "; every controller keeps its plan")
+        if strict and any(f == 2 for f in self.last_flags):
+            bad = [b for b, f in enumerate(self.last_flags) if f == 2]
+            raise RuntimeError("MPC tick: the re-plan of controller(s) %s failed (%s); their previous plans stay in force "
+                               "(strict=False returns them, last_flags[b] == 2 says so)" % (bad, self.error(bad[0])))
+        return (g.copy(), q.copy(), v.copy(), tau.copy()) if copy else (g, q, v, tau)
+
+    def error(self, b):
+        return self._O.lib().idto_mpc_batch_error(self._h, int(b)).decode()
+
+    def start_time(self, b):
+        return self._O.lib().idto_mpc_batch_start_time(self._h, int(b))
+
+    def flag(self, b):
+        return self._O.lib().idto_mpc_batch_flag(self._h, int(b))
+
+    def state(self, b, t):
+        x = np.zeros(self.nq + self.nv)
+        self._chk(self._O.lib().idto_mpc_batch_state(self._h, int(b), float(t), self._O.dptr(x)))
+        return x
+
+    def control(self, b, t):
+        u = np.zeros(self.nu)
+        self._chk(self._O.lib().idto_mpc_batch_control(self._h, int(b), float(t), self._O.dptr(u)))
+        return u
+
+
+def spline_fit(breaks, knots):
+    """csrc/mpc_spline.h on the host: the knot derivatives [n, dim] of the not-a-knot cubic through `knots` [n, dim]"""
+    from . import optimizer as O
+    breaks, knots = O._d(breaks), O._d(knots)
+    n, dim = knots.shape
+    m = np.zeros((n, dim))
+    if O.lib().idto_mpc_spline_fit(O.dptr(breaks), O.dptr(knots), n, dim, O.dptr(m)):
+        raise RuntimeError(O.lib().idto_opt_last_error().decode())
+    return m
+
+
+def shift_reference(breaks, y_q, m_q, start_time, time, time_step, q0, selector, q_nom):
+    """csrc/mpc_spline.h on the host: (guess [n, nq], shifted q_nom [n, nq]) of one controller's tick"""
+    import ctypes as C
+    from . import optimizer as O
+    breaks, y_q, m_q, q0 = O._d(breaks), O._d(y_q), O._d(m_q), O._d(q0)
+    n, nq = y_q.shape
+    q_nom = np.array(q_nom, dtype=np.float64).reshape(n, nq).copy()
+    sel = np.ascontiguousarray(np.asarray(selector, dtype=np.int32))
+    guess = np.zeros((n, nq))
+    if O.lib().idto_mpc_shift_reference(O.dptr(breaks), O.dptr(y_q), O.dptr(m_q), n, nq, float(start_time), float(time),
+                                        float(time_step), O.dptr(q0), sel.ctypes.data_as(C.POINTER(C.c_int)), O.dptr(q_nom),
+                                        O.dptr(guess)):
+        raise RuntimeError(O.lib().idto_opt_last_error().decode())
+    return guess, q_nom
 
 
 def spline_eval(breaks, knots, times):

@@ -69,6 +69,20 @@ def lib():
         L.idto_mpc_start_time.argtypes = [C.c_void_p]
         L.idto_mpc_start_time.restype = C.c_double
         L.idto_mpc_spline_eval.argtypes = [P, P, C.c_int, C.c_int, P, C.c_int, P]
+        L.idto_mpc_stats.argtypes = [C.c_void_p, C.POINTER(CStats), P]
+        L.idto_mpc_batch_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(CProblem), P, P, P, I, I, C.POINTER(C.c_void_p)]
+        L.idto_mpc_batch_destroy.argtypes = [C.c_void_p]
+        L.idto_mpc_batch_num_actuators.argtypes = [C.c_void_p]
+        L.idto_mpc_batch_update.argtypes = [C.c_void_p, P, P, P, P, P, P, C.POINTER(CStats), I, P, I]
+        L.idto_mpc_batch_state.argtypes = [C.c_void_p, C.c_int, C.c_double, P]
+        L.idto_mpc_batch_control.argtypes = [C.c_void_p, C.c_int, C.c_double, P]
+        L.idto_mpc_batch_start_time.argtypes = [C.c_void_p, C.c_int]
+        L.idto_mpc_batch_start_time.restype = C.c_double
+        L.idto_mpc_batch_flag.argtypes = [C.c_void_p, C.c_int]
+        L.idto_mpc_batch_error.argtypes = [C.c_void_p, C.c_int]
+        L.idto_mpc_batch_error.restype = C.c_char_p
+        L.idto_mpc_spline_fit.argtypes = [P, P, C.c_int, C.c_int, P]
+        L.idto_mpc_shift_reference.argtypes = [P, P, P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, P, I, P, P]
         _lib = L
     return _lib
 
@@ -81,7 +95,10 @@ EXPORTED_SYMBOLS = [
     "idto_opt_solve_batch", "idto_opt_batch_error", "idto_opt_last_batch_route",
 ]
 MPC_SYMBOLS = ["idto_mpc_create", "idto_mpc_destroy", "idto_mpc_num_actuators", "idto_mpc_update", "idto_mpc_state",
-               "idto_mpc_control", "idto_mpc_start_time", "idto_mpc_spline_eval"]
+               "idto_mpc_control", "idto_mpc_start_time", "idto_mpc_spline_eval", "idto_mpc_stats",
+               "idto_mpc_batch_create", "idto_mpc_batch_destroy", "idto_mpc_batch_num_actuators", "idto_mpc_batch_update",
+               "idto_mpc_batch_state", "idto_mpc_batch_control", "idto_mpc_batch_start_time", "idto_mpc_batch_flag",
+               "idto_mpc_batch_error", "idto_mpc_spline_fit", "idto_mpc_shift_reference"]
 
 
 def _d(a):

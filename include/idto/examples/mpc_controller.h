@@ -13,6 +13,7 @@
 #pragma once
 
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "idto/optimizer/trajectory_optimizer.h"
@@ -40,6 +41,8 @@ class PiecewiseCubic {
   // (its storage is kept: no allocation when the sizes repeat)
   void Assign(const std::vector<double>& breaks, const std::vector<VectorXd>& knots, int count);
   void AssignFlat(const std::vector<double>& breaks, const double* knots, int dim);
+  // values and knot derivatives [break][dim] that were fitted elsewhere (csrc/mpc_spline.h on the device: the batch controller)
+  void AssignFitted(const std::vector<double>& breaks, const double* y, const double* m, int dim);
   bool empty() const { return t_.empty(); }
   double start_time() const { return t_.front(); }
   double end_time() const { return t_.back(); }
@@ -52,7 +55,7 @@ class PiecewiseCubic {
   int dim_ = 0;
   std::vector<double> t_;
   std::vector<double> y_, m_;   // [knot][dim]: values and first derivatives at the knots
-  std::vector<double> h_, lo_, di_, up_, B_;   // work space of Fit
+  std::vector<double> B_;       // work space of Fit
   void Fit(const std::vector<double>& breaks);
 };
 
@@ -78,6 +81,7 @@ class ModelPredictiveController {
   double replan_period() const { return replan_period_; }
   int num_actuators() const { return nu_; }
   const StoredTrajectory& stored_trajectory() const { return stored_; }
+  double trust_region_radius() const { return warm_start_->Delta; }   // what the next re-plan's loop starts from
   const TrajectoryOptimizerStats<double>& last_stats() const { return stats_; }
   const TrajectoryOptimizerSolution<double>& last_solution() const { return solution_; }
   // what the last UpdateAbstractState's SolveFromWarmStart returned; kFactorizationFailed: the stored trajectory and
@@ -111,6 +115,80 @@ class ModelPredictiveController {
   std::vector<VectorXd> guess_scratch_, q_nom_scratch_, v_nom_scratch_;   // (UpdateAbstractState's work trajectories: no allocation per re-plan)
   double replan_period_;
   std::vector<bool> selector_override_;
+};
+
+// B ModelPredictiveControllers of one model, horizon and parameter set (a parallel simulation, a multi-start MPC) whose
+// whole tick - the time-shifted guesses, the shifted nominal trajectories, the new initial conditions, the warm-started
+// trust-region loops and the new plans as splines - is enqueued on the device at once and waited for once
+// (include/idto_hip.h idto_hip_mpc_batch_replan; csrc/mpc_batch.h).  No counterpart in the reference, whose caller would
+// loop over B controllers.  Controller b's guess, solution, plan, flag, statistics and radius are those of a
+// ModelPredictiveController on an optimizer of its own with problem b (bit for bit where a batch entry equals its single
+// Solve: TrajectoryOptimizer::SolveBatch), because both run the arithmetic of csrc/mpc_spline.h.
+//
+// EVERY controller re-plans in EVERY tick.  A mask of idle controllers would need an "idle from the start" state in the
+// trust-region kernels; that is out of scope here - a caller with idle controllers passes them their current time and state.
+//
+// What the device's batch loop does not serve makes the constructor throw std::invalid_argument with the configuration's
+// name, before any device work: method = kLinesearch, the adaptive scalings, dense weights, several devices, verbose, the
+// debug switches, linear_solver = kDenseLdlt, the child-context constraint route (enforced constraints with nq + nu > 30),
+// B < 2.  There is no entry-by-entry fallback - one optimizer cannot hold B cumulative nominal trajectories: use B
+// ModelPredictiveControllers, each on an optimizer of its own.
+//
+// At run time:
+//   * controller b's factorisation fails (status bit 32; also a dogleg step that is not finite, bits 1 | 2, and a step that
+//     is not a descent direction, bit 4): last_flag(b) == kFactorizationFailed, last_error(b) says which, and its plan,
+//     last_solution(b) and radius stay the previous re-plan's - as the single controller keeps its own;
+//   * controller b meets a singular constraint Schur complement (bit 8), where the single controller would finish the solve
+//     in the host loop: reported as a failure of that controller in the same way; its plan stays;
+//   * the loop's workgroups time out on a shared device: UpdateAll returns false, last_tick_error() says so, every
+//     controller's plan, solution and radius stay, flags are kFactorizationFailed; the next tick proceeds (the context
+//     has stepped down to a solver variant with fewer co-resident workgroups; if the iteration kernel itself timed out,
+//     the next UpdateAll throws what idto_hip_tr_solve reports).
+class BatchModelPredictiveController {
+ public:
+  // `optimizer` (not owned; its model, horizon and parameters serve every controller), one warm-start solution per
+  // controller; `problems`: one per controller (SolveBatch's rule: the optimizer's num_steps and sizes), null: the
+  // optimizer's own for every controller.  `actuated`, `q_nom_relative_to_q_init`: as ModelPredictiveController's.
+  BatchModelPredictiveController(TrajectoryOptimizer<double>* optimizer,
+                                 const std::vector<TrajectoryOptimizerSolution<double>>& warm_start_solutions,
+                                 const std::vector<int>& actuated, const std::vector<bool>& q_nom_relative_to_q_init = {},
+                                 const std::vector<ProblemDefinition>* problems = nullptr);
+  ~BatchModelPredictiveController();
+  BatchModelPredictiveController(const BatchModelPredictiveController&) = delete;
+  BatchModelPredictiveController& operator=(const BatchModelPredictiveController&) = delete;
+
+  int num_controllers() const { return B_; }
+  int num_actuators() const { return nu_; }
+  // UpdateAbstractState of every controller: controller b at times[b] from the state estimate x0s[b] = [q0; v0].
+  // false: the tick did not count (last_tick_error()).
+  bool UpdateAll(const std::vector<double>& times, const std::vector<VectorXd>& x0s);
+  bool UpdateAll(const double* times, const double* x0s);   // [B], [B][nq + nv]
+  const std::string& last_tick_error() const { return tick_error_; }
+
+  const StoredTrajectory& stored_trajectory(int b) const { return stored_[b]; }   // (Interpolator works on it as before)
+  optimizer::SolverFlag last_flag(int b) const { return flags_[b]; }
+  const std::string& last_error(int b) const { return errors_[b]; }
+  const TrajectoryOptimizerStats<double>& last_stats(int b) const { return stats_[b]; }
+  const TrajectoryOptimizerSolution<double>& last_solution(int b) const { return solutions_[b]; }
+  const std::vector<VectorXd>& last_guess(int b) const { return guesses_[b]; }
+  double trust_region_radius(int b) const { return Delta_[b]; }   // what the next tick starts controller b's loop from
+
+ private:
+  void AdoptPlan(int b, const double* plan);
+  TrajectoryOptimizer<double>* optimizer_;
+  idto_hip_ctx* ctx_ = nullptr;             // the controllers' batch context (owned)
+  TrajectoryOptimizer<double>::BatchLoopArgs loop_{};
+  int B_ = 0, N_ = 0, nq_ = 0, nv_ = 0, nu_ = 0;
+  std::vector<double> breaks_;
+  std::vector<StoredTrajectory> stored_;
+  std::vector<optimizer::SolverFlag> flags_;
+  std::vector<std::string> errors_;
+  std::vector<TrajectoryOptimizerStats<double>> stats_;
+  std::vector<TrajectoryOptimizerSolution<double>> solutions_;
+  std::vector<std::vector<VectorXd>> guesses_;
+  std::vector<double> Delta_, Delta_out_, rows_, q_, v_, tau_, guess_, plans_, final_cost_, x0_;
+  std::vector<int> status_;
+  std::string tick_error_;
 };
 
 // reference examples/mpc_controller.h:155-214: x(t) = [q(t); v(t)] and u(t) of a stored trajectory

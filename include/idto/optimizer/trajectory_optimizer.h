@@ -125,6 +125,23 @@ class TrajectoryOptimizer<double> {
   // how the last SolveBatch ran: 1 the batch loop, 0 entry by entry (tests and tools/solve_batch_bench.py ask)
   int last_batch_route() const { return last_batch_route_; }
 
+  // ---- what examples::mpc::BatchModelPredictiveController (mpc_controller.h) builds on: the device's batch loop for B
+  // problems of this optimizer on a batch context of the caller's own.
+  // Why B controllers with these problems cannot take the batch loop - the name of the configuration it does not serve
+  // (SolveBatch's rule, without its entry-by-entry fallback) - or "" when they can.  No device work.
+  std::string BatchLoopRefusal(int B, const std::vector<const ProblemDefinition*>& probs) const;
+  // A batch context for `probs` (one entry per problem; SolveBatch's stays its own).  The caller destroys it: idto_hip_destroy.
+  idto_hip_ctx* CreateBatchContext(const std::vector<const ProblemDefinition*>& probs) const;
+  // What SolveBatch sets on a batch context in front of the loop (the |h| column's degrees of freedom, the convergence
+  // criteria), done for `ctx`, and the arguments it hands idto_hip_tr_solve_batch_fetch.
+  struct BatchLoopArgs {
+    int iterations, scaling_method, scaling, normalize_quaternions;
+    double Delta_max, eta;
+    const int* constrained_dofs;   // (this optimizer's storage)
+    int nu;
+  };
+  BatchLoopArgs PrepareBatchLoop(idto_hip_ctx* ctx) const;
+
   const std::vector<VectorXd>& EvalV(const TrajectoryOptimizerState<T>& state) const;
   const std::vector<VectorXd>& EvalA(const TrajectoryOptimizerState<T>& state) const;
   const std::vector<VectorXd>& EvalTau(const TrajectoryOptimizerState<T>& state) const;

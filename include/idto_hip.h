@@ -410,6 +410,45 @@ int idto_hip_tr_solve_batch_fetch(idto_hip_ctx* ctx, int iterations, int scaling
                                   double* rows_host, double* Delta_out, int only_best, double* q_out, double* v_out,
                                   double* tau_out, double* dq_out, double* w_out, double* final_cost, int* status, int* best);
 
+/* ---- B model-predictive controllers on a batch context (csrc/mpc_batch.h; the shell of
+ * include/idto/examples/mpc_controller.h for every problem of the batch at once).  The context keeps every problem's plan
+ * - the splines of q, v and u = the actuated components of tau over the n = num_steps + 1 knots i * time_step, and the
+ * time the plan was made at - on the device, in an allocation of its own made by idto_hip_mpc_batch_begin.  A plan as the
+ * host sees it is IDTO_MPC_PLAN_LEN(n, nq, nv, nu) doubles:
+ *   [start_time | y_q[n][nq] | m_q[n][nq] | y_v[n][nv] | m_v[n][nv] | y_u[n][nu] | m_u[n][nu]]
+ * values y and knot derivatives m of the not-a-knot cubic (csrc/mpc_spline.h: the arithmetic PiecewiseCubic runs on the
+ * host, so the numbers are those of B single controllers), enough to interpolate x(t), u(t) without a device call.
+ * These calls refuse, by name, a context with child contexts (idto_hip_tr_solve_batch_constrained's Schur-complement
+ * route made them): the shift changes q_nom, v_init and q on the device only, and keeps the context's host copies of the
+ * problems - which only that route reads - in step, but not the children. */
+#define IDTO_MPC_PLAN_LEN(n, nq, nv, nu) (1 + 2 * (size_t)(n) * ((nq) + (nv) + (nu)))
+/* selector[nq]: q_nom_relative_to_q_init (non-zero: q_nom of that position moves with the initial condition);
+ * actuated_dofs[nu]: the velocity index of every control component, 1 <= nu <= nv.  May be called again (new storage). */
+int idto_hip_mpc_batch_begin(idto_hip_ctx* ctx, const int* selector, const int* actuated_dofs, int nu);
+/* StoreOptimizerSolution for every problem: q[B][(N+1)*nq], v[B][(N+1)*nv], tau[B][N*nv], start_times[B] from the host
+ * become the stored plans; plans_out[B][IDTO_MPC_PLAN_LEN] (may be NULL) receives them.  Waits. */
+int idto_hip_mpc_batch_store(idto_hip_ctx* ctx, const double* q, const double* v, const double* tau, const double* start_times,
+                             double* plans_out);
+/* The front half of a tick alone: times[B], x0[B][nq + nv] = [q0; v0] go to the device in one copy, mpc_shift_kernel
+ * writes every problem's guess (row i = the stored q-spline at times[b] - start_time[b] + i * time_step, row 0 = q0) as
+ * the resident q, v_init = v0 and q_nom shifted for the selected positions; then guess_out[B][(N+1)*nq] and
+ * q_nom_out[B][(N+1)*nq] (either may be NULL) are fetched.  Waits.  The context is left as idto_hip_set_q_batch +
+ * idto_hip_set_problem_batch leave it. */
+int idto_hip_mpc_batch_shift(idto_hip_ctx* ctx, const double* times, const double* x0, double* guess_out, double* q_nom_out);
+/* One tick, enqueued at once and waited for once: the copy of times and x0, the shift, idto_hip_eval_tau, the loop of
+ * idto_hip_tr_solve_batch_fetch (its arguments, only_best = 0), mpc_store_kernel, one copy back.  Delta0[b]: the radius
+ * the previous tick returned in Delta_out[b] (the first tick: the solver parameters' Delta0).  A problem whose status
+ * carries one of the bits 1 | 2 | 4 | 8 | 32 keeps its plan; the others' plans are the splines through the loop's final
+ * q, v and tau, with start_time = times[b].  guess_out[B][(N+1)*nq] (may be NULL): the guesses the loop started from;
+ * plans_out[B][IDTO_MPC_PLAN_LEN] (may be NULL): every problem's plan after the tick (a failed problem's: its old one).
+ * Return value as idto_hip_tr_solve_batch_fetch; after IDTO_HIP_SOLVER_TIMEOUT or a negative value every stored plan is
+ * the one from before the tick. */
+int idto_hip_mpc_batch_replan(idto_hip_ctx* ctx, const double* times, const double* x0, int iterations, int scaling_method,
+                              int scaling, int normalize_quaternions, const double* Delta0, double Delta_max, double eta,
+                              const int* constrained_dofs, int nu, double* rows_host, double* Delta_out, double* q_out,
+                              double* v_out, double* tau_out, double* final_cost, int* status, int* best, double* guess_out,
+                              double* plans_out);
+
 /* Options: "gradients_method" = 0 forward differences (default), 1 / 2 central differences of
  * 2nd / 4th order (SolverParameters::gradients_method, reference solver_parameters.h:26-50,
  * trajectory_optimizer.cc:565-885); 3 (autodiff) is refused.  "reference_solver" = 1 selects the bit-exact restatement of the reference's

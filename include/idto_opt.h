@@ -105,6 +105,44 @@ double idto_mpc_start_time(const idto_mpc* mpc);
  * `dim` components at `breaks`, evaluated at nt times (clamped to the breaks' range); out: nt*dim. */
 int idto_mpc_spline_eval(const double* breaks, const double* knots, int n, int dim, const double* times, int nt, double* out);
 
+/* the statistics of the last idto_mpc_update's solve, and the trust-region radius the next one starts from */
+int idto_mpc_stats(const idto_mpc* mpc, idto_stats_t* stats, double* radius);
+
+/* ---- B controllers of one model, horizon and parameter set whose tick is one device pass, waited for once
+ * (idto::examples::mpc::BatchModelPredictiveController, include/idto/examples/mpc_controller.h; the device side:
+ * include/idto_hip.h idto_hip_mpc_batch_*).  Controller b equals an idto_mpc on an optimizer of its own created with
+ * problems[b].  Every controller re-plans in every tick.  idto_mpc_batch_create fails, naming the configuration, for what
+ * the device's batch loop does not serve (method = linesearch, adaptive scalings, dense weights, several devices, verbose,
+ * the debug switches, linear_solver = dense LDL^T, the child-context constraint route, B < 2): use B idto_mpc. */
+typedef struct idto_mpc_batch idto_mpc_batch;
+/* problems: [B] (NULL: the optimizer's own for every controller); warm_q / warm_v / warm_tau: [B][...] as idto_mpc_create's;
+ * actuated, q_nom_relative_to_q_init: as idto_mpc_create's, shared by the controllers.  `opt` must outlive the controllers. */
+int idto_mpc_batch_create(idto_opt* opt, int B, const idto_problem_t* problems, const double* warm_q, const double* warm_v,
+                          const double* warm_tau, const int* actuated, const int* q_nom_relative_to_q_init, idto_mpc_batch** out);
+void idto_mpc_batch_destroy(idto_mpc_batch* mpc);
+int idto_mpc_batch_num_actuators(const idto_mpc_batch* mpc);
+/* One tick: controller b re-plans at times[b] from x0[b] = [q0; v0] (x0: [B][nq + nv]).  Outputs (any may be NULL), [B][...]:
+ * the guesses used, the solutions (a controller that failed: its previous one), stats (B blocks), flags (SolverFlag;
+ * kFactorizationFailed = 2: controller b keeps its previous plan, idto_mpc_batch_error(mpc, b) says why), radii (what the
+ * next tick starts from), *tick_ok (0: the loop timed out on the device, nothing of this tick counts, every plan stays;
+ * idto_mpc_batch_error(mpc, -1)). */
+int idto_mpc_batch_update(idto_mpc_batch* mpc, const double* times, const double* x0, double* q_guess, double* sol_q, double* sol_v,
+                          double* sol_tau, idto_stats_t* stats, int* flags, double* radii, int* tick_ok);
+/* Interpolator on controller b's stored trajectory (host only: the plans come back with the tick) */
+int idto_mpc_batch_state(const idto_mpc_batch* mpc, int b, double time, double* x);
+int idto_mpc_batch_control(const idto_mpc_batch* mpc, int b, double time, double* u);
+double idto_mpc_batch_start_time(const idto_mpc_batch* mpc, int b);
+int idto_mpc_batch_flag(const idto_mpc_batch* mpc, int b);
+const char* idto_mpc_batch_error(const idto_mpc_batch* mpc, int b);   /* b = -1: the last tick's own */
+
+/* csrc/mpc_spline.h on the host (exported for the tests that hold the device's kernels to it): the knot derivatives
+ * m_out[n][dim] of the not-a-knot cubic through knots[n][dim] at `breaks`; and the front half of a controller's tick - the
+ * guess [n][nq] from the stored q-spline (y_q, m_q) made at start_time, evaluated for the tick at `time` with row 0 = q0,
+ * and q_nom[n][nq] shifted in place for the selected positions. */
+int idto_mpc_spline_fit(const double* breaks, const double* knots, int n, int dim, double* m_out);
+int idto_mpc_shift_reference(const double* breaks, const double* y_q, const double* m_q, int n, int nq, double start_time, double time,
+                             double time_step, const double* q0, const int* selector, double* q_nom, double* guess_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -661,6 +661,15 @@ int TimeDrain(idto_hip_ctx* c) {
   return 0;
 }
 
+// pinned staging that grows on demand (the superseded, smaller buffer is freed)
+int EnsurePinned(double** p, size_t* cap, size_t count) {
+  if (*cap >= count) return 0;
+  if (*p) (void)hipHostFree(*p);
+  *p = nullptr; *cap = 0;
+  HIP_OK(hipHostMalloc((void**)p, count * sizeof(double), hipHostMallocDefault));
+  *cap = count;
+  return 0;
+}
 int EnsureStage(idto_hip_ctx* c, size_t count) {
   if (count > c->stage_count) {  // staging buffers grow on demand and are reused
     double *a = nullptr, *b = nullptr;
@@ -1275,12 +1284,7 @@ static int LsSolve(idto_hip_ctx* c, int iterations, int method, int max_ls, int 
     c->ls_rows_cap = iterations;
   }
   const size_t nrow = (size_t)iterations * LSR_COUNT, nqa = (size_t)n, nva = (size_t)(N + 1) * nv, nta = (size_t)N * nv;
-  if (c->ls_fetch_cap < nrow + nqa + nva + nta) {
-    if (c->ls_fetch_pin) (void)hipHostFree(c->ls_fetch_pin);
-    c->ls_fetch_pin = nullptr; c->ls_fetch_cap = 0;
-    HIP_OK(hipHostMalloc((void**)&c->ls_fetch_pin, (nrow + nqa + nva + nta) * sizeof(double), hipHostMallocDefault));
-    c->ls_fetch_cap = nrow + nqa + nva + nta;
-  }
+  if (int rc = EnsurePinned(&c->ls_fetch_pin, &c->ls_fetch_cap, nrow + nqa + nva + nta)) return rc;
   if (!c->compute_units) {
     HIP_OK(hipDeviceGetAttribute(&c->compute_units, hipDeviceAttributeMultiprocessorCount, c->device));
   }
@@ -2318,6 +2322,7 @@ static int MakeKkt(idto_hip_ctx* c, int nu) {
 }
 
 static bool AsmInSolver(const idto_hip_ctx* c, SolverPlan* p);
+namespace {
 // idto_hip_tr_solve_batch_fetch's outputs beyond rows and radii (a batch of more than one problem)
 struct TrBatchFetch {
   int only_best;
@@ -2325,475 +2330,466 @@ struct TrBatchFetch {
   double* final_cost; int* status; int* best;
   const MpcTickHook* mpc = nullptr;   // idto_hip_mpc_batch_replan: the store behind the gather, its doubles behind the fetch's
 };
-// the doubles idto_hip_tr_solve_batch_fetch packs for the host
-static size_t BatchFetchDoubles(const idto_hip_ctx* c, int iterations, bool only_best) {
-  const size_t nqa = (size_t)(c->N + 1) * c->nq, nva = (size_t)(c->N + 1) * c->nv, nta = (size_t)c->N * c->nv;
-  return tr_gather_batch_header(c->batch) + (size_t)c->batch * (TRS_COUNT + (size_t)iterations * TRR_COUNT) +
-         (only_best ? 1 : (size_t)c->batch) * (3 * nqa + nva + nta);
-}
-// the fetches' staging on the device and its pinned mirror, grown on demand
-static int EnsureFetch(idto_hip_ctx* c, size_t total) {
-  if (c->fetch_cap >= total) return 0;
-  Release(c, &c->fetch_dev);
-  if (c->fetch_pin) (void)hipHostFree(c->fetch_pin);
-  c->fetch_pin = nullptr; c->fetch_cap = 0;
-  if (Alloc(c, total, &c->fetch_dev)) return -2;
-  HIP_OK(hipHostMalloc((void**)&c->fetch_pin, total * sizeof(double), hipHostMallocDefault));
-  c->fetch_cap = total;
+// One call of the device-resident trust-region loop: its parameters and where the results go.
+// Delta0s / Delta_out: one radius per problem of the context; rows_host: [batch][iterations][TRR_COUNT]
+struct TrRequest {
+  int iterations, scaling_method, scaling, normalize_quaternions;
+  const double* Delta0s; double Delta_max, eta; const int* constrained_dofs; int nu;
+  double* rows_host; double* Delta_out;
+  double* const* fetch = nullptr;         // idto_hip_tr_solve_fetch: q, v, tau, dq, w of the one problem; any may be null
+  const TrBatchFetch* bfetch = nullptr;   // idto_hip_tr_solve_batch_fetch
+};
+// What is loop-invariant of the way through TrSolve
+struct TrRoute {
+  bool use_kkt, lookahead, adaptive, tr_small, tr_fold_fits;
+  SolverPlan small_plan;   // of the system the small models' launch solves: H's, or the KKT context's
+  int passes; TrConvergence conv;
+};
+inline size_t TrRowDoubles(const TrRequest& rq) { return (size_t)rq.iterations * TRR_COUNT; }   // of one problem's rows
+// The fetching entry points' argument checks, `who` the message's prefix; missing: the required arrays when one is null.  (TrPlanRoute keeps its two, tr_resident_ok between them.)
+int TrCheckArgs(const char* who, const TrRequest& rq, const char* missing) {
+  if (missing) { g_err = std::string(who) + ": " + missing + " are required"; return -1; }
+  if (rq.nu < 0 || (rq.nu > 0 && !rq.constrained_dofs)) { g_err = std::string(who) + ": bad constraint arguments"; return -1; }
+  if (rq.iterations <= 0) { g_err = std::string(who) + ": iterations must be positive"; return -1; }
   return 0;
 }
-// Delta0s / Delta_out: one radius per problem of the context; rows_host: [batch][iterations][TRR_COUNT]
-static int TrSolve(idto_hip_ctx* c, int iterations, int scaling_method, int scaling, int normalize_quaternions,
-                   const double* Delta0s, double Delta_max, double eta, const int* constrained_dofs, int nu,
-                   double* rows_host, double* Delta_out, double* const* fetch = nullptr, const TrBatchFetch* bfetch = nullptr) {
-  HIP_OK(hipSetDevice(c->device));
-  const int B = c->batch;
-  if (bfetch && B == 1) { g_err = "tr_solve: the batch fetch serves batches of more than one problem"; return -1; }
+// Do these enforced constraints take the banded KKT step (kkt.h), the one route that serves a batch?  Blocks of nq + nu up to
+// the 30 x 30 instantiation of the two-workgroup factorisation: allegro's 23 + 6, N = 60, 0.523 against 0.665 ms per iteration with
+// the Schur-complement chain; the 32 x 32 one needs a third elimination wavefront and spills: 442 against 245 us at N = 20.
+bool TrKktRoute(const idto_hip_ctx* c, int nu) {
+  return nu > 0 && c->con_kkt && idto_host::SolverBlockSize(c->nq + nu, true) <= 30 && c->weights_diagonal;
+}
+// the fetches' staging on the device and its pinned mirror, grown on demand
+int EnsureFetch(idto_hip_ctx* c, size_t total) {
+  if (c->fetch_cap >= total) return 0;
+  Release(c, &c->fetch_dev);
+  c->fetch_cap = 0;   // (both or neither: the pinned mirror goes with it, in EnsurePinned)
+  if (Alloc(c, total, &c->fetch_dev)) return -2;
+  return EnsurePinned(&c->fetch_pin, &c->fetch_cap, total);
+}
+// where the batch fetch's parts lie in that staging (tr_fetch.h)
+TrFetchLayout BatchFetchLayout(const idto_hip_ctx* c, const TrRequest& rq) {
+  const TrBatchFetch* bf = rq.bfetch;
+  return TrFetchLayout::Make(c->batch, TRS_COUNT, TrRowDoubles(rq), c->N, c->nq, c->nv, bf->only_best != 0, true,
+                             bf->mpc ? bf->mpc->nguess : 0, bf->mpc ? bf->mpc->nplans : 0);
+}
+// The refusals in front of everything that is enqueued, and the decisions that need nothing of the device
+int TrPlanRoute(idto_hip_ctx* c, const TrRequest& rq, TrRoute* rt) {
+  if (rq.bfetch && c->batch == 1) { g_err = "tr_solve: the batch fetch serves batches of more than one problem"; return -1; }
   TRACE("hip: tr_solve begins");
-  if (iterations <= 0) { g_err = "tr_solve: iterations must be positive"; return -1; }
+  if (rq.iterations <= 0) { g_err = "tr_solve: iterations must be positive"; return -1; }
   if (!c->tr_resident_ok) {
     g_err = "tr_solve: the iteration kernel's workgroups timed out on this context before (option tr_resident_ok): use "
             "idto_hip_tr_prepare / trial / accept / reject";
     return -1;
   }
-  if (nu < 0 || (nu > 0 && !constrained_dofs)) { g_err = "tr_solve: bad constraint arguments"; return -1; }
-  const int neq = nu * c->N;
-  if (nu > 0) {
-    if (!c->weights_diagonal) { g_err = "tr_solve: enforced constraints need diagonal cost weights"; return -1; }
-  }
-  // (the adaptive methods, D = min(D_prev, f(diag H)): tr_iter_kernel keeps D_prev.  A rejected step leaves g and H
-  // where they are - the gated assembly - so the next iteration forms min(D, f(diag H)) = D again: the memory does
-  // not advance, as in the reference, whose cached scale factors belong to the state that did not change.)
-  if (scaling_method < -1 || scaling_method > 3) { g_err = "tr_solve: bad scaling method"; return -1; }
-  const bool adaptive = scaling_method == 1 || scaling_method == 3;
-  if (iterations > c->tr_rows_cap) {
+  if (rq.nu < 0 || (rq.nu > 0 && !rq.constrained_dofs)) { g_err = "tr_solve: bad constraint arguments"; return -1; }
+  if (rq.nu > 0 && !c->weights_diagonal) { g_err = "tr_solve: enforced constraints need diagonal cost weights"; return -1; }
+  // (the adaptive methods, D = min(D_prev, f(diag H)): tr_iter_kernel keeps D_prev.  A rejected step leaves g and H where they are - the gated
+  // assembly - so the next iteration forms min(D, f(diag H)) = D again: the memory does not advance, as in the reference, whose cached scale factors belong to the state that did not change.)
+  if (rq.scaling_method < -1 || rq.scaling_method > 3) { g_err = "tr_solve: bad scaling method"; return -1; }
+  rt->adaptive = rq.scaling_method == 1 || rq.scaling_method == 3;
+  // (nu > 0 has diagonal weights here - the refusal above - so that the predicate's own look at them decides nothing)
+  rt->use_kkt = TrKktRoute(c, rq.nu);
+  rt->lookahead = c->weights_diagonal && c->asm_stop == 0 && c->fd_stop == 0;
+  TrConvergence& conv = rt->conv = TrConvergence{};
+  conv.on = c->tr_conv_on ? 1 : 0;
+  conv.rel_cost = c->tr_conv_tol[0]; conv.abs_cost = c->tr_conv_tol[1]; conv.rel_grad = c->tr_conv_tol[2];
+  conv.abs_grad = c->tr_conv_tol[3]; conv.rel_state = c->tr_conv_tol[4]; conv.abs_state = c->tr_conv_tol[5];
+  // (with convergence checks the last iteration, too, is followed by g at its iterate: one more pass of the loop
+  // body up to tr_iter_kernel, which then only evaluates the criteria)
+  rt->passes = rq.iterations + (conv.on ? 1 : 0);
+  return 0;
+}
+// ... and the rest where they stand in the stream, behind g and H of the first iterate: a route's refusals, the KKT context, the output sets, the small launch
+int TrPlanLaunches(idto_hip_ctx* c, const TrRequest& rq, TrRoute* rt) {
+  const int B = c->batch, nu = rq.nu;
+  if (B != 1 && nu > 0 && !rt->use_kkt) { g_err = "tr_solve: enforced constraints on a batch need the banded KKT step (nq + nu <= 30, option con_kkt)"; return -1; }
+  int rc = rt->use_kkt ? ConstraintDofs(c, rq.constrained_dofs, nu) : 0;
+  if (!rc && rt->use_kkt) rc = MakeKkt(c, nu);
+  if (rc) return rc;
+  if (B != 1 && !rt->lookahead) { g_err = "tr_solve on a batch context needs the two-set evaluation (diagonal cost weights)"; return -1; }
+  if (rt->adaptive && !rt->lookahead) { g_err = "tr_solve: the adaptive scalings need the gated assembly (diagonal cost weights)"; return -1; }
+  if (nu > 0 && !rt->lookahead) { g_err = "tr_solve: enforced constraints need the two-set evaluation"; return -1; }
+  // from here on the trial point's v, a, N+, tau, partials go to the set the iterate does not occupy (TrSolve's guard clears them)
+  if (rt->lookahead) { c->alt_r = AltSel{c->tr_state, c->alt_off, 0}; c->alt_w = AltSel{c->tr_state, c->alt_off, 1}; }
+  // (the small models' one-workgroup launch, gn_small.h: unconstrained, or with ONE enforced constraint through the banded
+  // KKT step - the instantiations: acrobot 2 + 1, spinner 3 + 1 - whose context the scalar band solver takes)
+  rt->tr_small = c->tr_small && rt->lookahead && SmallEligible(c, &rt->small_plan) && c->h_assembled;
+  if (rt->tr_small && nu > 0)
+    rt->tr_small = rt->use_kkt && nu == 1 && c->kkt->batch == c->batch && Plan(c->kkt, true, WholeStep(c), &rt->small_plan) == 0 &&
+                   rt->small_plan.k == c->nq + 1;
+  // (the folded iteration's arrays live in the band solver's carve-up)
+  rt->tr_fold_fits = rt->tr_small && gn_small_fold_doubles(c->N, c->nq) <= rt->small_plan.lds_small;
+  return 0;
+}
+// The loop's state words - of every problem [Delta, L(q) (resident: the caller evaluated the cost of q), ...] - and the iteration kernel's counter
+int TrBegin(idto_hip_ctx* c, const TrRequest& rq) {
+  const int B = c->batch;
+  if (rq.iterations > c->tr_rows_cap) {
     double* p = nullptr;
-    if (Alloc(c, (size_t)B * iterations * TRR_COUNT, &p)) return -2;   // (the previous, smaller one stays in the context's pool)
-    c->tr_rows = p;
-    c->tr_rows_cap = iterations;
+    if (Alloc(c, (size_t)B * rq.iterations * TRR_COUNT, &p)) return -2;   // (the previous, smaller one stays in the context's pool)
+    c->tr_rows = p; c->tr_rows_cap = rq.iterations;
   }
-  const size_t rows_stride = (size_t)iterations * TRR_COUNT;
   c->spec_pending = false; c->spec_ready = false; c->trial_resident = false;
-  const int n = (c->N + 1) * c->nq, nblk = c->N + 1;
   // tr_iter_kernel finds its last workgroup by counter == target: both restart with every solve, so that a
   // launch that failed in an earlier solve cannot leave them out of step
   c->tr_target = 0;
-  // state of every problem: [Delta, L(q) (resident: the caller evaluated the cost of q), ...]
   if (B == 1) {
     // (one problem: one launch sets the state words, the cost among them, and the counter - no wait here, the loop is
     // enqueued while the evaluation of the initial guess still runs)
     static_assert(TRS_COUNT <= 16, "tr_pin holds 16 doubles");
     hipLaunchKernelGGL(tr_begin_kernel, dim3(1), dim3(64), 0, c->stream, c->tr_state, (int)TRS_COUNT, (int)TRS_DELTA,
-                       (int)TRS_ACCEPTED, (int)TRS_COST, Delta0s[0], c->cost, c->tr_cnt);
+                       (int)TRS_ACCEPTED, (int)TRS_COST, rq.Delta0s[0], c->cost, c->tr_cnt);
     HIP_OK(hipGetLastError());
-  } else {
-    HIP_OK(hipMemset2DAsync(c->tr_cnt, c->pstride, 0, sizeof(unsigned long long), (size_t)B, c->stream));
-    std::vector<double> tmp;
-    double* st = nullptr;
-    if (bfetch) {   // (pinned words of the context: no wait here - the call's one wait is behind the loop, and every return in between waits too)
-      if (!c->bstate_pin) HIP_OK(hipHostMalloc((void**)&c->bstate_pin, (size_t)B * TRS_COUNT * sizeof(double), hipHostMallocDefault));
-      st = c->bstate_pin;
-      std::fill(st, st + (size_t)B * TRS_COUNT, 0.0);
-    } else {
-      tmp.assign((size_t)B * TRS_COUNT, 0.0);
-      st = tmp.data();
-    }
-    for (int b = 0; b < B; ++b) { st[(size_t)b * TRS_COUNT + TRS_DELTA] = Delta0s[b]; st[(size_t)b * TRS_COUNT + TRS_ACCEPTED] = 1.0; }
-    HIP_OK(hipMemcpy2DAsync(c->tr_state, c->pstride, st, TRS_COUNT * sizeof(double), TRS_COUNT * sizeof(double), (size_t)B,
-                            hipMemcpyHostToDevice, c->stream));
-    if (!bfetch) HIP_OK(hipStreamSynchronize(c->stream));   // (the host buffer is a temporary)
+    return 0;
   }
-  if (B != 1)
-    HIP_OK(hipMemcpy2DAsync(c->tr_state + TRS_COST, c->pstride, c->cost, c->pstride, sizeof(double), (size_t)B,
-                            hipMemcpyDeviceToDevice, c->stream));
-  const double eps = 10 * std::numeric_limits<double>::epsilon() / c->P.dt / c->P.dt;   // TO.cc:2024
-  const int lds_iter = (int)sizeof(double) * (tr_rows_lds(c->nq) + TR_NSUM * nblk + 3 + TR_NSUM + 3 * c->nq);
-  // g, H and the Newton step of the first iterate (with constraints the step comes out of the multiplier chain)
-  int rc = 0;
-  if (nu > 0) {
-    rc = idto_hip_eval_partials(c);
-    if (!rc) rc = idto_hip_grad_hess(c);
-  } else {
-    rc = idto_hip_gn_step(c);
+  HIP_OK(hipMemset2DAsync(c->tr_cnt, c->pstride, 0, sizeof(unsigned long long), (size_t)B, c->stream));
+  std::vector<double> tmp; double* st = nullptr;
+  if (rq.bfetch) {   // (pinned words of the context: no wait here - the call's one wait is behind the loop, and every return in between waits too)
+    if (!c->bstate_pin) HIP_OK(hipHostMalloc((void**)&c->bstate_pin, (size_t)B * TRS_COUNT * sizeof(double), hipHostMallocDefault));
+    st = c->bstate_pin;
+    std::fill(st, st + (size_t)B * TRS_COUNT, 0.0);
+  } else { tmp.assign((size_t)B * TRS_COUNT, 0.0); st = tmp.data(); }
+  for (int b = 0; b < B; ++b) { st[(size_t)b * TRS_COUNT + TRS_DELTA] = rq.Delta0s[b]; st[(size_t)b * TRS_COUNT + TRS_ACCEPTED] = 1.0; }
+  HIP_OK(hipMemcpy2DAsync(c->tr_state, c->pstride, st, TRS_COUNT * sizeof(double), TRS_COUNT * sizeof(double), (size_t)B,
+                          hipMemcpyHostToDevice, c->stream));
+  if (!rq.bfetch) HIP_OK(hipStreamSynchronize(c->stream));   // (the host buffer is a temporary)
+  HIP_OK(hipMemcpy2DAsync(c->tr_state + TRS_COST, c->pstride, c->cost, c->pstride, sizeof(double), (size_t)B,
+                          hipMemcpyDeviceToDevice, c->stream));
+  return 0;
+}
+
+// Multipliers of the iterate and H^-1 (g + J^T lambda) (TO.cc:1371-1396, :2139-2149) from ONE banded solve of the KKT system
+// (kkt.h): build its bands from H and the slab's rows of J, factorise + solve, take the result apart.  ex: what taking it
+// apart needs, for tr_iter_kernel's fold.  built: the assembly of the previous iteration wrote the system along.
+int TrMultipliersKkt(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt, int k, bool* built, KktExtractArgs* ex) {
+  idto_hip_ctx* kc = c->kkt; const int nu = rq.nu, B = c->batch;
+  // (tr_small: from the second iteration on the launch that evaluated, decided and assembled has solved it too)
+  const bool solved = rt.tr_small && k > 0;
+  const bool was_built = *built;   // (option "kkt_in_asm")
+  *built = false;
+  KktBuildArgs Kb;
+  Kb.N = c->N; Kb.nq = c->nq; Kb.nv = c->nv; Kb.nu = nu; Kb.HA = c->HA; Kb.HB = c->HB; Kb.HC = c->HC; Kb.g = c->g;
+  Kb.slab = c->slab; Kb.slab_stride = c->slab_stride; Kb.dofs = c->con_dofs;
+  Kb.KA = kc->HA; Kb.KB = kc->HB; Kb.KC = kc->HC; Kb.rhs = kc->g; Kb.alt = c->alt_r;
+  Kb.pstride = c->pstride; Kb.kstride = kc->pstride;
+  if (!solved) {
+    if (!was_built) hipLaunchKernelGGL(kkt_build_kernel, dim3(c->N + 1, B), dim3(256), 0, c->stream, Kb);
+    HIP_OK(hipGetLastError());
+    if (int rc = idto_hip_factor_solve(kc, nullptr, 1, nullptr)) return rc;
   }
+  // (taking z apart - w, J^T lambda, lambda, the multiplier pivots' range - is folded into tr_iter_kernel; option
+  // "kkt_fold" 0 keeps kkt_extract_kernel's launch: tests hold the two against each other)
+  KktExtractArgs& Ke = *ex;
+  Ke.N = c->N; Ke.nq = c->nq; Ke.nv = c->nv; Ke.nu = nu;
+  Ke.z = kc->step; Ke.slab = c->slab; Ke.slab_stride = c->slab_stride; Ke.dofs = c->con_dofs;
+  Ke.w = c->con_out; Ke.jtl = c->con_out + (size_t)(c->N + 1) * c->nq; Ke.lambda = c->con_lambda;
+  Ke.Dinv = kc->Dst; Ke.dstride = idto_host::SolverBlockSize(kc->nq, true); Ke.first_row = idto_host::SolverFirstRow(kc->h_assembled, kc->N);
+  Ke.state = c->tr_state; Ke.alt = c->alt_r; Ke.pstride = c->pstride; Ke.kstride = kc->pstride;
+  if (!c->kkt_fold) hipLaunchKernelGGL(kkt_extract_kernel, dim3(c->N + 1, B), dim3(64), 0, c->stream, Ke);
+  HIP_OK(hipGetLastError());
+  c->con_lambda_at = c->con_lambda;
+  c->con_ready = false; c->con_begun = false;
+  return 0;
+}
+// Multipliers of the iterate (TO.cc:1371-1396), all on the device: Y = H^-1 [g | J^T], S = J Y_J, J y_g (idto_hip_constraint_schur_begin),
+// lambda = S^-1 (h - J y_g) in one workgroup, then H^-1 (g + J^T lambda) and J^T lambda (constraint_step_kernel)
+int TrMultipliersSchur(idto_hip_ctx* c, const TrRequest& rq) {
+  const int nu = rq.nu, neq = nu * c->N, n = (c->N + 1) * c->nq;
+  c->con_begun = false;
+  if (int rc = idto_hip_constraint_schur_begin(c, rq.constrained_dofs, nu)) return rc;
+  if (neq <= CON_LAMBDA_MAX) {   // S in the LDS of one workgroup
+    hipLaunchKernelGGL(constraint_lambda_kernel, dim3(1), dim3(CON_LAMBDA_THREADS),
+                       (size_t)con_lambda_lds_doubles(neq) * sizeof(double), c->stream,
+                       c->con_S, neq, c->slab, c->slab_stride, 3 * c->nv * c->nq, c->con_dofs, nu, c->con_lambda, c->tr_state,
+                       c->alt_r, c->solver_debug ? c->dbg : (double*)nullptr);
+    c->con_lambda_at = c->con_lambda;
+  } else {                       // the blocked factorisation of dense_ldl.h, as idto_hip_constraint_solve runs it
+    hipLaunchKernelGGL(constraint_h_kernel, dim3((neq + 255) / 256), dim3(256), 0, c->stream, c->slab, c->slab_stride,
+                       3 * c->nv * c->nq, c->con_dofs, nu, neq, c->con_h, c->alt_r);
+    double* S = c->con_S;
+    LaunchDenseLdl(c, S, neq, S + (size_t)neq * neq, -1.0, c->con_h + 2);
+    c->con_S_factored = true;
+    hipLaunchKernelGGL(dense_ldl_solve_kernel, dim3(1), dim3(512), (neq + 512 + DENSE_NB * (DENSE_NB + 1)) * sizeof(double),
+                       c->stream, c->con_L, neq, c->con_d, c->con_rv + neq, 1.0, (const double*)nullptr, c->con_lambda + 2, 1);
+    hipLaunchKernelGGL(constraint_flag_kernel, dim3(1), dim3(1), 0, c->stream, c->con_h, c->tr_state);
+    c->con_lambda_at = c->con_lambda + 2;
+  }
+  hipLaunchKernelGGL(constraint_step_kernel, dim3((n + 63) / 64), dim3(64 * STEP_WAVES),
+                     (neq + 64 * STEP_WAVES) * sizeof(double), c->stream, c->slab, c->slab_stride, c->con_dofs, nu, c->N,
+                     c->nq, c->nv, c->stage_x, neq, c->con_lambda_at, c->con_out, c->con_out + n, c->alt_r);
+  HIP_OK(hipGetLastError());
+  c->con_ready = true;
+  return 0;
+}
+// tr_iter_kernel's arguments for pass k; kkt_ex: the KKT result for the kernel to take apart, or null
+TrIterArgs TrIterArgsFor(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt, int k, const KktExtractArgs* kkt_ex) {
+  TrIterArgs T;
+  T.rows = PrepareArgs(c, rq.scaling_method, rq.nu > 0 ? 1 : 0);
+  T.alt = c->alt_r; T.rows.part_ll = c->tr_part_ll; T.part2 = c->tr_part2;
+  T.rows.epoch = ++c->tr_epoch;
+  if (T.rows.epoch == 0u) T.rows.epoch = ++c->tr_epoch;   // (0 is what an arena that was never written holds)
+  T.out = c->tr_out; T.state = c->tr_state; T.n = (c->N + 1) * c->nq; T.nq = c->nq; T.scaling = rq.scaling;
+  T.nquat = rq.normalize_quaternions ? c->tr_nquat : 0;
+  T.quat = c->tr_quat; T.q_trial = c->q_trial; T.dq = c->tr_dq;
+  T.conv = rt.conv; T.conv.rows = c->tr_rows; T.conv.check_only = (k == rq.iterations) ? 1 : 0;
+  T.fact_status = c->status_dev; T.fact_id = c->fact_id; T.timeout_status = c->status_dev + 2 * c->batch;   // (the most recent factorisation: this iteration's step)
+  if (rt.use_kkt) { T.fact_status = c->kkt->status_dev; T.fact_id = c->kkt->fact_id; T.timeout_status = c->kkt->status_dev + 2 * c->batch; }
+  T.rows.freeze = c->tr_state + TRS_FLAGS; T.pstride = c->pstride; T.rows_stride = TrRowDoubles(rq);
+  T.kdinv = nullptr; T.kdstride = 0; T.kfirst_row = 0; T.kstride = 0; T.curpre = c->decide_word + 2;
+  T.debug_skip_row = c->debug_skip_role >= 100 ? c->debug_skip_role - 100 : -1;
+  if (kkt_ex) {
+    T.rows.kx.z = kkt_ex->z; T.rows.kx.KK = c->nq + rq.nu; T.rows.kx.nv = c->nv;
+    T.rows.kx.w_out = kkt_ex->w; T.rows.kx.jtl_out = kkt_ex->jtl; T.rows.kx.lambda_out = kkt_ex->lambda;
+    T.kdinv = kkt_ex->Dinv; T.kdstride = kkt_ex->dstride; T.kfirst_row = kkt_ex->first_row; T.kstride = kkt_ex->kstride;
+  }
+  return T;
+}
+// the decision's arguments (cost_kernel's epilogue, or the launch that stands in for it)
+TrDecideArgs TrDecideArgsFor(const idto_hip_ctx* c, const TrRequest& rq) {
+  const int nu = rq.nu; TrDecideArgs Dc;
+  Dc.state = c->tr_state; Dc.out = c->tr_out; Dc.rows = c->tr_rows; Dc.q = c->q; Dc.q_trial = c->q_trial;
+  Dc.n = (c->N + 1) * c->nq; Dc.rows_stride = TrRowDoubles(rq); Dc.eta = rq.eta; Dc.Delta_max = rq.Delta_max;
+  Dc.eps = 10 * std::numeric_limits<double>::epsilon() / c->P.dt / c->P.dt;   // TO.cc:2024
+  Dc.lambda = nu > 0 ? c->con_lambda_at : nullptr; Dc.dofs = nu > 0 ? c->con_dofs : nullptr;
+  Dc.nu = nu; Dc.N = c->N; Dc.slab_stride = c->slab_stride; Dc.tau_off = 3 * c->nv * c->nq; Dc.part2 = c->tr_part2; Dc.nblk = c->N + 1;
+  return Dc;
+}
+// tau (with its partials: the trial point is the next iterate unless rejected) and the cost at the trial point, the decision, and - more:
+// an iteration follows - g, H and the next step.  fold: tr_iter_kernel's part of this pass for the small launch to take along, or null.
+int TrTrialAndNext(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt, const TrDecideArgs& Dc, bool more,
+                   const TrIterArgs* fold, bool* kkt_built) {
+  const int nu = rq.nu, B = c->batch; const bool lookahead = rt.lookahead;
+  // a small all-revolute model: the trial point's evaluation, its cost, the decision and - accepted - g, H and the next
+  // step in ONE workgroup of ONE launch (gn_small.h), the bits of the three launches below
+  if (rt.tr_small) return LaunchSmall(c, rt.small_plan, &Dc, !more, c->alt_w, nu > 0, fold);
+  std::swap(c->q, c->q_trial);
+  int rc = LaunchFd(c, (lookahead && more) ? 1 : 0, 0, c->N, c->alt_w);
+  c->fd_full = lookahead && more;   // (v, N+ of the trial point = of the iterate the gated assembly runs for)
+  // the cost of the trial point and the decision: a launch of their own (cost_kernel), or one more workgroup of the
+  // pipelined solver's launch that follows (penta_pipe.h PipeAsm::decide, option "decide_in_solver")
+  SolverPlan sp;   // the next solve's, when its launch is to carry the gated assembly
+  const bool asm_in_solver = !rc && more && lookahead && nu == 0 && c->h_assembled && AsmInSolver(c, &sp);
+  const bool decide_in_solver = asm_in_solver && c->decide_in_solver && sp.can_decide;
+  if (!rc && !decide_in_solver)
+    hipLaunchKernelGGL(cost_kernel, dim3(1, B), dim3(1024), c->cost_lds, c->stream, c->M, c->P, c->q, c->v, c->slab,
+                       c->slab_stride, c->cost, c->weights_diagonal ? 1 : 0, (double*)nullptr, c->pstride,
+                       (double*)nullptr, Dc, c->alt_w);
+  std::swap(c->q, c->q_trial);
   if (rc) return rc;
-  // (blocks of nq + nu up to the 30 x 30 instantiation of the two-workgroup factorisation: allegro's 23 + 6, N = 60,
-  // 0.523 against 0.665 ms per iteration with the Schur-complement chain; the 32 x 32 one needs a third elimination
-  // wavefront and spills: 442 against 245 us at N = 20)
-  const bool use_kkt = nu > 0 && c->con_kkt && idto_host::SolverBlockSize(c->nq + nu, true) <= 30;
-  if (B != 1 && nu > 0 && !use_kkt) { g_err = "tr_solve: enforced constraints on a batch need the banded KKT step (nq + nu <= 30, option con_kkt)"; return -1; }
+  HIP_OK(hipGetLastError());
+  if (!more) return 0;
+  if (asm_in_solver) {
+    // the gated assembly inside the pipelined solver's launch (penta_pipe.h PipeAsm): a problem whose step was
+    // rejected keeps g and H and the solver reads them where they are -> the same step
+    DropPrefetch(c, {IDTO_ARR_GRADIENT, IDTO_ARR_H_A, IDTO_ARR_H_B, IDTO_ARR_H_C, IDTO_ARR_HBANDS});
+    c->con_ready = false; c->con_begun = false;
+    SolverExtras ex; ex.assemble = true; ex.gate = c->tr_state + TRS_ACCEPTED; ex.decide = decide_in_solver ? &Dc : nullptr;
+    return FactorSolve(c, nullptr, 1, nullptr, nullptr, &sp, ex);
+  }
+  if (!lookahead) return idto_hip_gn_step(c);   // (dense cost weights: the partials again, at the iterate)
+  if (rt.use_kkt && c->kkt_in_asm) {
+    // (the next iteration's KKT system written by this assembly: a rejected step keeps g, H - and the system, which the
+    // solvers only read)
+    idto_hip_ctx* kc = c->kkt;
+    KktSink S{};
+    S.KA = kc->HA; S.KB = kc->HB; S.KC = kc->HC; S.rhs = kc->g; S.K = c->nq + nu; S.nu = nu; S.slab = c->slab; S.slab_stride = (int)c->slab_stride; S.dofs = c->con_dofs;
+    rc = LaunchAssemble(c, c->tr_state + TRS_ACCEPTED, &S, kc->pstride, kkt_built);
+  } else {
+    rc = LaunchAssemble(c, c->tr_state + TRS_ACCEPTED);
+  }
+  if (!rc && nu == 0) rc = idto_hip_factor_solve(c, nullptr, 1, nullptr);   // (after a rejection: the same H, g -> the same step)
+  return rc;
+}
+// One problem's code from the status words, after the wait (b < 0: the one problem of a single context).  A multiplier pivot that vanished -
+// redundant constraints, TRF_SINGULAR_S in the rows: the caller's pivoted factorisation takes over - leaves garbage in the rows of H behind it,
+// whose pivot test then fails as well: next to that flag a KKT pivot failure is no failure; a time-out always is.  (The batch-fetch exit used to ask
+// both contexts before it weighed either; it relies on this: with the KKT step the context's own solver ran nothing in this call and tr_iter_kernel's time-out word is the KKT context's.)
+int TrFactorVerdict(idto_hip_ctx* c, bool use_kkt, double flags_word, int b) {
   if (use_kkt) {
-    if ((rc = ConstraintDofs(c, constrained_dofs, nu)) != 0) return rc;
-    if ((rc = MakeKkt(c, nu)) != 0) return rc;
+    const int fs = FactorStatus(c->kkt, b);
+    const bool singular = ((int)flags_word & TRF_SINGULAR_S) != 0;
+    if (fs == IDTO_HIP_SOLVER_TIMEOUT || (fs && !singular)) return fs;
   }
-  const bool lookahead = c->weights_diagonal && c->asm_stop == 0 && c->fd_stop == 0;
-  if (B != 1 && !lookahead) { g_err = "tr_solve on a batch context needs the two-set evaluation (diagonal cost weights)"; return -1; }
-  if (adaptive && !lookahead) { g_err = "tr_solve: the adaptive scalings need the gated assembly (diagonal cost weights)"; return -1; }
-  if (nu > 0 && !lookahead) { g_err = "tr_solve: enforced constraints need the two-set evaluation"; return -1; }
-  // from here on the trial point's v, a, N+, tau, partials go to the set the iterate does not occupy
-  struct AltGuard {
-    idto_hip_ctx* c;
-    ~AltGuard() { c->alt_r.state = nullptr; c->alt_w.state = nullptr; }
-  } alt_guard{c};
-  if (lookahead) {
-    c->alt_r = AltSel{c->tr_state, c->alt_off, 0};
-    c->alt_w = AltSel{c->tr_state, c->alt_off, 1};
+  return FactorStatus(c, b);
+}
+// a batch: the problems whose iterate ended up in the other set get it copied over (a single-problem context swaps its pointers instead)
+int TrFoldSets(idto_hip_ctx* c) {
+  hipLaunchKernelGGL(tr_fold_sets_kernel, dim3(64, c->batch), dim3(256), 0, c->stream, c->v, (size_t)c->alt_off / sizeof(double),
+                     c->tr_state, c->pstride);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+// idto_hip_tr_solve_batch_fetch: state words, rows and the iterates of every problem (only_best: of the best one) packed
+// by ONE launch, which also chooses the best problem; one copy, one wait (trust_region.h tr_gather_batch_kernel)
+int TrFinishBatchFetch(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt) {
+  const TrBatchFetch* bfetch = rq.bfetch;
+  const MpcTickHook* hook = bfetch->mpc;
+  const int B = c->batch;
+  const TrFetchLayout L = BatchFetchLayout(c, rq);
+  const size_t lds = (size_t)B * (sizeof(double) + sizeof(int));
+  if (lds > 60 * 1024) { g_err = "tr_solve_batch_fetch: the batch is too large for the selecting workgroup's LDS"; return -1; }
+  if (int erc = EnsureFetch(c, L.total())) return erc;
+  TrGatherBatchArgs G;
+  G.state = c->tr_state; G.rows = c->tr_rows; G.B = B; G.iterations = rq.iterations; G.nrows = (int)L.nrows; G.only_best = bfetch->only_best ? 1 : 0;
+  G.q = c->q; G.v = c->v; G.slab = c->slab; G.dq = c->tr_dq; G.w = c->tr_w; G.nq = c->nq; G.nv = c->nv; G.slab_stride = (int)c->slab_stride;
+  G.alt_off = (long long)c->alt_off; G.pstride = c->pstride; G.L = L; G.out = c->fetch_dev;
+  hipLaunchKernelGGL(tr_gather_batch_kernel, dim3(TR_GATHER_BATCH_GX + 1, B), dim3(256), lds, c->stream, G);
+  HIP_OK(hipGetLastError());
+  if (hook) {
+    // the tick's new plans: fitted on the device from the loop's result, written to the plane that is not in force and
+    // behind the guesses in the same staging buffer (the shift left those there: idto_hip_mpc_batch_replan)
+    MpcBatchState* m = hook->m;
+    MpcStoreArgs S{};
+    S.L = m->L; S.breaks = m->breaks; S.actuated = m->actuated_dev; S.q = c->q; S.q_stride = c->pstride; S.v = c->v; S.v_stride = c->pstride;
+    S.tau = c->slab + 3 * (size_t)c->nv * c->nq; S.tau_stride = c->pstride; S.tau_row = (int)c->slab_stride;
+    S.state = c->tr_state; S.state_stride = c->pstride; S.alt_off = (long long)c->alt_off;
+    S.rows = c->tr_rows; S.iterations = rq.iterations; S.nrows = (int)L.nrows; S.times = m->tick_dev; S.times_stride = 1 + c->nq + c->nv;
+    S.plan_old = m->plan[m->cur]; S.plan_new = m->plan[m->cur ^ 1]; S.work = m->work; S.out = c->fetch_dev + L.plans();
+    hipLaunchKernelGGL(mpc_store_kernel, dim3((m->L.dims() + 63) / 64, B), dim3(64), 0, c->stream, S);
+    HIP_OK(hipGetLastError());
   }
-  // (the small models' one-workgroup launch, gn_small.h: unconstrained, or with ONE enforced constraint through the banded
-  // KKT step - the instantiations: acrobot 2 + 1, spinner 3 + 1 - whose context the scalar band solver takes)
-  SolverPlan small_plan;   // of the system the launch solves: H's, or the KKT context's
-  bool tr_small = c->tr_small && lookahead && SmallEligible(c, &small_plan) && c->h_assembled;
-  if (tr_small && nu > 0)
-    tr_small = use_kkt && nu == 1 && c->kkt->batch == c->batch && Plan(c->kkt, true, WholeStep(c), &small_plan) == 0 && small_plan.k == c->nq + 1;
-  bool kkt_built = false;
-  // (the folded iteration's arrays live in the band solver's carve-up)
-  const bool tr_fold_fits = tr_small && gn_small_fold_doubles(c->N, c->nq) <= small_plan.lds_small;
-  TrConvergence conv{};
-  conv.on = c->tr_conv_on ? 1 : 0;
-  conv.rel_cost = c->tr_conv_tol[0]; conv.abs_cost = c->tr_conv_tol[1]; conv.rel_grad = c->tr_conv_tol[2];
-  conv.abs_grad = c->tr_conv_tol[3]; conv.rel_state = c->tr_conv_tol[4]; conv.abs_state = c->tr_conv_tol[5];
-  conv.rows = c->tr_rows;
-  // (with convergence checks the last iteration, too, is followed by g at its iterate: one more pass of the loop
-  // body up to tr_iter_kernel, which then only evaluates the criteria)
-  const int passes = iterations + (conv.on ? 1 : 0);
-  // With the convergence criteria on, the loop is enqueued in chunks of TR_CHUNK iterations and the sticky flags
-  // are looked at in between: once a criterion holds (or an iteration failed) the iterations that are left would run
-  // every kernel in full - none of fd, cost and the solver reads the flags - only to decide nothing, and a solve that
-  // converges after 20 of max_iterations = 500 would take 25 times as long as the loop it replaces (TO.cc:2600-2612
-  // leaves the loop).  Rows of iterations that never ran are zeros.
+  HIP_OK(hipMemcpyAsync(c->fetch_pin, c->fetch_dev, L.total() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  // (behind the copy: the fold only makes the context's first set the iterate's for the calls that follow)
+  if (int rc = TrFoldSets(c)) return rc;
+  HIP_OK(hipStreamSynchronize(c->stream));
+  TRACE("hip: tr_solve: waited for the device (every problem's state words, rows and solution back)");
+  const double* p = c->fetch_pin;
+  const int best = *bfetch->best = (int)p[L.header()];
+  for (int b = 0; b < B; ++b) { bfetch->final_cost[b] = p[L.final_cost() + b]; bfetch->status[b] = (int)p[L.status() + b]; }
+  if (hook && hook->guess_out) std::memcpy(hook->guess_out, p + L.guess(), L.nguess * sizeof(double));
+  if (hook && hook->plans_out) std::memcpy(hook->plans_out, p + L.plans(), L.nplans * sizeof(double));
+  for (int b = 0; b < B; ++b) {
+    if (rq.Delta_out) rq.Delta_out[b] = p[L.state(b) + TRS_DELTA];
+    std::memcpy(rq.rows_host + (size_t)b * L.nrows, p + L.rows(b), L.nrows * sizeof(double));
+  }
+  if (!bfetch->only_best || best >= 0)
+    for (size_t t = 0; t < L.slots; ++t)
+      for (int i = 0; i < 5; ++i)
+        if (bfetch->out[i]) std::memcpy(bfetch->out[i] + t * L.cnt[i], p + L.part(t, i), L.cnt[i] * sizeof(double));
+  // every problem's outputs are filled; the return value: a time-out first, else whether any factorisation failed
+  int failed = 0;
+  for (int b = 0; b < B; ++b) {
+    const int fs = TrFactorVerdict(c, rt.use_kkt, p[L.state(b) + TRS_FLAGS], b);
+    if (fs == IDTO_HIP_SOLVER_TIMEOUT) return fs;
+    if (fs || (bfetch->status[b] & TRF_FACTORIZATION)) failed = IDTO_HIP_FACTORIZATION_FAILED;
+  }
+  return failed;
+}
+// idto_hip_tr_solve_batch: the state words of every problem and the rows; the first problem that reports decides the return value
+int TrFinishBatch(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt) {
+  const int B = c->batch;
+  if (int rc = TrFoldSets(c)) return rc;
+  std::vector<double> st((size_t)B * TRS_COUNT);
+  HIP_OK(hipMemcpy2DAsync(st.data(), TRS_COUNT * sizeof(double), c->tr_state, c->pstride, TRS_COUNT * sizeof(double), (size_t)B,
+                          hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  HIP_OK(hipMemcpy(rq.rows_host, c->tr_rows, (size_t)B * TrRowDoubles(rq) * sizeof(double), hipMemcpyDeviceToHost));
+  if (rq.Delta_out) for (int b = 0; b < B; ++b) rq.Delta_out[b] = st[(size_t)b * TRS_COUNT + TRS_DELTA];
+  for (int b = 0; b < B; ++b)
+    if (int fs = TrFactorVerdict(c, rt.use_kkt, st[(size_t)b * TRS_COUNT + TRS_FLAGS], b)) return fs;
+  return 0;
+}
+// the end of both single-problem exits, c->tr_pin holding the state words
+int TrFinishSingle(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt) {
+  if (rq.Delta_out) *rq.Delta_out = c->tr_pin[TRS_DELTA];
+  if (c->tr_pin[TRS_CUR] != 0.0) {   // the iterate's v, a, N+, slab, products ended up in the other set: it is "the" set now
+    c->v = at_problem(c->v, (size_t)c->alt_off); c->a = at_problem(c->a, (size_t)c->alt_off); c->nplus = at_problem(c->nplus, (size_t)c->alt_off);
+    c->slab = at_problem(c->slab, (size_t)c->alt_off); c->terms = at_problem(c->terms, (size_t)c->alt_off);
+    c->alt_off = -c->alt_off;
+  }
+  return TrFactorVerdict(c, rt.use_kkt, c->tr_pin[TRS_FLAGS], -1);
+}
+// idto_hip_tr_solve_fetch: the state words, the rows and the solution with them: one gathering launch, one copy, the same wait
+int TrFinishFetch(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt) {
+  const TrFetchLayout L = TrFetchLayout::Make(1, TRS_COUNT, TrRowDoubles(rq), c->N, c->nq, c->nv, false, false);
+  if (int rc = EnsureFetch(c, L.total())) return rc;
+  TrGatherArgs G;
+  G.state = c->tr_state; G.rows = c->tr_rows; G.alt_off = rt.lookahead ? (long long)c->alt_off : 0; G.L = L; G.out = c->fetch_dev;
+  G.q = c->q; G.v = c->v; G.slab = c->slab; G.dq = c->tr_dq; G.w = c->tr_w; G.nq = c->nq; G.nv = c->nv; G.slab_stride = (int)c->slab_stride;
+  hipLaunchKernelGGL(tr_gather_kernel, dim3(16), dim3(256), 0, c->stream, G);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(c->fetch_pin, c->fetch_dev, L.total() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  TRACE("hip: tr_solve: gather + one copy enqueued");
+  HIP_OK(hipStreamSynchronize(c->stream));
+  TRACE("hip: tr_solve: waited for the device (state words, rows and the solution back)");
+  const double* p = c->fetch_pin;
+  std::memcpy(c->tr_pin, p + L.state(0), TRS_COUNT * sizeof(double));
+  std::memcpy(rq.rows_host, p + L.rows(0), L.nrows * sizeof(double));
+  for (int i = 0; i < 5; ++i)
+    if (rq.fetch[i]) std::memcpy(rq.fetch[i], p + L.part(0, i), L.cnt[i] * sizeof(double));
+  return TrFinishSingle(c, rq, rt);
+}
+// idto_hip_tr_solve: the state words and the statistics rows with ONE wait (the rows through pinned staging of the context)
+int TrFinishRows(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt) {
+  const size_t nrow = TrRowDoubles(rq);
+  if (int rc = EnsurePinned(&c->rows_pin, &c->rows_cap, std::max<size_t>(nrow, 64 * TRR_COUNT))) return rc;
+  HIP_OK(hipMemcpyAsync(c->tr_pin, c->tr_state, TRS_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipMemcpyAsync(c->rows_pin, c->tr_rows, nrow * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  TRACE("hip: tr_solve: waited for the device (state words + rows back)");
+  std::memcpy(rq.rows_host, c->rows_pin, nrow * sizeof(double));
+  return TrFinishSingle(c, rq, rt);
+}
+// The device-resident trust-region loop: begin, per pass {multipliers, iterate, trial + decision, next step}, finish
+int TrSolve(idto_hip_ctx* c, const TrRequest& rq) {
+  HIP_OK(hipSetDevice(c->device));
+  const int B = c->batch, nu = rq.nu, iterations = rq.iterations;
+  TrRoute rt;
+  int rc = TrPlanRoute(c, rq, &rt);
+  if (!rc) rc = TrBegin(c, rq);
+  if (rc) return rc;
+  // g, H and the Newton step of the first iterate (with constraints the step comes out of the multiplier chain)
+  rc = nu > 0 ? idto_hip_eval_partials(c) : idto_hip_gn_step(c);
+  if (!rc && nu > 0) rc = idto_hip_grad_hess(c);
+  if (rc) return rc;
+  struct AltGuard { idto_hip_ctx* c; ~AltGuard() { c->alt_r.state = nullptr; c->alt_w.state = nullptr; } } alt_guard{c};
+  if ((rc = TrPlanLaunches(c, rq, &rt)) != 0) return rc;
+  // With the convergence criteria on, the loop is enqueued in chunks of TR_CHUNK iterations and the sticky flags are looked at in between:
+  // once a criterion holds (or an iteration failed) the iterations that are left would run every kernel in full - none of fd, cost and the
+  // solver reads the flags - only to decide nothing, and a solve that converges after 20 of max_iterations = 500 would take 25 times as
+  // long as the loop it replaces (TO.cc:2600-2612 leaves the loop).  Rows of iterations that never ran are zeros.
   constexpr int TR_CHUNK = 8;
-  if (conv.on) HIP_OK(hipMemsetAsync(c->tr_rows, 0, (size_t)B * rows_stride * sizeof(double), c->stream));
+  if (rt.conv.on) HIP_OK(hipMemsetAsync(c->tr_rows, 0, (size_t)B * TrRowDoubles(rq) * sizeof(double), c->stream));
   TRACE("hip: tr_solve: loop state enqueued, constraint buffers ready");
-  for (int k = 0; k < passes; ++k) {
-    if (conv.on && B == 1 && k > 0 && k % TR_CHUNK == 0) {
+  const int lds_iter = (int)sizeof(double) * (tr_rows_lds(c->nq) + TR_NSUM * (c->N + 1) + 3 + TR_NSUM + 3 * c->nq);
+  bool kkt_built = false;
+  for (int k = 0; k < rt.passes; ++k) {
+    if (rt.conv.on && B == 1 && k > 0 && k % TR_CHUNK == 0) {
       HIP_OK(hipMemcpyAsync(c->tr_pin, c->tr_state, TRS_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
       HIP_OK(hipStreamSynchronize(c->stream));
       if (c->tr_pin[TRS_FLAGS] != 0.0) break;
     }
-    conv.check_only = (k == iterations) ? 1 : 0;
-    bool kkt_fold = false;
     KktExtractArgs kkt_ex{};
-    if (nu > 0 && use_kkt) {
-      // multipliers of the iterate and H^-1 (g + J^T lambda) (TO.cc:1371-1396, :2139-2149) from ONE banded solve of the
-      // KKT system (kkt.h): build its bands from H and the slab's rows of J, factorise + solve, take the result apart
-      // (tr_small: from the second iteration on the launch that evaluated, decided and assembled has solved it too)
-      idto_hip_ctx* kc = c->kkt;
-      const bool solved = tr_small && k > 0;
-      const bool built = kkt_built;   // (the assembly of the previous iteration wrote the KKT system along: option "kkt_in_asm")
-      kkt_built = false;
-      KktBuildArgs Kb;
-      Kb.N = c->N; Kb.nq = c->nq; Kb.nv = c->nv; Kb.nu = nu;
-      Kb.HA = c->HA; Kb.HB = c->HB; Kb.HC = c->HC; Kb.g = c->g;
-      Kb.slab = c->slab; Kb.slab_stride = c->slab_stride; Kb.dofs = c->con_dofs;
-      Kb.KA = kc->HA; Kb.KB = kc->HB; Kb.KC = kc->HC; Kb.rhs = kc->g; Kb.alt = c->alt_r;
-      Kb.pstride = c->pstride; Kb.kstride = kc->pstride;
-      if (!solved) {
-        if (!built) hipLaunchKernelGGL(kkt_build_kernel, dim3(c->N + 1, B), dim3(256), 0, c->stream, Kb);
-        HIP_OK(hipGetLastError());
-        rc = idto_hip_factor_solve(kc, nullptr, 1, nullptr);
-        if (rc) return rc;
-      }
-      // (taking z apart - w, J^T lambda, lambda, the multiplier pivots' range - is folded into tr_iter_kernel below; option
-      // "kkt_fold" 0 keeps kkt_extract_kernel's launch: tests hold the two against each other)
-      KktExtractArgs Ke;
-      Ke.N = c->N; Ke.nq = c->nq; Ke.nv = c->nv; Ke.nu = nu;
-      Ke.z = kc->step; Ke.slab = c->slab; Ke.slab_stride = c->slab_stride; Ke.dofs = c->con_dofs;
-      Ke.w = c->con_out; Ke.jtl = c->con_out + n; Ke.lambda = c->con_lambda;
-      Ke.Dinv = kc->Dst; Ke.dstride = idto_host::SolverBlockSize(kc->nq, true); Ke.first_row = idto_host::SolverFirstRow(kc->h_assembled, kc->N);
-      Ke.state = c->tr_state; Ke.alt = c->alt_r;
-      Ke.pstride = c->pstride; Ke.kstride = kc->pstride;
-      kkt_fold = c->kkt_fold;
-      if (kkt_fold) kkt_ex = Ke;
-      else hipLaunchKernelGGL(kkt_extract_kernel, dim3(c->N + 1, B), dim3(64), 0, c->stream, Ke);
-      HIP_OK(hipGetLastError());
-      c->con_lambda_at = c->con_lambda;
-      c->con_ready = false; c->con_begun = false;
-    } else if (nu > 0) {
-      // multipliers of the iterate (TO.cc:1371-1396), all on the device: Y = H^-1 [g | J^T], S = J Y_J, J y_g
-      // (idto_hip_constraint_schur_begin), lambda = S^-1 (h - J y_g) in one workgroup, then H^-1 (g + J^T lambda)
-      // and J^T lambda (constraint_step_kernel)
-      c->con_begun = false;
-      rc = idto_hip_constraint_schur_begin(c, constrained_dofs, nu);
-      if (rc) return rc;
-      if (neq <= CON_LAMBDA_MAX) {   // S in the LDS of one workgroup
-        hipLaunchKernelGGL(constraint_lambda_kernel, dim3(1), dim3(CON_LAMBDA_THREADS),
-                           (size_t)con_lambda_lds_doubles(neq) * sizeof(double), c->stream,
-                           c->con_S, neq, c->slab, c->slab_stride, 3 * c->nv * c->nq, c->con_dofs, nu, c->con_lambda, c->tr_state,
-                           c->alt_r, c->solver_debug ? c->dbg : (double*)nullptr);
-        c->con_lambda_at = c->con_lambda;
-      } else {                       // the blocked factorisation of dense_ldl.h, as idto_hip_constraint_solve runs it
-        hipLaunchKernelGGL(constraint_h_kernel, dim3((neq + 255) / 256), dim3(256), 0, c->stream, c->slab, c->slab_stride,
-                           3 * c->nv * c->nq, c->con_dofs, nu, neq, c->con_h, c->alt_r);
-        double* S = c->con_S;
-        LaunchDenseLdl(c, S, neq, S + (size_t)neq * neq, -1.0, c->con_h + 2);
-        c->con_S_factored = true;
-        hipLaunchKernelGGL(dense_ldl_solve_kernel, dim3(1), dim3(512), (neq + 512 + DENSE_NB * (DENSE_NB + 1)) * sizeof(double),
-                           c->stream, c->con_L, neq, c->con_d, c->con_rv + neq, 1.0, (const double*)nullptr, c->con_lambda + 2, 1);
-        hipLaunchKernelGGL(constraint_flag_kernel, dim3(1), dim3(1), 0, c->stream, c->con_h, c->tr_state);
-        c->con_lambda_at = c->con_lambda + 2;
-      }
-      hipLaunchKernelGGL(constraint_step_kernel, dim3((n + 63) / 64), dim3(64 * STEP_WAVES),
-                         (neq + 64 * STEP_WAVES) * sizeof(double), c->stream, c->slab, c->slab_stride, c->con_dofs, nu, c->N,
-                         c->nq, c->nv, c->stage_x, neq, c->con_lambda_at, c->con_out, c->con_out + n, c->alt_r);
-      HIP_OK(hipGetLastError());
-      c->con_ready = true;
-    }
-    TrIterArgs T;
-    T.rows = PrepareArgs(c, scaling_method, nu > 0 ? 1 : 0);
-    T.alt = c->alt_r;
-    T.rows.part_ll = c->tr_part_ll;
-    T.rows.epoch = ++c->tr_epoch;
-    if (T.rows.epoch == 0u) T.rows.epoch = ++c->tr_epoch;   // (0 is what an arena that was never written holds)
-    T.part2 = c->tr_part2;
-    T.out = c->tr_out; T.state = c->tr_state;
-    T.n = n; T.nq = c->nq; T.scaling = scaling;
-    T.nquat = normalize_quaternions ? c->tr_nquat : 0;
-    T.quat = c->tr_quat; T.q_trial = c->q_trial; T.dq = c->tr_dq;
-    T.conv = conv;
-    T.fact_status = c->status_dev; T.fact_id = c->fact_id;   // (the most recent factorisation: this iteration's step)
-    T.timeout_status = c->status_dev + 2 * c->batch;
-    if (nu > 0 && use_kkt) { T.fact_status = c->kkt->status_dev; T.fact_id = c->kkt->fact_id; T.timeout_status = c->kkt->status_dev + 2 * B; }
-    T.rows.freeze = c->tr_state + TRS_FLAGS;
-    T.pstride = c->pstride; T.rows_stride = rows_stride;
-    T.kdinv = nullptr; T.kdstride = 0; T.kfirst_row = 0; T.kstride = 0;
-    T.debug_skip_row = c->debug_skip_role >= 100 ? c->debug_skip_role - 100 : -1;
-    T.curpre = c->decide_word + 2;
-    if (kkt_fold) {
-      T.rows.kx.z = kkt_ex.z; T.rows.kx.KK = c->nq + nu; T.rows.kx.nv = c->nv;
-      T.rows.kx.w_out = kkt_ex.w; T.rows.kx.jtl_out = kkt_ex.jtl; T.rows.kx.lambda_out = kkt_ex.lambda;
-      T.kdinv = kkt_ex.Dinv; T.kdstride = kkt_ex.dstride; T.kfirst_row = kkt_ex.first_row; T.kstride = kkt_ex.kstride;
-    }
+    if (rt.use_kkt) rc = TrMultipliersKkt(c, rq, rt, k, &kkt_built, &kkt_ex);
+    else if (nu > 0) rc = TrMultipliersSchur(c, rq);
+    if (rc) return rc;
+    const TrIterArgs T = TrIterArgsFor(c, rq, rt, k, (rt.use_kkt && c->kkt_fold) ? &kkt_ex : nullptr);
     // (the small models' launch below takes this kernel's part too - option "tr_fold" -: the whole iteration is one launch)
-    const bool fold = tr_small && tr_fold_fits && c->tr_fold && k < iterations && T.nquat == 0 && T.rows.nu <= 4;
-    if (!fold) hipLaunchKernelGGL(tr_iter_kernel, dim3(nblk + 1, B), dim3(256), lds_iter, c->stream, T);
+    const bool fold = rt.tr_small && rt.tr_fold_fits && c->tr_fold && k < iterations && T.nquat == 0 && T.rows.nu <= 4;
+    if (!fold) hipLaunchKernelGGL(tr_iter_kernel, dim3(c->N + 2, B), dim3(256), lds_iter, c->stream, T);
     HIP_OK(hipGetLastError());
     if (k == iterations) break;   // (the check-only pass)
-    // tau (with its partials: the trial point is the next iterate unless rejected) and the cost at the
-    // trial point, then the decision (cost_kernel's epilogue)
-    TrDecideArgs Dc;
-    Dc.state = c->tr_state; Dc.out = c->tr_out; Dc.rows = c->tr_rows; Dc.q = c->q; Dc.q_trial = c->q_trial; Dc.n = n;
-    Dc.rows_stride = rows_stride;
-    Dc.eta = eta; Dc.Delta_max = Delta_max; Dc.eps = eps;
-    Dc.lambda = nu > 0 ? c->con_lambda_at : nullptr; Dc.dofs = nu > 0 ? c->con_dofs : nullptr;
-    Dc.nu = nu; Dc.N = c->N; Dc.slab_stride = c->slab_stride; Dc.tau_off = 3 * c->nv * c->nq;
-    Dc.part2 = c->tr_part2; Dc.nblk = nblk;
-    const bool more = k + 1 < passes;
-    if (tr_small) {
-      // a small all-revolute model: the trial point's evaluation, its cost, the decision and - accepted - g, H and the next
-      // step in ONE workgroup of ONE launch (gn_small.h), the bits of the three launches below
-      rc = LaunchSmall(c, small_plan, &Dc, !more, c->alt_w, nu > 0, fold ? &T : nullptr);
-      if (rc) return rc;
-      if (!more) break;
-      continue;
-    }
-    std::swap(c->q, c->q_trial);
-    rc = LaunchFd(c, (lookahead && more) ? 1 : 0, 0, c->N, c->alt_w);
-    c->fd_full = lookahead && more;   // (v, N+ of the trial point = of the iterate the gated assembly runs for)
-    // the cost of the trial point and the decision: a launch of their own (cost_kernel), or one more workgroup of the
-    // pipelined solver's launch that follows (penta_pipe.h PipeAsm::decide, option "decide_in_solver")
-    SolverPlan sp;   // the next solve's, when its launch is to carry the gated assembly
-    const bool asm_in_solver = !rc && more && lookahead && nu == 0 && c->h_assembled && AsmInSolver(c, &sp);
-    const bool decide_in_solver = asm_in_solver && c->decide_in_solver && sp.can_decide;
-    if (!rc && !decide_in_solver)
-      hipLaunchKernelGGL(cost_kernel, dim3(1, B), dim3(1024), c->cost_lds, c->stream, c->M, c->P, c->q, c->v, c->slab,
-                         c->slab_stride, c->cost, c->weights_diagonal ? 1 : 0, (double*)nullptr, c->pstride,
-                         (double*)nullptr, Dc, c->alt_w);
-    std::swap(c->q, c->q_trial);
-    if (rc) return rc;
-    HIP_OK(hipGetLastError());
+    const bool more = k + 1 < rt.passes;
+    if ((rc = TrTrialAndNext(c, rq, rt, TrDecideArgsFor(c, rq), more, fold ? &T : nullptr, &kkt_built)) != 0) return rc;
     if (!more) break;
-    if (asm_in_solver) {
-      // the gated assembly inside the pipelined solver's launch (penta_pipe.h PipeAsm): a problem whose step was
-      // rejected keeps g and H and the solver reads them where they are -> the same step
-      DropPrefetch(c, {IDTO_ARR_GRADIENT, IDTO_ARR_H_A, IDTO_ARR_H_B, IDTO_ARR_H_C, IDTO_ARR_HBANDS});
-      c->con_ready = false; c->con_begun = false;
-      SolverExtras ex;
-      ex.assemble = true; ex.gate = c->tr_state + TRS_ACCEPTED; ex.decide = decide_in_solver ? &Dc : nullptr;
-      rc = FactorSolve(c, nullptr, 1, nullptr, nullptr, &sp, ex);
-    } else if (lookahead) {
-      if (nu > 0 && use_kkt && c->kkt_in_asm) {
-        // (the next iteration's KKT system written by this assembly: a rejected step keeps g, H - and the system, which the
-        // solvers only read)
-        idto_hip_ctx* kc = c->kkt;
-        KktSink S{};
-        S.KA = kc->HA; S.KB = kc->HB; S.KC = kc->HC; S.rhs = kc->g; S.K = c->nq + nu; S.nu = nu;
-        S.slab = c->slab; S.slab_stride = (int)c->slab_stride; S.dofs = c->con_dofs;
-        rc = LaunchAssemble(c, c->tr_state + TRS_ACCEPTED, &S, kc->pstride, &kkt_built);
-      } else {
-        rc = LaunchAssemble(c, c->tr_state + TRS_ACCEPTED);
-      }
-      if (!rc && nu == 0) rc = idto_hip_factor_solve(c, nullptr, 1, nullptr);   // (after a rejection: the same H, g -> the same step)
-    } else {
-      rc = idto_hip_gn_step(c);   // (dense cost weights: the partials again, at the iterate)
-    }
-    if (rc) return rc;
   }
   c->fd_full = false; c->partials_ahead = false;
   TRACE("hip: tr_solve: every iteration enqueued");
-  if (B != 1) {
-    // every problem has its own current set: the ones whose iterate ended up in the other set get it copied over
-    // (a single-problem context swaps its pointers instead, below)
+  if (B != 1) {   // (every problem has its own current set)
     if (c->alt_off <= 0) { g_err = "tr_solve: batch contexts keep their primary output set"; return -1; }
-    if (bfetch) {
-      // idto_hip_tr_solve_batch_fetch: state words, rows and the iterates of every problem (only_best: of the best one) packed
-      // by ONE launch, which also chooses the best problem; one copy, one wait (trust_region.h tr_gather_batch_kernel)
-      const size_t nrow = rows_stride;
-      const size_t nqa = (size_t)(c->N + 1) * c->nq, nva = (size_t)(c->N + 1) * c->nv, nta = (size_t)c->N * c->nv;
-      const size_t ntraj = 3 * nqa + nva + nta, head = tr_gather_batch_header(B);
-      const size_t base = head + (size_t)B * (TRS_COUNT + nrow) + (bfetch->only_best ? 1 : (size_t)B) * ntraj;
-      const MpcTickHook* hook = bfetch->mpc;
-      const size_t total = base + (hook ? hook->nguess + hook->nplans : 0);
-      const size_t lds = (size_t)B * (sizeof(double) + sizeof(int));
-      if (lds > 60 * 1024) { g_err = "tr_solve_batch_fetch: the batch is too large for the selecting workgroup's LDS"; return -1; }
-      if (int erc = EnsureFetch(c, total)) return erc;
-      TrGatherBatchArgs G;
-      G.state = c->tr_state; G.rows = c->tr_rows; G.B = B; G.iterations = iterations; G.nrows = (int)nrow;
-      G.only_best = bfetch->only_best ? 1 : 0;
-      G.q = c->q; G.v = c->v; G.slab = c->slab; G.dq = c->tr_dq; G.w = c->tr_w;
-      G.N = c->N; G.nq = c->nq; G.nv = c->nv; G.slab_stride = (int)c->slab_stride;
-      G.alt_off = (long long)c->alt_off; G.pstride = c->pstride;
-      G.out = c->fetch_dev;
-      hipLaunchKernelGGL(tr_gather_batch_kernel, dim3(TR_GATHER_BATCH_GX + 1, B), dim3(256), lds, c->stream, G);
-      HIP_OK(hipGetLastError());
-      if (hook) {
-        // the tick's new plans: fitted on the device from the loop's result, written to the plane that is not in force and
-        // behind the guesses in the same staging buffer (the shift left those there: idto_hip_mpc_batch_replan)
-        MpcBatchState* m = hook->m;
-        MpcStoreArgs S{};
-        S.L = m->L; S.breaks = m->breaks; S.actuated = m->actuated_dev;
-        S.q = c->q; S.q_stride = c->pstride; S.v = c->v; S.v_stride = c->pstride;
-        S.tau = c->slab + 3 * (size_t)c->nv * c->nq; S.tau_stride = c->pstride; S.tau_row = (int)c->slab_stride;
-        S.state = c->tr_state; S.state_stride = c->pstride; S.alt_off = (long long)c->alt_off;
-        S.rows = c->tr_rows; S.iterations = iterations; S.nrows = (int)nrow;
-        S.times = m->tick_dev; S.times_stride = 1 + c->nq + c->nv;
-        S.plan_old = m->plan[m->cur]; S.plan_new = m->plan[m->cur ^ 1]; S.work = m->work;
-        S.out = c->fetch_dev + base + hook->nguess;
-        hipLaunchKernelGGL(mpc_store_kernel, dim3((m->L.dims() + 63) / 64, B), dim3(64), 0, c->stream, S);
-        HIP_OK(hipGetLastError());
-      }
-      HIP_OK(hipMemcpyAsync(c->fetch_pin, c->fetch_dev, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      // (behind the copy: the fold only makes the context's first set the iterate's for the calls that follow)
-      hipLaunchKernelGGL(tr_fold_sets_kernel, dim3(64, B), dim3(256), 0, c->stream, c->v, (size_t)c->alt_off / sizeof(double),
-                         c->tr_state, c->pstride);
-      HIP_OK(hipGetLastError());
-      HIP_OK(hipStreamSynchronize(c->stream));
-      TRACE("hip: tr_solve: waited for the device (every problem's state words, rows and solution back)");
-      const double* p = c->fetch_pin;
-      const int best = (int)p[0];
-      *bfetch->best = best;
-      for (int b = 0; b < B; ++b) { bfetch->final_cost[b] = p[1 + b]; bfetch->status[b] = (int)p[1 + B + b]; }
-      if (hook) {
-        if (hook->guess_out) std::memcpy(hook->guess_out, c->fetch_pin + base, hook->nguess * sizeof(double));
-        if (hook->plans_out) std::memcpy(hook->plans_out, c->fetch_pin + base + hook->nguess, hook->nplans * sizeof(double));
-      }
-      p += head;
-      const double* states = p;
-      for (int b = 0; b < B; ++b, p += TRS_COUNT + nrow) {
-        if (Delta_out) Delta_out[b] = p[TRS_DELTA];
-        std::memcpy(rows_host + (size_t)b * nrow, p + TRS_COUNT, nrow * sizeof(double));
-      }
-      const size_t cnt[5] = {nqa, nva, nta, nqa, nqa};
-      if (!bfetch->only_best || best >= 0) {
-        const size_t T = bfetch->only_best ? 1 : (size_t)B;
-        for (size_t t = 0; t < T; ++t)
-          for (int i = 0; i < 5; ++i) { if (bfetch->out[i]) std::memcpy(bfetch->out[i] + t * cnt[i], p, cnt[i] * sizeof(double)); p += cnt[i]; }
-      }
-      // every problem's outputs are filled; the return value: a time-out first, else whether any factorisation failed
-      int failed = 0;
-      for (int b = 0; b < B; ++b) {
-        const bool singular = ((int)states[(size_t)b * (TRS_COUNT + nrow) + TRS_FLAGS] & TRF_SINGULAR_S) != 0;
-        const int fk = use_kkt ? FactorStatus(c->kkt, b) : 0, fh = FactorStatus(c, b);
-        if (fk == IDTO_HIP_SOLVER_TIMEOUT || fh == IDTO_HIP_SOLVER_TIMEOUT) return IDTO_HIP_SOLVER_TIMEOUT;
-        if ((fk && !singular) || fh || (bfetch->status[b] & TRF_FACTORIZATION)) failed = IDTO_HIP_FACTORIZATION_FAILED;
-      }
-      return failed;
-    }
-    hipLaunchKernelGGL(tr_fold_sets_kernel, dim3(64, B), dim3(256), 0, c->stream, c->v, (size_t)c->alt_off / sizeof(double),
-                       c->tr_state, c->pstride);
-    HIP_OK(hipGetLastError());
-    std::vector<double> st((size_t)B * TRS_COUNT);
-    HIP_OK(hipMemcpy2DAsync(st.data(), TRS_COUNT * sizeof(double), c->tr_state, c->pstride, TRS_COUNT * sizeof(double), (size_t)B,
-                            hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    HIP_OK(hipMemcpy(rows_host, c->tr_rows, (size_t)B * rows_stride * sizeof(double), hipMemcpyDeviceToHost));
-    if (Delta_out) for (int b = 0; b < B; ++b) Delta_out[b] = st[(size_t)b * TRS_COUNT + TRS_DELTA];
-    for (int b = 0; b < B; ++b) {
-      if (use_kkt) {   // (see the single-problem exit below)
-        const int fs = FactorStatus(c->kkt, b);
-        const bool singular = ((int)st[(size_t)b * TRS_COUNT + TRS_FLAGS] & TRF_SINGULAR_S) != 0;
-        if (fs == IDTO_HIP_SOLVER_TIMEOUT || (fs && !singular)) return fs;
-      }
-      if (int fs = FactorStatus(c, b)) return fs;
-    }
-    return 0;
+    return rq.bfetch ? TrFinishBatchFetch(c, rq, rt) : TrFinishBatch(c, rq, rt);
   }
-  if (fetch) {
-    // ... and the solution with them (idto_hip_tr_solve_fetch): one gathering launch, one copy, the same wait
-    const size_t nrow = (size_t)iterations * TRR_COUNT;
-    const size_t nqa = (size_t)(c->N + 1) * c->nq, nva = (size_t)(c->N + 1) * c->nv, nta = (size_t)c->N * c->nv;
-    const size_t total = TRS_COUNT + nrow + nqa + nva + nta + 2 * nqa;
-    if (c->fetch_cap < total) {
-      Release(c, &c->fetch_dev);
-      if (c->fetch_pin) (void)hipHostFree(c->fetch_pin);
-      c->fetch_pin = nullptr; c->fetch_cap = 0;
-      if (Alloc(c, total, &c->fetch_dev)) return -2;
-      HIP_OK(hipHostMalloc((void**)&c->fetch_pin, total * sizeof(double), hipHostMallocDefault));
-      c->fetch_cap = total;
-    }
-    TrGatherArgs G;
-    G.state = c->tr_state; G.rows = c->tr_rows; G.nstate = TRS_COUNT; G.nrows = (int)nrow;
-    G.q = c->q; G.v = c->v; G.slab = c->slab; G.dq = c->tr_dq; G.w = c->tr_w;
-    G.N = c->N; G.nq = c->nq; G.nv = c->nv; G.slab_stride = (int)c->slab_stride;
-    G.alt_off = lookahead ? (long long)c->alt_off : 0;
-    G.out = c->fetch_dev;
-    hipLaunchKernelGGL(tr_gather_kernel, dim3(16), dim3(256), 0, c->stream, G);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(c->fetch_pin, c->fetch_dev, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    TRACE("hip: tr_solve: gather + one copy enqueued");
-    HIP_OK(hipStreamSynchronize(c->stream));
-    TRACE("hip: tr_solve: waited for the device (state words, rows and the solution back)");
-    const double* p = c->fetch_pin;
-    std::memcpy(c->tr_pin, p, TRS_COUNT * sizeof(double)); p += TRS_COUNT;
-    std::memcpy(rows_host, p, nrow * sizeof(double)); p += nrow;
-    const size_t cnt[5] = {nqa, nva, nta, nqa, nqa};
-    for (int i = 0; i < 5; ++i) { if (fetch[i]) std::memcpy(fetch[i], p, cnt[i] * sizeof(double)); p += cnt[i]; }
-  } else {   // the state words and the statistics rows with ONE wait (the rows through pinned staging of the context)
-    const size_t nrow = (size_t)iterations * TRR_COUNT;
-    if (c->rows_cap < nrow) {
-      if (c->rows_pin) (void)hipHostFree(c->rows_pin);
-      c->rows_pin = nullptr; c->rows_cap = 0;
-      HIP_OK(hipHostMalloc((void**)&c->rows_pin, std::max<size_t>(nrow, 64 * TRR_COUNT) * sizeof(double), hipHostMallocDefault));
-      c->rows_cap = std::max<size_t>(nrow, 64 * TRR_COUNT);
-    }
-    HIP_OK(hipMemcpyAsync(c->tr_pin, c->tr_state, TRS_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipMemcpyAsync(c->rows_pin, c->tr_rows, nrow * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    TRACE("hip: tr_solve: waited for the device (state words + rows back)");
-    std::memcpy(rows_host, c->rows_pin, nrow * sizeof(double));
-  }
-  if (Delta_out) *Delta_out = c->tr_pin[TRS_DELTA];
-  if (c->tr_pin[TRS_CUR] != 0.0) {   // the iterate's v, a, N+, slab, products ended up in the other set: it is "the" set now
-    c->v = at_problem(c->v, (size_t)c->alt_off); c->a = at_problem(c->a, (size_t)c->alt_off);
-    c->nplus = at_problem(c->nplus, (size_t)c->alt_off); c->slab = at_problem(c->slab, (size_t)c->alt_off);
-    c->terms = at_problem(c->terms, (size_t)c->alt_off);
-    c->alt_off = -c->alt_off;
-  }
-  if (use_kkt) {
-    // (a multiplier pivot that vanished - redundant constraints, TRF_SINGULAR_S in the rows: the caller's pivoted
-    // factorisation takes over - leaves garbage in the rows of H behind it, whose pivot test then fails as well)
-    const int fs = FactorStatus(c->kkt);
-    const bool singular = ((int)c->tr_pin[TRS_FLAGS] & TRF_SINGULAR_S) != 0;
-    if (fs == IDTO_HIP_SOLVER_TIMEOUT || (fs && !singular)) return fs;
-  }
-  return FactorStatus(c);
+  return rq.fetch ? TrFinishFetch(c, rq, rt) : TrFinishRows(c, rq, rt);
 }
+}  // namespace
 
 int idto_hip_tr_solve(idto_hip_ctx* c, int iterations, int scaling_method, int scaling, int normalize_quaternions,
                       double Delta0, double Delta_max, double eta, const int* constrained_dofs, int nu,
                       double* rows_host, double* Delta_out) {
   if (c->batch != 1) { g_err = "tr_solve serves single-problem contexts (batches: idto_hip_tr_solve_batch)"; return -1; }
-  return TrSolve(c, iterations, scaling_method, scaling, normalize_quaternions, &Delta0, Delta_max, eta, constrained_dofs, nu,
-                 rows_host, Delta_out);
+  return TrSolve(c, TrRequest{iterations, scaling_method, scaling, normalize_quaternions, &Delta0, Delta_max, eta, constrained_dofs, nu, rows_host, Delta_out});
 }
 
 int idto_hip_tr_solve_fetch(idto_hip_ctx* c, int iterations, int scaling_method, int scaling, int normalize_quaternions,
@@ -2802,15 +2798,24 @@ int idto_hip_tr_solve_fetch(idto_hip_ctx* c, int iterations, int scaling_method,
                             double* w_out) {
   if (c->batch != 1) { g_err = "tr_solve_fetch serves single-problem contexts"; return -1; }
   double* const fetch[5] = {q_out, v_out, tau_out, dq_out, w_out};
-  return TrSolve(c, iterations, scaling_method, scaling, normalize_quaternions, &Delta0, Delta_max, eta, constrained_dofs, nu,
-                 rows_host, Delta_out, fetch);
+  return TrSolve(c, TrRequest{iterations, scaling_method, scaling, normalize_quaternions, &Delta0, Delta_max, eta, constrained_dofs, nu, rows_host, Delta_out, fetch});
 }
 
 int idto_hip_tr_solve_batch(idto_hip_ctx* c, int iterations, int scaling_method, int scaling, int normalize_quaternions,
                             const double* Delta0, double Delta_max, double eta, double* rows_host, double* Delta_out) {
   if (!Delta0 || !rows_host) { g_err = "tr_solve_batch: Delta0[batch] and rows_host[batch][iterations][IDTO_TR_ROW] are required"; return -1; }
-  return TrSolve(c, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, nullptr, 0, rows_host,
-                 Delta_out);
+  return TrSolve(c, TrRequest{iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, nullptr, 0, rows_host, Delta_out});
+}
+
+// The options and the |h| column's degrees of freedom of a batch context, given to the single-problem context that advances one of its
+// problems.  (at EVERY call, not only when the child is created - options set on the batch context afterwards, a solver
+// stepped down after a time-out must reach the children, or "rows bit for bit those of idto_hip_tr_solve" breaks silently)
+static int CopyOptionsToChild(const idto_hip_ctx* c, idto_hip_ctx* ch) {
+  ch->gradients_method = c->gradients_method; ch->fd_fast = c->fd_fast; ch->asm_fold = c->asm_fold;
+  ch->solver_pipe = c->solver_pipe; ch->solver_nd = c->solver_nd; ch->two_sided = c->two_sided; ch->fused = c->fused;
+  ch->reference_solver = c->reference_solver; ch->solver_band = c->solver_band; ch->asm_in_solver = c->asm_in_solver;
+  ch->con_kkt = c->con_kkt;
+  return idto_hip_set_unactuated_dofs(ch, c->una_dofs_host.data(), c->una_nu);
 }
 
 // The trust-region loop with ENFORCED equality constraints for every problem of a batch context (BASELINE config 5:
@@ -2824,18 +2829,17 @@ int idto_hip_tr_solve_batch(idto_hip_ctx* c, int iterations, int scaling_method,
 int idto_hip_tr_solve_batch_constrained(idto_hip_ctx* c, int iterations, int scaling_method, int scaling, int normalize_quaternions,
                                         const double* Delta0, double Delta_max, double eta, const int* constrained_dofs, int nu,
                                         double* rows_host, double* Delta_out) {
+  TrRequest rq{iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu, rows_host, Delta_out};
   if (!Delta0 || !rows_host) { g_err = "tr_solve_batch_constrained: Delta0[batch] and rows_host[batch][iterations][IDTO_TR_ROW] are required"; return -1; }
-  if (nu <= 0 || !constrained_dofs)
-    return idto_hip_tr_solve_batch(c, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, rows_host, Delta_out);
+  if (nu <= 0 || !constrained_dofs) { rq.constrained_dofs = nullptr; rq.nu = 0; }   // (idto_hip_tr_solve_batch)
   const int B = c->batch;
-  if (B == 1)
-    return TrSolve(c, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu, rows_host, Delta_out);
+  if (B == 1 || rq.nu == 0) return TrSolve(c, rq);
   // the banded KKT step (kkt.h) is a sequence of launches with grid.y = problem like everything else of the loop: one
   // launch set per iteration for the whole batch.  The Schur-complement route (option con_kkt = 0, or nq + nu > 30) is
   // single-problem launches: a child context, stream and host thread per problem.
-  if (c->con_kkt && idto_host::SolverBlockSize(c->nq + nu, true) <= 30 && c->weights_diagonal) {
+  if (TrKktRoute(c, nu)) {
     if (int rc = idto_hip_eval_tau(c)) return rc;   // (the loop starts from the cost of the resident q; the other route evaluates it per problem)
-    return TrSolve(c, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu, rows_host, Delta_out);
+    return TrSolve(c, rq);
   }
   if (!c->host_model) { g_err = "tr_solve_batch_constrained: the context keeps no host copy of its model"; return -1; }
   HIP_OK(hipSetDevice(c->device));
@@ -2848,16 +2852,9 @@ int idto_hip_tr_solve_batch_constrained(idto_hip_ctx* c, int iterations, int sca
       if (rc) return rc;
       c->children[b] = ch;
     }
-    // (at EVERY call, not only when the child is created - options set on the batch context afterwards, the
-    // |h| column's degrees of freedom, a solver stepped down after a time-out must reach the children, or "rows bit for
-    // bit those of idto_hip_tr_solve" breaks silently)
-    ch->gradients_method = c->gradients_method; ch->fd_fast = c->fd_fast; ch->asm_fold = c->asm_fold;
-    ch->solver_pipe = c->solver_pipe; ch->solver_nd = c->solver_nd; ch->two_sided = c->two_sided; ch->fused = c->fused;
-    ch->reference_solver = c->reference_solver; ch->solver_band = c->solver_band; ch->asm_in_solver = c->asm_in_solver;
-    ch->con_kkt = c->con_kkt;
-    if (int rc = idto_hip_set_unactuated_dofs(ch, c->una_dofs_host.data(), c->una_nu)) return rc;
+    if (int rc = CopyOptionsToChild(c, ch)) return rc;
   }
-  const size_t qbytes = (size_t)(c->N + 1) * c->nq * sizeof(double), row = (size_t)iterations * TRR_COUNT;
+  const size_t qbytes = (size_t)(c->N + 1) * c->nq * sizeof(double);
   std::vector<int> rcs((size_t)B, 0);
   std::vector<std::string> errs((size_t)B);
   auto work = [&](int b) {
@@ -2870,8 +2867,9 @@ int idto_hip_tr_solve_batch_constrained(idto_hip_ctx* c, int iterations, int sca
     ch->fd_full = false; ch->partials_ahead = false; ch->con_ready = false; ch->con_begun = false; ch->trial_resident = false;
     int rc = idto_hip_eval_tau(ch);
     if (rc) return fail(rc, "eval_tau failed");
-    rc = TrSolve(ch, iterations, scaling_method, scaling, normalize_quaternions, Delta0 + b, Delta_max, eta, constrained_dofs, nu,
-                 rows_host + (size_t)b * row, Delta_out ? Delta_out + b : nullptr);
+    TrRequest one = rq;   // problem b's radius, rows and radius out
+    one.Delta0s = Delta0 + b; one.rows_host = rows_host + (size_t)b * iterations * TRR_COUNT; one.Delta_out = Delta_out ? Delta_out + b : nullptr;
+    rc = TrSolve(ch, one);
     if (rc) return fail(rc, "tr_solve failed");
     if (hipMemcpyAsync(at_problem(c->q, (size_t)b * c->pstride), ch->q, qbytes, hipMemcpyDeviceToDevice, ch->stream) != hipSuccess ||
         hipStreamSynchronize(ch->stream) != hipSuccess)
@@ -3024,12 +3022,11 @@ int idto_hip_mpc_batch_shift(idto_hip_ctx* c, const double* times, const double*
   return 0;
 }
 
-// The inside of idto_hip_tr_solve_batch_fetch for a batch of more than one problem; with bf->mpc a controllers' tick
-// (idto_hip_mpc_batch_replan): the shift and idto_hip_eval_tau in front of the loop, the store behind it.
-static int TrSolveBatchFetch(idto_hip_ctx* c, int iterations, int scaling_method, int scaling, int normalize_quaternions,
-                             const double* Delta0, double Delta_max, double eta, const int* constrained_dofs, int nu,
-                             double* rows_host, double* Delta_out, const TrBatchFetch* bf) {
-  if (nu > 0 && !(c->con_kkt && idto_host::SolverBlockSize(c->nq + nu, true) <= 30 && c->weights_diagonal)) {
+// The inside of idto_hip_tr_solve_batch_fetch for a batch of more than one problem (rq.bfetch); with its mpc a controllers'
+// tick (idto_hip_mpc_batch_replan): the shift and idto_hip_eval_tau in front of the loop, the store behind it.
+static int TrSolveBatchFetch(idto_hip_ctx* c, const TrRequest& rq) {
+  const TrBatchFetch* bf = rq.bfetch;
+  if (rq.nu > 0 && !TrKktRoute(c, rq.nu)) {
     g_err = "tr_solve_batch_fetch: these enforced constraints take the child-context route of idto_hip_tr_solve_batch_constrained "
             "(option con_kkt = 0, nq + nu > 30 or dense cost weights: every problem advanced in a single-problem context of "
             "its own), which has no gathered fetch: use idto_hip_tr_solve_batch_constrained + idto_hip_get_batch";
@@ -3039,15 +3036,13 @@ static int TrSolveBatchFetch(idto_hip_ctx* c, int iterations, int scaling_method
   int rc = 0;
   if (bf->mpc) {
     // (the guesses go where the one copy back finds them: behind the fetch's own doubles)
-    const size_t base = BatchFetchDoubles(c, iterations, bf->only_best != 0);
-    if ((rc = EnsureFetch(c, base + bf->mpc->nguess + bf->mpc->nplans)) != 0) return rc;
-    rc = MpcShiftEnqueue(c, bf->mpc->times, bf->mpc->x0, c->fetch_dev + base);
+    const TrFetchLayout L = BatchFetchLayout(c, rq);
+    if ((rc = EnsureFetch(c, L.total())) != 0) return rc;
+    rc = MpcShiftEnqueue(c, bf->mpc->times, bf->mpc->x0, c->fetch_dev + L.guess());
   }
-  if (!rc && (nu > 0 || bf->mpc))
+  if (!rc && (rq.nu > 0 || bf->mpc))
     rc = idto_hip_eval_tau(c);   // (as idto_hip_tr_solve_batch_constrained: the loop starts from the cost of the resident q)
-  if (!rc)
-    rc = TrSolve(c, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu,
-                 rows_host, Delta_out, nullptr, bf);
+  if (!rc) rc = TrSolve(c, rq);
   // (a return from inside the loop's enqueueing: the initial state words travel from pinned memory of the context, which the
   // next call rewrites - wait for what is enqueued)
   if (rc < 0) (void)hipStreamSynchronize(c->stream);
@@ -3060,19 +3055,15 @@ int idto_hip_mpc_batch_replan(idto_hip_ctx* c, const double* times, const double
                               double* v_out, double* tau_out, double* final_cost, int* status, int* best, double* guess_out,
                               double* plans_out) {
   if (int rc = MpcReady(c, "mpc_batch_replan")) return rc;
-  if (!times || !x0 || !Delta0 || !rows_host || !final_cost || !status || !best) {
-    g_err = "mpc_batch_replan: times[batch], x0[batch][nq + nv], Delta0[batch], rows_host[batch][iterations][IDTO_TR_ROW], "
-            "final_cost[batch], status[batch] and best are required";
-    return -1;
-  }
-  if (nu < 0 || (nu > 0 && !constrained_dofs)) { g_err = "mpc_batch_replan: bad constraint arguments"; return -1; }
-  if (iterations <= 0) { g_err = "mpc_batch_replan: iterations must be positive"; return -1; }
+  TrRequest rq{iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu, rows_host, Delta_out};
+  const bool missing = !times || !x0 || !Delta0 || !rows_host || !final_cost || !status || !best;
+  if (int rc = TrCheckArgs("mpc_batch_replan", rq, missing ? "times[batch], x0[batch][nq + nv], Delta0[batch], rows_host[batch][iterations][IDTO_TR_ROW], "
+                                                             "final_cost[batch], status[batch] and best" : nullptr)) return rc;
   if (c->batch < 2) { g_err = "mpc_batch_replan: serves batches of more than one problem (one controller: idto_hip_tr_solve_fetch)"; return -1; }
   MpcBatchState* m = c->mpc;
   MpcTickHook hook{m, times, x0, guess_out, plans_out, (size_t)c->batch * m->L.n * c->nq, (size_t)c->batch * m->L.len()};
-  TrBatchFetch bf{0, {q_out, v_out, tau_out, nullptr, nullptr}, final_cost, status, best, &hook};
-  const int rc = TrSolveBatchFetch(c, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta,
-                                   constrained_dofs, nu, rows_host, Delta_out, &bf);
+  TrBatchFetch bf{0, {q_out, v_out, tau_out, nullptr, nullptr}, final_cost, status, best, &hook}; rq.bfetch = &bf;
+  const int rc = TrSolveBatchFetch(c, rq);
   // the plane the store wrote is in force once the tick counted; a loop that timed out, or a call that failed, leaves every plan
   if (rc == 0 || rc == IDTO_HIP_FACTORIZATION_FAILED) m->cur ^= 1;
   return rc;
@@ -3084,18 +3075,14 @@ int idto_hip_tr_solve_batch_fetch(idto_hip_ctx* c, int iterations, int scaling_m
                                   const double* Delta0, double Delta_max, double eta, const int* constrained_dofs, int nu,
                                   double* rows_host, double* Delta_out, int only_best, double* q_out, double* v_out,
                                   double* tau_out, double* dq_out, double* w_out, double* final_cost, int* status, int* best) {
-  if (!Delta0 || !rows_host || !final_cost || !status || !best) {
-    g_err = "tr_solve_batch_fetch: Delta0[batch], rows_host[batch][iterations][IDTO_TR_ROW], final_cost[batch], status[batch] and best are required";
-    return -1;
-  }
-  if (nu < 0 || (nu > 0 && !constrained_dofs)) { g_err = "tr_solve_batch_fetch: bad constraint arguments"; return -1; }
-  if (iterations <= 0) { g_err = "tr_solve_batch_fetch: iterations must be positive"; return -1; }
-  const int B = c->batch;
-  if (B == 1) {
+  TrRequest rq{iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu, rows_host, Delta_out};
+  const bool missing = !Delta0 || !rows_host || !final_cost || !status || !best;
+  if (int rc = TrCheckArgs("tr_solve_batch_fetch", rq, missing ? "Delta0[batch], rows_host[batch][iterations][IDTO_TR_ROW], final_cost[batch], status[batch] and best" : nullptr))
+    return rc;
+  if (c->batch == 1) {
     // one problem: idto_hip_tr_solve_fetch, and the choice among one made here from what it returned
-    double* const fetch[5] = {q_out, v_out, tau_out, dq_out, w_out};
-    const int rc = TrSolve(c, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu,
-                           rows_host, Delta_out, fetch);
+    double* const fetch[5] = {q_out, v_out, tau_out, dq_out, w_out}; rq.fetch = fetch;
+    const int rc = TrSolve(c, rq);
     if (rc < 0 || rc == IDTO_HIP_SOLVER_TIMEOUT) return rc;
     int f = 0;
     for (int k = 0; k < iterations; ++k) f |= (int)rows_host[(size_t)k * TRR_COUNT + TRR_FLAGS];
@@ -3104,9 +3091,8 @@ int idto_hip_tr_solve_batch_fetch(idto_hip_ctx* c, int iterations, int scaling_m
     *best = ((f & TR_ELIGIBLE_MASK) == 0 && std::isfinite(final_cost[0])) ? 0 : -1;
     return rc;
   }
-  TrBatchFetch bf{only_best ? 1 : 0, {q_out, v_out, tau_out, dq_out, w_out}, final_cost, status, best};
-  return TrSolveBatchFetch(c, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu,
-                           rows_host, Delta_out, &bf);
+  TrBatchFetch bf{only_best ? 1 : 0, {q_out, v_out, tau_out, dq_out, w_out}, final_cost, status, best}; rq.bfetch = &bf;
+  return TrSolveBatchFetch(c, rq);
 }
 
 #define NCCL_OK(expr)                                                                 \

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "batch.h"
+#include "tr_fetch.h"
 
 namespace idto_dev {
 
@@ -817,41 +818,39 @@ __global__ void tr_begin_kernel(double* state, int nstate, int i_delta, int i_ac
 // words, its statistics rows and the iterate's q, v, tau (rows of the slab), the last step dq and w = H^-1 (g + J^T lambda)
 // go into ONE contiguous staging buffer - v and tau from the set the iterate ended up in - so that a single copy and the
 // solve's own wait bring everything to the host (round 4: seven copies, ~4 us each on the device, and a second wait: 65 us
-// of an MPC re-plan).  Layout: [state TRS_COUNT | rows nrows | q | v | tau | dq | w].
+// of an MPC re-plan).  Where each part lies: tr_fetch.h TrFetchLayout, the single-problem form.
+using idto_fetch::TrFetchLayout;
+// one trajectory block [q | v | tau | dq | w] (L.cnt) from `out` on, by the threads tid, tid + nt, ...
+__device__ inline void tr_gather_traj(double* out, const double* q, const double* v, const double* slab, const double* dq,
+                                      const double* w, const TrFetchLayout& L, int nq, int nv, int slab_stride, int tid, int nt) {
+  const int nqa = (int)L.cnt[TrFetchLayout::Q], nva = (int)L.cnt[TrFetchLayout::V], nta = (int)L.cnt[TrFetchLayout::TAU];
+  double *ov = out + nqa, *ot = ov + nva, *od = ot + nta, *ow = od + nqa;
+  for (int i = tid; i < nqa; i += nt) out[i] = q[i];
+  for (int i = tid; i < nva; i += nt) ov[i] = v[i];
+  for (int i = tid; i < nta; i += nt) { const int t = i / nv, r = i - t * nv; ot[i] = slab[(size_t)t * slab_stride + 3 * nv * nq + r]; }
+  for (int i = tid; i < nqa; i += nt) od[i] = dq[i];
+  for (int i = tid; i < nqa; i += nt) ow[i] = w[i];
+}
 struct TrGatherArgs {
-  const double* state; const double* rows; int nstate, nrows;
-  const double* q; const double* v; const double* slab; const double* dq; const double* w;
-  int N, nq, nv, slab_stride;
+  const double* state; const double* rows;   // (a batch: problem 0's state, arenas pstride bytes apart; rows: [B][nrows])
+  const double* q; const double* v; const double* slab; const double* dq; const double* w;   // (a batch: problem 0's)
+  int nq, nv, slab_stride;
   long long alt_off;   // bytes between the two output sets (0: one set)
+  TrFetchLayout L;
   double* out;
 };
 __global__ void tr_gather_kernel(TrGatherArgs A) {
   const int tid = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
   const long long off = (A.alt_off != 0 && A.state[IDTO_TRS_CUR] != 0.0) ? A.alt_off : 0;
-  const double* v = at_problem(A.v, (size_t)off);
-  const double* slab = at_problem(A.slab, (size_t)off);
-  const int nqa = (A.N + 1) * A.nq, nva = (A.N + 1) * A.nv, nta = A.N * A.nv;
-  double* o = A.out;
-  for (int i = tid; i < A.nstate; i += nt) o[i] = A.state[i];
-  o += A.nstate;
-  for (int i = tid; i < A.nrows; i += nt) o[i] = A.rows[i];
-  o += A.nrows;
-  for (int i = tid; i < nqa; i += nt) o[i] = A.q[i];
-  o += nqa;
-  for (int i = tid; i < nva; i += nt) o[i] = v[i];
-  o += nva;
-  for (int i = tid; i < nta; i += nt) { const int t = i / A.nv, r = i - t * A.nv; o[i] = slab[(size_t)t * A.slab_stride + 3 * A.nv * A.nq + r]; }
-  o += nta;
-  for (int i = tid; i < nqa; i += nt) o[i] = A.dq[i];
-  o += nqa;
-  for (int i = tid; i < nqa; i += nt) o[i] = A.w[i];
+  const int nstate = (int)A.L.nstate, nrows = (int)A.L.nrows;
+  for (int i = tid; i < nstate; i += nt) A.out[A.L.state(0) + i] = A.state[i];
+  for (int i = tid; i < nrows; i += nt) A.out[A.L.rows(0) + i] = A.rows[i];
+  tr_gather_traj(A.out + A.L.traj(0), A.q, at_problem(A.v, (size_t)off), at_problem(A.slab, (size_t)off), A.dq, A.w, A.L, A.nq,
+                 A.nv, A.slab_stride, tid, nt);
 }
 
 // The same for a batch (idto_hip_tr_solve_batch_fetch), grid (TR_GATHER_BATCH_GX + 1, problem), together with the choice of
-// the best problem.  Layout of `out`:
-//   [best | final_cost[B] | status[B]]   (doubles; tr_gather_batch_header)
-//   B x [state TRS_COUNT | rows nrows]
-//   T x [q | v | tau | dq | w]            T = B, or - only_best - 1: the best problem's
+// the best problem.  Where each part of `out` lies: tr_fetch.h TrFetchLayout, the batch form.
 // v and tau of a problem come from the set its own TRS_CUR names.  final_cost = TRS_COST, status = the OR of the rows' flags;
 // eligible: none of TRF_DOGLEG / NONFINITE / NOT_DESCENT / SINGULAR_S / FACTORIZATION and a finite cost; best = the eligible
 // problem of the lowest cost, the lowest index among equals, -1: none.  The choice reads state words and rows only - inputs
@@ -860,16 +859,7 @@ __global__ void tr_gather_kernel(TrGatherArgs A) {
 // workgroups make the same choice themselves (B state words and B x iterations flag words: nothing to wait for).
 constexpr int TR_GATHER_BATCH_GX = 16;
 constexpr int TR_ELIGIBLE_MASK = TRF_DOGLEG | TRF_NONFINITE | TRF_NOT_DESCENT | TRF_SINGULAR_S | TRF_FACTORIZATION;
-__host__ __device__ inline size_t tr_gather_batch_header(int B) { return 1 + 2 * (size_t)B; }
-struct TrGatherBatchArgs {
-  const double* state; const double* rows;   // state: problem 0's (arenas pstride bytes apart); rows: [B][nrows]
-  int B, iterations, nrows, only_best;
-  const double* q; const double* v; const double* slab; const double* dq; const double* w;   // problem 0's
-  int N, nq, nv, slab_stride;
-  long long alt_off;
-  size_t pstride;
-  double* out;
-};
+struct TrGatherBatchArgs : TrGatherArgs { int B, iterations, nrows, only_best; size_t pstride; };
 // (LDS: B doubles + B ints)
 __device__ inline int tr_select_best(const TrGatherBatchArgs& A, double* cost, int* status) {
   __shared__ int best_s;
@@ -898,12 +888,11 @@ __global__ void tr_gather_batch_kernel(TrGatherBatchArgs A) {
   double* cost = gb_lds;
   int* status = reinterpret_cast<int*>(gb_lds + A.B);
   const int b = blockIdx.y;
-  const size_t head = tr_gather_batch_header(A.B), nblk = (size_t)TRS_COUNT + A.nrows;
   if (blockIdx.x == TR_GATHER_BATCH_GX) {   // the selecting workgroup
     if (b != 0) return;
     const int best = tr_select_best(A, cost, status);
-    if (threadIdx.x == 0) A.out[0] = (double)best;
-    for (int i = threadIdx.x; i < A.B; i += blockDim.x) { A.out[1 + i] = cost[i]; A.out[1 + A.B + i] = (double)status[i]; }
+    if (threadIdx.x == 0) A.out[A.L.header()] = (double)best;
+    for (int i = threadIdx.x; i < A.B; i += blockDim.x) { A.out[A.L.final_cost() + i] = cost[i]; A.out[A.L.status() + i] = (double)status[i]; }
     return;
   }
   int slot = b;
@@ -915,28 +904,12 @@ __global__ void tr_gather_batch_kernel(TrGatherBatchArgs A) {
   const size_t po = (size_t)b * A.pstride;
   const double* st = at_problem(A.state, po);
   const double* rows = A.rows + (size_t)b * A.nrows;
-  double* o = A.out + head + (size_t)b * nblk;
-  for (int i = tid; i < TRS_COUNT; i += nt) o[i] = st[i];
-  o += TRS_COUNT;
-  for (int i = tid; i < A.nrows; i += nt) o[i] = rows[i];
+  for (int i = tid; i < TRS_COUNT; i += nt) A.out[A.L.state(b) + i] = st[i];
+  for (int i = tid; i < A.nrows; i += nt) A.out[A.L.rows(b) + i] = rows[i];
   if (slot < 0) return;
   const size_t off = po + (size_t)((A.alt_off != 0 && st[IDTO_TRS_CUR] != 0.0) ? A.alt_off : 0);
-  const double* v = at_problem(A.v, off);
-  const double* slab = at_problem(A.slab, off);
-  const double* q = at_problem(A.q, po);
-  const double* dq = at_problem(A.dq, po);
-  const double* w = at_problem(A.w, po);
-  const int nqa = (A.N + 1) * A.nq, nva = (A.N + 1) * A.nv, nta = A.N * A.nv;
-  o = A.out + head + (size_t)A.B * nblk + (size_t)slot * (3 * (size_t)nqa + nva + nta);
-  for (int i = tid; i < nqa; i += nt) o[i] = q[i];
-  o += nqa;
-  for (int i = tid; i < nva; i += nt) o[i] = v[i];
-  o += nva;
-  for (int i = tid; i < nta; i += nt) { const int t = i / A.nv, r = i - t * A.nv; o[i] = slab[(size_t)t * A.slab_stride + 3 * A.nv * A.nq + r]; }
-  o += nta;
-  for (int i = tid; i < nqa; i += nt) o[i] = dq[i];
-  o += nqa;
-  for (int i = tid; i < nqa; i += nt) o[i] = w[i];
+  tr_gather_traj(A.out + A.L.traj(slot), at_problem(A.q, po), at_problem(A.v, off), at_problem(A.slab, off), at_problem(A.dq, po),
+                 at_problem(A.w, po), A.L, A.nq, A.nv, A.slab_stride, tid, nt);
 }
 
 // batch contexts after idto_hip_tr_solve_batch: a problem whose iterate's v, a, N+, slab and products ended up in the

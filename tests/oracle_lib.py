@@ -287,17 +287,22 @@ def penta_make_dense(A, B, C_, D, E):
     return M.T.copy()
 
 
-def refined_solution(Hd, rhs, steps=6):
+def refined_solution(Hd, rhs, steps=6, half_bandwidth=None):
     """Extended-precision reference solution of H x = rhs (H dense, symmetric positive definite): iterative
     refinement with the residual and the accumulated solution in 80-bit long double (numpy.longdouble;
     x86 extended precision, eps = 1.1e-19), run twice with two different working factorisations
     (LAPACK Cholesky and pivoted LU).  Returns (x, uncertainty): x as float64 and the relative max-norm
     distance between the two runs - the accuracy to which x itself is known (~cond * 1e-19).
     This is the yardstick the solver parity tests measure BOTH device solvers against: the
-    reference's algorithm (pivoted-LU block Thomas) and the production block LDL^T."""
+    reference's algorithm (pivoted-LU block Thomas) and the production block LDL^T.
+    half_bandwidth w: H[i, j] = 0 for |i - j| > w (checked) - the same two runs with LAPACK's band Cholesky and band
+    pivoted LU as the working factorisations and the long-double residual formed from the 2 w + 1 diagonals: what the
+    systems of a few thousand unknowns cost is then the band's share of the dense work."""
     import scipy.linalg as sl
     assert np.finfo(np.longdouble).eps < 1e-18, "long double is not extended precision on this platform"
     Hd = np.asarray(Hd, dtype=np.float64)
+    if half_bandwidth is not None:
+        return _refined_solution_banded(Hd, np.asarray(rhs, dtype=np.float64).ravel(), steps, int(half_bandwidth))
     Hl, bl = Hd.astype(np.longdouble), np.asarray(rhs, dtype=np.float64).ravel().astype(np.longdouble)
     outs = []
     for kind in ("cho", "lu"):
@@ -307,6 +312,37 @@ def refined_solution(Hd, rhs, steps=6):
         for _ in range(steps):
             r = bl - Hl @ x
             x = x + solve(r.astype(np.float64)).astype(np.longdouble)
+        outs.append(x)
+    nrm = float(np.abs(outs[0]).max()) + 1e-300
+    return outs[0].astype(np.float64), float(np.abs(outs[0] - outs[1]).max()) / nrm
+
+
+def _refined_solution_banded(Hd, b, steps, w):
+    import scipy.linalg as sl
+    size = Hd.shape[0]
+    assert not np.triu(Hd, w + 1).any() and not np.tril(Hd, -w - 1).any(), "entries outside the band"
+    ab = np.zeros((2 * w + 1, size))          # LAPACK band storage: ab[w + i - j, j] = H[i, j]
+    for d in range(-w, w + 1):                # d = j - i
+        if d >= 0:
+            ab[w - d, d:] = np.diagonal(Hd, d)
+        else:
+            ab[w - d, :size + d] = np.diagonal(Hd, d)
+    abl, bl = ab.astype(np.longdouble), b.astype(np.longdouble)
+
+    def residual(x):
+        r = bl.copy()
+        for d in range(-w, w + 1):
+            if d >= 0:
+                r[:size - d] -= abl[w - d, d:] * x[d:]
+            else:
+                r[-d:] -= abl[w - d, :size + d] * x[:size + d]
+        return r
+    cb = sl.cholesky_banded(ab[w:], lower=True)
+    outs = []
+    for solve in (lambda r: sl.cho_solve_banded((cb, True), r), lambda r: sl.solve_banded((w, w), ab, r)):
+        x = solve(b).astype(np.longdouble)
+        for _ in range(steps):
+            x = x + solve(residual(x).astype(np.float64)).astype(np.longdouble)
         outs.append(x)
     nrm = float(np.abs(outs[0]).max()) + 1e-300
     return outs[0].astype(np.float64), float(np.abs(outs[0] - outs[1]).max()) / nrm

@@ -224,9 +224,10 @@ def case(k, n, cond_target):
     H = banded_spd(n, k, cond_target, seed=1000 * k + n)
     bands = from_lower_dense(H, n, k)
     b = H @ np.linspace(-3, 12.4, n * k)
-    # (three refinement steps gain more than the nineteen digits there are at LONG_COND: the long-double products of
-    # the long horizons are what a case costs)
-    x_ref, unc = ol.refined_solution(H, b, steps=3 if (k, n) in LONG else 6)
+    # (three refinement steps gain more than the nineteen digits there are at LONG_COND; the long horizons' systems of
+    # ~3500 unknowns go through the band factorisations: dense ones and dense long-double products cost seconds)
+    long = (k, n) in LONG
+    x_ref, unc = ol.refined_solution(H, b, steps=3 if long else 6, half_bandwidth=3 * k - 1 if long else None)
     for a in (H, b, x_ref) + tuple(bands):
         a.setflags(write=False)
     return SimpleNamespace(k=k, n=n, K=solver_block_size(k), target=cond_target, H=H, bands=bands, b=b, x_ref=x_ref, unc=unc,

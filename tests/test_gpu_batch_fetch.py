@@ -10,6 +10,7 @@ import pytest
 from idto_amd import hip
 from idto_amd.problem import SCALING
 from oracle_lib import Oracle
+from test_dense_weights import balanced_dense_problem
 from test_gpu_batch import _problems, _same
 
 pytestmark = pytest.mark.gpu
@@ -200,6 +201,49 @@ def test_a_context_of_one_equals_tr_solve_fetch():
         assert np.array_equal(r0[:, COLS], r1[:, COLS]) and d0 == d1
         for k in TRAJ:
             assert _same(t0[k], t1[k]), (name, k)
+
+
+# name, N, constraints enforced, option con_kkt, dense cost weights
+ROUTES = {"small launch": ("acrobot", 3, False, 1, False), "small launch, one constraint": ("acrobot", 3, True, 1, False),
+          "kkt": ("hopper", 4, True, 1, False), "schur chain": ("hopper", 4, True, 0, False),
+          "dense weights, no lookahead": ("hopper", 4, False, 1, True)}
+
+
+@pytest.mark.parametrize("route", list(ROUTES))
+def test_tr_solve_fetch_equals_tr_solve_and_get_on_every_route(route):
+    """the single-problem fetch against idto_hip_tr_solve + idto_hip_get, on the routes through the loop that the batch
+    cases above do not take.  3 iterations whose accepted steps are odd in number: the iterate ends in the SECOND output set
+    (TRS_CUR != 0), where a gather that reads the wrong set, or a wrong swap behind it, shows in v and tau"""
+    name, n, constrained, kkt, dense = ROUTES[route]
+    if dense:
+        model, prob, sp, q = balanced_dense_problem(name, n)
+    else:
+        model, probs, sp, qs = _problems(name, n, 2)
+        prob, q = probs[1], qs[1]
+    dofs = list(model.unactuated_dofs) if constrained else []
+    assert bool(dofs) == constrained
+    res = []
+    for fetch in (False, True):
+        dev = hip.HipPath(model, prob, sp)
+        dev.set_option("con_kkt", kkt)
+        dev.set_q(q)
+        dev.eval_tau()
+        if fetch:
+            res.append(dev.tr_solve_fetch(3, SM, True, False, 0.15, 1e5, constrained_dofs=dofs))
+        else:
+            rows, delta = dev.tr_solve(3, SM, True, False, 0.15, 1e5, constrained_dofs=dofs)
+            res.append((rows, delta, {k.replace("tr_", ""): dev.get(k) for k in ("q", "v", "tau", "tr_dq", "tr_w")}))
+        assert dev.solver_status() == (False, 0)
+        dev.close()
+    (r0, d0, t0), (r1, d1, t1) = res
+    assert r0[:, 9].sum() % 2 == 1, ("the case tests nothing: the iterate ends in the first output set", r0[:, 9])
+    assert np.array_equal(r0[:, COLS], r1[:, COLS]) and d0 == d1
+    # (OPEN DEFECT, older than this test: without the two-set evaluation tr_decide still flips TRS_CUR on an accepted step and the
+    # single-problem epilogue of idto_hip_tr_solve follows it, so idto_hip_get reads v and tau from a set that route never writes,
+    # while the fetch reads the set that was written.  Until that is fixed the single-set arrays are what can be compared on this
+    # route; then `dense` leaves this line and v, tau are compared like everywhere else.)
+    for k in (("q", "dq", "w") if dense else TRAJ):
+        assert _same(np.reshape(t0[k], t1[k].shape), t1[k]), (route, k)   # (idto_hip_get hands dq and w back flat)
 
 
 def test_the_child_context_route_is_refused(monkeypatch):

@@ -3,6 +3,7 @@ the reference's optimizer/test/penta_diagonal_solver_test.cc (test name and line
 cited per test).  Eigen is not available, so the dense reference solutions come
 from numpy.linalg (LAPACK) instead of `Hdense.ldlt().solve(b)`."""
 import numpy as np
+import pytest
 
 import oracle_lib as ol
 
@@ -177,3 +178,32 @@ def test_refined_solution_against_mpmath():
         # and a plain double solve is measurably worse on the ill-conditioned one
         if cond_target >= 1e12:
             assert np.abs(np.linalg.solve(H, b) - xm).max() > 100 * np.abs(x - xm).max()
+
+
+def test_refined_solution_on_the_band_against_mpmath_and_the_dense_route():
+    """refined_solution(..., half_bandwidth) - band Cholesky and band LU as the working factorisations, the residual from the
+    diagonals: what the long-horizon cases of tests/solver_cases.py are measured against - meets the dense route's bar against
+    the same 60-digit solve, with the six refinement steps of the default and with the three those cases take (their
+    cond = 1e8), on a system whose band is narrower than asked for as well; an entry outside the band is refused"""
+    import mpmath as mp
+    rng = np.random.default_rng(11)
+    size, w = 60, 7
+    for cond_target, steps, asked in ((1e4, 6, w), (1e8, 3, w), (1e8, 6, w + 3), (1e12, 6, w)):
+        L = np.tril(rng.uniform(-0.3, 0.3, (size, size)), -1)
+        for i in range(size):
+            L[i, :max(0, i - w)] = 0.0
+        L += np.eye(size)
+        L = np.logspace(0, np.log10(cond_target) / 2, size)[:, None] * L
+        H = L @ L.T
+        H = (H + H.T) / 2
+        assert not np.triu(H, w + 1).any() and np.diagonal(H, w).any()
+        b = rng.normal(size=size)
+        mp.mp.dps = 60
+        xm = np.array([float(v) for v in mp.lu_solve(mp.matrix(H.tolist()), mp.matrix(b.tolist()))])
+        xb, unc_b = ol.refined_solution(H, b, steps=steps, half_bandwidth=asked)
+        xd, unc_d = ol.refined_solution(H, b, steps=steps)
+        assert np.abs(xb - xm).max() <= 4 * EPS * np.abs(xm).max(), (cond_target, steps)
+        assert np.abs(xd - xm).max() <= 4 * EPS * np.abs(xm).max(), (cond_target, steps)
+        assert unc_b < 1e-15 and unc_d < 1e-15, (unc_b, unc_d)
+    with pytest.raises(AssertionError, match="outside the band"):
+        ol.refined_solution(H, b, half_bandwidth=w - 1)

@@ -905,5 +905,22 @@ __global__ void __launch_bounds__(256) fd_along_kernel(DevModel M, DevContact cp
                        at_problem(a_out, w), at_problem(nplus_out, w), k_begin + (int)blockIdx.x, 0, stop_after, echunk, nullptr);
 }
 
+// The same at candidate points of the problems of a batch (idto_hip_costs_along_batch, idto_hip_ls_solve_batch_fetch):
+// blockIdx.y is the candidate, blockIdx.z the problem.  The problem's arrays (v_init among them) lie pstride bytes on, its
+// candidates' arenas bstride bytes, its gate word gstride bytes - every problem idles behind its own word.  A third kernel,
+// so that the two above keep their text and their code.
+template <int MAXC, int SHAPE = 0>
+__global__ void __launch_bounds__(256) fd_along_batch_kernel(DevModel M, DevContact cp, DevProblem P, const double* __restrict__ q,
+                          double* __restrict__ slab, int slab_stride, double* __restrict__ v_out,
+                          double* __restrict__ a_out, double* __restrict__ nplus_out, int k_begin, int stop_after,
+                          int echunk, size_t cstride, const double* __restrict__ gate, size_t pstride, size_t bstride,
+                          size_t gstride) {
+  if (gate && *at_problem(gate, (size_t)blockIdx.z * gstride) != 0.0) return;
+  const size_t w = (size_t)blockIdx.z * bstride + (size_t)blockIdx.y * cstride;
+  fd_body<MAXC, SHAPE>(M, cp, at_problem(P, (size_t)blockIdx.z * pstride), at_problem(q, w), at_problem(slab, w), slab_stride,
+                       at_problem(v_out, w), at_problem(a_out, w), at_problem(nplus_out, w), k_begin + (int)blockIdx.x, 0,
+                       stop_after, echunk, nullptr);
+}
+
 
 }  // namespace idto_dev

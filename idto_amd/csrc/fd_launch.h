@@ -25,6 +25,9 @@ struct FdLaunch {
   AltSel alt;
   const double* gate = nullptr;   // a device word: the launch returns at once when it is not 0.0
   size_t cstride = 0;   // != 0: grid.y counts candidate points of one problem, cstride bytes apart: fd_along_kernel, mode 0
+  // along_batch: grid.z counts the problems of a batch as well (fd_along_batch_kernel): their arrays pstride bytes apart, their
+  // candidates' arenas bstride bytes, their gate words gstride bytes
+  bool along_batch = false; size_t bstride = 0, gstride = 0;
   int shape;   // id_fast.h: the model's instantiated tree shape, 0: id_eval<MAXC>, SHAPE_XCH: id_eval<8, true> (shared pairs), SHAPE_STEM: id_eval<8, true, true>
   int maxc;
 };

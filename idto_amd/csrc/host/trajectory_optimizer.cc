@@ -1631,6 +1631,63 @@ void TO::SolveBatch(const std::vector<std::vector<VectorXd>>& q_guesses, const s
       Check(rc);
     }
   }
+  // The linesearch method: the device's batch linesearch loop (idto_hip_ls_solve_batch_fetch: every iteration of every entry
+  // enqueued at once, one wait) serves what the single problem's device loop serves (LinesearchLoopEligible: scaling off,
+  // no enforced constraints, the banded solver, no debug switches, at most IDTO_LS_MAX_CANDIDATES linesearch iterations, no
+  // forced host loop) on one device with verbose off and diagonal weights in every entry.
+  bool ls_route = B >= 2 && params_.method == kLinesearch && shard_ctx_.empty() && !params_.verbose && LinesearchLoopEligible();
+  for (int b = 0; ls_route && b < B; ++b) ls_route = DiagonalWeights(*probs[b]);
+  if (ls_route) {
+    BatchContext* bc = GetBatchContext(B, probs);
+    const std::size_t nqa = (std::size_t)num_vars(), nva = (std::size_t)(num_steps() + 1) * nv_, nta = (std::size_t)num_steps() * nv_;
+    const int iters = params_.max_iterations;
+    for (int b = 0; b < B; ++b)
+      for (int t = 0; t <= num_steps(); ++t)
+        std::copy(q_guesses[b][t].begin(), q_guesses[b][t].end(), bc->q.begin() + b * nqa + (std::size_t)t * nq_);
+    Check(idto_hip_set_q_batch(bc->ctx, bc->q.data()));
+    Check(idto_hip_set_unactuated_dofs(bc->ctx, unactuated_dofs_.data(), (int)unactuated_dofs_.size()));
+    static_assert(IDTO_LS_ROW <= IDTO_TR_ROW, "GetBatchContext sizes the rows for the trust-region loop's");
+    const int rc = idto_hip_ls_solve_batch_fetch(bc->ctx, iters, static_cast<int>(params_.linesearch_method),
+                                                 params_.max_linesearch_iterations, params_.normalize_quaternions ? 1 : 0,
+                                                 bc->rows.data(), bc->sol_q.data(), bc->sol_v.data(), bc->sol_tau.data(),
+                                                 bc->final_cost.data(), bc->status.data());
+    idto_hip_trace_mark("opt: idto_hip_ls_solve_batch_fetch returned");
+    if (rc == 0 || rc == IDTO_HIP_FACTORIZATION_FAILED) {
+      std::fill(alone.begin(), alone.end(), 0);
+      const double total = std::chrono::duration<double>(clock::now() - start_time).count();
+      for (int b = 0; b < B; ++b) {
+        ClearStats(&out->stats[b]);
+        ClearSolution(&out->solutions[b]);
+        out->errors[b].clear();
+        internal::LsRowsResult r;
+        internal::LsRowsToStats(bc->rows.data() + (std::size_t)b * iters * IDTO_LS_ROW, iters, total, params_.linesearch_method,
+                                &out->stats[b], &r);
+        out->flags[b] = r.flag;
+        out->final_costs[b] = bc->final_cost[b];
+        // (backtracking undecided within the device's candidates: the entry is solved again alone, where the host loop takes over)
+        if (r.outcome == internal::LsRowsOutcome::kNeedsHostLoop) { alone[b] = 1; continue; }
+        if (r.outcome != internal::LsRowsOutcome::kDone) {   // the entry's own failure, with the host loop's text
+          out->flags[b] = SolverFlag::kFactorizationFailed;
+          out->errors[b] = r.error;
+          out->final_costs[b] = std::numeric_limits<double>::quiet_NaN();
+          continue;
+        }
+        if (!Usable(r.flag)) out->final_costs[b] = std::numeric_limits<double>::quiet_NaN();   // (kLinesearchMaxIters: as the entry alone)
+        Vec tmp;
+        tmp.assign(bc->sol_q.begin() + b * nqa, bc->sol_q.begin() + (b + 1) * nqa);
+        UnflattenInto(tmp, num_steps() + 1, nq_, &out->solutions[b].q);
+        tmp.assign(bc->sol_v.begin() + b * nva, bc->sol_v.begin() + (b + 1) * nva);
+        UnflattenInto(tmp, num_steps() + 1, nv_, &out->solutions[b].v);
+        tmp.assign(bc->sol_tau.begin() + b * nta, bc->sol_tau.begin() + (b + 1) * nta);
+        UnflattenInto(tmp, num_steps(), nv_, &out->solutions[b].tau);
+      }
+      batch_route = true;
+    } else if (rc == IDTO_HIP_SOLVER_TIMEOUT) {
+      // a solver launch's workgroups timed out on a shared device: every entry runs alone (alone[] says so already)
+    } else {
+      Check(rc);
+    }
+  }
   last_batch_route_ = batch_route ? 1 : 0;
   for (int b = 0; b < B; ++b)
     if (alone[b]) SolveBatchEntryAlone(problems ? probs[b] : nullptr, q_guesses[b], b, out);

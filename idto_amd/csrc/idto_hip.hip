@@ -313,6 +313,11 @@ struct idto_hip_ctx {
   double *ls_state = nullptr, *ls_rows = nullptr, *ls_work = nullptr; idto_ls::LsScan* ls_scan = nullptr; int ls_rows_cap = 0;
   double* ls_fetch_pin = nullptr; size_t ls_fetch_cap = 0;
   int ls_waves = 0, ls_solves = 0, compute_units = 0;
+  // (a batch context: every one of them per problem - arenas [batch][ls_cap], costs and their staging [batch][64], state
+  // words, scans, rows [batch][ls_rows_cap], work vectors) idto_hip_ls_solve_batch_fetch: the device side of the staging that
+  // ls_gather_batch_kernel packs (ls_fetch.h), calls so far
+  double* ls_fetch_dev = nullptr; size_t ls_fetch_dev_cap = 0;
+  int ls_batch_solves = 0;
   char* prob_pin = nullptr; size_t prob_pin_bytes = 0;   // ... of the problem arrays (UploadProblemArrays)
   double* many_pin = nullptr; size_t many_cap = 0;        // ... of idto_hip_get_many
   double* rows_pin = nullptr; size_t rows_cap = 0;        // ... of idto_hip_tr_solve's statistics rows
@@ -586,7 +591,8 @@ static bool FoldTerms(const idto_hip_ctx* c, int mode) { return c->asm_fold && c
 // along (idto_hip_costs_along, mode 0): the launch evaluates `m` candidate points of the context's one problem instead
 // of the resident q - grid.y = candidate, q and the outputs in arenas of their own (linesearch.h LsArena), nothing of the
 // resident iterate is written
-struct FdAlong { const double* q; double *slab, *v, *a, *nplus; int slab_stride; size_t cstride; int m; const double* gate; };
+// (a batch context: grid.z = problem - the problems' arenas bstride bytes apart, their gate words gstride bytes)
+struct FdAlong { const double* q; double *slab, *v, *a, *nplus; int slab_stride; size_t cstride; int m; const double* gate; size_t bstride = 0, gstride = 0; };
 int LaunchFd(idto_hip_ctx* c, int mode, int kb, int ke, AltSel alt = AltSel{nullptr, 0, 0}, const FdAlong* along = nullptr) {
   if (!along) c->partials_ahead = false;   // (whatever idto_hip_eval_tau_partials left is about to be overwritten; it sets the flag after its own launch)
   if (ke <= kb) return 0;
@@ -611,6 +617,10 @@ int LaunchFd(idto_hip_ctx* c, int mode, int kb, int ke, AltSel alt = AltSel{null
   if (along) {
     fl.q = along->q; fl.slab = along->slab; fl.slab_stride = along->slab_stride; fl.v = along->v; fl.a = along->a;
     fl.nplus = along->nplus; fl.cstride = along->cstride; fl.gate = along->gate;
+    if (c->batch > 1) {
+      fl.grid = dim3(ke - kb, along->m, c->batch);
+      fl.along_batch = true; fl.bstride = along->bstride; fl.gstride = along->gstride;
+    }
   }
   fl.shape = c->fd_fast ? c->M.fast_shape : 0;   // id_fast.h: the straight-line evaluation of the model's tree shape
   if (c->M.nxb) fl.shape = SHAPE_XCH;             // shared pairs: the generic evaluation with the exchange (whatever fd_fast says)
@@ -1204,16 +1214,22 @@ int idto_hip_ls_alphas(int linesearch_method, int m, double* alphas_host) {
 
 // the candidates' arenas for m step lengths (grown to the largest m asked for; they hold nothing between calls), their
 // costs and the costs' pinned staging
+// (a batch context: m arenas, IDTO_LS_MAX_CANDIDATES costs for every problem - [problem][candidate])
 static int LsEnsureArenas(idto_hip_ctx* c, int m) {
   const LsArena A = ls_arena(c->N, c->nq, c->nv);
+  const size_t B = (size_t)c->batch;
   if (c->ls_cap < m) {
     Release(c, &c->ls_arenas);
     c->ls_cap = 0;
-    if (Alloc(c, A.stride * (size_t)m, &c->ls_arenas)) return -2;
+    if (Alloc(c, A.stride * (size_t)m * B, &c->ls_arenas)) {
+      g_err = "linesearch: the candidates' arenas could not be allocated (" + std::to_string(A.stride * (size_t)m * B * sizeof(double)) +
+              " bytes for " + std::to_string(B) + " problems x " + std::to_string(m) + " candidates): " + g_err;
+      return -2;
+    }
     c->ls_cap = m;
   }
-  if (!c->ls_costs && Alloc(c, (size_t)IDTO_LS_MAX_CANDIDATES, &c->ls_costs)) return -2;
-  if (!c->ls_pin) HIP_OK(hipHostMalloc((void**)&c->ls_pin, IDTO_LS_MAX_CANDIDATES * sizeof(double), hipHostMallocDefault));
+  if (!c->ls_costs && Alloc(c, B * IDTO_LS_MAX_CANDIDATES, &c->ls_costs)) return -2;
+  if (!c->ls_pin) HIP_OK(hipHostMalloc((void**)&c->ls_pin, B * IDTO_LS_MAX_CANDIDATES * sizeof(double), hipHostMallocDefault));
   return 0;
 }
 
@@ -1222,16 +1238,21 @@ static int LsEvaluate(idto_hip_ctx* c, const LsAlphas& al, int first, int m, int
                       const double* alpha_dev) {
   const int N = c->N, nq = c->nq, nv = c->nv, n = (N + 1) * nq;
   const LsArena A = ls_arena(N, nq, nv);
-  hipLaunchKernelGGL(ls_trial_kernel, dim3(m), dim3(256), 0, c->stream, n, nq, c->q, c->step, al, c->tr_quat,
-                     normalize_quaternions ? c->tr_nquat : 0, c->ls_arenas, A.stride, first, gate, alpha_dev);
+  // (a batch context: the same candidates of every problem - the problems' arenas pcstride doubles apart, their costs
+  // IDTO_LS_MAX_CANDIDATES, their gate / alpha words LSS_COUNT)
+  const size_t pcstride = (size_t)c->ls_cap * A.stride, gstride = LSS_COUNT, cstride = IDTO_LS_MAX_CANDIDATES;
+  hipLaunchKernelGGL(ls_trial_kernel, dim3(m, c->batch), dim3(256), 0, c->stream, n, nq, c->q, c->step, al, c->tr_quat,
+                     normalize_quaternions ? c->tr_nquat : 0, c->ls_arenas, A.stride, first, gate, alpha_dev, c->pstride,
+                     pcstride, gstride);
   HIP_OK(hipGetLastError());
   double* base = c->ls_arenas + (size_t)first * A.stride;
   FdAlong along;
   along.q = base + A.q; along.slab = base + A.slab; along.slab_stride = nv; along.v = base + A.v; along.a = base + A.a;
   along.nplus = base + A.nplus; along.cstride = A.stride * sizeof(double); along.m = m; along.gate = gate;
+  along.bstride = pcstride * sizeof(double); along.gstride = gstride * sizeof(double);
   if (int rc = LaunchFd(c, 0, 0, N, AltSel{nullptr, 0, 0}, &along)) return rc;
-  hipLaunchKernelGGL(ls_cost_kernel, dim3(m), dim3(1024), c->cost_lds, c->stream, c->M, c->P, c->ls_arenas, A,
-                     c->weights_diagonal ? 1 : 0, c->ls_costs, first, gate);
+  hipLaunchKernelGGL(ls_cost_kernel, dim3(m, c->batch), dim3(1024), c->cost_lds, c->stream, c->M, c->P, c->ls_arenas, A,
+                     c->weights_diagonal ? 1 : 0, c->ls_costs, first, gate, c->pstride, pcstride, cstride, gstride);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -1255,12 +1276,77 @@ int idto_hip_costs_along(idto_hip_ctx* c, const double* alphas_host, int m, int 
   return 0;
 }
 
-static int LsSolve(idto_hip_ctx* c, int iterations, int method, int max_ls, int normalize_quaternions, double* rows_host,
-                   double* q_out, double* v_out, double* tau_out) {
+// the same m step lengths along every problem's own step: one launch set, one wait; costs_host[batch][m]
+int idto_hip_costs_along_batch(idto_hip_ctx* c, const double* alphas_host, int m, int normalize_quaternions, double* costs_host) {
   HIP_OK(hipSetDevice(c->device));
-  if (c->batch != 1) { g_err = "ls_solve serves single-problem contexts"; return -1; }
-  if (iterations < 1 || !rows_host || (method != idto_ls::kArmijo && method != idto_ls::kBacktracking)) {
-    g_err = "ls_solve: bad arguments";
+  if (c->batch < 2) { g_err = "costs_along_batch serves batch contexts (idto_hip_costs_along: a single problem)"; return -1; }
+  if (!alphas_host || !costs_host || m < 1 || m > IDTO_LS_MAX_CANDIDATES) {
+    g_err = "costs_along_batch: 1 .. IDTO_LS_MAX_CANDIDATES step lengths and room for their costs";
+    return -1;
+  }
+  TRACE("hip: costs_along_batch begins");
+  if (int rc = LsEnsureArenas(c, m)) return rc;
+  LsAlphas al;
+  for (int j = 0; j < IDTO_LS_MAX_CANDIDATES; ++j) al.a[j] = j < m ? alphas_host[j] : 0.0;
+  if (int rc = LsEvaluate(c, al, 0, m, normalize_quaternions, nullptr, nullptr)) return rc;
+  HIP_OK(hipMemcpyAsync(c->ls_pin, c->ls_costs, (size_t)c->batch * IDTO_LS_MAX_CANDIDATES * sizeof(double), hipMemcpyDeviceToHost,
+                        c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  TRACE("hip: costs_along_batch: waited for the device (the candidates' costs of every problem back)");
+  for (int b = 0; b < c->batch; ++b)
+    std::memcpy(costs_host + (size_t)b * m, c->ls_pin + (size_t)b * IDTO_LS_MAX_CANDIDATES, (size_t)m * sizeof(double));
+  return 0;
+}
+
+// bo: (idto_hip_ls_solve_batch_fetch) the loop of every problem of a batch context side by side - the same launches with the
+// problem in the grid, every problem behind gate and stop words of its own; rows_host [batch][iterations][IDTO_LS_ROW], the
+// outputs [batch][...], one gather launch and one copy (ls_fetch.h) instead of the single problem's four copies
+struct LsBatchOut { double* final_cost; int* status; };
+// every problem's final cost and [rows | q | v | tau] packed by one launch, one copy, the call's one wait
+static int LsFinishBatch(idto_hip_ctx* c, const idto_fetch::LsFetchLayout& FL, int iterations, double* rows_host, double* q_out,
+                         double* v_out, double* tau_out, const LsBatchOut& bo) {
+  using idto_fetch::LsFetchLayout;
+  const int B = c->batch;
+  LsGatherArgs G;
+  G.state = c->ls_state; G.rows = c->ls_rows; G.q = c->q; G.v = c->v; G.slab = c->slab; G.N = c->N; G.nv = c->nv;
+  G.slab_stride = c->slab_stride; G.tau_off = 3 * c->nv * c->nq; G.pstride = c->pstride; G.rows_stride = FL.nrows; G.L = FL;
+  G.out = c->ls_fetch_dev;
+  hipLaunchKernelGGL(ls_gather_batch_kernel, dim3(4, B), dim3(256), 0, c->stream, G);
+  HIP_OK(hipGetLastError());
+  const double* pin = c->ls_fetch_pin;
+  HIP_OK(hipMemcpyAsync(c->ls_fetch_pin, c->ls_fetch_dev, FL.total() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  TRACE("hip: ls_solve_batch: every iteration of every problem and the copy enqueued");
+  HIP_OK(hipStreamSynchronize(c->stream));
+  TRACE("hip: ls_solve_batch: waited for the device (every problem's rows and solution back)");
+  bool named = false;
+  for (int b = 0; b < B; ++b) {
+    double* rows = rows_host + (size_t)b * FL.nrows;
+    std::memcpy(rows, pin + FL.rows(b), FL.nrows * sizeof(double));
+    if (q_out) std::memcpy(q_out + (size_t)b * FL.cnt[LsFetchLayout::Q], pin + FL.part(b, LsFetchLayout::Q), FL.cnt[LsFetchLayout::Q] * sizeof(double));
+    if (v_out) std::memcpy(v_out + (size_t)b * FL.cnt[LsFetchLayout::V], pin + FL.part(b, LsFetchLayout::V), FL.cnt[LsFetchLayout::V] * sizeof(double));
+    if (tau_out) std::memcpy(tau_out + (size_t)b * FL.cnt[LsFetchLayout::TAU], pin + FL.part(b, LsFetchLayout::TAU), FL.cnt[LsFetchLayout::TAU] * sizeof(double));
+    bo.final_cost[b] = pin[FL.final_cost() + b];
+    int st = 0;
+    for (int k = 0; k < iterations; ++k) st |= (int)rows[(size_t)k * LSR_COUNT + LSR_FLAGS];
+    bo.status[b] = st;
+    named = named || (st & LSF_BAD_PIVOT) != 0;
+  }
+  // (as in the single problem's loop: a failed factorisation that no row names belongs to an idle iteration behind a
+  // problem's stop flag and is nobody's failure; a time-out of a solver's waits is the whole call's)
+  const int fs = FactorStatus(c);
+  if (fs != 0 && fs != IDTO_HIP_FACTORIZATION_FAILED) return fs;
+  if (named && fs == 0) g_err = "factorisation failed: the Hessian is not numerically positive definite (the row with flag 32 names the problem and the iteration)";
+  return named ? IDTO_HIP_FACTORIZATION_FAILED : 0;
+}
+static int LsSolve(idto_hip_ctx* c, int iterations, int method, int max_ls, int normalize_quaternions, double* rows_host,
+                   double* q_out, double* v_out, double* tau_out, const LsBatchOut* bo = nullptr) {
+  HIP_OK(hipSetDevice(c->device));
+  if (!bo && c->batch != 1) { g_err = "ls_solve serves single-problem contexts"; return -1; }
+  if (bo && c->batch < 2) { g_err = "ls_solve_batch serves batch contexts (idto_hip_ls_solve: a single problem)"; return -1; }
+  if (bo && (!bo->final_cost || !bo->status)) { g_err = "ls_solve_batch: bad arguments (final_cost and status are required)"; return -1; }
+  if (iterations < 1 || !rows_host) { g_err = bo ? "ls_solve_batch: bad arguments" : "ls_solve: bad arguments"; return -1; }
+  if (method != idto_ls::kArmijo && method != idto_ls::kBacktracking) {
+    g_err = bo ? "ls_solve_batch: bad arguments (linesearch_method is 0, Armijo, or 1, backtracking)" : "ls_solve: bad arguments";
     return -1;
   }
   static_assert(LSR_COUNT == IDTO_LS_ROW, "a statistics row as idto_hip.h documents it");
@@ -1270,36 +1356,53 @@ static int LsSolve(idto_hip_ctx* c, int iterations, int method, int max_ls, int 
   const int N = c->N, nq = c->nq, nv = c->nv, n = (N + 1) * nq;
   const LsArena A = ls_arena(N, nq, nv);
   if (int rc = LsEnsureArenas(c, IDTO_LS_MAX_CANDIDATES)) return rc;
+  const size_t B = (size_t)c->batch;
+  static_assert(sizeof(idto_ls::LsScan) % 8 == 0, "the problems' scans lie one LsScan apart in an array of doubles");
   if (!c->ls_state) {
     double* scan = nullptr;
-    if (Alloc(c, (size_t)LSS_COUNT, &c->ls_state) || Alloc(c, (size_t)2 * n, &c->ls_work) ||
-        Alloc(c, (sizeof(idto_ls::LsScan) + 7) / 8, &scan))
+    if (Alloc(c, B * LSS_COUNT, &c->ls_state) || Alloc(c, B * 2 * n, &c->ls_work) ||
+        Alloc(c, B * ((sizeof(idto_ls::LsScan) + 7) / 8), &scan))
       return -2;
     c->ls_scan = reinterpret_cast<idto_ls::LsScan*>(scan);
   }
   if (c->ls_rows_cap < iterations) {
     Release(c, &c->ls_rows);
     c->ls_rows_cap = 0;
-    if (Alloc(c, (size_t)iterations * LSR_COUNT, &c->ls_rows)) return -2;
+    if (Alloc(c, B * iterations * LSR_COUNT, &c->ls_rows)) return -2;
     c->ls_rows_cap = iterations;
   }
   const size_t nrow = (size_t)iterations * LSR_COUNT, nqa = (size_t)n, nva = (size_t)(N + 1) * nv, nta = (size_t)N * nv;
-  if (int rc = EnsurePinned(&c->ls_fetch_pin, &c->ls_fetch_cap, nrow + nqa + nva + nta)) return rc;
+  const idto_fetch::LsFetchLayout FL = idto_fetch::LsFetchLayout::Make(c->batch, iterations, LSR_COUNT, N, nq, nv, bo != nullptr);
+  if (int rc = EnsurePinned(&c->ls_fetch_pin, &c->ls_fetch_cap, FL.total())) return rc;
+  if (bo && c->ls_fetch_dev_cap < FL.total()) {
+    Release(c, &c->ls_fetch_dev);
+    c->ls_fetch_dev_cap = 0;
+    if (Alloc(c, FL.total(), &c->ls_fetch_dev)) return -2;
+    c->ls_fetch_dev_cap = FL.total();
+  }
   if (!c->compute_units) {
     HIP_OK(hipDeviceGetAttribute(&c->compute_units, hipDeviceAttributeMultiprocessorCount, c->device));
   }
+  // (a batch: a wave of k candidates is k N workgroups of every problem - the first wave gives every compute unit one
+  // workgroup across the whole batch, which is the plan of a horizon of N B)
   int widths[idto_host::kLsMaxCandidates];
-  const int nwaves = idto_host::PlanLsWaves(N, c->compute_units, method, max_ls, c->ls_waves, widths);
+  const int nwaves = idto_host::PlanLsWaves(N * c->batch, c->compute_units, method, max_ls, c->ls_waves, widths);
   LsAlphas al;
   idto_ls::ls_alpha_chain(method, IDTO_LS_MAX_CANDIDATES, al.a);
-  ++c->ls_solves;
-  TRACE("hip: ls_solve begins");
+  if (bo) { ++c->ls_batch_solves; TRACE("hip: ls_solve_batch begins"); }
+  else { ++c->ls_solves; TRACE("hip: ls_solve begins"); }
   // L(q_0) and the loop's state
   if (int rc = idto_hip_eval_tau(c)) return rc;
-  HIP_OK(hipMemsetAsync(c->ls_state, 0, LSS_COUNT * sizeof(double), c->stream));
-  HIP_OK(hipMemsetAsync(c->ls_rows, 0, nrow * sizeof(double), c->stream));
-  HIP_OK(hipMemcpyAsync(c->ls_state + LSS_COST, c->cost, sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  HIP_OK(hipMemsetAsync(c->ls_state, 0, B * LSS_COUNT * sizeof(double), c->stream));
+  HIP_OK(hipMemsetAsync(c->ls_rows, 0, B * nrow * sizeof(double), c->stream));
+  if (!bo) {
+    HIP_OK(hipMemcpyAsync(c->ls_state + LSS_COST, c->cost, sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  } else {
+    HIP_OK(hipMemcpy2DAsync(c->ls_state + LSS_COST, LSS_COUNT * sizeof(double), c->cost, c->pstride, sizeof(double), B,
+                            hipMemcpyDeviceToDevice, c->stream));
+  }
   LsLoopArgs L;
+  L.pstride = c->pstride; L.rows_stride = nrow; L.costs_stride = IDTO_LS_MAX_CANDIDATES; L.pcstride = (size_t)c->ls_cap * A.stride;
   L.n = n; L.nq = nq; L.nv = nv; L.N = N; L.g = c->g; L.dq = c->step; L.HA = c->HA; L.HB = c->HB; L.HC = c->HC;
   L.slab = c->slab; L.slab_stride = c->slab_stride; L.tau_off = 3 * nv * nq; L.dofs = c->una_dofs; L.nu = c->una_nu;
   L.q = c->q; L.cost = c->cost; L.state = c->ls_state; L.scan = c->ls_scan; L.rows = c->ls_rows; L.work = c->ls_work;
@@ -1313,16 +1416,16 @@ static int LsSolve(idto_hip_ctx* c, int iterations, int method, int max_ls, int 
     if (int rc = idto_hip_grad_hess(c)) return rc;
     if (int rc = idto_hip_factor_solve(c, nullptr, 1, nullptr)) return rc;
     L.fact_id = c->fact_id;
-    hipLaunchKernelGGL(ls_prepare_kernel, dim3(1), dim3(256), 0, c->stream, L);
+    hipLaunchKernelGGL(ls_prepare_kernel, dim3(1, c->batch), dim3(256), 0, c->stream, L);
     HIP_OK(hipGetLastError());
     for (int w = 0, first = 0; w < nwaves; first += widths[w], ++w) {
       if (int rc = LsEvaluate(c, al, first, widths[w], normalize_quaternions, gate, nullptr)) return rc;
-      hipLaunchKernelGGL(ls_scan_kernel, dim3(1), dim3(64), 0, c->stream, L, c->ls_costs, first, widths[w], w + 1 == nwaves ? 1 : 0);
+      hipLaunchKernelGGL(ls_scan_kernel, dim3(1, c->batch), dim3(64), 0, c->stream, L, c->ls_costs, first, widths[w], w + 1 == nwaves ? 1 : 0);
       HIP_OK(hipGetLastError());
     }
     // the accepted step: its trial point once more at the decided alpha (arena 0), the ratio, the row, q <- q + alpha dq
     if (int rc = LsEvaluate(c, al, 0, 1, normalize_quaternions, stop, c->ls_state + LSS_ALPHA)) return rc;
-    hipLaunchKernelGGL(ls_finish_kernel, dim3(1), dim3(256), 0, c->stream, L);
+    hipLaunchKernelGGL(ls_finish_kernel, dim3(1, c->batch), dim3(256), 0, c->stream, L);
     HIP_OK(hipGetLastError());
     // (what the context remembers about the resident q: it has moved on)
     c->fd_full = false; c->partials_ahead = false; c->terms_valid = false; c->con_ready = false; c->con_begun = false;
@@ -1332,6 +1435,7 @@ static int LsSolve(idto_hip_ctx* c, int iterations, int method, int max_ls, int 
   // v, a, tau of the final iterate, then [rows | q | v | tau] under one wait
   if (int rc = idto_hip_eval_tau(c)) return rc;
   double* pin = c->ls_fetch_pin;
+  if (bo) return LsFinishBatch(c, FL, iterations, rows_host, q_out, v_out, tau_out, *bo);
   HIP_OK(hipMemcpyAsync(pin, c->ls_rows, nrow * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_OK(hipMemcpyAsync(pin + nrow, c->q, nqa * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_OK(hipMemcpyAsync(pin + nrow + nqa, c->v, nva * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1366,6 +1470,14 @@ int idto_hip_ls_solve_fetch(idto_hip_ctx* c, int iterations, int linesearch_meth
                             int normalize_quaternions, double* rows_host, double* q_out, double* v_out, double* tau_out) {
   return LsSolve(c, iterations, linesearch_method, max_linesearch_iterations, normalize_quaternions, rows_host, q_out, v_out,
                  tau_out);
+}
+
+int idto_hip_ls_solve_batch_fetch(idto_hip_ctx* c, int iterations, int linesearch_method, int max_linesearch_iterations,
+                                  int normalize_quaternions, double* rows_host, double* q_out, double* v_out, double* tau_out,
+                                  double* final_cost, int* status) {
+  const LsBatchOut bo{final_cost, status};
+  return LsSolve(c, iterations, linesearch_method, max_linesearch_iterations, normalize_quaternions, rows_host, q_out, v_out,
+                 tau_out, &bo);
 }
 
 int idto_hip_eval_partials(idto_hip_ctx* c) {
@@ -3256,6 +3368,7 @@ int idto_hip_get_option(idto_hip_ctx* c, const char* name, int* value) {
   if (std::strcmp(name, "kkt_fold") == 0) { *value = c->kkt_fold; return 0; }
   if (std::strcmp(name, "ls_waves") == 0) { *value = c->ls_waves; return 0; }
   if (std::strcmp(name, "ls_solves") == 0) { *value = c->ls_solves; return 0; }
+  if (std::strcmp(name, "ls_batch_solves") == 0) { *value = c->ls_batch_solves; return 0; }
   if (std::strcmp(name, "tr_small") == 0) { *value = c->tr_small; return 0; }
   if (std::strcmp(name, "tr_fold") == 0) { *value = c->tr_fold; return 0; }
   if (std::strcmp(name, "kkt_in_asm") == 0) { *value = c->kkt_in_asm; return 0; }

@@ -2,13 +2,18 @@
 // linesearch iteration (reference optimizer/trajectory_optimizer.cc:1852-1977) asks for one step length at a time, each
 // a round trip, are independent evaluations known in advance - alpha_j = rho^j - and one of them is only N workgroups.
 //   ls_trial_kernel   candidate j's trial point q + alpha_j dq, formed as the host forms it, into candidate j's arena
-//   fd_along_kernel   fd_body's tau-only mode with the candidate in blockIdx.y (fd_kernel.h)
+//   fd_along_kernel   fd_body's tau-only mode with the candidate in blockIdx.y (fd_kernel.h; fd_along_batch_kernel: the
+//                     problem of a batch in blockIdx.z)
 //   ls_cost_kernel    cost_body (kernels.h) unchanged, one workgroup per candidate
 // Nothing of the resident iterate is written: q, its tau, cost, partials, g, H and the step stay as they are.
+// Every kernel here takes the problem of a batch from blockIdx.y (fd_along_batch_kernel: blockIdx.z): the context's arrays
+// lie pstride bytes apart (batch.h at_problem), the candidate arenas are laid out [problem][candidate], and every problem
+// has its own costs, loop state words, scan, rows and work vectors.  With one problem the strides multiply 0.
 #pragma once
 
 #include "kernels.h"
 #include "ls_decide.h"
+#include "ls_fetch.h"
 
 namespace idto_dev {
 
@@ -40,14 +45,19 @@ struct LsAlphas { double a[64]; };   // (IDTO_LS_MAX_CANDIDATES step lengths, by
 // divisions by n.  quat[]: the quaternions' start indices within one time step.
 // (idto_hip_ls_solve) first: the launch's candidates are [first, first + gridDim.x); gate: a device word, not 0.0 = nothing
 // to do; alpha_dev: the one step length of the launch, decided on the device
+// (a batch) pstride: bytes between the problems' q and dq; pcstride: doubles between the problems' arenas; gstride:
+// doubles between the problems' gate / alpha_dev words
 __global__ void __launch_bounds__(256)
 ls_trial_kernel(int n, int nq, const double* __restrict__ q, const double* __restrict__ dq, LsAlphas alphas,
                 const int* __restrict__ quat, int nquat, double* __restrict__ arenas, size_t stride, int first,
-                const double* __restrict__ gate, const double* __restrict__ alpha_dev) {
-  if (gate && *gate != 0.0) return;
+                const double* __restrict__ gate, const double* __restrict__ alpha_dev, size_t pstride, size_t pcstride,
+                size_t gstride) {
+  const size_t pb = blockIdx.y;
+  if (gate && gate[pb * gstride] != 0.0) return;
+  q = at_problem(q, pb * pstride); dq = at_problem(dq, pb * pstride);
   const int tid = threadIdx.x, nt = blockDim.x, nsteps = n / nq, cand = first + (int)blockIdx.x;
-  const double alpha = alpha_dev ? *alpha_dev : alphas.a[cand];
-  double* qc = arenas + (size_t)cand * stride;   // (LsArena::q == 0)
+  const double alpha = alpha_dev ? alpha_dev[pb * gstride] : alphas.a[cand];
+  double* qc = arenas + pb * pcstride + (size_t)cand * stride;   // (LsArena::q == 0)
   for (int idx = tid; idx < n; idx += nt) {
     const double step = alpha * dq[idx];
     qc[idx] = q[idx] + step;
@@ -63,13 +73,17 @@ ls_trial_kernel(int n, int nq, const double* __restrict__ q, const double* __res
 }
 
 // L(candidate first + blockIdx.x) into its arena's cost word and into costs[first + blockIdx.x]
+// (a batch) the problem's weights and nominal trajectories pstride bytes on, its arenas pcstride doubles, its costs
+// costs_stride doubles and its gate word gstride doubles
 __global__ void ls_cost_kernel(DevModel M, DevProblem P, double* __restrict__ arenas, LsArena A, int diag,
-                               double* __restrict__ costs, int first, const double* __restrict__ gate) {
-  if (gate && *gate != 0.0) return;
+                               double* __restrict__ costs, int first, const double* __restrict__ gate, size_t pstride,
+                               size_t pcstride, size_t costs_stride, size_t gstride) {
+  const size_t pb = blockIdx.y;
+  if (gate && gate[pb * gstride] != 0.0) return;
   const int cand = first + (int)blockIdx.x;
-  double* base = arenas + (size_t)cand * A.stride;
-  (void)cost_body(M.nq, M.nv, P, base + A.q, base + A.v, base + A.slab, M.nv, base + A.cost, diag, nullptr,
-                  costs + cand, TrDecideArgs{});
+  double* base = arenas + pb * pcstride + (size_t)cand * A.stride;
+  (void)cost_body(M.nq, M.nv, at_problem(P, pb * pstride), base + A.q, base + A.v, base + A.slab, M.nv, base + A.cost, diag,
+                  nullptr, costs + pb * costs_stride + cand, TrDecideArgs{});
 }
 
 // ---------------------------------------------------------------------------
@@ -83,6 +97,9 @@ __global__ void ls_cost_kernel(DevModel M, DevProblem P, double* __restrict__ ar
 //                       candidate's), fd_kernel, ls_cost_kernel and ls_finish_kernel: the trust ratio, the statistics row,
 //                       q <- q + alpha dq
 // No kernel waits for another workgroup: launch order carries every dependency.
+// (idto_hip_ls_solve_batch_fetch) The same launches for the problems of a batch side by side, the problem in the grid: every
+// problem has its own state words, so its own gate and stop - a problem that has decided, or that carries a flag, idles while
+// the others go on -, and ls_gather_batch_kernel packs what goes back to the host (ls_fetch.h).
 enum {
   LSS_COST = 0,   // L(q_k)
   LSS_ALPHA,      // the iteration's answer
@@ -119,7 +136,22 @@ struct LsLoopArgs {
   const unsigned* status; unsigned fact_id;   // the solver's status words (host-mapped) and this iteration's factorisation
   int method, max_iters;
   double dt;
+  // (a batch: the pointers above are problem 0's) bytes between the problems' context arrays; doubles between their rows,
+  // their candidate costs and their arenas.  state, scan and work lie LSS_COUNT, one LsScan and 2 n apart.
+  size_t pstride, rows_stride, costs_stride, pcstride;
 };
+
+// problem pb's view of the loop's arguments
+__device__ inline LsLoopArgs ls_at_problem(LsLoopArgs A, size_t pb) {
+  const size_t o = pb * A.pstride;
+  A.g = at_problem(A.g, o); A.dq = at_problem(A.dq, o);
+  A.HA = at_problem(A.HA, o); A.HB = at_problem(A.HB, o); A.HC = at_problem(A.HC, o);
+  A.slab = at_problem(A.slab, o); A.q = at_problem(A.q, o); A.cost = at_problem(A.cost, o);
+  A.state += pb * LSS_COUNT; A.scan += pb; A.rows += pb * A.rows_stride; A.work += pb * 2 * (size_t)A.n;
+  A.arena += pb * A.pcstride;
+  if (A.status) A.status += 2 * pb;   // (the solvers' status words: [2 b] the id of problem b's last failing factorisation)
+  return A;
+}
 
 __device__ inline void ls_stop_row(const LsLoopArgs& A, int flags) {
   double* S = A.state;
@@ -131,7 +163,8 @@ __device__ inline void ls_stop_row(const LsLoopArgs& A, int flags) {
 }
 
 // The sums are the host's Dot / Norm: one thread each, in index order.
-__global__ void __launch_bounds__(256) ls_prepare_kernel(LsLoopArgs A) {
+__global__ void __launch_bounds__(256) ls_prepare_kernel(LsLoopArgs A0) {
+  const LsLoopArgs A = ls_at_problem(A0, blockIdx.y);
   double* S = A.state;
   if (S[LSS_STOP] != 0.0) return;
   __shared__ double sums[4];
@@ -166,7 +199,9 @@ __global__ void __launch_bounds__(256) ls_prepare_kernel(LsLoopArgs A) {
 }
 
 // costs[first .. first + count) into the scan, in index order; last: no wave follows
-__global__ void ls_scan_kernel(LsLoopArgs A, const double* __restrict__ costs, int first, int count, int last) {
+__global__ void ls_scan_kernel(LsLoopArgs A0, const double* __restrict__ costs, int first, int count, int last) {
+  const LsLoopArgs A = ls_at_problem(A0, blockIdx.y);
+  costs += (size_t)blockIdx.y * A.costs_stride;
   double* S = A.state;
   if (threadIdx.x != 0 || S[LSS_GATE] != 0.0) return;
   idto_ls::LsScan sc = *A.scan;
@@ -183,7 +218,8 @@ __global__ void ls_scan_kernel(LsLoopArgs A, const double* __restrict__ costs, i
 // PentaDiagonalMatrix::MultiplyBy (y = 0, then the blocks A_i, B_i, C_i, D_i = B_{i+1}^T, E_i = A_{i+2}^T, columns in order;
 // C's upper triangle is the mirror of its lower one), the two dot products by one thread each in index order -, the row,
 // q <- q + alpha dq.
-__global__ void __launch_bounds__(256) ls_finish_kernel(LsLoopArgs A) {
+__global__ void __launch_bounds__(256) ls_finish_kernel(LsLoopArgs A0) {
+  const LsLoopArgs A = ls_at_problem(A0, blockIdx.y);
   double* S = A.state;
   if (S[LSS_STOP] != 0.0) return;
   __shared__ double sums[3];
@@ -224,6 +260,34 @@ __global__ void __launch_bounds__(256) ls_finish_kernel(LsLoopArgs A) {
   R[LSR_CLOCK] = (double)wall_clock64(); R[LSR_FLAGS] = (double)flags;
   S[LSS_ROWS] += 1.0; S[LSS_COST] = L_new; *A.cost = L_new;
   if (flags) S[LSS_STOP] = (double)flags;
+}
+
+// idto_hip_ls_solve_batch_fetch: problem blockIdx.y's [rows | q | v | tau] and its final cost packed into the staging
+// buffer (ls_fetch.h) - one launch, one copy to the host behind it.  tau: row t of the slab at slab + t slab_stride + tau_off.
+struct LsGatherArgs {
+  const double *state, *rows, *q, *v, *slab;
+  int N, nv, slab_stride, tau_off;
+  size_t pstride, rows_stride;
+  idto_fetch::LsFetchLayout L;
+  double* out;
+};
+__global__ void __launch_bounds__(256) ls_gather_batch_kernel(LsGatherArgs G) {
+  const size_t pb = blockIdx.y, o = pb * G.pstride;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (size_t)gridDim.x * blockDim.x;
+  using idto_fetch::LsFetchLayout;
+  const double* rows = G.rows + pb * G.rows_stride;
+  const double* q = at_problem(G.q, o);
+  const double* v = at_problem(G.v, o);
+  const double* slab = at_problem(G.slab, o);
+  double* out = G.out;
+  if (tid == 0) out[G.L.final_cost() + pb] = G.state[pb * LSS_COUNT + LSS_COST];
+  for (size_t i = tid; i < G.L.nrows; i += nt) out[G.L.rows(pb) + i] = rows[i];
+  for (size_t i = tid; i < G.L.cnt[LsFetchLayout::Q]; i += nt) out[G.L.part(pb, LsFetchLayout::Q) + i] = q[i];
+  for (size_t i = tid; i < G.L.cnt[LsFetchLayout::V]; i += nt) out[G.L.part(pb, LsFetchLayout::V) + i] = v[i];
+  for (size_t i = tid; i < G.L.cnt[LsFetchLayout::TAU]; i += nt) {
+    const size_t t = i / (size_t)G.nv, j = i - t * (size_t)G.nv;
+    out[G.L.part(pb, LsFetchLayout::TAU) + i] = slab[t * (size_t)G.slab_stride + G.tau_off + j];
+  }
 }
 
 }  // namespace idto_dev

@@ -96,6 +96,8 @@ def lib():
         L.idto_hip_ls_alphas.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double)]
         L.idto_hip_ls_solve.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
         L.idto_hip_ls_solve_fetch.argtypes = L.idto_hip_ls_solve.argtypes + [C.POINTER(C.c_double)] * 3
+        L.idto_hip_costs_along_batch.argtypes = L.idto_hip_costs_along.argtypes
+        L.idto_hip_ls_solve_batch_fetch.argtypes = L.idto_hip_ls_solve.argtypes + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int)]
         for f in ("eval_tau", "eval_partials", "grad_hess", "gn_step", "sync", "timing_reset"):
             getattr(L, "idto_hip_" + f).argtypes = [C.c_void_p]
         L.idto_hip_factor_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -126,7 +128,7 @@ def lib():
 
 EXPORTED_SYMBOLS = [
     "idto_hip_last_error", "idto_hip_create", "idto_hip_destroy", "idto_hip_set_problem", "idto_hip_set_stream",
-    "idto_hip_get_stream", "idto_hip_set_shard", "idto_hip_set_q", "idto_hip_set_q_device", "idto_hip_eval_tau", "idto_hip_eval_tau_partials", "idto_hip_trial_cost", "idto_hip_costs_along", "idto_hip_ls_alphas", "idto_hip_ls_solve", "idto_hip_ls_solve_fetch", "idto_hip_constraint_schur",
+    "idto_hip_get_stream", "idto_hip_set_shard", "idto_hip_set_q", "idto_hip_set_q_device", "idto_hip_eval_tau", "idto_hip_eval_tau_partials", "idto_hip_trial_cost", "idto_hip_costs_along", "idto_hip_ls_alphas", "idto_hip_ls_solve", "idto_hip_ls_solve_fetch", "idto_hip_costs_along_batch", "idto_hip_ls_solve_batch_fetch", "idto_hip_constraint_schur",
     "idto_hip_constraint_schur_begin", "idto_hip_constraint_solve", "idto_hip_constraint_step", "idto_hip_prefetch",
     "idto_hip_eval_partials", "idto_hip_grad_hess", "idto_hip_factor_solve", "idto_hip_gn_step", "idto_hip_solve_host",
     "idto_hip_solve_dense_ldlt", "idto_hip_dense_solve_count",
@@ -499,6 +501,32 @@ class HipPath:
             return dict(rows=rows)
         out = dict(rows=rows, q=np.zeros((self.N + 1, self.nq)), v=np.zeros((self.N + 1, self.nv)), tau=np.zeros((self.N, self.nv)))
         _chk(lib().idto_hip_ls_solve_fetch(*args, dptr(out["q"]), dptr(out["v"]), dptr(out["tau"])))
+        return out
+
+    def costs_along_batch(self, alphas, normalize_quaternions: bool = False):
+        """(a batch context) L_b(q_b + alpha dq_b) for every problem b at the same step lengths, one launch set and one wait
+        (idto_hip_costs_along_batch): costs [B, m]; nothing resident of any problem is disturbed"""
+        alphas = np.ascontiguousarray(np.asarray(alphas, dtype=np.float64).ravel())
+        costs = np.empty((self.batch, alphas.size))
+        _chk(lib().idto_hip_costs_along_batch(self.h, dptr(alphas), int(alphas.size), int(bool(normalize_quaternions)), dptr(costs)))
+        return costs
+
+    def ls_solve_batch(self, iterations, linesearch_method=0, max_linesearch_iterations=50, normalize_quaternions=False,
+                       check: bool = True):
+        """(a batch context) the linesearch method's loop of every problem side by side, one wait
+        (idto_hip_ls_solve_batch_fetch).  Returns a dict: rows [B, iterations, LS_ROW], q, v, tau [B, ...], final_cost [B],
+        status [B] (the OR of each problem's row flags), rc (check=False hands IDTO_HIP_FACTORIZATION_FAILED back there
+        instead of raising)."""
+        B, N = self.batch, self.N
+        out = dict(rows=np.zeros((B, int(iterations), LS_ROW)), q=np.zeros((B, N + 1, self.nq)), v=np.zeros((B, N + 1, self.nv)),
+                   tau=np.zeros((B, N, self.nv)), final_cost=np.zeros(B), status=np.zeros(B, dtype=np.int32))
+        rc = lib().idto_hip_ls_solve_batch_fetch(
+            self.h, int(iterations), int(linesearch_method), int(max_linesearch_iterations), int(bool(normalize_quaternions)),
+            dptr(out["rows"]), dptr(out["q"]), dptr(out["v"]), dptr(out["tau"]), dptr(out["final_cost"]),
+            out["status"].ctypes.data_as(C.POINTER(C.c_int)))
+        if check or rc not in (0, FACTORIZATION_FAILED):
+            _chk(rc)
+        out["rc"] = rc
         return out
 
     def eval_partials(self):

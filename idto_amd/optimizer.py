@@ -262,8 +262,9 @@ class TrajectoryOptimizer:
 
     def solve_batch(self, q_guesses, problems=None, only_best: bool = False) -> BatchSolveResult:
         """TrajectoryOptimizer::SolveBatch: entry b is `Solve(q_guesses[b])` on an optimizer made with `problems[b]` (None:
-        this optimizer's own problem for every entry), all entries through ONE trust-region loop on the device where the
-        configuration allows it, one after another otherwise."""
+        this optimizer's own problem for every entry), all entries through ONE loop on the device - the trust-region batch
+        loop or, with method = linesearch, the batch linesearch loop - where the configuration allows it (DESIGN.md section
+        12.1), one after another otherwise."""
         q = _d(q_guesses)
         if q.ndim != 3 or q.shape[1:] != (self.N + 1, self.nq):
             raise RuntimeError(f"solve_batch: q_guesses must be [B, {self.N + 1}, {self.nq}]")

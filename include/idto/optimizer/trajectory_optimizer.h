@@ -114,7 +114,11 @@ class TrajectoryOptimizer<double> {
   // flags[b] / errors[b].  Configurations the device's batch loop serves (trust region, one device, the device-resident
   // loop, diagonal cost weights, no adaptive scaling, verbose off, enforced constraints through the banded KKT step) run as
   // ONE loop for all entries with one wait for everything that comes back (idto_hip_tr_solve_batch_fetch) on a batch context
-  // created on first use and kept per B; every other configuration runs the entries one after another on this
+  // created on first use and kept per B.  method = kLinesearch takes the device's batch linesearch loop the same way
+  // (idto_hip_ls_solve_batch_fetch, one wait) where the single problem takes the device's linesearch loop - scaling off, no
+  // enforced constraints, the banded solver, no debug switches, max_linesearch_iterations <= 64 - with B >= 2, one device,
+  // verbose off and diagonal weights in every entry; an entry whose backtracking stays undecided within the device's
+  // candidates is solved again alone, a loop time-out sends every entry there.  Every other configuration runs the entries one after another on this
   // optimizer's own context, with the same result layout.  A batch of more than two small models (blocks up to 4) takes
   // the block solver kernels where one problem alone takes the scalar band kernels: the entries then agree with Solve to
   // the solver's round-off, otherwise bit for bit.
@@ -122,7 +126,7 @@ class TrajectoryOptimizer<double> {
   // sizes differ from this optimizer's.
   void SolveBatch(const std::vector<std::vector<VectorXd>>& q_guesses, const std::vector<ProblemDefinition>* problems,
                   BatchSolveResult* out, bool only_best = false) const;
-  // how the last SolveBatch ran: 1 the batch loop, 0 entry by entry (tests and tools/solve_batch_bench.py ask)
+  // how the last SolveBatch ran: 1 a batch loop of the device (trust region or linesearch), 0 entry by entry (tests and tools/solve_batch_bench.py ask)
   int last_batch_route() const { return last_batch_route_; }
 
   // ---- what examples::mpc::BatchModelPredictiveController (mpc_controller.h) builds on: the device's batch loop for B

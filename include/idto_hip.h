@@ -191,6 +191,13 @@ int idto_hip_trial_cost(idto_hip_ctx* ctx, const double* q_host, double* tau_hos
  * a, tau, cost, partials, g, H and the step are afterwards what they were.  Single-problem contexts. */
 #define IDTO_LS_MAX_CANDIDATES 64
 int idto_hip_costs_along(idto_hip_ctx* ctx, const double* alphas_host, int m, int normalize_quaternions, double* costs_host);
+/* The same for a batch context: the same m step lengths along every problem's own step (IDTO_ARR_STEP of problem b, e.g.
+ * behind idto_hip_gn_step_batch), one launch set with the problem in the grid (fd_along_batch_kernel: candidate in
+ * blockIdx.y, problem in blockIdx.z), one wait.  costs_host[batch][m]; costs_host[b][j] is bit for bit what
+ * idto_hip_costs_along returns on a single-problem context holding problem b.  Nothing resident of any problem is written.
+ * The candidates' arenas are batch x m x ls_arena(N, nq, nv).stride doubles (csrc/linesearch.h; mini_cheetah, N = 40:
+ * 144 KB a candidate), allocated on first use and grown to the largest m asked for. */
+int idto_hip_costs_along_batch(idto_hip_ctx* ctx, const double* alphas_host, int m, int normalize_quaternions, double* costs_host);
 /* The step lengths the two linesearches try, in the order they try them, formed as the host loops form them (repeated
  * IEEE multiplication by rho = 0.8, never pow; csrc/ls_decide.h): linesearch_method 0 kArmijo (1/rho * rho = 1.0, 0.8,
  * 0.6400000000000001, ...), 1 kBacktracking (1.0, then the same products).  No device involved. */
@@ -225,6 +232,27 @@ int idto_hip_ls_solve(idto_hip_ctx* ctx, int iterations, int linesearch_method, 
                       int normalize_quaternions, double* rows_host);
 int idto_hip_ls_solve_fetch(idto_hip_ctx* ctx, int iterations, int linesearch_method, int max_linesearch_iterations,
                             int normalize_quaternions, double* rows_host, double* q_out, double* v_out, double* tau_out);
+/* The same loop for every problem of a batch context side by side: every iteration of every problem is enqueued at once -
+ * the Newton-step launches with their batch dimension, the ls_* kernels and the tau-only evaluation with the problem in the
+ * grid - and the call waits once.  Every problem has its own loop state, scan, rows and gate and stop words: a problem that
+ * has decided its iteration, or that carries a flag, idles on its own while the others go on; no kernel waits for another
+ * workgroup.  A wave takes the same candidates of every problem; its width is PlanLsWaves' for a horizon of N * batch (the
+ * first wave gives every compute unit one workgroup across the whole batch), option "ls_waves" = k: k candidates per problem.
+ * The iterates must be resident (idto_hip_set_q_batch).  rows_host[batch][iterations][IDTO_LS_ROW] in the row format above;
+ * q_out [batch][(N+1) nq], v_out [batch][(N+1) nv], tau_out [batch][N nv] (any may be NULL) come back packed by one launch
+ * under one copy (csrc/ls_fetch.h); final_cost[b] is the cost at problem b's final iterate, status[b] the OR of its rows'
+ * flags.  With equal inputs problem b's rows and iterate are bit for bit those of idto_hip_ls_solve_fetch on a
+ * single-problem context wherever both run the same solver kernel.
+ * Device memory: the candidates' arenas are batch x IDTO_LS_MAX_CANDIDATES x ls_arena(N, nq, nv).stride doubles
+ * (csrc/linesearch.h: (N+1)(nq + nv + nv nq) + 2 N nv + 3 nv nq + 1 doubles rounded up to 8 - hopper, N = 50: 19 KB a
+ * candidate, 1.2 MB a problem; mini_cheetah, N = 40: 144 KB a candidate, 9.2 MB a problem, 590 MB at batch = 64); an
+ * allocation that fails is reported by name, with the bytes asked for.
+ * Returns IDTO_HIP_FACTORIZATION_FAILED when some row carries flag 32 (that row names the problem and the iteration; every
+ * other problem's outputs are valid), IDTO_HIP_SOLVER_TIMEOUT as the other loops.  Option "ls_batch_solves" (read-only)
+ * counts the calls on the context. */
+int idto_hip_ls_solve_batch_fetch(idto_hip_ctx* ctx, int iterations, int linesearch_method, int max_linesearch_iterations,
+                                  int normalize_quaternions, double* rows_host, double* q_out, double* v_out, double* tau_out,
+                                  double* final_cost, int* status);
 int idto_hip_eval_partials(idto_hip_ctx* ctx);
 int idto_hip_grad_hess(idto_hip_ctx* ctx);
 /* Factorises the resident Hessian and solves H x = rhs for `nrhs` right-hand

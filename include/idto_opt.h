@@ -54,12 +54,17 @@ int idto_opt_solve(idto_opt* opt, const double* q_guess, double* sol_q, double* 
  * entry of the lowest final cost among those that ended kSuccess / kMaxIterationsReached, -1: none.  One entry's failure is
  * its own flag (kFactorizationFailed) and text (idto_opt_batch_error, valid until the next idto_opt_solve_batch of the
  * optimizer; "" for an entry that has its solution); the call itself fails only for what concerns the whole batch: a
- * problem of another num_steps / time_step, a device error. */
+ * problem of another num_steps / time_step, a device error.
+ * Routes: method = trust region runs the device's batch loop (idto_hip_tr_solve_batch_fetch) for what it serves; method =
+ * linesearch runs the batch linesearch loop (idto_hip_ls_solve_batch_fetch: every iteration of every entry enqueued at
+ * once, one wait) with scaling off, no enforced constraints, the banded solver, no debug switches,
+ * max_linesearch_iterations <= 64, B >= 2, one device, verbose off and diagonal weights in every entry; everything else
+ * runs entry by entry.  (The batch of MPC controllers below still does not serve method = linesearch.) */
 int idto_opt_solve_batch(idto_opt* opt, int B, const idto_problem_t* problems, const double* q_guesses, int only_best,
                          double* sol_q, double* sol_v, double* sol_tau, idto_stats_t* stats, int* flags, int* reasons,
                          double* final_costs, int* best);
 const char* idto_opt_batch_error(const idto_opt* opt, int b);
-/* 1: the last idto_opt_solve_batch ran the device's batch loop, 0: entry by entry on the optimizer's own context, -1: none yet */
+/* 1: the last idto_opt_solve_batch ran one of the device's batch loops (trust region or linesearch), 0: entry by entry on the optimizer's own context, -1: none yet */
 int idto_opt_last_batch_route(const idto_opt* opt);
 
 /* CreateWarmStart / SolveFromWarmStart (trajectory_optimizer.h:156-211, warm_start.h:23-76) */

@@ -79,6 +79,18 @@ LIMITS = {
     "fd_along_kernel<8, 6>": (0, 0, 65 + 24),
     "fd_along_kernel<8, 7>": (0, 0, 76 + 24),
     "fd_along_kernel<8, 8>": (0, 0, 65 + 24),
+    # (the same with the problem of a batch in blockIdx.z, csrc/fd_kernel.h: three more strides and the problem's own
+    # DevProblem - four scalar registers more are spilled to lanes than in fd_along_kernel, no vector register; the
+    # one-path shape <8, 6> reserves fd_kernel's 20 B of private segment)
+    "fd_along_batch_kernel<2, 1>": (0, 0, 16 + 24),
+    "fd_along_batch_kernel<3, 2>": (0, 0, 16 + 24),
+    "fd_along_batch_kernel<3, 3>": (0, 0, 19 + 24),
+    "fd_along_batch_kernel<3, 5>": (0, 0, 18 + 24),
+    "fd_along_batch_kernel<4, 4>": (0, 0, 20 + 24),
+    "fd_along_batch_kernel<8, 6>": (0, 20, 69 + 24),
+    "fd_along_batch_kernel<8, 7>": (0, 0, 79 + 24),
+    "fd_along_batch_kernel<8, 8>": (0, 0, 69 + 24),
+    "ls_gather_batch_kernel": (0, 0, 0 + 24),
     "ls_trial_kernel": (0, 0, 0 + 24),
     "ls_cost_kernel": (0, 0, 0 + 24),
     "ls_prepare_kernel": (0, 0, 0 + 24),

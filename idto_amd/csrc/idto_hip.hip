@@ -288,7 +288,7 @@ struct idto_hip_ctx {
   unsigned timeouts_handled = 0;          // ... the device's count of them (status word) that FactorStatus has acted on
   int last_step_kind = 0;                 // what produced IDTO_ARR_STEP last: 1 factor_solve of -g, 2 the fused launch, 0 other
   int debug_skip_role = -1;               // test aid: a role of the nested-dissection kernels that returns at once
-  int debug_pipe_tail = 0;                // measurement aid: pipelined solver with the row-by-row back substitution
+  int debug_pipe_tail = 0;                // measurement aid: pipelined solver with 1 the row-by-row back substitution, 2 the recursion form without the producers' closed form
   double* nd_buf = nullptr;
   double* nd_wst = nullptr;   // the seven-workgroup kernel's W rows (penta_pipe.h chain_recursion_tail), blocks of 21 .. 32 only
   int nd_recursion = 1;       // option "nd_recursion": its back substitution in recursion form where the matrices fit the LDS

@@ -58,7 +58,7 @@ struct NdArgs {
   int asm_first;
   int wt_rows;                   // 1 (penta_pipe_kernel): the chains publish a row's spike block, 1 / d and rt with write-through stores, the separator reads past the L2 (no acquire);
                                  // 0 (penta_nd_kernel): write-through stores, the readers acquire and read with plain loads; 2: plain stores and a releasing fence (measurement aid IDTO_ND_WT)
-  int debug_pipe_tail;           // measurement aid: penta_pipe_kernel takes the row-by-row back substitution
+  int debug_pipe_tail;           // measurement aid: penta_pipe_kernel takes 1 the row-by-row back substitution, 2 the recursion form walked row after row by the producers too (no closed form)
   int npos;                      // > 0: a KKT system (kkt.h) - the pivots [npos, k) of every block row are not tested (ldl_pivot_bad)
   int lds_rows;                  // the chains' carve-up holds this many local rows (penta_ldl_layout `rows`; 0: all n)
   // back substitution in recursion form (penta_pipe.h chain_recursion_tail; K > 20): the launch has lds_doubles of LDS

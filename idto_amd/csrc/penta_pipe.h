@@ -305,6 +305,7 @@ struct PipeArgs {
   // part p of block row i is in memory; solver row o is assembly row o + asm_first.  nullptr: they were there before.
   const unsigned* asm_ready; int asm_first, asm_rows;
   double* ts;
+  int closed_tail;    // pipe_backward, a producer of the pipelined kernel: its recursion in closed form (pipe_closed_tail)
 };
 
 // ---- g and the band blocks formed INSIDE the solver's launch (idto_hip_gn_step): the 4 (N + 1) workgroups behind the
@@ -1171,6 +1172,114 @@ __device__ __forceinline__ double pipe_half_sum(double v) {
 template <int K, bool SPK>
 __device__ __forceinline__ bool pipe_backward_fits(const PipeLds& L, int nloc) { return nloc * PipeBack<K, SPK>::BS + 4 * PipeBack<K, SPK>::KE + 2 <= L.xall; }
 
+// ---- a producer's recursion in closed form.
+// A producer has its [Y_i | Z_i | c_i] ~16 us before the joiner's two join rows of x arrive, and then walks its rows one
+// after the other on one wavefront (0.24 us a row).  Everything in that walk but the 2K numbers of the join rows is known
+// beforehand: with T_nloc = [I 0 | 0], T_nloc+1 = [0 I | 0] and
+//   T_i = [G_i | chat_i] = [0 | c_i] - Y_i T_{i+1} - Z_i T_{i+2}            (the recursion on 2K + 1 right-hand sides)
+// every row is x_i = chat_i + G_i [x_nloc ; x_nloc+1].  The T_i are formed in the idle time - nloc dependent products
+// [Y_i | Z_i] (K x 2KE) times [T_{i+1} ; T_{i+2}] (2KE x (2KE + 1)) on the matrix cores, a 16 x 16 tile per wavefront,
+// a barrier per row - and the arrival of the join rows costs one mat-vec, all rows side by side.
+// (The order of every sum is fixed by the tiling: the result does not depend on timing.  PipeClosed: solver_layout.h)
+template <int K>
+__device__ __forceinline__ bool pipe_closed_fits(const PipeLds& L, int nloc) { return PipeClosed<K>::end(nloc) <= L.xall; }
+
+// (Called from the kernel's body behind pipe_backward, which returns after phase 1 and leaves what this needs to know
+// in the LDS, PipeClosed::PAR: as a part of pipe_backward with its arguments in scalar registers, the deciding launch's
+// kernel <19, true> spilled 241 .. 249 SGPRs instead of 204 - tools/check_resources.py allows 228 -, although this runs
+// behind the forward pass and shares nothing with it; as a function that is called, it rounds the kernels' 36 B of
+// scratch up to 48.  This way: 221.)
+template <int K>
+__device__ __forceinline__ void pipe_closed_tail() {
+  extern __shared__ double lds[];
+  using B = PipeBack<K, false>;
+  using C = PipeClosed<K>;
+  using d4 = __attribute__((ext_vector_type(4))) double;
+  constexpr int KE = B::KE, YS = B::YS, TS = C::TS, NC = C::NC;
+  constexpr int TT = (K + 15) / 16, CT = (NC + 15) / 16, SK = 2 * KE / 4;
+  static_assert(2 * K <= 64, "a lane per component of the two join rows");
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nt = blockDim.x, nwaves = nt >> 6;
+  // (what the caller knows comes through the LDS, PipeClosed::PAR, and stays in vector registers)
+  const int xall = pipe_layout<K>(0, false).xall;
+  const unsigned long long* par = reinterpret_cast<const unsigned long long*>(lds + xall + C::PAR);
+  const int nloc = __builtin_amdgcn_readfirstlane((int)(unsigned)par[5]);
+  double* x = reinterpret_cast<double*>(par[0]);
+  const double* xjoin_ll = reinterpret_cast<const double*>(par[1]);
+  const SpinCtl spin = {reinterpret_cast<unsigned*>(par[2]), (unsigned)(par[4] >> 32)};
+  double* ts = reinterpret_cast<double*>(par[3]);
+  const unsigned epoch = (unsigned)par[4];
+  const int k = (int)(unsigned)(par[5] >> 32), base = (int)(unsigned)par[6], mirror = (int)(unsigned)(par[6] >> 32);
+  auto orig = [&](int il) { const int o = mirror ? base - il : base + il; return o < 0 ? 0 : o; };
+  double* T = lds + C::base(nloc);
+  // the two join rows' slots: the identity
+  for (int idx = tid; idx < 2 * C::SLOT; idx += nt) {
+    const int h = idx / C::SLOT, r = (idx - h * C::SLOT) / TS, n = idx - h * C::SLOT - r * TS;
+    T[nloc * C::SLOT + idx] = (n == h * KE + r) ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  const int fl = lane & 15, fk = lane >> 4;
+  for (int il = nloc - 1; il >= 0; --il) {
+    const double* yz = lds + il * B::BS + B::oYZ;
+    const double* cc = lds + il * B::BS + B::oC;
+    double* Ti = T + il * C::SLOT;
+    for (int tile = wave; tile < TT * CT; tile += nwaves) {
+      const int tr = tile / CT, tc = tile - tr * CT;
+      const int ar = 16 * tr + fl < K ? 16 * tr + fl : K - 1;      // (rows past K: a copy of the last row, never stored)
+      const int bn = 16 * tc + fl < NC ? 16 * tc + fl : NC - 1;    // (columns past chat likewise)
+      double a[SK], b[SK];
+#pragma unroll
+      for (int sq = 0; sq < SK; ++sq) {
+        const int p = 4 * sq + fk, h = p >= KE ? 1 : 0, pr = p - h * KE;   // position in [Y | Z]: row pr of T_{il+1+h}
+        a[sq] = yz[ar * YS + p];
+        const double t = Ti[(1 + h) * C::SLOT + (pr < K ? pr : K - 1) * TS + bn];
+        b[sq] = pr < K ? t : 0.0;   // (the pad column of Y, Z is zero; what it meets must be a number)
+      }
+      d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int sq = 0; sq < SK; ++sq) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[sq], b[sq], acc, 0, 0, 0);
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        const int r = 16 * tr + fk + 4 * rg, n = 16 * tc + fl;
+        if (r < K && n < NC) Ti[r * TS + n] = (n == NC - 1 ? cc[r] : 0.0) - acc[rg];
+      }
+    }
+    __syncthreads();
+  }
+  if (ts && tid == 0) ts[21] = (double)wall_clock64();
+  // ---- the join rows arrive: a thread per (row, component), its row of G and chat in registers before the wait.
+  // Every wavefront that has rows polls the 2K words itself (the existing flagged words, the bounded poll) and keeps
+  // its own copy in what held rt of the local rows: no barrier behind the arrival.
+  if (wave * 64 >= nloc * K) return;
+  double* xj = lds + xall + wave * 2 * KE;
+  if (lane < 2 * KE) xj[lane] = 0.0;
+  __atomic_signal_fence(__ATOMIC_SEQ_CST);
+  const int idx0 = wave * 64 + lane, idx = idx0 < nloc * K ? idx0 : 0, il = idx / K, r = idx - il * K;
+  double g[2 * KE];
+  {
+    const double2* g2 = reinterpret_cast<const double2*>(T + il * C::SLOT + r * TS);
+#pragma unroll
+    for (int m = 0; m < KE; ++m) { const double2 v = g2[m]; g[2 * m] = v.x; g[2 * m + 1] = v.y; }
+  }
+  const double chat = T[il * C::SLOT + r * TS + NC - 1];
+  if (lane < 2 * K) {   // local row nloc (next to this chain) is the joiner's second join row
+    const int h = lane >= K ? 1 : 0, c = lane - h * K;
+    xj[h * KE + c] = ll_load(xjoin_ll + 2 * ((1 - h) * K + c), epoch, spin);
+  }
+  __atomic_signal_fence(__ATOMIC_SEQ_CST);
+  if (ts && tid == 0) ts[22] = (double)wall_clock64();
+  const double2* x2 = reinterpret_cast<const double2*>(xj);
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+  for (int m = 0; m < KE; m += 2) {
+    const double2 u = x2[m], v = x2[m + 1];
+    a0 = __builtin_fma(g[2 * m], u.x, a0); a1 = __builtin_fma(g[2 * m + 1], u.y, a1);
+    a2 = __builtin_fma(g[2 * m + 2], v.x, a2); a3 = __builtin_fma(g[2 * m + 3], v.y, a3);
+  }
+  const double v = chat + ((a0 + a1) + (a2 + a3));
+  if (idx0 < nloc * K && r < k) x[(size_t)orig(il) * k + r] = v;
+  if (ts && tid == 0) ts[4] = (double)wall_clock64();
+}
+
 // WGLOB (the seven-workgroup kernel's chains, 4 wavefronts, K = 23 / 29: 16 rows of [Y | Z | c] are 141 KB): W_il goes
 // to global memory (A.wst) instead of the LDS - it is read once, a row per thread, and those loads are issued before the
 // wait for the separator, where the row-by-row tail fetched Ft_il.  The spike rows come from another workgroup there
@@ -1332,6 +1441,19 @@ __device__ __forceinline__ void pipe_backward(const PipeArgs& A, const ChainCfg&
   __syncthreads();
   chain_ts(cfg, 3);
   if (cfg.ts && tid == 0) cfg.ts[6] = (double)wall_clock64();
+  if constexpr (!WGLOB && !SPK) {
+    if (A.closed_tail) {   // a producer of the pipelined kernel: no row of it waits for another once the join rows are known
+      if (tid == 0) {
+        unsigned long long* par = reinterpret_cast<unsigned long long*>(lds + L.xall + PipeClosed<K>::PAR);
+        par[0] = (unsigned long long)A.x; par[1] = (unsigned long long)A.xjoin_ll; par[2] = (unsigned long long)cfg.spin.word;
+        par[3] = (unsigned long long)cfg.ts; par[4] = (unsigned long long)A.epoch | ((unsigned long long)cfg.spin.id << 32);
+        par[5] = (unsigned long long)(unsigned)nloc | ((unsigned long long)(unsigned)k << 32);
+        par[6] = (unsigned long long)(unsigned)cfg.base | ((unsigned long long)(unsigned)cfg.mirror << 32);
+      }
+      __syncthreads();
+      return;
+    }
+  }
   // ---- phase 2 (spike chains): once the separator is solved, c_i -= W_i [x_near ; x_far]
   if (WGLOB && cfg.fst) {
     // a thread per (row, component), two of them per thread at most (pipe_recursion_tail_fits); the rows of W are in
@@ -1378,35 +1500,63 @@ __device__ __forceinline__ void pipe_backward(const PipeArgs& A, const ChainCfg&
     }
     __syncthreads();
   }
-  if (!WGLOB && SPK && cfg.fst) {
+  const int hf = lane >> 5, r_ = lane & 31, rr = r_ < K ? r_ : 0;
+  static_assert(K <= 32, "one row per lane of a half-wavefront");
+  double M0[KE], M1[KE], c0 = 0.0, c1 = 0.0;
+  auto fetch_m = [&](int il, double (&M)[KE]) __attribute__((always_inline)) {
+    const double2* y2 = reinterpret_cast<const double2*>(lds + il * B::BS + B::oYZ + rr * YS + hf * KE);
+#pragma unroll
+    for (int m = 0; m < KE / 2; ++m) { const double2 a = y2[m]; M[2 * m] = a.x; M[2 * m + 1] = a.y; }
+  };
+  auto fetch = [&](int il, double (&M)[KE], double& c) __attribute__((always_inline)) {
+    fetch_m(il, M);
+    c = lds[il * B::BS + B::oC + rr];
+  };
+  // (a joiner of the pipelined kernel: what follows the separator's answer is on the launch's critical path)
+  // (the spike chains of penta_pipe_kernel always have their rows of Ft: cfg.fst is set)
+  constexpr bool early = !WGLOB && SPK;
+  if constexpr (early) {
     double* xs = lds + L.W;
+    // what does not depend on x_sep goes in front of the wait for it: the cleared x ring, the first row's matrices
+    if (wave == 0) {
+      for (int c = lane; c < 4 * KE; c += 64) xb[c] = 0.0;
+      if (nloc > 0) fetch_m(nloc - 1, M0);
+#pragma unroll
+      for (int m = 0; m < KE; ++m) asm volatile("" : "+v"(M0[m]));   // (the reads stay in front of the poll)
+    }
     // (the 2K threads that fetch x_sep poll their own entry, which carries the epoch: penta_nd.h ll_store)
     if (tid < 2 * KE) {
       const int half = tid / KE, r = tid - half * KE;
       xs[tid] = (r < K) ? ll_load(cfg.xsep_ll + 2 * ((mirror ? half : 1 - half) * K + r), A.epoch, cfg.spin) : 0.0;   // mirrored chain: nearest = s, else nearest = s + 1
     }
     __syncthreads();
-    for (int il = wave; il < nloc; il += nwaves) {
-      if (lane < K) {
-        const double2* w2 = reinterpret_cast<const double2*>(lds + il * B::BS + B::oW + lane * YS);
+    // one round: a half-wavefront per row (ten rows on eight wavefronts were two), counted from the join end - the
+    // two join rows, which the recursion takes first, are wavefront 0's own and are not waited for
+    for (int t = 2 * wave + hf; t < nloc; t += 2 * nwaves) {
+      const int il = nloc - 1 - t;
+      if (r_ < K) {
+        const double2* w2 = reinterpret_cast<const double2*>(lds + il * B::BS + B::oW + r_ * YS);
         const double2* x2 = reinterpret_cast<const double2*>(xs);
         double a0 = 0.0, a1 = 0.0;
 #pragma unroll
         for (int m = 0; m < KE; ++m) { const double2 w = w2[m], x = x2[m]; a0 = __builtin_fma(w.x, x.x, a0); a1 = __builtin_fma(w.y, x.y, a1); }
-        lds[il * B::BS + B::oC + lane] -= a0 + a1;
+        lds[il * B::BS + B::oC + r_] -= a0 + a1;
       }
     }
-    __syncthreads();
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);
   }
   // ---- phase 3: the recursion on one wavefront.  Lanes 0..31: row r of Y_il (times x_{il+1}), lanes 32..63: row r of
   // Z_il (times x_{il+2}); the halves meet in one exchange.  The matrix rows are in registers a row ahead (two sets,
   // the loop is unrolled by two); on the dependent chain of a row: x_{il+1} back from LDS (ten broadcast reads), K
   // FMAs in two accumulators, the exchange, x_il to LDS.
-  if (wave != 0) return;
+  if (wave != 0) {
+    if constexpr (early) lds_barrier();   // (their rows of c: wavefront 0 comes here after its first row)
+    return;
+  }
   if (cfg.ts && tid == 0) cfg.ts[21] = (double)wall_clock64();
-  const int hf = lane >> 5, r_ = lane & 31, rr = r_ < K ? r_ : 0;
-  static_assert(K <= 32, "one row per lane of a half-wavefront");
-  for (int c = lane; c < 4 * KE; c += 64) xb[c] = 0.0;
+  if constexpr (!early) {
+    for (int c = lane; c < 4 * KE; c += 64) xb[c] = 0.0;
+  }
   if (cfg.two && producer) {
     // x of local rows nloc (next to this chain) and nloc + 1 come from the joiner (its two join rows)
     if (lane < K) {
@@ -1414,13 +1564,6 @@ __device__ __forceinline__ void pipe_backward(const PipeArgs& A, const ChainCfg&
       xb[((nloc + 1) & 3) * KE + lane] = ll_load(A.xjoin_ll + 2 * lane, A.epoch, cfg.spin);
     }
   }
-  double M0[KE], M1[KE], c0 = 0.0, c1 = 0.0;
-  auto fetch = [&](int il, double (&M)[KE], double& c) __attribute__((always_inline)) {
-    const double2* y2 = reinterpret_cast<const double2*>(lds + il * B::BS + B::oYZ + rr * YS + hf * KE);
-#pragma unroll
-    for (int m = 0; m < KE / 2; ++m) { const double2 a = y2[m]; M[2 * m] = a.x; M[2 * m + 1] = a.y; }
-    c = lds[il * B::BS + B::oC + rr];
-  };
   auto row = [&](int il, const double (&M)[KE], const double c, double (&Mn)[KE], double& cn) __attribute__((always_inline)) {
     const double2* xv = reinterpret_cast<const double2*>(xb + ((il + 1 + hf) & 3) * KE);
     double x[KE];
@@ -1440,11 +1583,24 @@ __device__ __forceinline__ void pipe_backward(const PipeArgs& A, const ChainCfg&
     }
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
   };
-  if (nloc > 0) fetch(nloc - 1, M0, c0);
-  if (cfg.ts && tid == 0) cfg.ts[22] = (double)wall_clock64();
-  for (int il = nloc - 1; il >= 0; il -= 2) {
-    row(il, M0, c0, M1, c1);
-    if (il >= 1) row(il - 1, M1, c1, M0, c0);
+  if constexpr (early) {
+    // the first row's matrices are in registers since before the wait, its c and the next row's are this wavefront's
+    // own; the barrier stands where the first row of another wavefront's correction is asked for
+    if (nloc > 0) c0 = lds[(nloc - 1) * B::BS + B::oC + rr];
+    if (cfg.ts && tid == 0) cfg.ts[22] = (double)wall_clock64();
+    if (nloc > 0) row(nloc - 1, M0, c0, M1, c1);
+    lds_barrier();   // (LDS only: __syncthreads would wait here for the first join row's stores to be acknowledged, 0.36 us)
+    for (int il = nloc - 2; il >= 0; il -= 2) {
+      row(il, M1, c1, M0, c0);
+      if (il >= 1) row(il - 1, M0, c0, M1, c1);
+    }
+  } else {
+    if (nloc > 0) fetch(nloc - 1, M0, c0);
+    if (cfg.ts && tid == 0) cfg.ts[22] = (double)wall_clock64();
+    for (int il = nloc - 1; il >= 0; il -= 2) {
+      row(il, M0, c0, M1, c1);
+      if (il >= 1) row(il - 1, M1, c1, M0, c0);
+    }
   }
   chain_ts(cfg, 4);
 }
@@ -1549,6 +1705,7 @@ __global__ void __launch_bounds__(512) penta_pipe_kernel(NdArgs A, PipeAsm F) {
   P.join_ll = A.ndbuf + B.joinll + (size_t)pair * B.joinll_pair;
   P.asm_ready = asm_on ? at_problem(F.ready, (size_t)blockIdx.y * A.pstride) : nullptr;
   P.asm_first = F.first; P.asm_rows = F.rows;
+  P.closed_tail = 0;
   const bool spike = role >= 2;
   const PipeLds L = pipe_layout<K>(A.n, spike);
   if (spike) pipe_forward<K, true>(P, c, L);
@@ -1559,11 +1716,17 @@ __global__ void __launch_bounds__(512) penta_pipe_kernel(NdArgs A, PipeAsm F) {
   // Recursion form only where the triangular solves are long (K = 19): multiplying by precomputed U^-1 blocks costs
   // a factor ~cond(U) of backward error (measured 1e-14 componentwise against 1e-16; the forward error is unchanged),
   // which small blocks need not pay - their row-by-row chain is K steps anyway.
-  const bool recursion = K > 8 && !A.debug_pipe_tail && pipe_backward_fits<K, true>(pipe_layout<K>(A.n, true), max(A.s - A.j1, A.j2 - A.s)) &&
+  // (debug_pipe_tail: 1 row by row, 2 the recursion walked row after row by the producers too)
+  const bool recursion = K > 8 && A.debug_pipe_tail != 1 && pipe_backward_fits<K, true>(pipe_layout<K>(A.n, true), max(A.s - A.j1, A.j2 - A.s)) &&
                          pipe_backward_fits<K, false>(pipe_layout<K>(A.n, false), max(A.j1, A.n - A.j2 - 2));
   if (recursion) {
+    // the producers' rows in closed form where both producers' T_i fit behind their [Y | Z | c] (K = 19: up to 9 rows,
+    // horizons up to 42 block rows; both or none, as with the form itself) and a thread per (row, component) exists
+    const int np = max(A.j1, A.n - A.j2 - 2);
+    P.closed_tail = !spike && A.debug_pipe_tail != 2 && pipe_closed_fits<K>(pipe_layout<K>(A.n, false), np) && np * K <= (int)blockDim.x;
     if (spike) pipe_backward<K, true>(P, c, L);
     else pipe_backward<K, false>(P, c, L);
+    if (P.closed_tail) pipe_closed_tail<K>();
     return;
   }
   if (threadIdx.x >= 256) return;

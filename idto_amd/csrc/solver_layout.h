@@ -244,6 +244,19 @@ struct PipeBack {
   static constexpr int oYZ = 0, oW = K * YS, oC = oW + (SPK ? K * YS : 0), BS = oC + KE;
 };
 
+// A producer's recursion in closed form (penta_pipe.h pipe_closed_build): behind its rows of [Y | Z | c], the x ring and
+// the dump, per local row T_i = [G_i | chat_i] with x_i = chat_i + G_i [x_nloc ; x_nloc+1] - K rows of 2 KE + 1 entries,
+// the columns laid out like the two join rows in the x ring (pad columns zero) - and the identity in two more slots.
+// (Row stride: even, and no multiple of 16 dwords - the last pass reads a row per lane, as the recursion does.)
+template <int K>
+struct PipeClosed {
+  using B = PipeBack<K, false>;
+  static constexpr int KE = B::KE, NC = 2 * KE + 1, TS0 = 2 * KE + 2, TS = TS0 + (TS0 % 8 == 0 ? 2 : 0), SLOT = K * TS;
+  static constexpr int PAR = 8 * 2 * KE;   // behind the wavefronts' copies of the join rows, in what held rt of the local rows: seven words of arguments
+  IDTO_LAYOUT_HD static constexpr int base(int nloc) { return nloc * B::BS + 4 * KE + 2; }
+  IDTO_LAYOUT_HD static constexpr int end(int nloc) { return base(nloc) + (nloc + 2) * SLOT; }
+};
+
 // ---- the seven-workgroup kernel's chains (penta_nd.h, K = 23 / 29) take their back substitution in the same form.
 // Their forward pass (penta_ldl_body) leaves rt of the local rows at xall_off, in the middle of what the recursion
 // matrices will occupy: the rows move to the top of the launch's LDS first.

@@ -19,7 +19,10 @@ signed distance is beyond the contact threshold whichever end or point is taken 
 
 States.  The recipes restate the trajectory helpers of the tests (tests/test_model_cross_pairs.py touching_trajectory,
 tests/test_model_stem.py punyo_trajectory, tests/test_gpu_capsule.py frozen_case); tests/test_golden_examples.py
-rebuilds every stored q from those helpers and compares."""
+rebuilds every stored q from those helpers and compares.
+
+Directed contact states (the last section; tools/make_golden.py contact): the labels of a contact pair's branches, the
+margins every stored state keeps from the branch boundaries, and the names of a box's regions."""
 import copy
 import os
 
@@ -297,3 +300,138 @@ def traj_states(name, model, cfg, shared_change=None):
     for i, start, end in columns:
         q[:, i] = np.linspace(start, end, 4)
     return dict(helper="punyo_trajectory", N=3, seed=0, columns=columns), q
+
+
+# ---- directed contact states (tests/golden/contact/regions_<model>.json, tools/make_golden.py contact)
+# Labels.  Every pair of every stored state is labelled from the generator's own arithmetic (Kane.signed_distance,
+# Kane.pair_force), never from the oracle or the kernels:
+#   kind         "sphere-sphere" | "sphere-box" | "box-box"
+#   region       sphere-box: the clamped axes of the sphere's centre in the box frame with their signs, "+x" a face,
+#                "+x-z" an edge, "-x+y+z" a corner; "in+x" the centre inside the box, leaving through +x.  Otherwise "-"
+#   tie          "dx==dy" | "dy==dz" where the two smallest depths of an inside centre are EQUAL as doubles, else "-"
+#   active       phi <= threshold
+#   force        "softplus" | "linear" (exponent = -phi / smoothing_factor >= 37); "-" for an inactive pair
+#   dissipation  s = v_n / dissipation_velocity: "approach" s < 0, "separate" 0 <= s < 2, "zero" s >= 2 (the pair is
+#                active and its force is exactly zero); "-" inactive
+#   friction     |v_t| / stiction_velocity: "none" < 1e-8 (the tangential velocity vanishes up to the generator's
+#                numerical derivative), "stick" < 0.1, "slip" > 10, "mid" between; "-" inactive
+# Margins.  Each state stays clear of every branch boundary by at least the MIN_* below, except the one boundary a state
+# is aimed at ("just below the threshold"), where AIM_* holds instead; both are many orders above what double rounding
+# of the few operations between q and the compared value can move (1e-16 relative): a label cannot depend on whose
+# arithmetic evaluates it.
+MIN_CLAMP = 1e-6     # [m] | |c_i| - h_i | of a sphere's centre from every clamp plane of its box
+MIN_AXIS_GAP = 1e-6  # [m] second smallest depth - smallest depth of an inside centre (ties excepted: those are exact)
+MIN_PHI = 1e-6       # [m] |phi - threshold|
+AIM_PHI = 1e-8       # [m] the same for the states aimed at the threshold
+MIN_EXPONENT = 1e-3  # |exponent - 37| of an active pair
+AIM_EXPONENT = 1e-6  # the same for the states aimed at 37
+MIN_S = 1e-3         # min(|s|, |s - 2|) of an active pair
+MIN_VERTEX_DZ = 1e-6  # [m] box-box: second lowest vertex - lowest vertex
+MIN_CENTRES = 0.02   # [m] sphere-sphere: distance of the centres (the normal is d / |d|)
+REACH = 1e-3         # [m] n, Ca, Cb are stored for the pairs with phi <= threshold + REACH: the active ones and the
+                     # ones aimed just above the threshold
+STICK, SLIP, NONE = 0.1, 10.0, 1e-8
+
+
+class ContactMargins:
+    """smallest distance of the stored states from each branch boundary; `aimed` is the set of boundaries the state under
+    evaluation is aimed at ("phi", "exponent"): AIM_* instead of MIN_* holds there, for the pair `aimed_pair` only"""
+    KEYS = ("clamp", "axis_gap", "phi", "phi_aimed", "exponent", "exponent_aimed", "s", "vertex_dz", "centres")
+
+    def __init__(self):
+        self.least = {k: None for k in self.KEYS}
+
+    def check(self, key, value, bound, what):
+        value = float(value)
+        if value < bound:
+            raise ValueError(f"{what}: {key} margin {value} < {bound}")
+        old = self.least[key]
+        self.least[key] = value if old is None else min(old, value)
+
+    def merge(self, other):
+        for k, val in other.least.items():
+            if val is not None:
+                self.least[k] = val if self.least[k] is None else min(self.least[k], val)
+
+    def as_dict(self):
+        return dict(least=self.least,
+                    bound=dict(clamp=MIN_CLAMP, axis_gap=MIN_AXIS_GAP, phi=MIN_PHI, phi_aimed=AIM_PHI, exponent=MIN_EXPONENT,
+                               exponent_aimed=AIM_EXPONENT, s=MIN_S, vertex_dz=MIN_VERTEX_DZ, centres=MIN_CENTRES),
+                    rule="least over all pairs of all states; *_aimed: the pair a state aims at that boundary; null: no "
+                         "such pair")
+
+
+def box_region(c, h):
+    """(region, tie, distance from the clamp planes, gap of the two smallest depths or None)"""
+    c, h = np.asarray(c, float), np.asarray(h, float)
+    clamp = float(np.abs(np.abs(c) - h).min())
+    out = "".join(("+" if c[i] > h[i] else "-") + "xyz"[i] for i in range(3) if abs(c[i]) > h[i])
+    if out:
+        return out, "-", clamp, None
+    depth = h - np.abs(c)
+    order = np.argsort(depth, kind="stable")
+    ax = int(order[0])
+    tie = "-"
+    if depth[order[0]] == depth[order[1]]:
+        tie = {(0, 1): "dx==dy", (1, 2): "dy==dz"}.get((int(order[0]), int(order[1])), "other")
+    return "in" + ("+" if c[ax] >= 0 else "-") + "xyz"[ax], tie, clamp, float(depth[order[1]] - depth[order[0]])
+
+
+def contact_labels(kane, model, X, q, v, aimed=None, what=""):
+    """per pair: dict(kind, region, tie, active, force, dissipation, friction, phi[, n, Ca, Cb]); and the ContactMargins of
+    the state.  X: the generator's body poses at q (make_golden.fk).  aimed: {"phi": pair} / {"exponent": pair}.  Raises
+    ValueError when a margin is missed."""
+    aimed = aimed or {}
+    margins = ContactMargins()
+    vs, vd = kane.cp["stiction_velocity"], kane.cp["dissipation_velocity"]
+    pairs = []
+    for k, (ga, gb) in enumerate(zip(model.pair_a, model.pair_b)):
+        ga, gb = int(ga), int(gb)
+        types = sorted((int(model.geom_type[ga]), int(model.geom_type[gb])))
+        kind = {(SPHERE, SPHERE): "sphere-sphere", (SPHERE, BOX): "sphere-box", (BOX, BOX): "box-box"}[tuple(types)]
+        detail = {}
+        phi, n, Ca, Cb = kane.signed_distance(ga, gb, X, detail)
+        lab = dict(kind=kind, region="-", tie="-", active=bool(phi <= kane.threshold), force="-", dissipation="-",
+                   friction="-", phi=float(phi))
+        w = f"{what} pair {k}"
+        if kind == "sphere-box":
+            lab["region"], lab["tie"], clamp, gap = box_region(detail["c"], detail["h"])
+            margins.check("clamp", clamp, MIN_CLAMP, w)
+            if gap is not None and lab["tie"] == "-":
+                margins.check("axis_gap", gap, MIN_AXIS_GAP, w)
+        elif kind == "box-box":
+            z = detail["vertex_z"]
+            margins.check("vertex_dz", z[1] - z[0], MIN_VERTEX_DZ, w)
+        else:
+            margins.check("centres", phi + model.geom_size[ga][0] + model.geom_size[gb][0], MIN_CENTRES, w)
+        if aimed.get("phi") == k:
+            margins.check("phi_aimed", abs(phi - kane.threshold), AIM_PHI, w)
+        else:
+            margins.check("phi", abs(phi - kane.threshold), MIN_PHI, w)
+        if lab["active"]:
+            pf = kane.pair_force(q, v, X, ga, gb)
+            if aimed.get("exponent") == k:
+                margins.check("exponent_aimed", abs(pf["exponent"] - 37), AIM_EXPONENT, w)
+            else:
+                margins.check("exponent", abs(pf["exponent"] - 37), MIN_EXPONENT, w)
+            margins.check("s", min(abs(pf["s"]), abs(pf["s"] - 2)), MIN_S, w)
+            lab["force"] = "linear" if pf["exponent"] >= 37 else "softplus"
+            lab["dissipation"] = "approach" if pf["s"] < 0 else ("separate" if pf["s"] < 2 else "zero")
+            r = float(np.sqrt(pf["vt"] @ pf["vt"])) / vs
+            lab["friction"] = "none" if r < NONE else ("stick" if r < STICK else ("slip" if r > SLIP else "mid"))
+            if lab["dissipation"] == "zero":
+                assert pf["fn"] == 0.0 and not np.any(pf["fB"]), "s >= 2 must give a force that is exactly zero"
+        if phi <= kane.threshold + REACH:
+            lab.update(n=[float(x) for x in n], Ca=[float(x) for x in Ca], Cb=[float(x) for x in Cb])
+        pairs.append(lab)
+    return pairs, margins
+
+
+# The labels every fixture must cover (tools/make_golden.py contact asserts them; tests/test_contact_regions.py states
+# them again and compares).  "pairs" below: the sphere-box pairs of the model's box under test.
+FACES = ["+x", "-x", "+y", "-y", "+z", "-z"]
+EDGES = [a + b for a, b in (("+x", "+y"), ("+x", "-y"), ("-x", "+y"), ("-x", "-y"), ("+x", "+z"), ("+x", "-z"), ("-x", "+z"),
+                            ("-x", "-z"), ("+y", "+z"), ("+y", "-z"), ("-y", "+z"), ("-y", "-z"))]
+CORNERS = [a + b + c for a in ("+x", "-x") for b in ("+y", "-y") for c in ("+z", "-z")]
+INSIDE = ["in+x", "in-x", "in+y", "in-y", "in+z", "in-z"]
+

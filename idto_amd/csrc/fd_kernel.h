@@ -922,5 +922,37 @@ __global__ void __launch_bounds__(256) fd_along_batch_kernel(DevModel M, DevCont
                        stop_after, echunk, nullptr);
 }
 
+// fd_kernel for a batch whose problems have models, contact parameters and gravity of their own
+// (idto_hip_set_model_batch): problem blockIdx.y has them in its parameter record, mstride bytes on from problem 0's - the
+// DevContact cat bytes into the record, the DevModel (its tables the record's own blob) mat bytes (model_layout.h
+// model_record_*).  The topology, hence everything the launch was sized by, is the batch's.  A kernel of its own, so that
+// fd_kernel's own code is what it was: the same fd_body, its M and cp read from the record where fd_kernel reads its arguments.
+template <int MAXC, int SHAPE = 0>
+__global__ void __launch_bounds__(256) fd_models_kernel(const double* __restrict__ records, size_t mstride, size_t cat, size_t mat,
+                          DevProblem P, const double* __restrict__ q, double* __restrict__ slab, int slab_stride,
+                          double* __restrict__ v_out, double* __restrict__ a_out, double* __restrict__ nplus_out, int k_begin,
+                          int mode, int stop_after, int echunk, size_t pstride, double* __restrict__ terms, AltSel alt) {
+  const size_t o = (size_t)blockIdx.y * pstride;
+  const size_t w = o + (size_t)alt_offset(alt, o);
+  const RecordPtr rec = record_at(records, (size_t)blockIdx.y * mstride);
+  fd_body<MAXC, SHAPE>(*(const DevModel*)(rec + mat), *(const DevContact*)(rec + cat), at_problem(P, o), at_problem(q, o),
+                       at_problem(slab, w), slab_stride, at_problem(v_out, w), at_problem(a_out, w), at_problem(nplus_out, w),
+                       k_begin + (int)blockIdx.x, mode, stop_after, echunk, terms ? at_problem(terms, w) : nullptr);
+}
+
+// ... and fd_along_batch_kernel for such a batch: blockIdx.y is the candidate, blockIdx.z the problem and its record.
+template <int MAXC, int SHAPE = 0>
+__global__ void __launch_bounds__(256) fd_along_models_kernel(const double* __restrict__ records, size_t mstride, size_t cat,
+                          size_t mat, DevProblem P, const double* __restrict__ q, double* __restrict__ slab, int slab_stride,
+                          double* __restrict__ v_out, double* __restrict__ a_out, double* __restrict__ nplus_out, int k_begin,
+                          int stop_after, int echunk, size_t cstride, const double* __restrict__ gate, size_t pstride,
+                          size_t bstride, size_t gstride) {
+  if (gate && *at_problem(gate, (size_t)blockIdx.z * gstride) != 0.0) return;
+  const size_t w = (size_t)blockIdx.z * bstride + (size_t)blockIdx.y * cstride;
+  const RecordPtr rec = record_at(records, (size_t)blockIdx.z * mstride);
+  fd_body<MAXC, SHAPE>(*(const DevModel*)(rec + mat), *(const DevContact*)(rec + cat), at_problem(P, (size_t)blockIdx.z * pstride),
+                       at_problem(q, w), at_problem(slab, w), slab_stride, at_problem(v_out, w), at_problem(a_out, w),
+                       at_problem(nplus_out, w), k_begin + (int)blockIdx.x, 0, stop_after, echunk, nullptr);
+}
 
 }  // namespace idto_dev

@@ -28,6 +28,10 @@ struct FdLaunch {
   // along_batch: grid.z counts the problems of a batch as well (fd_along_batch_kernel): their arrays pstride bytes apart, their
   // candidates' arenas bstride bytes, their gate words gstride bytes
   bool along_batch = false; size_t bstride = 0, gstride = 0;
+  // records != nullptr: a batch whose problems have parameter records of their own, mstride bytes apart (fd_models_kernel,
+  // fd_along_models_kernel): the kernel reads the problem's DevModel and DevContact rec_model / rec_contact bytes into its
+  // record (model_layout.h model_record_*), not this struct's M and cp
+  const double* records = nullptr; size_t mstride = 0, rec_contact = 0, rec_model = 0;
   int shape;   // id_fast.h: the model's instantiated tree shape, 0: id_eval<MAXC>, SHAPE_XCH: id_eval<8, true> (shared pairs), SHAPE_STEM: id_eval<8, true, true>
   int maxc;
 };

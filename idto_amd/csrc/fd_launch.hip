@@ -9,6 +9,17 @@ namespace idto_dev {
 // model_layout.h's shapes - the tree shapes, SHAPE_XCH, SHAPE_STEM - with the chain bound the table gives it.
 template <int MC, int SH>
 static void go(const FdLaunch& a) {
+  if (a.records && a.cstride) {   // candidate points of a batch with per-problem parameter records (LaunchFd: always a batch)
+    hipLaunchKernelGGL((fd_along_models_kernel<MC, SH>), a.grid, a.block, a.lds, a.stream, a.records, a.mstride, a.rec_contact,
+                       a.rec_model, a.P, a.q, a.slab, a.slab_stride, a.v, a.a, a.nplus, a.k_begin, a.stop_after, a.echunk, a.cstride, a.gate, a.pstride,
+                       a.bstride, a.gstride);
+    return;
+  }
+  if (a.records) {   // a batch with per-problem parameter records (fd_models_kernel)
+    hipLaunchKernelGGL((fd_models_kernel<MC, SH>), a.grid, a.block, a.lds, a.stream, a.records, a.mstride, a.rec_contact, a.rec_model,
+                       a.P, a.q, a.slab, a.slab_stride, a.v, a.a, a.nplus, a.k_begin, a.mode, a.stop_after, a.echunk, a.pstride, a.terms, a.alt);
+    return;
+  }
   if (a.cstride && a.along_batch) {   // candidate points of the problems of a batch, tau only (fd_along_batch_kernel)
     hipLaunchKernelGGL((fd_along_batch_kernel<MC, SH>), a.grid, a.block, a.lds, a.stream, a.M, a.cp, a.P, a.q, a.slab,
                        a.slab_stride, a.v, a.a, a.nplus, a.k_begin, a.stop_after, a.echunk, a.cstride, a.gate, a.pstride,
@@ -28,6 +39,8 @@ static void allow(int max_lds) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fd_kernel<MC, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fd_along_kernel<MC, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fd_along_batch_kernel<MC, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fd_models_kernel<MC, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fd_along_models_kernel<MC, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
 }
 using Shapes = std::make_integer_sequence<int, SHAPE_STEM>;   // (shape = 1 + the index)
 

@@ -203,6 +203,14 @@ int idto_opt_solve(idto_opt* o, const double* q_guess, double* sol_q, double* so
 int idto_opt_solve_batch(idto_opt* o, int B, const idto_problem_t* problems, const double* q_guesses, int only_best,
                          double* sol_q, double* sol_v, double* sol_tau, idto_stats_t* stats, int* flags, int* reasons,
                          double* final_costs, int* best) {
+  return idto_opt_solve_batch_models(o, B, problems, nullptr, nullptr, q_guesses, only_best, sol_q, sol_v, sol_tau, stats, flags,
+                                     reasons, final_costs, best);
+}
+
+int idto_opt_solve_batch_models(idto_opt* o, int B, const idto_problem_t* problems, const idto_model_t* const* models,
+                                const idto_contact_params_t* const* contacts, const double* q_guesses, int only_best,
+                                double* sol_q, double* sol_v, double* sol_tau, idto_stats_t* stats, int* flags, int* reasons,
+                                double* final_costs, int* best) {
   return Guard([&] {
     if (B < 1 || !q_guesses) throw std::runtime_error("solve_batch: B >= 1 problems and their q_guesses are required");
     const int nq = o->nq, nv = o->nv;
@@ -212,7 +220,15 @@ int idto_opt_solve_batch(idto_opt* o, int B, const idto_problem_t* problems, con
     const size_t nqa = (size_t)(o->N + 1) * nq, nva = (size_t)(o->N + 1) * nv, nta = (size_t)o->N * nv;
     for (int b = 0; b < B; ++b) guesses[b] = Rows(q_guesses + b * nqa, o->N + 1, nq);
     auto& R = o->batch;
-    o->to->SolveBatch(guesses, problems ? &probs : nullptr, &R, only_best != 0);
+    if (models || contacts) {
+      std::vector<const idto_model_t*> ms;
+      std::vector<const idto_contact_params_t*> cs;
+      if (models) ms.assign(models, models + B);
+      if (contacts) cs.assign(contacts, contacts + B);
+      o->to->SolveBatch(guesses, problems ? &probs : nullptr, ms, cs, &R, only_best != 0);
+    } else {
+      o->to->SolveBatch(guesses, problems ? &probs : nullptr, &R, only_best != 0);
+    }
     for (int b = 0; b < B; ++b) {
       if (!R.solutions[b].q.empty()) {   // (only_best: the best entry's alone; an entry that failed has none)
         Flat(R.solutions[b].q, sol_q ? sol_q + b * nqa : nullptr);

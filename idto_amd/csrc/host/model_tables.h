@@ -8,15 +8,9 @@
 #include <vector>
 
 #include "idto_model.h"
+#include "model_layout.h"   // IDTO_MODEL_DOUBLE_TABLES / IDTO_MODEL_INT_TABLES: DevModel's table pointers, by member name
 
 namespace idto_host {
-
-// DevModel's table pointers, by member name
-#define IDTO_MODEL_DOUBLE_TABLES(X) \
-  X(X_PF) X(axis) X(mass) X(com) X(inertia) X(damping) X(geom_X) X(geom_size) X(nplus_const) X(f_body) X(f_cbody) X(f_pairs)
-#define IDTO_MODEL_INT_TABLES(X)                                                                                      \
-  X(parent) X(jtype) X(qstart) X(vstart) X(geom_type) X(chain) X(nchain) X(pkind) X(path_npairs) X(path_pairs) X(pair_ga) \
-  X(pair_gb) X(pair_sa) X(pair_sb) X(colinfo) X(rowinfo) X(f_seg) X(xrec) X(pair_xa) X(pair_xb) X(stem)
 
 struct ModelTables {
   // the double tables, then the int tables (two per double slot) and a trailing pad

@@ -1467,8 +1467,8 @@ void ClearStats(TrajectoryOptimizerStats<double>* s) {
 void ClearSolution(TrajectoryOptimizerSolution<double>* s) { s->q.clear(); s->v.clear(); s->tau.clear(); }
 }  // namespace
 
-TO::BatchContext* TO::GetBatchContext(int B, const std::vector<const ProblemDefinition*>& probs) const {
-  BatchContext& bc = batch_ctx_[B];
+TO::BatchContext* TO::GetBatchContext(int B, const std::vector<const ProblemDefinition*>& probs, const BatchPhysics* physics) const {
+  BatchContext& bc = batch_ctx_[physics ? -B : B];
   const std::size_t nqa = (std::size_t)num_vars(), nva = (std::size_t)(num_steps() + 1) * nv_, nta = (std::size_t)num_steps() * nv_;
   if (!bc.ctx) {
     bc.q.resize(B * nqa); bc.q_nom.resize(nqa); bc.v_nom.resize(nva);
@@ -1498,6 +1498,7 @@ TO::BatchContext* TO::GetBatchContext(int B, const std::vector<const ProblemDefi
     p.Qq = pd.Qq.data(); p.Qv = pd.Qv.data(); p.Qf_q = pd.Qf_q.data(); p.Qf_v = pd.Qf_v.data();
     p.R = pd.R.data(); p.q_nom = bc.q_nom.data(); p.v_nom = bc.v_nom.data();
     Check(idto_hip_set_problem_batch(bc.ctx, b, &p));
+    if (physics) Check(idto_hip_set_model_batch(bc.ctx, b, physics->models[b], physics->contacts[b]));
   }
   return &bc;
 }
@@ -1536,6 +1537,37 @@ void TO::SolveBatchEntryAlone(const ProblemDefinition* prob, const std::vector<V
 
 void TO::SolveBatch(const std::vector<std::vector<VectorXd>>& q_guesses, const std::vector<ProblemDefinition>* problems,
                     BatchSolveResult* out, bool only_best) const {
+  SolveBatchImpl(q_guesses, problems, nullptr, out, only_best);
+}
+
+void TO::SolveBatch(const std::vector<std::vector<VectorXd>>& q_guesses, const std::vector<ProblemDefinition>* problems,
+                    const std::vector<const idto_model_t*>& models, const std::vector<const idto_contact_params_t*>& contacts,
+                    BatchSolveResult* out, bool only_best) const {
+  const std::size_t B = q_guesses.size();
+  if ((!models.empty() && models.size() != B) || (!contacts.empty() && contacts.size() != B))
+    throw std::invalid_argument("SolveBatch: models and contacts are empty or have one entry per q_guess");
+  BatchPhysics physics;
+  physics.models = models.empty() ? std::vector<const idto_model_t*>(B, nullptr) : models;
+  physics.contacts = contacts.empty() ? std::vector<const idto_contact_params_t*>(B, nullptr) : contacts;
+  SolveBatchImpl(q_guesses, problems, &physics, out, only_best);
+}
+
+// why the batch linesearch loop does not serve B problems of this optimizer ("": it does) - the conditions of SolveBatch's
+// linesearch route, by name
+std::string TO::LinesearchBatchRefusal(int B, const std::vector<const ProblemDefinition*>& probs) const {
+  if (B < 2) return "B < 2 (a batch of fewer than two entries)";
+  if (!shard_ctx_.empty()) return "several devices";
+  if (params_.verbose) return "verbose";
+  for (const ProblemDefinition* p : probs)
+    if (!DiagonalWeights(*p)) return "dense weights (a cost weight matrix that is not diagonal)";
+  if (!LinesearchLoopEligible())
+    return "method = kLinesearch outside the device's linesearch loop (scaling, enforced constraints, linear_solver = kDenseLdlt, "
+           "the debug switches, max_linesearch_iterations > 64 or the host loop)";
+  return "";
+}
+
+void TO::SolveBatchImpl(const std::vector<std::vector<VectorXd>>& q_guesses, const std::vector<ProblemDefinition>* problems,
+                        const BatchPhysics* physics, BatchSolveResult* out, bool only_best) const {
   using clock = std::chrono::high_resolution_clock;
   const int B = (int)q_guesses.size();
   if (B < 1) throw std::runtime_error("SolveBatch: no q_guesses");
@@ -1563,10 +1595,20 @@ void TO::SolveBatch(const std::vector<std::vector<VectorXd>>& q_guesses, const s
   bool batch_route = B >= 2 && params_.method == kTrustRegion && shard_ctx_.empty() && !adaptive && !params_.verbose &&
                      DeviceLoopEligible() && ResidentLoopEligible();
   for (int b = 0; batch_route && b < B; ++b) batch_route = DiagonalWeights(*probs[b]);
+  if (physics) {
+    // per-entry models: no entry-by-entry route.  Every refusal here, before any device work, by name.
+    const char* who = "SolveBatch with per-entry models has no entry-by-entry route and the batch loops do not serve ";
+    std::string why = params_.method == kTrustRegion ? BatchLoopRefusal(B, probs) : LinesearchBatchRefusal(B, probs);
+    if (why.empty() && params_.method == kTrustRegion && !batch_route) why = "this configuration (the device's resident loop is not eligible)";
+    if (!why.empty()) throw std::invalid_argument(who + why);
+    for (int b = 0; b < B; ++b)
+      if (idto_hip_check_model_batch(hip_, b, physics->models[b], physics->contacts[b]) != 0)
+        throw std::invalid_argument(std::string("SolveBatch: ") + idto_hip_last_error());
+  }
 
   std::vector<char> alone((std::size_t)B, batch_route ? 0 : 1);
   if (batch_route) {
-    BatchContext* bc = GetBatchContext(B, probs);
+    BatchContext* bc = GetBatchContext(B, probs, physics);
     int resident_ok = 1;
     Check(idto_hip_get_option(bc->ctx, "tr_resident_ok", &resident_ok));
     const std::size_t nqa = (std::size_t)num_vars(), nva = (std::size_t)(num_steps() + 1) * nv_, nta = (std::size_t)num_steps() * nv_;
@@ -1605,6 +1647,12 @@ void TO::SolveBatch(const std::vector<std::vector<VectorXd>>& q_guesses, const s
                               &out->stats[b], &r);
         out->flags[b] = r.flag;
         out->final_costs[b] = bc->final_cost[b];
+        if (r.outcome == internal::RowsOutcome::kNeedsHostLoop && physics) {   // (no context holds this entry's model alone)
+          out->flags[b] = SolverFlag::kFactorizationFailed;
+          out->errors[b] = "the batch loop left this entry to the host loop, which a batch with per-entry models does not have";
+          out->final_costs[b] = std::numeric_limits<double>::quiet_NaN();
+          continue;
+        }
         if (r.outcome == internal::RowsOutcome::kNeedsHostLoop) { alone[b] = 1; continue; }
         if (r.outcome != internal::RowsOutcome::kDone) {
           out->flags[b] = SolverFlag::kFactorizationFailed;
@@ -1625,6 +1673,9 @@ void TO::SolveBatch(const std::vector<std::vector<VectorXd>>& q_guesses, const s
     } else if (!resident_ok || rc == IDTO_HIP_SOLVER_TIMEOUT ||
                (rc == -1 && std::strstr(idto_hip_last_error(), "child-context route"))) {
       // the loop's workgroups timed out on a shared device, or these constraints take the child-context route: entry by entry
+      if (physics) throw std::runtime_error(std::string("SolveBatch with per-entry models: the batch loop did not run (") +
+                                            (resident_ok ? idto_hip_last_error() : "the context's resident loop is off after a time-out") +
+                                            ") and there is no entry-by-entry route");
       batch_route = false;
       std::fill(alone.begin(), alone.end(), 1);
     } else {
@@ -1638,7 +1689,7 @@ void TO::SolveBatch(const std::vector<std::vector<VectorXd>>& q_guesses, const s
   bool ls_route = B >= 2 && params_.method == kLinesearch && shard_ctx_.empty() && !params_.verbose && LinesearchLoopEligible();
   for (int b = 0; ls_route && b < B; ++b) ls_route = DiagonalWeights(*probs[b]);
   if (ls_route) {
-    BatchContext* bc = GetBatchContext(B, probs);
+    BatchContext* bc = GetBatchContext(B, probs, physics);
     const std::size_t nqa = (std::size_t)num_vars(), nva = (std::size_t)(num_steps() + 1) * nv_, nta = (std::size_t)num_steps() * nv_;
     const int iters = params_.max_iterations;
     for (int b = 0; b < B; ++b)
@@ -1665,6 +1716,12 @@ void TO::SolveBatch(const std::vector<std::vector<VectorXd>>& q_guesses, const s
         out->flags[b] = r.flag;
         out->final_costs[b] = bc->final_cost[b];
         // (backtracking undecided within the device's candidates: the entry is solved again alone, where the host loop takes over)
+        if (r.outcome == internal::LsRowsOutcome::kNeedsHostLoop && physics) {   // (no context holds this entry's model alone)
+          out->flags[b] = SolverFlag::kFactorizationFailed;
+          out->errors[b] = "the batch loop left this entry to the host loop, which a batch with per-entry models does not have";
+          out->final_costs[b] = std::numeric_limits<double>::quiet_NaN();
+          continue;
+        }
         if (r.outcome == internal::LsRowsOutcome::kNeedsHostLoop) { alone[b] = 1; continue; }
         if (r.outcome != internal::LsRowsOutcome::kDone) {   // the entry's own failure, with the host loop's text
           out->flags[b] = SolverFlag::kFactorizationFailed;
@@ -1684,6 +1741,8 @@ void TO::SolveBatch(const std::vector<std::vector<VectorXd>>& q_guesses, const s
       batch_route = true;
     } else if (rc == IDTO_HIP_SOLVER_TIMEOUT) {
       // a solver launch's workgroups timed out on a shared device: every entry runs alone (alone[] says so already)
+      if (physics) throw std::runtime_error(std::string("SolveBatch with per-entry models: the batch linesearch loop timed out (") +
+                                            idto_hip_last_error() + ") and there is no entry-by-entry route");
     } else {
       Check(rc);
     }

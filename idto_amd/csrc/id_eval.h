@@ -120,6 +120,27 @@ struct DevContact {
   double k, vd, vs, mu, sigma, threshold;
 };
 
+static_assert(sizeof(DevContact) == MREC_CONTACT * sizeof(double), "model_layout.h: the record's contact doubles are a DevContact");
+static_assert(sizeof(DevModel) <= MREC_DEVMODEL * sizeof(double), "model_layout.h: the record's room for a DevModel");
+
+// M with every table pointer (model_layout.h's two lists) and the blob moved from its blob to a copy of it at `blob`:
+// how the DevModel in a problem's parameter record is made from the context's (idto_hip_set_model_batch)
+__host__ __device__ inline void shift_model(DevModel& M, const double* blob) {
+  const ptrdiff_t shift = reinterpret_cast<const char*>(blob) - reinterpret_cast<const char*>(M.blob);
+#define X(name) M.name = reinterpret_cast<decltype(M.name)>(reinterpret_cast<const char*>(M.name) + shift);
+  IDTO_MODEL_DOUBLE_TABLES(X) IDTO_MODEL_INT_TABLES(X)
+#undef X
+  M.blob = blob;
+}
+// A problem's parameter record, read like a kernel's arguments are: through the constant address space - the record is
+// written by the host before the launch and by nobody during it -, so that a uniform access is a scalar load whatever the
+// kernel has stored in between, a member indexed at run time (float_qs) included.  (A DevModel shifted inside the kernel
+// is a private copy that such an index keeps in scratch: 424 B a lane, and up to 107 spilled vector registers.)
+typedef const char __attribute__((address_space(4))) * RecordPtr;
+IDTO_DEV RecordPtr record_at(const double* records, size_t byte_off) {
+  return (RecordPtr)(reinterpret_cast<const char*>(records) + byte_off);
+}
+
 struct BodyState {  // what later stages need of a body
   M3 R;
   V3 p, w, v;

@@ -39,6 +39,7 @@
 #include "kkt.h"
 #include "linesearch.h"
 #include "mpc_batch.h"
+#include "host/model_batch.h"
 #include "host/model_tables.h"
 #include "host/solver_plan.h"
 
@@ -214,6 +215,12 @@ struct idto_hip_ctx {
   std::unique_ptr<HostModelCopy> host_model;
   std::vector<std::unique_ptr<HostProblemCopy>> host_problems;
   idto_contact_params_t host_contact{};
+  // per-problem models (idto_hip_set_model_batch): the base model's tables (every batch context keeps them, for the
+  // check of a variant) and, from the first successful call on, one parameter record per problem (model_layout.h
+  // model_record_*: blob | contact | gravity), mstride bytes apart - LaunchFd then starts fd_models_kernel /
+  // fd_along_models_kernel, which read problem b's model, contact parameters and gravity from record b
+  std::unique_ptr<idto_host::ModelTables> host_tables;
+  double* model_records = nullptr; size_t mstride = 0;
   std::vector<idto_hip_ctx*> children;
   // batch: `batch` problems of the same model / horizon, one arena each (identical layout,
   // `pstride` bytes apart); the pointers below address problem 0
@@ -614,6 +621,11 @@ int LaunchFd(idto_hip_ctx* c, int mode, int kb, int ke, AltSel alt = AltSel{null
   fl.q = c->q; fl.slab = c->slab; fl.slab_stride = c->slab_stride; fl.v = c->v; fl.a = c->a; fl.nplus = c->nplus;
   fl.k_begin = kb; fl.mode = mode; fl.stop_after = c->fd_stop; fl.echunk = ec; fl.pstride = c->pstride; fl.terms = terms;
   fl.alt = alt;
+  if (c->model_records) {   // (a batch: idto_hip_set_model_batch)
+    fl.records = c->model_records; fl.mstride = c->mstride;
+    fl.rec_contact = model_record_contact_at((size_t)c->M.blob_n) * sizeof(double);
+    fl.rec_model = model_record_devmodel_at((size_t)c->M.blob_n) * sizeof(double);
+  }
   if (along) {
     fl.q = along->q; fl.slab = along->slab; fl.slab_stride = along->slab_stride; fl.v = along->v; fl.a = along->a;
     fl.nplus = along->nplus; fl.cstride = along->cstride; fl.gate = along->gate;
@@ -784,18 +796,17 @@ int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* probl
   c->host_model = std::make_unique<HostModelCopy>();
   c->host_model->Set(*model);
   c->host_contact = *contact;
+  c->host_tables = std::make_unique<idto_host::ModelTables>(tables);
   if (batch > 1) {
     for (int b = 0; b < batch; ++b) {
       c->host_problems.push_back(std::make_unique<HostProblemCopy>());
       c->host_problems.back()->Set(problems[b], model->nq, model->nv);
     }
   }
-  c->cp.k = contact->contact_stiffness; c->cp.vd = contact->dissipation_velocity;
-  c->cp.vs = contact->stiction_velocity; c->cp.mu = contact->friction_coefficient;
-  c->cp.sigma = contact->smoothing_factor;
-  {  // reference TO.cc:266-269, evaluated with the same deterministic exp/log as the device code
-    const double eps = std::sqrt(2.220446049250313e-16);
-    c->cp.threshold = -c->cp.sigma * idto::detmath::log(idto::detmath::exp(eps / (c->cp.sigma * c->cp.k)) - 1.0);
+  {
+    double cv[6];
+    idto_host::ContactValues(*contact, cv);   // (host/model_batch.h: the threshold's one expression)
+    c->cp.k = cv[0]; c->cp.vd = cv[1]; c->cp.vs = cv[2]; c->cp.mu = cv[3]; c->cp.sigma = cv[4]; c->cp.threshold = cv[5];
   }
   const size_t bsz = (size_t)nv * nq, qq = (size_t)nq * nq;
   c->slab_stride = (int)(3 * bsz + nv);
@@ -1071,6 +1082,68 @@ int idto_hip_set_problem_batch(idto_hip_ctx* c, int b, const idto_problem_t* p) 
 }
 
 int idto_hip_batch_size(idto_hip_ctx* c) { return c->batch; }
+
+int idto_hip_check_model_batch(idto_hip_ctx* c, int b, const idto_model_t* model, const idto_contact_params_t* contact) {
+  if (!c->host_tables || !c->host_model) { g_err = "check_model_batch: the context keeps no host copy of its model"; return -1; }
+  const idto_model_t* base = &c->host_model->m;
+  std::vector<double> record;
+  return idto_host::BuildModelVariant(base, *c->host_tables, b, model ? model : base, contact ? *contact : c->host_contact, &record, &g_err);
+}
+
+int idto_hip_set_model_batch(idto_hip_ctx* c, int b, const idto_model_t* model, const idto_contact_params_t* contact) {
+  if (!c->host_tables || !c->host_model || c->batch < 2) {
+    g_err = "set_model_batch: a context of one problem (a model of its own is what idto_hip_create gives it)";
+    return -1;
+  }
+  if (b < 0 || b >= c->batch) { g_err = "problem index outside the batch"; return -1; }
+  const idto_model_t* base = &c->host_model->m;
+  // every refusal is made here, on the host's tables: nothing has been enqueued or allocated by then
+  std::vector<double> record;
+  if (int rc = idto_host::BuildModelVariant(base, *c->host_tables, b, model ? model : base, contact ? *contact : c->host_contact,
+                                            &record, &g_err))
+    return rc;
+  HIP_OK(hipSetDevice(c->device));
+  const size_t bytes = record.size() * sizeof(double), mat = model_record_devmodel_at((size_t)c->M.blob_n);
+  // the record's DevModel: the context's, its tables the blob at the head of the record at device address `dev`
+  auto put_model = [&](std::vector<double>& rec, size_t at, const double* dev, const double* gravity) {
+    DevModel Mb = c->M;
+    shift_model(Mb, dev);
+    for (int i = 0; i < 3; ++i) Mb.gravity[i] = gravity[i];
+    std::memcpy(rec.data() + at + mat, &Mb, sizeof(DevModel));
+  };
+  if (!c->model_records) {   // the first call: every problem gets a record, the base model's
+    const std::vector<double> base_record = idto_host::ModelRecord(base, *c->host_tables, c->host_contact);
+    std::vector<double> all((size_t)c->batch * base_record.size());
+    double* dev = nullptr;
+    if (Alloc(c, all.size(), &dev)) return -2;
+    for (int p = 0; p < c->batch; ++p) {
+      std::copy(base_record.begin(), base_record.end(), all.begin() + (size_t)p * base_record.size());
+      put_model(all, (size_t)p * base_record.size(), dev + (size_t)p * base_record.size(), base->gravity);
+    }
+    if (hipMemcpy(dev, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+      g_err = "hipMemcpy (parameter records) failed"; Release(c, &dev); return -2;
+    }
+    c->model_records = dev; c->mstride = bytes;
+  }
+  put_model(record, 0, at_problem(c->model_records, (size_t)b * c->mstride), (model ? model : base)->gravity);
+  // (behind whatever the context has enqueued: a launch in flight keeps the record it started with)
+  if (c->async_uploads) {   // (from the context's pinned staging, no wait: as idto_hip_set_problem_batch uploads)
+    char* buf = nullptr; int slot = 0;
+    if (int rc = UploadStage(c, bytes, &buf, &slot)) return rc;
+    std::memcpy(buf, record.data(), bytes);
+    HIP_OK(hipMemcpyAsync(at_problem(c->model_records, (size_t)b * c->mstride), buf, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipEventRecord(c->up_ev[slot], c->stream));
+  } else {
+    HIP_OK(hipMemcpyAsync(at_problem(c->model_records, (size_t)b * c->mstride), record.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+  }
+  // what the device holds of the resident q belongs to the old record
+  c->fd_full = false; c->partials_ahead = false; c->terms_valid = false;
+  c->trial_resident = false; c->spec_pending = false; c->spec_ready = false;
+  c->con_ready = false; c->con_begun = false;
+  DropPrefetch(c, {IDTO_ARR_V, IDTO_ARR_A, IDTO_ARR_NPLUS, IDTO_ARR_SLAB, IDTO_ARR_COST});
+  return 0;
+}
 
 int idto_hip_create_batch_like(idto_hip_ctx* like, const idto_problem_t* problems, int batch, idto_hip_ctx** out) {
   *out = nullptr;
@@ -1798,6 +1871,7 @@ static int LaunchFused(idto_hip_ctx* c) {
 // weights, the whole horizon, the scalar band factorisation (BandEligible), nothing switched to a measurement mode.
 // p: the plan of the system the launch solves - H's, or the KKT context's with blocks of nq + nu
 static bool SmallEligible(const idto_hip_ctx* c, SolverPlan* p) {
+  if (c->model_records) return false;   // (the kernel stages the context's one model: idto_hip_set_model_batch)
   if (!c->gn_small || !c->fd_fast || c->gradients_method != 0 || !c->weights_diagonal || c->reference_solver) return false;
   if (c->M.nxb || c->M.nstem > 1) return false;   // (id_eval_fast has no shared pairs and no stem)
   if (!(c->M.fast_shape == 1 || c->M.fast_shape == 5) || c->M.nfloat != 0 || c->nq != c->nv || c->npaths != 1) return false;
@@ -2954,6 +3028,11 @@ int idto_hip_tr_solve_batch_constrained(idto_hip_ctx* c, int iterations, int sca
     return TrSolve(c, rq);
   }
   if (!c->host_model) { g_err = "tr_solve_batch_constrained: the context keeps no host copy of its model"; return -1; }
+  if (c->model_records) {   // (a child context is built from the host copy of the ONE model)
+    g_err = "tr_solve_batch_constrained: the child-context route of the constraints (option con_kkt 0, or nq + nu > 30) does "
+            "not serve a batch with per-problem models (idto_hip_set_model_batch)";
+    return -1;
+  }
   HIP_OK(hipSetDevice(c->device));
   HIP_OK(hipStreamSynchronize(c->stream));
   c->children.resize((size_t)B, nullptr);
@@ -3385,6 +3464,7 @@ int idto_hip_get_option(idto_hip_ctx* c, const char* name, int* value) {
   if (std::strcmp(name, "gradients_method") == 0) { *value = c->gradients_method; return 0; }
   if (std::strcmp(name, "fast_shape") == 0) { *value = c->M.fast_shape; return 0; }   // id_fast.h: 0 none, 1 acrobot, 2 hopper, 3 mini_cheetah, 4 allegro_hand, 5 spinner, 6 free object + one 7-body arm
   if (std::strcmp(name, "fd_fast") == 0) { *value = c->fd_fast ? 1 : 0; return 0; }
+  if (std::strcmp(name, "model_batch") == 0) { *value = c->model_records ? 1 : 0; return 0; }   // read-only: idto_hip_set_model_batch has switched the context to per-problem records
   g_err = std::string("unknown option ") + name;
   return -1;
 }

@@ -2,9 +2,30 @@
 // tables, the layout of id_fast.h's gathered records, and the instantiated tree shapes.  Constants only: no device code.
 #pragma once
 
+#include <cstddef>
+
 #include "idto_model.h"
 
+// DevModel's table pointers, by member name: what the host's packer places in the blob and what a kernel shifts when it
+// moves the model to another copy of the blob (id_eval.h shift_model)
+#define IDTO_MODEL_DOUBLE_TABLES(X) \
+  X(X_PF) X(axis) X(mass) X(com) X(inertia) X(damping) X(geom_X) X(geom_size) X(nplus_const) X(f_body) X(f_cbody) X(f_pairs)
+#define IDTO_MODEL_INT_TABLES(X)                                                                                      \
+  X(parent) X(jtype) X(qstart) X(vstart) X(geom_type) X(chain) X(nchain) X(pkind) X(path_npairs) X(path_pairs) X(pair_ga) \
+  X(pair_gb) X(pair_sa) X(pair_sb) X(colinfo) X(rowinfo) X(f_seg) X(xrec) X(pair_xa) X(pair_xb) X(stem)
+
 namespace idto_dev {
+
+// The parameter record of one problem of a batch with per-problem models (idto_hip_set_model_batch): the model's blob,
+// then - on the next 64-byte boundary - DevContact's six doubles and the three of gravity (host/model_batch.cc forms the
+// record up to here), then - 128 bytes on - the problem's DevModel as the kernels read it: the context's, its table
+// pointers moved to THIS record's blob and its gravity the problem's (idto_hip.hip writes it: it knows the device
+// address).  The record ends on a 64-byte boundary.  In doubles, for a blob of blob_n of them:
+constexpr int MREC_CONTACT = 6, MREC_GRAVITY = 3, MREC_PARAMS = 16, MREC_DEVMODEL = 64;
+constexpr size_t model_record_contact_at(size_t blob_n) { return (blob_n + 7) & ~(size_t)7; }
+constexpr size_t model_record_gravity_at(size_t blob_n) { return model_record_contact_at(blob_n) + MREC_CONTACT; }
+constexpr size_t model_record_devmodel_at(size_t blob_n) { return model_record_contact_at(blob_n) + MREC_PARAMS; }
+constexpr size_t model_record_doubles(size_t blob_n) { return model_record_devmodel_at(blob_n) + MREC_DEVMODEL; }
 
 // DevModel::pkind: what a chain slot's body hangs off
 enum { PK_WORLD = 0, PK_COMMON = 1, PK_PREV = 2 };

@@ -46,6 +46,8 @@ def lib():
                                             C.c_int, C.POINTER(C.c_void_p)]
         L.idto_hip_batch_size.argtypes = [C.c_void_p]
         L.idto_hip_set_problem_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(CProblem)]
+        L.idto_hip_set_model_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(CModel), C.POINTER(CContactParams)]
+        L.idto_hip_check_model_batch.argtypes = L.idto_hip_set_model_batch.argtypes
         L.idto_hip_set_q_batch.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.idto_hip_gn_step_batch.argtypes = [C.c_void_p]
         L.idto_hip_get_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
@@ -135,7 +137,7 @@ EXPORTED_SYMBOLS = [
     "idto_hip_set_option", "idto_hip_get_option",
     "idto_hip_timing_enable", "idto_hip_timing_reset", "idto_hip_timing_get", "idto_hip_sync", "idto_hip_get",
     "idto_hip_device_ptr", "idto_hip_array_size", "idto_hip_slab_stride", "idto_hip_math_probe",
-    "idto_hip_solver_status", "idto_hip_create_batch", "idto_hip_create_batch_like", "idto_hip_batch_size", "idto_hip_set_problem_batch",
+    "idto_hip_solver_status", "idto_hip_create_batch", "idto_hip_create_batch_like", "idto_hip_batch_size", "idto_hip_set_problem_batch", "idto_hip_set_model_batch", "idto_hip_check_model_batch",
     "idto_hip_set_q_batch", "idto_hip_gn_step_batch", "idto_hip_get_batch", "idto_hip_get_many", "idto_hip_solver_status_batch",
     "idto_hip_tr_prepare", "idto_hip_tr_trial", "idto_hip_tr_accept", "idto_hip_tr_reject", "idto_hip_tr_set_scale_memory", "idto_hip_tr_set_convergence", "idto_hip_tr_solve", "idto_hip_tr_solve_fetch", "idto_hip_tr_solve_batch", "idto_hip_tr_solve_batch_constrained", "idto_hip_tr_solve_batch_fetch", "idto_hip_set_unactuated_dofs",
     "idto_hip_mpc_batch_begin", "idto_hip_mpc_batch_store", "idto_hip_mpc_batch_shift", "idto_hip_mpc_batch_replan",
@@ -237,6 +239,14 @@ class HipPath:
     def set_problem_batch(self, b: int, prob: ProblemDefinition):
         cp, keep = prob.to_c()
         _chk(lib().idto_hip_set_problem_batch(self.h, int(b), C.byref(cp)))
+
+    def set_model_batch(self, b: int, model: Model = None, params: SolverParameters = None):
+        """idto_hip_set_model_batch: problem b of the batch gets `model` (same topology; None: the batch's) and the contact
+        parameters of `params` (None: the batch's)"""
+        cm, keep = model.to_c() if model is not None else (None, None)
+        cc = params.contact_to_c() if params is not None else None
+        _chk(lib().idto_hip_set_model_batch(self.h, int(b), C.byref(cm) if cm is not None else None,
+                                            C.byref(cc) if cc is not None else None))
 
     def solver_status_batch(self):
         out = (C.c_int * self.batch)()

@@ -43,6 +43,9 @@ def lib():
         L.idto_opt_num_equality_constraints.argtypes = [C.c_void_p]
         P = C.POINTER(C.c_double)
         L.idto_opt_solve.argtypes = [C.c_void_p, P, P, P, P, C.POINTER(CStats), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.idto_opt_solve_batch_models.argtypes = [C.c_void_p, C.c_int, C.POINTER(CProblem), C.POINTER(C.POINTER(CModel)),
+                                                  C.POINTER(C.POINTER(CContactParams)), P, C.c_int, P, P, P, C.POINTER(CStats),
+                                                  C.POINTER(C.c_int), C.POINTER(C.c_int), P, C.POINTER(C.c_int)]
         L.idto_opt_solve_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(CProblem), P, C.c_int, P, P, P, C.POINTER(CStats),
                                            C.POINTER(C.c_int), C.POINTER(C.c_int), P, C.POINTER(C.c_int)]
         L.idto_opt_batch_error.argtypes = [C.c_void_p, C.c_int]
@@ -92,7 +95,7 @@ EXPORTED_SYMBOLS = [
     "idto_opt_num_equality_constraints", "idto_opt_solve", "idto_opt_ws_create", "idto_opt_ws_destroy",
     "idto_opt_ws_set_q", "idto_opt_ws_get", "idto_opt_ws_solve", "idto_opt_reset_initial_conditions",
     "idto_opt_update_nominal_trajectory", "idto_opt_eval", "idto_opt_dogleg", "idto_opt_trust_ratio",
-    "idto_opt_solve_batch", "idto_opt_batch_error", "idto_opt_last_batch_route",
+    "idto_opt_solve_batch", "idto_opt_solve_batch_models", "idto_opt_batch_error", "idto_opt_last_batch_route",
 ]
 MPC_SYMBOLS = ["idto_mpc_create", "idto_mpc_destroy", "idto_mpc_num_actuators", "idto_mpc_update", "idto_mpc_state",
                "idto_mpc_control", "idto_mpc_start_time", "idto_mpc_spline_eval", "idto_mpc_stats",
@@ -260,11 +263,14 @@ class TrajectoryOptimizer:
         self.last_convergence_reason = reason.value
         return SOLVER_FLAGS[flag.value]
 
-    def solve_batch(self, q_guesses, problems=None, only_best: bool = False) -> BatchSolveResult:
+    def solve_batch(self, q_guesses, problems=None, only_best: bool = False, models=None, contacts=None) -> BatchSolveResult:
         """TrajectoryOptimizer::SolveBatch: entry b is `Solve(q_guesses[b])` on an optimizer made with `problems[b]` (None:
         this optimizer's own problem for every entry), all entries through ONE loop on the device - the trust-region batch
         loop or, with method = linesearch, the batch linesearch loop - where the configuration allows it (DESIGN.md section
-        12.1), one after another otherwise."""
+        12.1), one after another otherwise.
+        models / contacts: per entry a Model of the optimizer's topology / SolverParameters whose contact parameters the
+        entry takes (None, or an entry None: the optimizer's own).  Such a batch runs the batch loops only (DESIGN.md section
+        12.2): what they do not serve, B < 2 and a model that differs in a shared table raise before any device work."""
         q = _d(q_guesses)
         if q.ndim != 3 or q.shape[1:] != (self.N + 1, self.nq):
             raise RuntimeError(f"solve_batch: q_guesses must be [B, {self.N + 1}, {self.nq}]")
@@ -287,8 +293,27 @@ class TrajectoryOptimizer:
             cst[b] = stats[b].c
         flags, reasons, best = (C.c_int * B)(), (C.c_int * B)(), C.c_int(-1)
         costs = np.zeros(B)
-        self._chk(lib().idto_opt_solve_batch(self._h, B, carr, dptr(q), int(only_best), dptr(sq), dptr(sv), dptr(st), cst, flags,
-                                             reasons, dptr(costs), C.byref(best)))
+        marr = carr_c = None
+        if models is not None or contacts is not None:
+            for what, seq in (("models", models), ("contacts", contacts)):
+                if seq is not None and len(seq) != B:
+                    raise RuntimeError(f"solve_batch: q_guesses and {what} disagree in length ({B} and {len(seq)})")
+            if models is not None:
+                marr = (C.POINTER(CModel) * B)()
+                for b, m in enumerate(models):
+                    if m is not None:
+                        cm, k = m.to_c()
+                        keep.append((cm, k))
+                        marr[b] = C.pointer(cm)
+            if contacts is not None:
+                carr_c = (C.POINTER(CContactParams) * B)()
+                for b, sp in enumerate(contacts):
+                    if sp is not None:
+                        cc = sp.contact_to_c()
+                        keep.append(cc)
+                        carr_c[b] = C.pointer(cc)
+        self._chk(lib().idto_opt_solve_batch_models(self._h, B, carr, marr, carr_c, dptr(q), int(only_best), dptr(sq), dptr(sv),
+                                                    dptr(st), cst, flags, reasons, dptr(costs), C.byref(best)))
         errors = [lib().idto_opt_batch_error(self._h, b).decode() for b in range(B)]
         sols = []
         for b in range(B):

@@ -144,6 +144,9 @@ class ModelPredictiveController {
 //     controller's plan, solution and radius stay, flags are kFactorizationFailed; the next tick proceeds (the context
 //     has stepped down to a solver variant with fewer co-resident workgroups; if the iteration kernel itself timed out,
 //     the next UpdateAll throws what idto_hip_tr_solve reports).
+//
+// The B controllers share ONE model and ONE set of contact parameters: a model per controller (idto_hip_set_model_batch,
+// SolveBatch with models) is out of scope here.
 class BatchModelPredictiveController {
  public:
   // `optimizer` (not owned; its model, horizon and parameters serve every controller), one warm-start solution per

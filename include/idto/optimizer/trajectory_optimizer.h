@@ -126,6 +126,18 @@ class TrajectoryOptimizer<double> {
   // sizes differ from this optimizer's.
   void SolveBatch(const std::vector<std::vector<VectorXd>>& q_guesses, const std::vector<ProblemDefinition>* problems,
                   BatchSolveResult* out, bool only_best = false) const;
+  // The same with a model and contact parameters per entry (each vector empty or of B entries, an entry nullptr: the
+  // optimizer's own): entry b is Solve(q_guesses[b]) on an optimizer constructed with entry b's model, contact
+  // parameters and problem.  The models share the optimizer's topology - sizes, tree, joint and geometry types, pairs
+  // and paths, actuated mask, gravity switches - and may differ in the double tables, gravity and the five contact
+  // parameters (include/idto_hip.h idto_hip_set_model_batch).  Such a batch has NO entry-by-entry route - this
+  // optimizer's own context holds its own model -: std::invalid_argument, before any device work, names what the two
+  // batch loops do not serve (BatchLoopRefusal's list for the trust region, the linesearch loop's conditions above), B < 2
+  // or the table in which a model differs from the optimizer's; an entry the loop leaves to the host loop is reported in
+  // its own flags[b] / errors[b], and a loop time-out on a shared device is a std::runtime_error.  last_batch_route() is 1.
+  void SolveBatch(const std::vector<std::vector<VectorXd>>& q_guesses, const std::vector<ProblemDefinition>* problems,
+                  const std::vector<const idto_model_t*>& models, const std::vector<const idto_contact_params_t*>& contacts,
+                  BatchSolveResult* out, bool only_best = false) const;
   // how the last SolveBatch ran: 1 a batch loop of the device (trust region or linesearch), 0 entry by entry (tests and tools/solve_batch_bench.py ask)
   int last_batch_route() const { return last_batch_route_; }
 
@@ -185,7 +197,13 @@ class TrajectoryOptimizer<double> {
     std::vector<double> q, rows, Delta0, Delta_out, sol_q, sol_v, sol_tau, final_cost, q_nom, v_nom;
     std::vector<int> status;
   };
-  BatchContext* GetBatchContext(int B, const std::vector<const ProblemDefinition*>& probs) const;
+  // SolveBatch's per-entry models and contact parameters ([B] each, nullptr: the optimizer's own)
+  struct BatchPhysics { std::vector<const idto_model_t*> models; std::vector<const idto_contact_params_t*> contacts; };
+  // (physics != nullptr: a context of its own per B, its parameter records uploaded per call as its problems are)
+  BatchContext* GetBatchContext(int B, const std::vector<const ProblemDefinition*>& probs, const BatchPhysics* physics = nullptr) const;
+  void SolveBatchImpl(const std::vector<std::vector<VectorXd>>& q_guesses, const std::vector<ProblemDefinition>* problems,
+                      const BatchPhysics* physics, BatchSolveResult* out, bool only_best) const;
+  std::string LinesearchBatchRefusal(int B, const std::vector<const ProblemDefinition*>& probs) const;
   void CheckBatchProblem(const ProblemDefinition& p, int b) const;
   // entry b of a batch solved alone on this optimizer's own context (the fallback of SolveBatch)
   void SolveBatchEntryAlone(const ProblemDefinition* prob, const std::vector<VectorXd>& q_guess, int b, BatchSolveResult* out) const;
@@ -242,7 +260,7 @@ class TrajectoryOptimizer<double> {
   // host loop (pivoted LDL^T) finishes the solve from that iterate
   mutable bool force_host_loop_ = false;
   mutable int resume_k_ = 0;
-  mutable std::map<int, BatchContext> batch_ctx_;   // SolveBatch: per batch size
+  mutable std::map<int, BatchContext> batch_ctx_;   // SolveBatch: per batch size (key -B: the context of a batch with per-entry models)
   mutable int last_batch_route_ = -1;
   mutable double last_sparse_vs_dense_ = -1.0;   // debug_compare_against_dense: the figure CalcDoglegPoint printed last
 };

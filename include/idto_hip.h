@@ -105,7 +105,12 @@ void idto_hip_destroy(idto_hip_ctx* ctx);
  * idto_hip_eval_tau / eval_partials / grad_hess / factor_solve(NULL) / gn_step work on all problems
  * at once (grid.y = problem).  Entry points with explicit right-hand sides, the trial-point call
  * and the equality-constraint step serve single-problem contexts only (the host-side
- * TrajectoryOptimizer uses those).  idto_hip_create == idto_hip_create_batch(..., 1, ...). */
+ * TrajectoryOptimizer uses those).  idto_hip_create == idto_hip_create_batch(..., 1, ...).
+ * The problems share ONE model and ONE set of contact parameters unless idto_hip_set_model_batch (below) gives a problem
+ * its own.  What may then differ per problem: the model's double tables (X_PF, axis, mass, com, inertia, damping, geom_X,
+ * geom_size), gravity[3] and all five contact parameters.  What may not: the sizes, the tree, the joint and geometry
+ * types, the pairs and their paths, the actuated mask and the gravity switches - the batch's topology, by which its
+ * launches are sized. */
 int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* problems /* [batch] */,
                           const idto_contact_params_t* contact, int device, int batch, idto_hip_ctx** out);
 int idto_hip_batch_size(idto_hip_ctx* ctx);
@@ -114,6 +119,21 @@ int idto_hip_batch_size(idto_hip_ctx* ctx);
  * not the model it was made from, gets the batch behind SolveBatch. */
 int idto_hip_create_batch_like(idto_hip_ctx* like, const idto_problem_t* problems /* [batch] */, int batch, idto_hip_ctx** out);
 int idto_hip_set_problem_batch(idto_hip_ctx* ctx, int problem, const idto_problem_t* p);
+/* Gives problem `problem` of a batch context (batch >= 2) a model and contact parameters of its own (copied; NULL: the
+ * ones the context was created with).  The model is checked like any model, then against the batch's: a difference
+ * outside the free tables is refused with "model of problem 2 differs from the batch's model in pair_path" (the first
+ * size, table or derived scalar that differs) in the last error, before anything is enqueued.  The first successful call
+ * switches the context to kernels that read every problem's model from a parameter record per problem - problems that
+ * were never named hold the context's model - and option "model_batch" (read-only) reads 1 from then on; a context
+ * that never gets the call runs the launches it always ran.  Such a context takes no single-workgroup step (gn_small)
+ * and its constrained loop only the banded KKT route: the child-context route is refused by name.  The call waits for
+ * the upload (with option "async_uploads" it goes from pinned staging, ordered on the context's stream, without a
+ * wait); what the device holds of the resident q (v, a, tau, partials, cost) is stale afterwards. */
+int idto_hip_set_model_batch(idto_hip_ctx* ctx, int problem, const idto_model_t* model, const idto_contact_params_t* contact);
+/* The check of idto_hip_set_model_batch alone, against the model of any context (a single-problem one included), with
+ * `problem` only the number the refusal names: no device work.  How a caller that builds its batch context later - the
+ * host-side TrajectoryOptimizer's SolveBatch - refuses a batch before it creates or uploads anything. */
+int idto_hip_check_model_batch(idto_hip_ctx* ctx, int problem, const idto_model_t* model, const idto_contact_params_t* contact);
 int idto_hip_set_q_batch(idto_hip_ctx* ctx, const double* q_host /* [batch][(N+1)*nq] */);
 int idto_hip_gn_step_batch(idto_hip_ctx* ctx); /* = idto_hip_gn_step: every problem of the batch */
 int idto_hip_get_batch(idto_hip_ctx* ctx, int what, int problem, double* host_out);

@@ -63,6 +63,16 @@ int idto_opt_solve(idto_opt* opt, const double* q_guess, double* sol_q, double* 
 int idto_opt_solve_batch(idto_opt* opt, int B, const idto_problem_t* problems, const double* q_guesses, int only_best,
                          double* sol_q, double* sol_v, double* sol_tau, idto_stats_t* stats, int* flags, int* reasons,
                          double* final_costs, int* best);
+/* idto_opt_solve_batch with a model and contact parameters per entry: models / contacts are NULL or [B] pointers, an entry
+ * NULL = the optimizer's own (both NULL: idto_opt_solve_batch).  Entry b is idto_opt_solve on an optimizer created with
+ * models[b], contacts[b] and problems[b].  The models share the optimizer's topology and differ in the double tables,
+ * gravity and the contact parameters (include/idto_hip.h idto_hip_set_model_batch).  Such a batch runs the device's batch
+ * loops only: the call fails, before any device work and with the name in idto_opt_last_error, for B < 2, for a
+ * configuration the loops do not serve, and for a model that differs in a shared table. */
+int idto_opt_solve_batch_models(idto_opt* opt, int B, const idto_problem_t* problems, const idto_model_t* const* models,
+                                const idto_contact_params_t* const* contacts, const double* q_guesses, int only_best,
+                                double* sol_q, double* sol_v, double* sol_tau, idto_stats_t* stats, int* flags, int* reasons,
+                                double* final_costs, int* best);
 const char* idto_opt_batch_error(const idto_opt* opt, int b);
 /* 1: the last idto_opt_solve_batch ran one of the device's batch loops (trust region or linesearch), 0: entry by entry on the optimizer's own context, -1: none yet */
 int idto_opt_last_batch_route(const idto_opt* opt);

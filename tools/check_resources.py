@@ -90,6 +90,26 @@ LIMITS = {
     "fd_along_batch_kernel<8, 6>": (0, 20, 69 + 24),
     "fd_along_batch_kernel<8, 7>": (0, 0, 79 + 24),
     "fd_along_batch_kernel<8, 8>": (0, 0, 69 + 24),
+    # (a batch with per-problem models, csrc/fd_kernel.h: fd_kernel's and fd_along_batch_kernel's fd_body with the DevModel and
+    # the DevContact read from the problem's parameter record through the constant address space instead of the kernel's
+    # arguments - no vector register spilled, fd_kernel's 20 B of private segment; where the model's fields were argument
+    # registers they are scalar loads' results now, and up to 49 more scalar registers are spilled to lanes)
+    "fd_models_kernel<2, 1>": (0, 20, 90 + 24),
+    "fd_models_kernel<3, 2>": (0, 20, 92 + 24),
+    "fd_models_kernel<3, 3>": (0, 20, 109 + 24),
+    "fd_models_kernel<3, 5>": (0, 20, 91 + 24),
+    "fd_models_kernel<4, 4>": (0, 20, 109 + 24),
+    "fd_models_kernel<8, 6>": (0, 0, 176 + 24),
+    "fd_models_kernel<8, 7>": (0, 20, 169 + 24),
+    "fd_models_kernel<8, 8>": (0, 20, 183 + 24),
+    "fd_along_models_kernel<2, 1>": (0, 0, 15 + 24),
+    "fd_along_models_kernel<3, 2>": (0, 0, 15 + 24),
+    "fd_along_models_kernel<3, 3>": (0, 20, 24 + 24),
+    "fd_along_models_kernel<3, 5>": (0, 0, 15 + 24),
+    "fd_along_models_kernel<4, 4>": (0, 20, 26 + 24),
+    "fd_along_models_kernel<8, 6>": (0, 20, 71 + 24),
+    "fd_along_models_kernel<8, 7>": (0, 0, 120 + 24),
+    "fd_along_models_kernel<8, 8>": (0, 0, 127 + 24),
     "ls_gather_batch_kernel": (0, 0, 0 + 24),
     "ls_trial_kernel": (0, 0, 0 + 24),
     "ls_cost_kernel": (0, 0, 0 + 24),

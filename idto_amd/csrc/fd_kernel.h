@@ -6,6 +6,7 @@
 // the fused launch (fused.h), which embeds fd_body.
 #pragma once
 
+#include "arena_sizes.h"
 #include "batch.h"
 #include "id_eval.h"
 #include "id_fast.h"
@@ -298,7 +299,7 @@ IDTO_DEV void asm_dot_tile(const double* const (&A)[TB], const double* const (&B
 //   gP = P_k^T R' tau_k -> g_{k+1} gT = T_k^T R' tau_k -> g_k gM = M_k^T R' tau_k -> g_{k-1}
 // assemble_terms_kernel adds them in the reference's order.  Each entry is the very expression
 // assemble_diag_kernel evaluates (asm_dot on the weighted column), so both paths give the same bits.
-__host__ __device__ inline int asm_terms_stride(int nq) { return 6 * nq * nq + 3 * nq + ((3 * nq) & 1); }
+// (asm_terms_stride doubles a record: arena_sizes.h)
 
 // ---------------------------------------------------------------------------
 // fd_kernel: block <-> tau index k.  Produces slab_k = [dtau_k/dq_{k-1} |

@@ -72,8 +72,8 @@ int SolverBlockSize(int k, bool single_rhs_only = false);
 // penta_apply_kernel: LDS for n block rows of K (the right-hand side of each of its four wavefronts, the chains' exchange)
 int ApplyLds(int n, int K);
 
-// Element counts of the solver-only arrays of a context with blocks of K and horizon N (idto_hip_create_batch and the
-// KKT context carve them, each in its own order).
+// Element counts of the solver-only arrays of a context with blocks of K and horizon N (where they lie in the arena of the
+// model's context and of the KKT context: host/context_layout.h IDTO_MODEL_ARENA, IDTO_KKT_ARENA).
 struct SolverBuffers {
   size_t bands;        // HA | HB | HC in one allocation, two extra zero blocks each (five are reserved)
   size_t factors;      // each of Ust, Hst, Est: padded blocks of 32 x 36

@@ -39,6 +39,7 @@
 #include "kkt.h"
 #include "linesearch.h"
 #include "mpc_batch.h"
+#include "host/context_layout.h"
 #include "host/model_batch.h"
 #include "host/model_tables.h"
 #include "host/solver_plan.h"
@@ -412,9 +413,108 @@ struct idto_hip_ctx {
   bool tr_resident_ok = true;              // false once tr_iter_kernel's wait between its workgroups ran out (FactorStatus): idto_hip_tr_solve then refuses
   int ldl_npos = 0;                        // (a KKT context) the solver expects the pivots [ldl_npos, nq) of a block negative
 };
-enum { IDTO_SLAB_PAD = 64 };
+
+// The options: X(name = the field of idto_hip_ctx, kind, access, environment variable that seeds the default at create or
+// nullptr, follows the parent into its KKT context, is given to a batch context's children).  idto_hip_get_option,
+// idto_hip_set_option, OptionsFromEnvironment, MakeKkt and CopyOptionsToChild are generated from it; what an option does
+// beyond storing a value stands in front of the lookup in those functions.
+enum { OPT_BOOL, OPT_FLAG, OPT_INT };   // environment "1" / value != 0; atoi != 0 / value != 0; atoi / value
+enum { OPT_GET = 1, OPT_SET = 2, OPT_RW = 3 };
+#define IDTO_OPTIONS(X)                                                          \
+  X(reference_solver, OPT_BOOL, OPT_RW, "IDTO_SOLVER_REFERENCE", 0, 1)           \
+  X(two_sided, OPT_BOOL, OPT_RW, "IDTO_TWO_SIDED", 0, 1)                         \
+  X(fused, OPT_BOOL, OPT_RW, "IDTO_FUSED", 0, 1)                                 \
+  X(async_uploads, OPT_BOOL, OPT_RW, nullptr, 0, 0)                              \
+  X(nd_min_rows, OPT_INT, OPT_RW, "IDTO_ND_MIN_ROWS", 1, 0)                      \
+  X(nd_recursion, OPT_FLAG, OPT_RW, "IDTO_ND_RECURSION", 1, 0)                   \
+  X(solver_nd, OPT_BOOL, OPT_RW, "IDTO_SOLVER_ND", 0, 1)                         \
+  X(solver_pipe, OPT_BOOL, OPT_RW, "IDTO_SOLVER_PIPE", 0, 1)                     \
+  X(solver_band, OPT_INT, OPT_RW, "IDTO_SOLVER_BAND", 1, 1) /* measurement aid: penta_band.h off / on / on for blocks of 5 too */ \
+  X(gn_small, OPT_FLAG, OPT_RW, nullptr, 0, 0)                                   \
+  X(asm_in_solver, OPT_BOOL, OPT_RW, nullptr, 0, 1)                              \
+  X(debug_skip_role, OPT_INT, OPT_SET, "IDTO_DEBUG_SKIP_ROLE", 1, 0) /* test aid (tests/test_gpu_timeout.py) */ \
+  X(debug_pipe_tail, OPT_INT, OPT_SET, nullptr, 0, 0)                /* measurement aid */ \
+  X(asm_fold, OPT_BOOL, OPT_RW, "IDTO_ASM_FOLD", 0, 1)                           \
+  X(con_kkt, OPT_BOOL, OPT_RW, "IDTO_CON_KKT", 0, 1)                             \
+  X(kkt_fold, OPT_BOOL, OPT_RW, "IDTO_KKT_FOLD", 0, 0)                           \
+  X(ls_waves, OPT_INT, OPT_RW, nullptr, 0, 0)                                    \
+  X(tr_small, OPT_BOOL, OPT_RW, "IDTO_TR_SMALL", 0, 0)                           \
+  X(tr_fold, OPT_BOOL, OPT_RW, "IDTO_TR_FOLD", 0, 0)                             \
+  X(kkt_in_asm, OPT_BOOL, OPT_RW, "IDTO_KKT_IN_ASM", 0, 0)                       \
+  X(decide_in_solver, OPT_BOOL, OPT_RW, "IDTO_DECIDE_IN_SOLVER", 0, 0)           \
+  X(fused_debug, OPT_BOOL, OPT_SET, nullptr, 0, 0)                               \
+  X(asm_stop, OPT_INT, OPT_SET, nullptr, 0, 0) /* profiling aid */               \
+  X(fd_stop, OPT_INT, OPT_SET, nullptr, 0, 0)  /* profiling aid */               \
+  X(fd_fast, OPT_BOOL, OPT_RW, nullptr, 0, 1)                                    \
+  X(gradients_method, OPT_INT, OPT_RW, nullptr, 0, 1)                            \
+  X(last_solver, OPT_INT, OPT_GET, nullptr, 0, 0)                                \
+  X(last_assembly, OPT_INT, OPT_GET, nullptr, 0, 0)                              \
+  X(weights_diagonal, OPT_BOOL, OPT_GET, nullptr, 0, 0)                          \
+  X(solver_timeouts, OPT_INT, OPT_GET, nullptr, 0, 0)                            \
+  X(ls_solves, OPT_INT, OPT_GET, nullptr, 0, 0)                                  \
+  X(ls_batch_solves, OPT_INT, OPT_GET, nullptr, 0, 0)                            \
+  X(tr_resident_ok, OPT_BOOL, OPT_GET, nullptr, 0, 0)
 
 namespace {
+
+template <class T>
+void OptAssign(T& field, int kind, int value) { field = kind == OPT_INT ? (T)value : (T)(value != 0); }
+
+// the defaults that the environment seeds (debugging and measurement aids)
+void OptionsFromEnvironment(idto_hip_ctx* c) {
+#define X(name, kind, access, env, to_kkt, to_child)                                                    \
+  if (const char* v = env)                                                                              \
+    if (const char* e = getenv(v)) OptAssign(c->name, kind, kind == OPT_BOOL ? (e[0] == '1') : std::atoi(e));
+  IDTO_OPTIONS(X)
+#undef X
+  c->nd_min_rows = std::max(16, c->nd_min_rows);   // (idto_hip_set_option's bound)
+}
+
+// One arena per problem: the plan of host/context_layout.cc, one allocation of batch * pstride bytes, zero-filled, and the
+// context's fields - problem 0's - pointed into it in the table's order.
+int PointIntoArena(idto_hip_ctx* c, idto_host::ArenaKind kind, const char* what) {
+  const idto_host::ArenaPlan plan = idto_host::PlanArena(kind, c->nq, c->nv, c->N);
+  c->pstride = plan.pstride; c->alt_off = plan.alt_off; c->slab_stride = plan.slab_stride;
+  c->xch_count = plan.xch_count; c->flag_count = plan.flag_count;
+  void* p = nullptr;
+  const size_t bytes = c->pstride * (size_t)c->batch;
+  if (hipMalloc(&p, bytes) != hipSuccess || hipMemset(p, 0, bytes) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess) {   // (see Alloc: the fill must not trail the uploads on the context's stream)
+    g_err = what;
+    return -2;
+  }
+  c->allocs.push_back(p);
+  c->arena = static_cast<char*>(p);
+  if (getenv("IDTO_DEBUG_PTRS")) {   // (investigation aid: where a faulting address lies)
+    fprintf(stderr, "%s arena %p .. %p (pstride %zu x %d):", kind == idto_host::ARENA_KKT ? "kkt" : "model", p, (void*)(c->arena + bytes), c->pstride, c->batch);
+    for (const idto_host::ArenaEntry& e : plan.entries) fprintf(stderr, " %s %zu", e.name, e.offset);
+    fprintf(stderr, "\n");
+  }
+  size_t i = 0;
+#define X(field, type, count) c->field = reinterpret_cast<type*>(c->arena + plan.entries[i++].offset);
+#define U(name, type, count) ++i;
+#define B(field, entry, index) c->field = c->entry + (size_t)index * plan.band;
+  if (kind == idto_host::ARENA_MODEL) { IDTO_MODEL_ARENA(X, U) IDTO_MODEL_BANDS(B) }
+  else { IDTO_KKT_ARENA(X, U) IDTO_KKT_BANDS(B) }
+#undef X
+#undef U
+#undef B
+  if (!plan.has_wst) c->nd_wst = nullptr;
+  return 0;
+}
+
+// The solver's status words in pinned host memory, zeroed: per problem [id of the last failed factorisation, count];
+// behind them [id of the last launch in which a wait between workgroups ran out, count] (penta_ldl.h spin_wait)
+int AllocStatusWords(idto_hip_ctx* c, const char* what) {
+  const size_t words = 2 * (size_t)c->batch + 2;
+  if (hipHostMalloc((void**)&c->status_pin, words * sizeof(unsigned), hipHostMallocDefault) != hipSuccess ||
+      hipHostGetDevicePointer((void**)&c->status_dev, c->status_pin, 0) != hipSuccess) {
+    g_err = what;
+    return -2;
+  }
+  for (size_t i = 0; i < words; ++i) c->status_pin[i] = 0;
+  return 0;
+}
 
 template <class T>
 int Upload(idto_hip_ctx* c, const T* host, size_t count, T** dev) {
@@ -808,103 +908,10 @@ int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* probl
     idto_host::ContactValues(*contact, cv);   // (host/model_batch.h: the threshold's one expression)
     c->cp.k = cv[0]; c->cp.vd = cv[1]; c->cp.vs = cv[2]; c->cp.mu = cv[3]; c->cp.sigma = cv[4]; c->cp.threshold = cv[5];
   }
-  const size_t bsz = (size_t)nv * nq, qq = (size_t)nq * nq;
-  c->slab_stride = (int)(3 * bsz + nv);
-  // ---- one arena per problem (identical layout): carve offsets first, allocate batch * pstride
-  // bytes at once (zero-filled), then point the problem-0 pointers into the first arena
-  size_t top = 0;
-  auto carve = [&](size_t count, size_t elem) {
-    const size_t o = (top + 63) & ~(size_t)63;
-    top = o + std::max<size_t>(count, 1) * elem;
-    return o;
-  };
-  const size_t D = sizeof(double);
-  const size_t o_vinit = carve(nv, D), o_qnom = carve((size_t)(N + 1) * nq, D), o_vnom = carve((size_t)(N + 1) * nv, D);
-  size_t o_w[10];
-  for (int i = 0; i < 10; ++i) o_w[i] = carve((i == 0 || i == 3 || i == 5 || i == 8) ? qq : (size_t)nv * nv, D);
-  const size_t o_q = carve((size_t)(N + 1) * nq, D);
-  // what fd_kernel writes, twice (batch.h AltSel): two identical carve sequences = identical relative offsets
-  size_t o_v = 0, o_a = 0, o_np = 0, o_slab = 0, o_terms = 0, o_setB = 0;
-  for (int set = 0; set < 2; ++set) {
-    const size_t v0 = carve((size_t)(N + 1) * nv, D), a0 = carve((size_t)N * nv, D), n0 = carve((size_t)(N + 1) * bsz, D);
-    const size_t s0 = carve((size_t)(N + IDTO_SLAB_PAD) * c->slab_stride, D), t0 = carve((size_t)N * asm_terms_stride(nq), D);
-    if (set == 0) { o_v = v0; o_a = a0; o_np = n0; o_slab = s0; o_terms = t0; }
-    else o_setB = v0;
-  }
-  c->alt_off = (long long)(o_setB - o_v);
-  const size_t o_g = carve((size_t)(N + 1) * nq, D);
-  // two extra zero blocks (five are reserved): the solver prefetches rows i+1, i+2 without bounds
-  // checks (one allocation: the solver addresses all three bands from HA with 32-bit offsets)
-  const size_t o_H = carve((size_t)3 * (N + 6) * qq, D);
-  // (a second g and H: the trial point's, formed by the solver's launch while it decides on the point - penta_pipe.h PipeAsm::g2)
-  const size_t o_H2 = carve((size_t)3 * (N + 6) * qq, D), o_g2 = carve((size_t)(N + 1) * nq, D);
-  const size_t o_step = carve((size_t)(N + 1) * nq, D), o_cost = carve(1, D);
-  const size_t o_K = carve((size_t)(N + 1) * qq, D), o_LU = carve((size_t)(N + 1) * qq, D);
-  const size_t o_Y = carve((size_t)(N + 1) * qq, D), o_Z = carve((size_t)(N + 1) * qq, D);
-  const size_t o_piv = carve((size_t)(N + 1) * nq, sizeof(int));
-  // the solvers' own arrays (host/solver_plan.cc SolverBufferCounts)
-  const idto_host::SolverBuffers sb = idto_host::SolverBufferCounts(nq, N);
-  const size_t o_dbg = carve(sb.dbg, D);
-  const size_t o_U = carve(sb.factors, D), o_Hs = carve(sb.factors, D);
-  const size_t o_E = carve(sb.factors, D), o_Ds = carve(sb.dinv, D);
-  c->xch_count = sb.xch_count;
-  const size_t o_xch = carve(sb.xch, D);
-  const size_t o_ndcnt = carve(sb.rowcnt, sizeof(unsigned long long)), o_ndbuf = carve(sb.nd_buf, D);
-  const size_t o_pipecnt = carve(sb.rowcnt, sizeof(unsigned long long));
-  const bool nd_wst_on = sb.has_wst;
-  const size_t o_ndwst = carve(sb.nd_wst, D);
-  const size_t o_asmready = carve(4 * (size_t)(N + 1), sizeof(unsigned));
-  c->flag_count = sb.flags;
-  const size_t o_flags = carve(c->flag_count, sizeof(unsigned)), o_sync = carve(2, sizeof(unsigned long long));
+  // ---- one arena per problem (identical layout, host/context_layout.h): batch * pstride bytes at once (zero-filled), the
+  // problem-0 pointers into the first arena
+  if (PointIntoArena(c, idto_host::ARENA_MODEL, "hipMalloc of the problem arenas failed")) { idto_hip_destroy(c); return -2; }
   const size_t nvars = (size_t)(N + 1) * nq;
-  const size_t o_trD = carve(nvars, D), o_trg = carve(nvars, D), o_trw = carve(nvars, D), o_trdq = carve(nvars, D),
-               o_qt = carve(nvars, D), o_trout = carve(16, D), o_trDp = carve(nvars, D), o_trpart = carve((size_t)9 * (N + 1), D),
-               o_trpll = carve((size_t)2 * (TR_NSUM * (N + 1) + 3), D), o_trp2 = carve((size_t)2 * (N + 1), D),
-               o_decide = carve(4, D);
-  const size_t o_trstate = carve(TRS_COUNT, D), o_trcnt = carve(1, sizeof(unsigned long long));
-  // the equality-constraint step's outputs (per problem, so that the batched loop finds them at the arena stride):
-  // [H^-1 (g + J^T lambda) | J^T lambda] and the multipliers (nu <= nv; + 2: the blocked dense LDL^T's [min, max | ...])
-  const size_t o_conout = carve(2 * nvars, D), o_conlam = carve((size_t)N * nv + 4, D);
-  c->pstride = (top + 255) & ~(size_t)255;
-  {
-    void* p = nullptr;
-    if (hipMalloc(&p, c->pstride * (size_t)batch) != hipSuccess || hipMemset(p, 0, c->pstride * (size_t)batch) != hipSuccess ||
-        hipDeviceSynchronize() != hipSuccess) {   // (see Alloc: the fill must not trail the uploads on the context's stream)
-      g_err = "hipMalloc of the problem arenas failed";
-      idto_hip_destroy(c);
-      return -2;
-    }
-    c->allocs.push_back(p);
-    c->arena = static_cast<char*>(p);
-  }
-  auto dp = [&](size_t o) { return reinterpret_cast<double*>(c->arena + o); };
-  c->d_vinit = dp(o_vinit); c->d_qnom = dp(o_qnom); c->d_vnom = dp(o_vnom);
-  for (int i = 0; i < 10; ++i) c->d_w[i] = dp(o_w[i]);
-  c->q = dp(o_q); c->v = dp(o_v); c->a = dp(o_a); c->nplus = dp(o_np); c->slab = dp(o_slab); c->g = dp(o_g);
-  c->HA = dp(o_H);
-  c->HB = c->HA + (size_t)(N + 6) * qq;
-  c->HC = c->HB + (size_t)(N + 6) * qq;
-  c->HA2 = dp(o_H2); c->HB2 = c->HA2 + (size_t)(N + 6) * qq; c->HC2 = c->HB2 + (size_t)(N + 6) * qq; c->g2 = dp(o_g2);
-  c->step = dp(o_step); c->cost = dp(o_cost);
-  c->Kst = dp(o_K); c->LUst = dp(o_LU); c->Yst = dp(o_Y); c->Zst = dp(o_Z);
-  c->pivst = reinterpret_cast<int*>(c->arena + o_piv);
-  c->dbg = dp(o_dbg);
-  c->Ust = dp(o_U); c->Hst = dp(o_Hs); c->Est = dp(o_E); c->Dst = dp(o_Ds);
-  c->xch = dp(o_xch);
-  c->flags = reinterpret_cast<unsigned*>(c->arena + o_flags);
-  c->sync_cnt = reinterpret_cast<unsigned long long*>(c->arena + o_sync);
-  c->nd_rowcnt = reinterpret_cast<unsigned long long*>(c->arena + o_ndcnt);
-  c->pipe_rowcnt = reinterpret_cast<unsigned long long*>(c->arena + o_pipecnt);
-  c->asm_ready = reinterpret_cast<unsigned*>(c->arena + o_asmready);
-  c->nd_buf = dp(o_ndbuf);
-  c->nd_wst = nd_wst_on ? dp(o_ndwst) : nullptr;
-  c->tr_D = dp(o_trD); c->tr_gt = dp(o_trg); c->tr_w = dp(o_trw); c->tr_dq = dp(o_trdq); c->q_trial = dp(o_qt);
-  c->tr_out = dp(o_trout); c->tr_Dprev = dp(o_trDp); c->tr_part = dp(o_trpart);
-  c->tr_part_ll = dp(o_trpll); c->tr_part2 = dp(o_trp2); c->decide_word = dp(o_decide);
-  c->terms = dp(o_terms);
-  c->tr_state = dp(o_trstate);
-  c->con_out = dp(o_conout); c->con_lambda = dp(o_conlam);
-  c->tr_cnt = reinterpret_cast<unsigned long long*>(c->arena + o_trcnt);
   {  // adaptive scaling methods start from D = 1 (TO.cc:1233-1236: scale_factors initialised to ones)
     std::vector<double> ones(nvars, 1.0);
     for (int b = 0; b < batch; ++b)
@@ -927,15 +934,7 @@ int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* probl
     rc = UploadProblemArrays(c, problems + b, b);
     if (rc) { idto_hip_destroy(c); return rc; }
   }
-  // per problem [id of the last failed factorisation, count]; behind them [id of the last launch in which a
-  // wait between workgroups ran out, count] (penta_ldl.h spin_wait)
-  if (hipHostMalloc((void**)&c->status_pin, (2 * (size_t)batch + 2) * sizeof(unsigned), hipHostMallocDefault) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&c->status_dev, c->status_pin, 0) != hipSuccess) {
-    g_err = "hipHostMalloc (solver status) failed";
-    idto_hip_destroy(c);
-    return -2;
-  }
-  for (int i = 0; i < 2 * batch + 2; ++i) c->status_pin[i] = 0;
+  if (AllocStatusWords(c, "hipHostMalloc (solver status) failed")) { idto_hip_destroy(c); return -2; }
   c->k_begin = 0; c->k_end = N;
 
   // launch geometry
@@ -948,20 +947,13 @@ int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* probl
   // smallest LDS carve-up of the finite-difference kernel: the inputs of one round of concurrent
   // evaluations per pass (LaunchFd uses more when they fit)
   c->fd_lds = FdLds(c, 1, threads / K, false, true, threads);
-  c->asm_lds = (int)sizeof(double) * (3 * nq + 5 * (int)bsz + 4 * nv + nq + std::max(nq, nv) + (int)bsz + 3 * (int)qq + nq);
-  c->asm_diag_lds = (int)sizeof(double) * (14 * ((nv + 1) & ~1) * nq + 2 * (int)bsz + 10 * nv + 6 * nq + 2);
-  c->asm_terms_lds = (int)sizeof(double) * (5 * ((nv + 1) & ~1) * nq + 4 * nv + nq + 2);
-  c->asm_terms_threads = std::min(512, std::max(256, (std::max(nq * (nq + 1) / 2 + nq, ((nq + 1) / 2) * nq) + 63) / 64 * 64));
-  const int n = N + 1;
-  c->penta_lds = (int)sizeof(double) * (10 * (int)qq + nq * (3 * nq + 1) + (n + 2) * nq + nq) + (int)sizeof(int) * nq + 16;
-  c->solve_lds = (int)sizeof(double) * ((n + 2) * nq + nq);
-  c->cost_lds = (int)sizeof(double) * ((3 * N + 2) * (1 + std::max(nq, nv)) + 2 * (N + 1) + 2);
+  // (the launches whose sizes are a pure function of nq, nv, N: host/context_layout.cc)
+  const idto_host::LaunchSizes ls = idto_host::PlanLaunchSizes(nq, nv, N);
+  c->asm_lds = ls.asm_lds; c->asm_diag_lds = ls.asm_diag_lds; c->asm_terms_lds = ls.asm_terms_lds; c->asm_terms_threads = ls.asm_terms_threads;
+  c->penta_lds = ls.penta_lds; c->solve_lds = ls.solve_lds; c->cost_lds = ls.cost_lds;
   const int max_lds = 160 * 1024;
-  // (cost_kernel is a single block holding one column of every cost term; penta_apply_kernel keeps
-  // the right-hand side of each of its four wavefronts: both bound the horizon as well)
-  const int apply_lds = idto_host::ApplyLds(n, idto_host::SolverBlockSize(nq));
   if (c->fd_lds > max_lds || c->asm_lds > max_lds || c->penta_lds > max_lds || c->cost_lds > max_lds ||
-      apply_lds > max_lds) {
+      ls.apply_lds > max_lds) {
     g_err = "problem too large for the 160 KiB LDS carve-up of the v1 kernels (fd / assemble / solver / cost / "
             "multi-rhs substitution)";
     idto_hip_destroy(c);
@@ -1003,22 +995,7 @@ int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* probl
   IDTO_FUSED_KERNELS(FUSED_ATTR)
 #undef FUSED_ATTR
 #undef MAX_LDS
-  if (const char* e = getenv("IDTO_SOLVER_REFERENCE")) c->reference_solver = (e[0] == '1');
-  if (const char* e = getenv("IDTO_TWO_SIDED")) c->two_sided = (e[0] == '1');   // (debugging aids: option defaults)
-  if (const char* e = getenv("IDTO_FUSED")) c->fused = (e[0] == '1');
-  if (const char* e = getenv("IDTO_ND_MIN_ROWS")) c->nd_min_rows = std::max(16, std::atoi(e));
-  if (const char* e = getenv("IDTO_ND_RECURSION")) c->nd_recursion = std::atoi(e) != 0;
-  if (const char* e = getenv("IDTO_SOLVER_ND")) c->solver_nd = (e[0] == '1');
-  if (const char* e = getenv("IDTO_SOLVER_PIPE")) c->solver_pipe = (e[0] == '1');
-  if (const char* e = getenv("IDTO_ASM_FOLD")) c->asm_fold = (e[0] == '1');
-  if (const char* e = getenv("IDTO_CON_KKT")) c->con_kkt = (e[0] == '1');
-  if (const char* e = getenv("IDTO_KKT_FOLD")) c->kkt_fold = (e[0] == '1');
-  if (const char* e = getenv("IDTO_DEBUG_SKIP_ROLE")) c->debug_skip_role = std::atoi(e);   // test aid (tests/test_gpu_timeout.py)
-  if (const char* e = getenv("IDTO_TR_SMALL")) c->tr_small = (e[0] == '1');
-  if (const char* e = getenv("IDTO_TR_FOLD")) c->tr_fold = (e[0] == '1');
-  if (const char* e = getenv("IDTO_KKT_IN_ASM")) c->kkt_in_asm = (e[0] == '1');
-  if (const char* e = getenv("IDTO_DECIDE_IN_SOLVER")) c->decide_in_solver = (e[0] == '1');
-  if (const char* e = getenv("IDTO_SOLVER_BAND")) c->solver_band = std::atoi(e);   // (measurement aid: penta_band.h off / on / on for blocks of 5 too)
+  OptionsFromEnvironment(c);
   (void)hipGetLastError();
   *out = c;
   return 0;
@@ -2453,56 +2430,20 @@ static int MakeKkt(idto_hip_ctx* c, int nu) {
   k->batch = B; k->nq = K; k->nv = 0; k->N = N; k->dt = c->dt;
   // (seven workgroups for allegro's 29 x 29 blocks: 0.46 -> 0.29 ms per iteration; the small systems stay on two - the
   // nested-dissection order buys them 3 us and costs acrobot's multipliers a digit: 2e-8 against 3e-9)
+  // (these two as they are when the context is made; the options of the table follow the parent from then on)
   k->two_sided = c->two_sided; k->solver_nd = c->solver_nd && (K == 29 || K == 8); k->solver_pipe = false; k->fused = false; k->asm_in_solver = false;
-  k->solver_band = c->solver_band; k->nd_min_rows = c->nd_min_rows; k->nd_recursion = c->nd_recursion; k->solver_debug = c->kkt_debug; k->debug_skip_role = c->debug_skip_role;
+  k->solver_debug = c->kkt_debug;
+#define X(name, kind, access, env, to_kkt, to_child) if (to_kkt) OptAssign(k->name, OPT_INT, c->name);
+  IDTO_OPTIONS(X)
+#undef X
   k->h_assembled = true;      // block row 0 is decoupled (q_0 is no variable, mu_0 a dummy): the chains start at row 1
   k->ldl_npos = c->nq;
-  const size_t kk = (size_t)K * K;
-  idto_hip_ctx* kc = k.get();
-  auto fail = [&](const char* what) { g_err = what; idto_hip_destroy(k.release()); return -2; };
-  // one arena per problem, as in idto_hip_create_batch (the same SolverBufferCounts): the solver kernels take the problem from blockIdx.y
-  size_t top = 0;
-  auto carve = [&](size_t count, size_t elem) {
-    const size_t o = (top + 63) & ~(size_t)63;
-    top = o + std::max<size_t>(count, 1) * elem;
-    return o;
-  };
-  const size_t D = sizeof(double);
-  const idto_host::SolverBuffers sb = idto_host::SolverBufferCounts(K, N);
-  kc->xch_count = sb.xch_count;
-  kc->flag_count = sb.flags;
-  const size_t o_H = carve(sb.bands, D), o_g = carve((size_t)(N + 1) * K, D), o_step = carve((size_t)(N + 1) * K, D);
-  const size_t o_U = carve(sb.factors, D), o_Hs = carve(sb.factors, D), o_E = carve(sb.factors, D);
-  const size_t o_Ds = carve(sb.dinv, D), o_dbg = carve(sb.dbg, D);
-  const size_t o_xch = carve(sb.xch, D), o_flags = carve(kc->flag_count, sizeof(unsigned));
-  const size_t o_ndcnt = carve(sb.rowcnt, sizeof(unsigned long long)), o_pipecnt = carve(sb.rowcnt, sizeof(unsigned long long));
-  const size_t o_ndbuf = carve(sb.nd_buf, D);
-  const bool nd_wst_on = sb.has_wst;
-  const size_t o_ndwst = carve(sb.nd_wst, D);
-  kc->pstride = (top + 255) & ~(size_t)255;
-  {
-    void* p = nullptr;
-    if (hipMalloc(&p, kc->pstride * (size_t)B) != hipSuccess || hipMemset(p, 0, kc->pstride * (size_t)B) != hipSuccess ||
-        hipDeviceSynchronize() != hipSuccess)
-      return fail("hipMalloc (KKT context) failed");
-    kc->allocs.push_back(p);
-    kc->arena = static_cast<char*>(p);
-    if (getenv("IDTO_DEBUG_PTRS"))   // (investigation aid: where a faulting address lies)
-      fprintf(stderr, "kkt arena %p .. %p (pstride %zu x %d): H %zu g %zu step %zu U %zu Hs %zu E %zu Ds %zu dbg %zu xch %zu flags %zu ndcnt %zu pipecnt %zu ndbuf %zu ndwst %zu\n",
-              p, (void*)((char*)p + kc->pstride * (size_t)B), kc->pstride, B, o_H, o_g, o_step, o_U, o_Hs, o_E, o_Ds, o_dbg, o_xch, o_flags, o_ndcnt, o_pipecnt, o_ndbuf, o_ndwst);
+  // one arena per problem, as in idto_hip_create_batch: the solver kernels take the problem from blockIdx.y
+  if (PointIntoArena(k.get(), idto_host::ARENA_KKT, "hipMalloc (KKT context) failed") ||
+      AllocStatusWords(k.get(), "hipHostMalloc (KKT solver status) failed")) {
+    idto_hip_destroy(k.release());
+    return -2;
   }
-  auto dp = [&](size_t o) { return reinterpret_cast<double*>(kc->arena + o); };
-  kc->HA = dp(o_H); kc->HB = kc->HA + (size_t)(N + 6) * kk; kc->HC = kc->HB + (size_t)(N + 6) * kk;
-  kc->g = dp(o_g); kc->step = dp(o_step); kc->Ust = dp(o_U); kc->Hst = dp(o_Hs); kc->Est = dp(o_E); kc->Dst = dp(o_Ds); kc->dbg = dp(o_dbg);
-  kc->xch = dp(o_xch); kc->flags = reinterpret_cast<unsigned*>(kc->arena + o_flags);
-  kc->nd_rowcnt = reinterpret_cast<unsigned long long*>(kc->arena + o_ndcnt);
-  kc->pipe_rowcnt = reinterpret_cast<unsigned long long*>(kc->arena + o_pipecnt);
-  kc->nd_buf = dp(o_ndbuf);
-  kc->nd_wst = nd_wst_on ? dp(o_ndwst) : nullptr;
-  if (hipHostMalloc((void**)&kc->status_pin, (2 * (size_t)B + 2) * sizeof(unsigned), hipHostMallocDefault) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&kc->status_dev, kc->status_pin, 0) != hipSuccess)
-    return fail("hipHostMalloc (KKT solver status) failed");
-  for (int i = 0; i < 2 * B + 2; ++i) kc->status_pin[i] = 0;
   c->kkt = k.release(); c->kkt_nu = nu;
   return 0;
 }
@@ -2997,10 +2938,9 @@ int idto_hip_tr_solve_batch(idto_hip_ctx* c, int iterations, int scaling_method,
 // problems.  (at EVERY call, not only when the child is created - options set on the batch context afterwards, a solver
 // stepped down after a time-out must reach the children, or "rows bit for bit those of idto_hip_tr_solve" breaks silently)
 static int CopyOptionsToChild(const idto_hip_ctx* c, idto_hip_ctx* ch) {
-  ch->gradients_method = c->gradients_method; ch->fd_fast = c->fd_fast; ch->asm_fold = c->asm_fold;
-  ch->solver_pipe = c->solver_pipe; ch->solver_nd = c->solver_nd; ch->two_sided = c->two_sided; ch->fused = c->fused;
-  ch->reference_solver = c->reference_solver; ch->solver_band = c->solver_band; ch->asm_in_solver = c->asm_in_solver;
-  ch->con_kkt = c->con_kkt;
+#define X(name, kind, access, env, to_kkt, to_child) if (to_child) OptAssign(ch->name, OPT_INT, c->name);
+  IDTO_OPTIONS(X)
+#undef X
   return idto_hip_set_unactuated_dofs(ch, c->una_dofs_host.data(), c->una_nu);
 }
 
@@ -3433,79 +3373,34 @@ int idto_hip_rccl_info(char* path_out, int path_cap, int* version_out) {
 }
 
 int idto_hip_get_option(idto_hip_ctx* c, const char* name, int* value) {
+  // the computed ones, read-only
   if (std::strcmp(name, "rccl_version") == 0) { return idto_hip_rccl_info(nullptr, 0, value); }
-  if (std::strcmp(name, "last_solver") == 0) { *value = c->last_solver; return 0; }
-  if (std::strcmp(name, "weights_diagonal") == 0) { *value = c->weights_diagonal ? 1 : 0; return 0; }
-  if (std::strcmp(name, "solver_nd") == 0) { *value = c->solver_nd; return 0; }
-  if (std::strcmp(name, "solver_pipe") == 0) { *value = c->solver_pipe; return 0; }
-  if (std::strcmp(name, "solver_band") == 0) { *value = c->solver_band; return 0; }
-  if (std::strcmp(name, "gn_small") == 0) { *value = c->gn_small; return 0; }
-  if (std::strcmp(name, "asm_in_solver") == 0) { *value = c->asm_in_solver; return 0; }
-  if (std::strcmp(name, "solver_timeouts") == 0) { *value = c->solver_timeouts; return 0; }
-  if (std::strcmp(name, "asm_fold") == 0) { *value = c->asm_fold; return 0; }
-  if (std::strcmp(name, "con_kkt") == 0) { *value = c->con_kkt; return 0; }
-  if (std::strcmp(name, "kkt_fold") == 0) { *value = c->kkt_fold; return 0; }
-  if (std::strcmp(name, "ls_waves") == 0) { *value = c->ls_waves; return 0; }
-  if (std::strcmp(name, "ls_solves") == 0) { *value = c->ls_solves; return 0; }
-  if (std::strcmp(name, "ls_batch_solves") == 0) { *value = c->ls_batch_solves; return 0; }
-  if (std::strcmp(name, "tr_small") == 0) { *value = c->tr_small; return 0; }
-  if (std::strcmp(name, "tr_fold") == 0) { *value = c->tr_fold; return 0; }
-  if (std::strcmp(name, "kkt_in_asm") == 0) { *value = c->kkt_in_asm; return 0; }
-  if (std::strcmp(name, "decide_in_solver") == 0) { *value = c->decide_in_solver; return 0; }
-  if (std::strcmp(name, "tr_resident_ok") == 0) { *value = c->tr_resident_ok; return 0; }
   if (std::strcmp(name, "kkt_last_solver") == 0) { *value = c->kkt ? c->kkt->last_solver : 0; return 0; }
-  if (std::strcmp(name, "last_assembly") == 0) { *value = c->last_assembly; return 0; }
-  if (std::strcmp(name, "fused") == 0) { *value = c->fused; return 0; }
-  if (std::strcmp(name, "nd_min_rows") == 0) { *value = c->nd_min_rows; return 0; }
-  if (std::strcmp(name, "nd_recursion") == 0) { *value = c->nd_recursion; return 0; }
-  if (std::strcmp(name, "async_uploads") == 0) { *value = c->async_uploads ? 1 : 0; return 0; }
-  if (std::strcmp(name, "two_sided") == 0) { *value = c->two_sided; return 0; }
-  if (std::strcmp(name, "reference_solver") == 0) { *value = c->reference_solver; return 0; }
-  if (std::strcmp(name, "gradients_method") == 0) { *value = c->gradients_method; return 0; }
   if (std::strcmp(name, "fast_shape") == 0) { *value = c->M.fast_shape; return 0; }   // id_fast.h: 0 none, 1 acrobot, 2 hopper, 3 mini_cheetah, 4 allegro_hand, 5 spinner, 6 free object + one 7-body arm
-  if (std::strcmp(name, "fd_fast") == 0) { *value = c->fd_fast ? 1 : 0; return 0; }
-  if (std::strcmp(name, "model_batch") == 0) { *value = c->model_records ? 1 : 0; return 0; }   // read-only: idto_hip_set_model_batch has switched the context to per-problem records
+  if (std::strcmp(name, "model_batch") == 0) { *value = c->model_records ? 1 : 0; return 0; }   // idto_hip_set_model_batch has switched the context to per-problem records
+#define X(nm, kind, access, env, to_kkt, to_child) if (((access) & OPT_GET) && std::strcmp(name, #nm) == 0) { *value = c->nm; return 0; }
+  IDTO_OPTIONS(X)
+#undef X
   g_err = std::string("unknown option ") + name;
   return -1;
 }
 
 int idto_hip_set_option(idto_hip_ctx* c, const char* name, int value) {
-  if (std::strcmp(name, "reference_solver") == 0) { c->reference_solver = value != 0; return 0; }
   // (2: the stamps of the KKT context's solver - the constrained step's banded solve - are what IDTO_ARR_DEBUG returns)
   if (std::strcmp(name, "solver_debug") == 0) { c->solver_debug = value == 1; c->kkt_debug = value == 2; if (c->kkt) c->kkt->solver_debug = c->kkt_debug; return 0; }
-  if (std::strcmp(name, "two_sided") == 0) { c->two_sided = value != 0; return 0; }
-  if (std::strcmp(name, "fused") == 0) { c->fused = value != 0; return 0; }
-  if (std::strcmp(name, "async_uploads") == 0) { c->async_uploads = value != 0; return 0; }
-  if (std::strcmp(name, "nd_min_rows") == 0) { c->nd_min_rows = std::max(16, value); /* (below 16 block rows nd_split leaves a joiner chains of three rows with one row of their own: untested, not offered) */ if (c->kkt) c->kkt->nd_min_rows = c->nd_min_rows; return 0; }
-  if (std::strcmp(name, "nd_recursion") == 0) { c->nd_recursion = value != 0; if (c->kkt) c->kkt->nd_recursion = c->nd_recursion; return 0; }
-  if (std::strcmp(name, "solver_nd") == 0) { c->solver_nd = value != 0; return 0; }
-  if (std::strcmp(name, "solver_pipe") == 0) { c->solver_pipe = value != 0; return 0; }
-  if (std::strcmp(name, "solver_band") == 0) { c->solver_band = value; if (c->kkt) c->kkt->solver_band = value; return 0; }
-  if (std::strcmp(name, "gn_small") == 0) { c->gn_small = value != 0; return 0; }
-  if (std::strcmp(name, "asm_in_solver") == 0) { c->asm_in_solver = value != 0; return 0; }
-  if (std::strcmp(name, "debug_skip_role") == 0) { c->debug_skip_role = value; if (c->kkt) c->kkt->debug_skip_role = value; return 0; }   // test aid
-  if (std::strcmp(name, "debug_pipe_tail") == 0) { c->debug_pipe_tail = value; return 0; }   // measurement aid
-  if (std::strcmp(name, "asm_fold") == 0) { c->asm_fold = value != 0; c->terms_valid = false; return 0; }
-  if (std::strcmp(name, "con_kkt") == 0) { c->con_kkt = value != 0; return 0; }
-  if (std::strcmp(name, "kkt_fold") == 0) { c->kkt_fold = value != 0; return 0; }
-  if (std::strcmp(name, "ls_waves") == 0) {
-    if (value < 0 || value > IDTO_LS_MAX_CANDIDATES) { g_err = "ls_waves: 0 (planned) .. IDTO_LS_MAX_CANDIDATES candidates per wave"; return -1; }
-    c->ls_waves = value;
-    return 0;
+  // (below 16 block rows nd_split leaves a joiner chains of three rows with one row of their own: untested, not offered)
+  if (std::strcmp(name, "nd_min_rows") == 0) value = std::max(16, value);
+  if (std::strcmp(name, "ls_waves") == 0 && (value < 0 || value > IDTO_LS_MAX_CANDIDATES)) { g_err = "ls_waves: 0 (planned) .. IDTO_LS_MAX_CANDIDATES candidates per wave"; return -1; }
+  if (std::strcmp(name, "gradients_method") == 0 && (value < 0 || value > 2)) { g_err = "gradients_method: 0 forward, 1 central, 2 central4 (autodiff needs Drake)"; return -1; }
+  if (std::strcmp(name, "asm_fold") == 0) c->terms_valid = false;
+#define X(nm, kind, access, env, to_kkt, to_child)             \
+  if (((access) & OPT_SET) && std::strcmp(name, #nm) == 0) {     \
+    OptAssign(c->nm, kind, value);                             \
+    if (to_kkt && c->kkt) OptAssign(c->kkt->nm, OPT_INT, c->nm); \
+    return 0;                                                  \
   }
-  if (std::strcmp(name, "tr_small") == 0) { c->tr_small = value != 0; return 0; }
-  if (std::strcmp(name, "tr_fold") == 0) { c->tr_fold = value != 0; return 0; }
-  if (std::strcmp(name, "kkt_in_asm") == 0) { c->kkt_in_asm = value != 0; return 0; }
-  if (std::strcmp(name, "decide_in_solver") == 0) { c->decide_in_solver = value != 0; return 0; }
-  if (std::strcmp(name, "fused_debug") == 0) { c->fused_debug = value != 0; return 0; }
-  if (std::strcmp(name, "asm_stop") == 0) { c->asm_stop = value; return 0; }  // profiling aid
-  if (std::strcmp(name, "fd_stop") == 0) { c->fd_stop = value; return 0; }    // profiling aid
-  if (std::strcmp(name, "fd_fast") == 0) { c->fd_fast = value != 0; return 0; }
-  if (std::strcmp(name, "gradients_method") == 0) {
-    if (value < 0 || value > 2) { g_err = "gradients_method: 0 forward, 1 central, 2 central4 (autodiff needs Drake)"; return -1; }
-    c->gradients_method = value;
-    return 0;
-  }
+  IDTO_OPTIONS(X)
+#undef X
   g_err = std::string("unknown option ") + name;
   return -1;
 }
@@ -3570,54 +3465,37 @@ int idto_hip_sync(idto_hip_ctx* c) {
   return 0;
 }
 
+// (every array id, its place and its count: host/context_layout.h IDTO_ARRAYS; the constraint step's two are sized by the
+// constraints in force)
 long idto_hip_array_size(idto_hip_ctx* c, int what) {
-  const long nq = c->nq, nv = c->nv, N = c->N, bsz = nv * nq, qq = nq * nq;
-  switch (what) {
-    case IDTO_ARR_Q: return (N + 1) * nq;
-    case IDTO_ARR_V: return (N + 1) * nv;
-    case IDTO_ARR_A: case IDTO_ARR_TAU: return N * nv;
-    case IDTO_ARR_NPLUS: return (N + 1) * bsz;
-    case IDTO_ARR_DTAU_DQM: case IDTO_ARR_DTAU_DQT: case IDTO_ARR_DTAU_DQP: return N * bsz;
-    case IDTO_ARR_GRADIENT: case IDTO_ARR_STEP: return (N + 1) * nq;
-    case IDTO_ARR_H_A: case IDTO_ARR_H_B: case IDTO_ARR_H_C: return (N + 1) * qq;
-    case IDTO_ARR_COST: return 1;
-    case IDTO_ARR_SLAB: return N * (long)c->slab_stride;
-    case IDTO_ARR_HBANDS: return 3 * (N + 6) * qq;
-    case 15: return (N + 4) * 8 * 32;
-    case IDTO_ARR_TR_DQ: case IDTO_ARR_TR_W: case IDTO_ARR_TR_SCALE: return (N + 1) * nq;
-    case IDTO_ARR_ASM_TERMS: return N * (long)asm_terms_stride((int)nq);
-    case IDTO_ARR_CON_S: return c->con_S ? (long)c->con_neq * c->con_neq + c->con_neq : -1;
-    case IDTO_ARR_CON_LAMBDA: return (c->con_lambda_at && c->con_neq > 0) ? (long)c->con_neq : -1;
-    default: return -1;
-  }
+  if (what == IDTO_ARR_CON_S) return c->con_S ? (long)c->con_neq * c->con_neq + c->con_neq : -1;
+  if (what == IDTO_ARR_CON_LAMBDA) return (c->con_lambda_at && c->con_neq > 0) ? (long)c->con_neq : -1;
+  return idto_host::ArrayLookup(what, c->nq, c->nv, c->N).count;
 }
 int idto_hip_slab_stride(idto_hip_ctx* c) { return c->slab_stride; }
 
 }  // extern "C"
 namespace {
 void* DevPtr(idto_hip_ctx* c, int what) {
+  if (what == IDTO_ARR_DEBUG && c->kkt_debug && c->kkt) return c->kkt->dbg;
+  if (what == IDTO_ARR_CON_S) return c->con_S;
+  if (what == IDTO_ARR_CON_LAMBDA) return const_cast<double*>(c->con_lambda_at);
   switch (what) {
-    case IDTO_ARR_Q: return c->q;
-    case IDTO_ARR_V: return c->v;
-    case IDTO_ARR_A: return c->a;
-    case IDTO_ARR_NPLUS: return c->nplus;
-    case IDTO_ARR_GRADIENT: return c->g;
-    case IDTO_ARR_H_A: return c->HA;
-    case IDTO_ARR_H_B: return c->HB;
-    case IDTO_ARR_H_C: return c->HC;
-    case IDTO_ARR_STEP: return c->step;
-    case IDTO_ARR_COST: return c->cost;
-    case IDTO_ARR_SLAB: return c->slab;
-    case IDTO_ARR_HBANDS: return c->HA;
-    case 15: return (c->kkt_debug && c->kkt) ? c->kkt->dbg : c->dbg;
-    case IDTO_ARR_TR_DQ: return c->tr_dq;
-    case IDTO_ARR_TR_W: return c->tr_w;
-    case IDTO_ARR_TR_SCALE: return c->tr_D;
-    case IDTO_ARR_ASM_TERMS: return c->terms;
-    case IDTO_ARR_CON_S: return c->con_S;
-    case IDTO_ARR_CON_LAMBDA: return const_cast<double*>(c->con_lambda_at);
-    default: return nullptr;  // tau and the three partials live strided inside the slab
+#define A(id, field, count) case id: return c->field;
+#define S(id, at, width)    // (tau and the three partials live strided inside the slab: SlabRows)
+#define O(id)
+    IDTO_ARRAYS(A, S, O)
+#undef A
+#undef S
+#undef O
+    default: return nullptr;
   }
+}
+// is the array rows of the slab's records?  *at, *width: doubles into a record, doubles of a row
+bool SlabRows(const idto_hip_ctx* c, int what, size_t* at, size_t* width) {
+  const idto_host::ArrayInfo ai = idto_host::ArrayLookup(what, c->nq, c->nv, c->N);
+  *at = ai.at; *width = ai.width;
+  return ai.where == idto_host::ArrayInfo::SLAB_ROWS;
 }
 }  // namespace
 extern "C" {
@@ -3681,10 +3559,9 @@ int idto_hip_get_batch(idto_hip_ctx* c, int what, int pb, double* out) {
   HIP_OK(hipStreamSynchronize(c->stream));
   const long count = idto_hip_array_size(c, what);
   if (count < 0) { g_err = "unknown array id"; return -1; }
-  const size_t bsz = (size_t)c->nv * c->nq, po = (size_t)pb * c->pstride;
-  if (what == IDTO_ARR_TAU || (what >= IDTO_ARR_DTAU_DQM && what <= IDTO_ARR_DTAU_DQP)) {
-    const size_t off = what == IDTO_ARR_TAU ? 3 * bsz : (size_t)(what - IDTO_ARR_DTAU_DQM) * bsz;
-    const size_t width = what == IDTO_ARR_TAU ? (size_t)c->nv : bsz;
+  const size_t po = (size_t)pb * c->pstride;
+  size_t off = 0, width = 0;
+  if (SlabRows(c, what, &off, &width)) {
     HIP_OK(hipMemcpy2D(out, width * sizeof(double), at_problem(c->slab, po) + off, (size_t)c->slab_stride * sizeof(double),
                        width * sizeof(double), c->N, hipMemcpyDeviceToHost));
     return 0;
@@ -3721,14 +3598,12 @@ int idto_hip_get_many(idto_hip_ctx* c, int n, const int* what, double* const* ou
     HIP_OK(hipHostMalloc((void**)&c->many_pin, std::max<size_t>(off[n], 1) * sizeof(double), hipHostMallocDefault));
     c->many_cap = off[n];
   }
-  const size_t bsz = (size_t)c->nv * c->nq;
   for (int i = 0; i < n; ++i) {
     const int w = what[i];
     for (auto& pf : c->pre) if (pf.what == w) pf.pending = false;   // (a staged copy of it is superseded)
     double* dst = c->many_pin + off[i];
-    if (w == IDTO_ARR_TAU || (w >= IDTO_ARR_DTAU_DQM && w <= IDTO_ARR_DTAU_DQP)) {   // rows of the slab's records
-      const size_t o = w == IDTO_ARR_TAU ? 3 * bsz : (size_t)(w - IDTO_ARR_DTAU_DQM) * bsz;
-      const size_t width = w == IDTO_ARR_TAU ? (size_t)c->nv : bsz;
+    size_t o = 0, width = 0;
+    if (SlabRows(c, w, &o, &width)) {   // rows of the slab's records
       HIP_OK(hipMemcpy2DAsync(dst, width * sizeof(double), c->slab + o, (size_t)c->slab_stride * sizeof(double), width * sizeof(double),
                               c->N, hipMemcpyDeviceToHost, c->stream));
     } else {

@@ -6,6 +6,7 @@
 // -ffp-contract=off; every sum has the association order of DESIGN.md §3.2.
 #pragma once
 
+#include "arena_sizes.h"
 #include "fd_kernel.h"
 #include "trust_region.h"
 

@@ -15,6 +15,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "arena_sizes.h"
 #include "batch.h"
 #include "tr_fetch.h"
 
@@ -131,7 +132,7 @@ struct TrRowsArgs {
   const double* dq_old;   // the step that led to this iterate, or null
   TrKkt kx;
 };
-constexpr int TR_NSUM = 10;
+// (TR_NSUM: arena_sizes.h)
 // LDS of tr_prepare_rows_body, in doubles (nt = 256): its arrays, then the scratch of the sums
 __host__ __device__ constexpr int tr_rows_lds(int K) { return 24 * K + TR_NSUM * 32; }
 
@@ -410,9 +411,9 @@ enum {
   TRS_PREVCOST,    // convergence check: L of the iterate the last accepted step started from (VerifyConvergenceCriteria's previous_cost)
   TRS_CUR,         // which of the two sets of fd_kernel outputs holds the iterate's (batch.h AltSel)
   TRS_CHECK,       // an accepted step's convergence criteria are to be evaluated by the next tr_iter_kernel (it needs g there)
-  TRS_DQN,         // |dq| of that step
-  TRS_COUNT = 12
+  TRS_DQN          // |dq| of that step
 };
+static_assert(TRS_DQN + 1 == TRS_COUNT, "arena_sizes.h and trust_region.h disagree");
 static_assert(TRS_CUR == IDTO_TRS_CUR, "batch.h and trust_region.h disagree");
 enum { TRF_DOGLEG = 1, TRF_NONFINITE = 2, TRF_NOT_DESCENT = 4, TRF_SINGULAR_S = 8 /* constraints.h constraint_lambda_kernel */,
        TRF_CONVERGED = 16 /* a convergence criterion held after an accepted step (TO.cc:2654-2689): not an error */,

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "host/context_layout.h"
 #include "host/solver_plan.h"
 #include "sha256.h"
 #include "solver_layout.h"
@@ -202,32 +203,18 @@ static std::string Produce(bool hold) {
         }
   // the solver-only arrays: the KKT context's carve (offsets in bytes, arena stride), idto_hip_create_batch's from its
   // stamp array on (relative offsets; what lies in front of it does not move them: every array starts 64-byte aligned)
+  // (both from host/context_layout.cc's plan, the one the library allocates by)
   for (int K = 1; K <= 32; ++K)
     for (int N : {1, 2, 10, 40, 140}) {
-      const SolverBuffers b = SolverBufferCounts(K, N);
-      size_t top = 0;
-      auto carve = [&](size_t count, size_t elem) {
-        const size_t o = (top + 63) & ~(size_t)63;
-        top = o + std::max<size_t>(count, 1) * elem;
-        return o;
-      };
-      const size_t D = sizeof(double), U = sizeof(unsigned), L = sizeof(unsigned long long), rows = (size_t)N + 1;
-      {
-        const size_t o[14] = {carve(b.bands, D), carve(rows * K, D), carve(rows * K, D), carve(b.factors, D), carve(b.factors, D), carve(b.factors, D),
-                              carve(b.dinv, D), carve(b.dbg, D), carve(b.xch, D), carve(b.flags, U), carve(b.rowcnt, L), carve(b.rowcnt, L),
-                              carve(b.nd_buf, D), carve(b.nd_wst, D)};
-        out += "kkt " + std::to_string(K) + " " + std::to_string(N) + " :";
-        for (size_t v : o) out += " " + std::to_string(v);
-        out += " " + std::to_string((top + 255) & ~(size_t)255) + "\n";
-      }
-      {
-        top = 0;
-        const size_t o[12] = {carve(b.dbg, D), carve(b.factors, D), carve(b.factors, D), carve(b.factors, D), carve(b.dinv, D), carve(b.xch, D),
-                              carve(b.rowcnt, L), carve(b.nd_buf, D), carve(b.rowcnt, L), carve(b.nd_wst, D), carve(4 * rows, U), carve(b.flags, U)};
-        out += "main " + std::to_string(K) + " " + std::to_string(N) + " :";
-        for (size_t v : o) out += " " + std::to_string(v);
-        out += " " + std::to_string(top) + "\n";
-      }
+      const ArenaPlan kkt = PlanArena(ARENA_KKT, K, 0, N), mdl = PlanArena(ARENA_MODEL, K, K, N);
+      out += "kkt " + std::to_string(K) + " " + std::to_string(N) + " :";
+      for (const ArenaEntry& e : kkt.entries) out += " " + std::to_string(e.offset);
+      out += " " + std::to_string(kkt.pstride) + "\n";
+      // dbg .. flags, and where flags ends
+      const ArenaEntry *first = mdl.Find("dbg"), *last = mdl.Find("flags");
+      out += "main " + std::to_string(K) + " " + std::to_string(N) + " :";
+      for (const ArenaEntry* e = first; e <= last; ++e) out += " " + std::to_string(e->offset - first->offset);
+      out += " " + std::to_string(last->offset + last->count * last->elem - first->offset) + "\n";
     }
   return out;
 }

@@ -22,6 +22,7 @@ def test_solver_plans_match_the_recorded_ones_and_fit_the_kernels(tmp_path):
     subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                     "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
                     "-I" + os.path.join(ROOT, "tests", "cpp"), os.path.join(ROOT, "tests", "cpp", "solver_plan_check.cc"),
-                    os.path.join(CSRC, "host", "solver_plan.cc"), "-o", exe], check=True)
+                    os.path.join(CSRC, "host", "solver_plan.cc"), os.path.join(CSRC, "host", "context_layout.cc"), "-o", exe],
+                   check=True)
     run = subprocess.run([exe, os.path.join(ROOT, "tests", "golden", "solver_plan.txt")], capture_output=True, text=True)
     assert run.returncode == 0 and run.stdout.startswith("ok:"), run.stdout[-4000:] + run.stderr[-4000:]

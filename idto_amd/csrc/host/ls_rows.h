@@ -7,6 +7,7 @@
 
 #include <string>
 
+#include "host/batch_rows.h"
 #include "idto/optimizer/solver_parameters.h"
 #include "idto/optimizer/trajectory_optimizer_solution.h"
 
@@ -16,12 +17,12 @@ namespace internal {
 
 constexpr int kLsRow = 12;   // IDTO_LS_ROW (static_assert where idto_hip.h is included as well)
 
-enum class LsRowsOutcome {
-  kDone,            // `flag` is kSuccess or kLinesearchMaxIters
-  kNeedsHostLoop,   // flag 128: backtracking undecided within the device's candidates - the host loop runs the solve
-  kFailed,          // flag 32: the factorisation failed (`flag` is kFactorizationFailed, `error` says where)
-  kError            // flag 4 (2): not a descent direction - `error` is the host loop's text
-};
+// One enum for both loops' rows (SolveBatch takes an entry of either loop the same way).  Here:
+//   kDone            `flag` is kSuccess or kLinesearchMaxIters
+//   kNeedsHostLoop   flag 128: backtracking undecided within the device's candidates - the host loop runs the solve
+//   kFailed          flag 32: the factorisation failed (`flag` is kFactorizationFailed, `error` says where)
+//   kError           flag 4 (2): not a descent direction - `error` is the host loop's text
+using LsRowsOutcome = RowsOutcome;
 
 struct LsRowsResult {
   LsRowsOutcome outcome = LsRowsOutcome::kDone;

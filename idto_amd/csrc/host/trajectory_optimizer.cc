@@ -95,10 +95,9 @@ std::vector<Vec> Unflatten(const Vec& flat, int count, int width) {
   return out;
 }
 // the same into `out`, whose rows keep their storage when the sizes repeat (the solution object of an MPC re-plan)
-void UnflattenInto(const Vec& flat, int count, int width, std::vector<Vec>* out) {
+void UnflattenInto(const double* flat, int count, int width, std::vector<Vec>* out) {
   out->resize((std::size_t)count);
-  for (int t = 0; t < count; ++t)
-    (*out)[t].assign(flat.begin() + (std::size_t)t * width, flat.begin() + (std::size_t)(t + 1) * width);
+  for (int t = 0; t < count; ++t) (*out)[t].assign(flat + (std::size_t)t * width, flat + (std::size_t)(t + 1) * width);
 }
 std::vector<MatrixXd> UnflattenBlocks(const Vec& flat, int count, int rows, int cols) {
   std::vector<MatrixXd> out((std::size_t)count, MatrixXd(rows, cols));
@@ -107,6 +106,25 @@ std::vector<MatrixXd> UnflattenBlocks(const Vec& flat, int count, int rows, int 
               out[t].data());
   return out;
 }
+
+// A ProblemDefinition as the device library reads it: `p` points into `pd` and into the flattened nominal trajectories -
+// the view's own, or the caller's buffers (which keep their storage from call to call), for as long as they live.
+struct ProblemView {
+  Vec own_q_nom, own_v_nom;
+  idto_problem_t p = {};
+  ProblemView(const ProblemDefinition& pd, int num_steps, double time_step, Vec* q_nom = nullptr, Vec* v_nom = nullptr) {
+    Vec& qn = q_nom ? *q_nom : own_q_nom;
+    Vec& vn = v_nom ? *v_nom : own_v_nom;
+    qn.clear(); vn.clear();
+    for (const Vec& x : pd.q_nom) qn.insert(qn.end(), x.begin(), x.end());
+    for (const Vec& x : pd.v_nom) vn.insert(vn.end(), x.begin(), x.end());
+    p.num_steps = num_steps; p.time_step = time_step;
+    p.q_init = pd.q_init.data(); p.v_init = pd.v_init.data();
+    p.Qq = pd.Qq.data(); p.Qv = pd.Qv.data(); p.Qf_q = pd.Qf_q.data(); p.Qf_v = pd.Qf_v.data();
+    p.R = pd.R.data(); p.q_nom = qn.data(); p.v_nom = vn.data();
+  }
+  ProblemView(const ProblemView&) = delete;
+};
 
 }  // namespace
 
@@ -281,15 +299,10 @@ TO::TrajectoryOptimizer(const idto_model_t& model, double time_step, const Probl
     for (int j = 0; j < nv_; ++j)
       if (!model.actuated[j]) unactuated_dofs_.push_back(j);
 
-  const Vec qn = Flatten(prob_.q_nom), vn = Flatten(prob_.v_nom);
-  idto_problem_t p = {};
-  p.num_steps = num_steps(); p.time_step = time_step_;
-  p.q_init = prob_.q_init.data(); p.v_init = prob_.v_init.data();
-  p.Qq = prob_.Qq.data(); p.Qv = prob_.Qv.data(); p.Qf_q = prob_.Qf_q.data(); p.Qf_v = prob_.Qf_v.data();
-  p.R = prob_.R.data(); p.q_nom = qn.data(); p.v_nom = vn.data();
+  const ProblemView view(prob_, num_steps(), time_step_);
   idto_contact_params_t c = {params_.contact_stiffness, params_.dissipation_velocity, params_.stiction_velocity,
                              params_.friction_coefficient, params_.smoothing_factor};
-  Check(idto_hip_create(&model, &p, &c, device, &hip_));
+  Check(idto_hip_create(&model, &view.p, &c, device, &hip_));
   Check(idto_hip_set_option(hip_, "gradients_method", static_cast<int>(params_.gradients_method)));
   // (this class talks to the context through its stream-ordered entry points only: q and the problem's arrays go up from
   // pinned staging without a wait of their own - two of the five waits of an MPC re-plan)
@@ -300,18 +313,13 @@ TO::TrajectoryOptimizer(const idto_model_t& model, double time_step, const Probl
                         const SolverParameters& params, const std::vector<int>& devices)
     : TrajectoryOptimizer(model, time_step, prob, params, devices.empty() ? 0 : devices[0]) {
   if (devices.empty()) return;
-  const Vec qn = Flatten(prob_.q_nom), vn = Flatten(prob_.v_nom);
-  idto_problem_t p = {};
-  p.num_steps = num_steps(); p.time_step = time_step_;
-  p.q_init = prob_.q_init.data(); p.v_init = prob_.v_init.data();
-  p.Qq = prob_.Qq.data(); p.Qv = prob_.Qv.data(); p.Qf_q = prob_.Qf_q.data(); p.Qf_v = prob_.Qf_v.data();
-  p.R = prob_.R.data(); p.q_nom = qn.data(); p.v_nom = vn.data();
+  const ProblemView view(prob_, num_steps(), time_step_);
   idto_contact_params_t c = {params_.contact_stiffness, params_.dissipation_velocity, params_.stiction_velocity,
                              params_.friction_coefficient, params_.smoothing_factor};
   shard_ctx_.push_back(hip_);
   for (std::size_t i = 1; i < devices.size(); ++i) {
     idto_hip_ctx* h = nullptr;
-    Check(idto_hip_create(&model, &p, &c, devices[i], &h));
+    Check(idto_hip_create(&model, &view.p, &c, devices[i], &h));
     shard_ctx_.push_back(h);
     Check(idto_hip_set_option(h, "gradients_method", static_cast<int>(params_.gradients_method)));
   }
@@ -329,16 +337,10 @@ void TO::UploadProblem() const { UploadProblemDefinition(prob_); }
 
 void TO::UploadProblemDefinition(const ProblemDefinition& prob) const {
   problem_dirty_ = false;
-  const Vec qn = Flatten(prob.q_nom), vn = Flatten(prob.v_nom);
-  idto_problem_t p = {};
-  p.num_steps = num_steps(); p.time_step = time_step_;
-  p.q_init = prob.q_init.data(); p.v_init = prob.v_init.data();
-  p.Qq = prob.Qq.data(); p.Qv = prob.Qv.data(); p.Qf_q = prob.Qf_q.data(); p.Qf_v = prob.Qf_v.data();
-  p.R = prob.R.data(); p.q_nom = qn.data(); p.v_nom = vn.data();
-  Check(idto_hip_set_problem(hip_, &p));
-  for (std::size_t i = 1; i < shard_ctx_.size(); ++i) Check(idto_hip_set_problem(shard_ctx_[i], &p));
-  resident_ = nullptr;  // every cached device result depends on the problem data
-  device_level_ = 0;
+  const ProblemView view(prob, num_steps(), time_step_);
+  Check(idto_hip_set_problem(hip_, &view.p));
+  for (std::size_t i = 1; i < shard_ctx_.size(); ++i) Check(idto_hip_set_problem(shard_ctx_[i], &view.p));
+  InvalidateDevice();  // every cached device result depends on the problem data
 }
 
 // TO.h:429-450
@@ -347,8 +349,7 @@ void TO::ResetInitialConditions(const VectorXd& q_init, const VectorXd& v_init) 
   prob_.q_init = q_init;
   prob_.v_init = v_init;
   problem_dirty_ = true;   // (uploaded with the next device call: dev())
-  resident_ = nullptr;     // every cached device result depends on the problem data
-  device_level_ = 0;
+  InvalidateDevice();      // every cached device result depends on the problem data
 }
 // TO.h:452-470
 void TO::UpdateNominalTrajectory(const std::vector<VectorXd>& q_nom, const std::vector<VectorXd>& v_nom) {
@@ -357,8 +358,7 @@ void TO::UpdateNominalTrajectory(const std::vector<VectorXd>& q_nom, const std::
   prob_.q_nom = q_nom;
   prob_.v_nom = v_nom;
   problem_dirty_ = true;
-  resident_ = nullptr;
-  device_level_ = 0;
+  InvalidateDevice();
 }
 
 // ---- device residency: level 0 = q, 1 = + tau/cost, 2 = + partials, 3 = + gradient/Hessian
@@ -475,7 +475,7 @@ void TO::CalcGradHess(const TrajectoryOptimizerState<T>& state) const {
   // next (CalcDoglegPoint :2139-2149 / CalcLagrangeMultipliers :1371-1396) - already runs
   Check(idto_hip_prefetch(dev(), IDTO_ARR_GRADIENT));
   Check(idto_hip_prefetch(dev(), IDTO_ARR_HBANDS));
-  if (params_.equality_constraints && num_equality_constraints() > 0) {
+  if (Constrained()) {
     Scope prof2_("  launch constraint solve");
     Check(idto_hip_constraint_schur_begin(dev(), unactuated_dofs_.data(), (int)unactuated_dofs_.size()));
   } else if (!DenseLinearSolver()) {
@@ -685,7 +685,7 @@ double TO::DebugConditionNumber(const TrajectoryOptimizerState<T>& s, bool scale
 // follows from it:  H~^-1 g~_merit = D^-1 H^-1 g_merit.
 const VectorXd& TO::EvalHinvMeritGradient(const TrajectoryOptimizerState<T>& s) const {
   auto& c = s.cache_;
-  if (params_.equality_constraints && num_equality_constraints() > 0) {
+  if (Constrained()) {
     EvalLagrangeMultipliers(s);
     if (DenseLinearSolver() && !c.hinv) {
       // the multipliers come from the block Thomas factorisation whatever `linear_solver` says (TO.cc:1385, "add options
@@ -803,24 +803,6 @@ void TO::NormalizeQuaternions(TrajectoryOptimizerState<T>* state) const {
   state->set_q(q);
 }
 
-namespace {
-// TO.cc:2037-2066
-double SolveDoglegQuadratic(double a, double b, double c) {
-  if (!(a > 0)) throw std::runtime_error("dogleg: a <= 0");
-  double s;
-  if (a < std::numeric_limits<double>::epsilon()) {
-    s = -c / b;
-  } else {
-    const double bt = b / a, ct = c / a;
-    const double det = bt * bt - 4 * ct;
-    if (!(det > 0)) throw std::runtime_error("dogleg: determinant <= 0");
-    s = (-bt + std::sqrt(det)) / 2;
-  }
-  if (!(0 < s && s < 1)) throw std::runtime_error("dogleg: s not in (0,1)");
-  return s;
-}
-}  // namespace
-
 // TO.cc:2108-2202
 bool TO::CalcDoglegPoint(const TrajectoryOptimizerState<T>& s, double Delta, VectorXd* dq, VectorXd* dqH) const {
   const PentaDiagonalMatrix<T>& H = EvalScaledHessian(s);
@@ -838,7 +820,7 @@ bool TO::CalcDoglegPoint(const TrajectoryOptimizerState<T>& s, double Delta, Vec
   }
   if (params_.debug_compare_against_dense) {  // :2142-2150 (the reference's reference solution: dense LDL^T)
     Vec gm_unscaled = EvalGradient(s), yd;   // g + J^T lambda, unscaled (see EvalHinvMeritGradient)
-    if (params_.equality_constraints && num_equality_constraints() > 0) {
+    if (Constrained()) {
       EvalLagrangeMultipliers(s);
       for (int i = 0; i < n; ++i) gm_unscaled[i] += s.cache_.JT_lambda[i];
     }
@@ -880,7 +862,7 @@ bool TO::CalcDoglegPoint(const TrajectoryOptimizerState<T>& s, double Delta, Vec
   Vec d((std::size_t)n);
   for (int i = 0; i < n; ++i) d[i] = pH[i] - pU[i];
   const double a = Dot(d, d), b = 2 * Dot(pU, d), c = Dot(pU, pU) - 1.0;  // :2192-2194
-  const double sq = SolveDoglegQuadratic(a, b, c);
+  const double sq = internal::SolveDoglegQuadratic(a, b, c);
   for (int i = 0; i < n; ++i) (*dq)[i] = (pU[i] + sq * d[i]) * Delta;  // :2197
   apply_scaling();
   return true;
@@ -1031,7 +1013,7 @@ std::pair<double, int> TO::BacktrackingLinesearch(const TrajectoryOptimizerState
 bool TO::LinesearchLoopEligible() const {
   if (std::getenv("IDTO_OPT_HOST_LOOP") || force_host_loop_) return false;
   if (!shard_ctx_.empty() || params_.max_iterations < 1) return false;
-  if (params_.scaling || (params_.equality_constraints && num_equality_constraints() > 0)) return false;
+  if (params_.scaling || (Constrained())) return false;
   if (DenseLinearSolver() || params_.debug_compare_against_dense || params_.print_debug_data || params_.verbose) return false;
   if (params_.max_linesearch_iterations > IDTO_LS_MAX_CANDIDATES) return false;
   int weights_diagonal = 0;
@@ -1048,8 +1030,7 @@ SolverFlag TO::SolveLinesearchOnDevice(const std::vector<VectorXd>& q_guess, Tra
   auto on_host = [&]() {
     force_host_loop_ = true;
     struct Reset { const TO* t; ~Reset() { t->force_host_loop_ = false; } } reset{this};
-    resident_ = nullptr;
-    device_level_ = 0;
+    InvalidateDevice();
     return SolveWithLinesearch(q_guess, solution, stats);
   };
   const int iters = params_.max_iterations, N = num_steps();
@@ -1057,8 +1038,7 @@ SolverFlag TO::SolveLinesearchOnDevice(const std::vector<VectorXd>& q_guess, Tra
     const Vec q0 = Flatten(q_guess);
     Check(idto_hip_set_q(dev(), q0.data()));
   }
-  resident_ = nullptr;
-  device_level_ = 0;
+  InvalidateDevice();
   Check(idto_hip_set_unactuated_dofs(dev(), unactuated_dofs_.data(), (int)unactuated_dofs_.size()));
   std::vector<double> rows((std::size_t)iters * IDTO_LS_ROW);
   Vec fq((std::size_t)num_vars()), fv((std::size_t)(N + 1) * nv_), ft((std::size_t)N * nv_);
@@ -1165,8 +1145,7 @@ SolverFlag TO::SolveFromWarmStart(WarmStart* ws, TrajectoryOptimizerSolution<T>*
       if (attempt >= 4) throw;
       if (params_.verbose) std::printf("%s\n", e.what());
       *stats = TrajectoryOptimizerStats<T>();
-      resident_ = nullptr;
-      device_level_ = 0;
+      InvalidateDevice();
     }
   }
 }
@@ -1185,7 +1164,7 @@ bool TO::DeviceLoopEligible() const {
   if (!shard_ctx_.empty()) return false;
   // the dense solver and the two debugging switches live in the stepwise loop (SolveLinearSystem, CalcDoglegPoint)
   if (DenseLinearSolver() || params_.debug_compare_against_dense || params_.print_debug_data) return false;
-  const bool constrained = params_.equality_constraints && num_equality_constraints() > 0;
+  const bool constrained = Constrained();
   if (!constrained && !params_.check_convergence) return true;
   // enforced constraints and the convergence criteria: only the resident loop (idto_hip_tr_solve) has them on the
   // device (multipliers by a single-workgroup LDL^T of S for n_eq <= 128, by the blocked one above; the criteria
@@ -1206,180 +1185,99 @@ bool TO::ResidentLoopEligible() const {
   int resident_ok = 1;   // (0 once the iteration kernel's workgroups timed out waiting for each other on this context)
   Check(idto_hip_get_option(dev(), "tr_resident_ok", &resident_ok));
   if (!resident_ok) return false;
-  const int scal = params_.scaling ? static_cast<int>(params_.scaling_method) : -1;
-  const bool adaptive = scal == static_cast<int>(kAdaptiveSqrt) || scal == static_cast<int>(kAdaptiveDoubleSqrt);
-  if (!adaptive) return true;
+  if (!AdaptiveScaling()) return true;
   int weights_diagonal = 0;   // (the adaptive scalings ride on the gated assembly, which serves diagonal cost weights)
   Check(idto_hip_get_option(dev(), "weights_diagonal", &weights_diagonal));
   return weights_diagonal != 0;
 }
 
-SolverFlag TO::SolveOnDevice(WarmStart* ws, TrajectoryOptimizerSolution<T>* solution,
-                             TrajectoryOptimizerStats<T>* stats, ConvergenceReason* reason_out) const {
+// every iteration enqueued at once, decisions on the device, one wait (idto_hip_tr_solve_fetch, which brings the solution
+// along under that wait); the rows become statistics by the one translation there is (host/batch_rows.h).  True: a
+// singular constraint system handed the rest of the solve to the host loop, whose flag is loop->handed_over.
+bool TO::ResidentPhase(WarmStart* ws, const BatchLoopArgs& a, TrajectoryOptimizerSolution<T>* solution,
+                       TrajectoryOptimizerStats<T>* stats, ConvergenceReason* reason_out, DeviceLoop* L) const {
   using clock = std::chrono::high_resolution_clock;
-  const auto start_time = clock::now();
-  auto iter_start = clock::now();
-  TrajectoryOptimizerState<T>& state = ws->state;
-  double& Delta = ws->Delta;
-  const double eta = 0.0;
-  {
-    const Vec q0 = Flatten(state.q());
-    Check(idto_hip_set_q(dev(), q0.data()));
+  SetConvergence(dev());   // VerifyConvergenceCriteria (TO.cc:2654-2689) inside the device loop
+  std::vector<double> rows((std::size_t)a.iterations * IDTO_TR_ROW);
+  double Delta_end = ws->Delta;
+  L->q.resize((std::size_t)num_vars()); L->v.resize((std::size_t)(num_steps() + 1) * nv_); L->tau.resize((std::size_t)num_steps() * nv_);
+  L->dq.resize((std::size_t)num_vars()); L->w.resize((std::size_t)num_vars());
+  Check(idto_hip_tr_solve_fetch(dev(), a.iterations, a.scaling_method, a.scaling, a.normalize_quaternions, ws->Delta, a.Delta_max,
+                                a.eta, a.constrained_dofs, a.nu, rows.data(), &Delta_end, L->q.data(), L->v.data(), L->tau.data(),
+                                L->dq.data(), L->w.data()));
+  L->fetched = true;
+  idto_hip_trace_mark("opt: idto_hip_tr_solve_fetch returned");
+  const double total = std::chrono::duration<double>(clock::now() - L->start).count();
+  const std::size_t first = stats->iteration_costs.size();
+  internal::BatchRowsResult r;
+  internal::RowsToStats(rows.data(), a.iterations, Delta_end, total, params_, stats, &r);
+  if (params_.verbose)
+    for (std::size_t i = first; i < first + (std::size_t)r.iterations; ++i)
+      std::printf("| %6d | %8.3g | %7.2g | %7.3g | %10.5g | %10.5g | %10.4g | %10.4g |\n", (int)(i - first), stats->iteration_costs[i],
+                  stats->trust_region_radii[i], stats->trust_ratios[i], stats->iteration_times[i],
+                  stats->gradient_norms[i] / stats->iteration_costs[i], stats->dL_dqs[i], stats->h_norms[i]);
+  if (r.reason_reported && reason_out) *reason_out = stats->convergence_reason;
+  // (the rows in front of a flagged one are in *stats when an exception leaves: SolveFromWarmStart returns with them)
+  if (r.outcome == internal::RowsOutcome::kFailed) throw FactorizationFailedError(r.error);
+  if (r.outcome == internal::RowsOutcome::kError) throw std::runtime_error(r.error);
+  ws->Delta = r.Delta;
+  if (r.outcome == internal::RowsOutcome::kNeedsHostLoop) {
+    // numerically singular S = J H^-1 J^T (redundant constraints) at this iterate: the host loop's pivoted
+    // LDL^T (Eigen's, in the reference) handles it; q on the device is still this iteration's iterate
+    ws->state.set_q(Unflatten(Fetch(IDTO_ARR_Q), num_steps() + 1, nq_));
+    InvalidateDevice();
+    force_host_loop_ = true;
+    resume_k_ = r.iterations;
+    struct Reset { const TO* t; ~Reset() { t->force_host_loop_ = false; t->resume_k_ = 0; } } reset{this};
+    const double device_part = std::chrono::duration<double>(clock::now() - L->start).count();
+    L->handed_over = SolveFromWarmStartImpl(ws, solution, stats, nullptr);
+    stats->solve_time += device_part;
+    return true;
   }
-  Check(idto_hip_set_unactuated_dofs(dev(), unactuated_dofs_.data(), (int)unactuated_dofs_.size()));
-  idto_hip_trace_mark("opt: q and the unactuated dofs set");
-  // (the resident loop starts with the partials of this q: one finite-difference launch for both)
-  Check(ResidentLoopEligible() ? idto_hip_eval_tau_partials(dev()) : idto_hip_eval_tau(dev()));
-  // (the resident loop keeps the cost on the device and reports it in its rows: no fetch, no synchronisation here)
-  double cost = ResidentLoopEligible() ? 0.0 : Fetch(IDTO_ARR_COST)[0];
-  const int scal = params_.scaling ? static_cast<int>(params_.scaling_method) : -1;
-  // the adaptive scalings' memory of D belongs to the state (TO.cc:1241-1255 reads the cached scale
-  // factors): ones for a fresh state, the last solve's for a warm start - never the context's leftovers
-  const bool adaptive = scal == static_cast<int>(kAdaptiveSqrt) || scal == static_cast<int>(kAdaptiveDoubleSqrt);
-  if (adaptive) {
-    const Vec& Dmem = state.cache_.scale_factors;
-    Check(idto_hip_tr_set_scale_memory(dev(), (int)Dmem.size() == num_vars() ? Dmem.data() : nullptr));
-  }
-  if (params_.verbose) {
-    std::printf("-------------------------------------------------------------------------------------\n");
-    std::printf("|  iter  |   cost   |    Δ    |    ρ    |  time (s)  |  |g|/cost  |    dL_dq   |    |h|     |\n");
-    std::printf("-------------------------------------------------------------------------------------\n");
-  }
-  bool have = false, last_accepted = true;
+  L->k = r.iterations;
+  L->last_accepted = r.last_accepted;
+  L->converged = r.converged;
+  // (the resident loop carries the cost on the device.  Every device flag either throws or yields a converged
+  // row, so the stepwise phase is not reached from here in normal operation - but if it ever is, after the chunked early
+  // exit's truncation say, its trust ratio must be formed against the iterate's cost: the last row's, as the rows unit
+  // reads it.)
+  L->cost = r.iterate_cost;
+  return false;
+}
+
+// two returns to the host per iteration: idto_hip_gn_step + idto_hip_tr_prepare (nine inner products), then the trial
+// point.  The dogleg step and the trust ratio are functions of those inner products (host/batch_rows.h), in the
+// expressions of the device's tr_conv_dogleg: the two loops walk the same bits.
+void TO::StepwisePhase(const BatchLoopArgs& args, double* Delta_io, TrajectoryOptimizerStats<T>* stats, DeviceLoop* L) const {
+  using clock = std::chrono::high_resolution_clock;
+  double& Delta = *Delta_io;
+  auto iter_start = L->start;
+  bool have = false;   // g, H and the Newton step of the iterate are on the device, their inner products in S
   double S[9] = {0};
-  int k = 0;
-  Vec fq, fv, ft, fdq, fw;   // what idto_hip_tr_solve_fetch brought along
-  bool fetched = false;
-  // every iteration enqueued at once, decisions on the device, one wait (idto_hip_tr_solve); the
-  // stepwise loop below serves IDTO_OPT_STEPWISE=1 (and the adaptive scalings with dense cost weights)
-  const bool resident_loop = ResidentLoopEligible();
-  bool converged = false;
-  if (resident_loop) {
-    if (params_.check_convergence) {   // VerifyConvergenceCriteria (TO.cc:2654-2689) inside the device loop
-      const auto& t = params_.convergence_tolerances;
-      const double tol[6] = {t.rel_cost_reduction, t.abs_cost_reduction, t.rel_gradient_along_dq, t.abs_gradient_along_dq,
-                             t.rel_state_change, t.abs_state_change};
-      Check(idto_hip_tr_set_convergence(dev(), tol));
-    } else {
-      Check(idto_hip_tr_set_convergence(dev(), nullptr));
-    }
-    const int iters = params_.max_iterations;
-    std::vector<double> rows((std::size_t)iters * IDTO_TR_ROW);
-    double Delta_end = Delta;
-    const bool constrained = params_.equality_constraints && num_equality_constraints() > 0;
-    // (the solution comes back under the loop's own wait: idto_hip_tr_solve_fetch)
-    fq.resize((std::size_t)num_vars()); fv.resize((std::size_t)(num_steps() + 1) * nv_); ft.resize((std::size_t)num_steps() * nv_);
-    fdq.resize((std::size_t)num_vars()); fw.resize((std::size_t)num_vars());
-    Check(idto_hip_tr_solve_fetch(dev(), iters, scal, params_.scaling ? 1 : 0, params_.normalize_quaternions ? 1 : 0, Delta,
-                                  params_.Delta_max, eta, constrained ? unactuated_dofs_.data() : nullptr,
-                                  constrained ? (int)unactuated_dofs_.size() : 0, rows.data(), &Delta_end, fq.data(), fv.data(),
-                                  ft.data(), fdq.data(), fw.data()));
-    fetched = true;
-    idto_hip_trace_mark("opt: idto_hip_tr_solve_fetch returned");
-    const double total = std::chrono::duration<double>(clock::now() - start_time).count();
-    // (with the convergence criteria on the device loop stops within eight iterations of the one that met them: the
-    // rows behind it are zeros)
-    int ran = iters;
-    while (ran > 1 && rows[(std::size_t)(ran - 1) * IDTO_TR_ROW + 10] == 0.0) --ran;
-    double timed = 0.0;
-    for (int i = 1; i < ran; ++i) timed += (rows[(std::size_t)i * IDTO_TR_ROW + 10] - rows[(std::size_t)(i - 1) * IDTO_TR_ROW + 10]) * 1e-8;
-    for (; k < ran; ++k) {
-      const double* R = rows.data() + (std::size_t)k * IDTO_TR_ROW;
-      const int flags = (int)R[14];
-      if (flags & 8) {
-        // numerically singular S = J H^-1 J^T (redundant constraints) at this iterate: the host loop's pivoted
-        // LDL^T (Eigen's, in the reference) handles it; q on the device is still this iteration's iterate
-        state.set_q(Unflatten(Fetch(IDTO_ARR_Q), num_steps() + 1, nq_));
-        resident_ = nullptr;
-        device_level_ = 0;
-        Delta = R[1];
-        force_host_loop_ = true;
-        resume_k_ = k;
-        struct Reset { const TO* t; ~Reset() { t->force_host_loop_ = false; t->resume_k_ = 0; } } reset{this};
-        const double device_part = std::chrono::duration<double>(clock::now() - start_time).count();
-        const SolverFlag flag = SolveFromWarmStartImpl(ws, solution, stats, nullptr);
-        stats->solve_time += device_part;
-        return flag;
-      }
-      if (flags & 32)   // (in the iteration it happened in, not only when it is the last one: idto_hip_tr_solve rows [14])
-        throw FactorizationFailedError("idto_hip: factorisation failed in iteration " + std::to_string(k));
-      if (flags & 3) throw FactorizationFailedError("idto_hip: the dogleg step is not finite");
-      if (flags & 4) throw std::runtime_error("step is not a descent direction (TO.cc:2531)");
-      const double iter_time = (k == 0) ? std::max(0.0, total - timed) : (R[10] - R[10 - IDTO_TR_ROW]) * 1e-8;
-      if (params_.verbose)
-        std::printf("| %6d | %8.3g | %7.2g | %7.3g | %10.5g | %10.5g | %10.4g | %10.4g |\n", k, R[0], R[1], R[2], iter_time,
-                    R[6] / R[0], R[7], R[8]);
-      stats->push_data(iter_time, R[0], 0, std::numeric_limits<double>::quiet_NaN(), R[1], R[3], R[4], R[5], R[2], R[6],
-                       R[7], R[8], R[15]);   // :2586-2598 (merit = cost without constraints)
-      last_accepted = R[9] != 0.0;
-      if (params_.check_convergence && last_accepted) {   // :2600-2612
-        const ConvergenceReason reason = static_cast<ConvergenceReason>((int)R[16]);
-        stats->convergence_reason = reason;
-        if (reason_out) *reason_out = reason;
-        if (reason != kNoConvergenceCriteriaSatisfied) {   // (the reference leaves the loop before the radius update)
-          converged = true;
-          Delta = R[1];
-          break;
-        }
-      }
-    }
-    if (!converged) Delta = Delta_end;
-    // (the resident loop carries the cost on the device and `cost` is still the placeholder.  Every device
-    // flag either throws or yields a converged row, so the stepwise loop below is not reached from here in normal
-    // operation - but if it ever is, after the chunked early exit's truncation say, its trust ratio must not be
-    // formed against 0.  The iterate's cost is in the last row: L(q_k + dq) if that step was accepted, L(q_k) if not -
-    // NOT IDTO_ARR_COST, which every trial point overwrites, a rejected one included.)
-    if (k < params_.max_iterations && !converged && ran > 0) {
-      const double* R = rows.data() + (std::size_t)(ran - 1) * IDTO_TR_ROW;
-      cost = (R[9] != 0.0) ? R[13] : R[0];
-    }
-  }
-  while (k < params_.max_iterations && !converged) {
-    fetched = false;   // (the device moves on: what the resident loop brought along is stale)
+  while (L->k < params_.max_iterations && !L->converged) {
+    L->fetched = false;   // (the device moves on: what the resident loop brought along is stale)
     if (!have) {
       Check(idto_hip_gn_step(dev()));
-      Check(idto_hip_tr_prepare(dev(), scal, 0, S));   // (reports a failed factorisation)
+      Check(idto_hip_tr_prepare(dev(), args.scaling_method, 0, S));   // (reports a failed factorisation)
       have = true;
     }
-    const double gg = S[0], gHg = S[1], ww = S[2], gw = S[3], gHw = S[4], wHw = S[5], qq = S[6], hh = S[7];
-    // CalcDoglegPoint, normalised by Delta: pU = cU g~ (:2157), pH = -w / Delta (:2139-2149)
-    const double cU = -(gg / gHg) / Delta;
-    const double pUn = std::fabs(cU) * std::sqrt(gg), pHn = std::sqrt(ww) / Delta;
-    double a, b;
-    bool active;
-    if (1.0 <= pUn) {          // :2160-2168
-      a = (Delta / pUn) * cU; b = 0.0; active = true;
-    } else if (1.0 >= pHn) {   // :2171-2178
-      a = 0.0; b = -1.0; active = false;
-    } else {                   // :2180-2199
-      const double pUpU = cU * cU * gg, pHpH = ww / (Delta * Delta), pUpH = -cU * gw / Delta;
-      const double sq = SolveDoglegQuadratic(pHpH - 2 * pUpH + pUpU, 2 * (pUpH - pUpU), pUpU - 1.0);
-      a = Delta * (1.0 - sq) * cU; b = -sq; active = true;
-    }
-    if (!std::isfinite(a) || !std::isfinite(b)) throw FactorizationFailedError("idto_hip: the dogleg step is not finite");
+    const internal::DoglegScalars d = internal::CalcDoglegScalars(S, Delta);
+    if (!d.finite) throw FactorizationFailedError("idto_hip: the dogleg step is not finite");
     double Tr[4];
     // speculate on acceptance (the next iteration is enqueued behind the trial point) unless the last
     // step was rejected: a rejection costs a recomputation of g and H at the old q
-    const bool speculate = last_accepted && !std::getenv("IDTO_OPT_NO_SPECULATION");
-    Check(idto_hip_tr_trial(dev(), a, b, params_.scaling ? 1 : 0, params_.normalize_quaternions ? 1 : 0, 0,
-                            speculate ? scal : -2, Tr));
-    const double dq_norm = std::sqrt(Tr[0]), gdqs = Tr[1], cost_trial = Tr[2];
+    const bool speculate = L->last_accepted && !std::getenv("IDTO_OPT_NO_SPECULATION");
+    Check(idto_hip_tr_trial(dev(), d.a, d.b, args.scaling, args.normalize_quaternions, 0, speculate ? args.scaling_method : -2, Tr));
+    const double dq_norm = std::sqrt(Tr[0]), cost_trial = Tr[2];
     if (!std::isfinite(Tr[0])) throw FactorizationFailedError("idto_hip: the dogleg step is not finite");
-    const double dL_dq = gdqs / cost;   // :2517-2524
-    // CalcTrustRatio (:2004-2034)
-    const double gradient_term = a * gg + b * gw;
-    const double hessian_term = 0.5 * (a * a * gHg + 2 * a * b * gHw + b * b * wHw);
-    const double predicted = -gradient_term - hessian_term, actual = cost - cost_trial;
-    const double eps = 10 * std::numeric_limits<double>::epsilon() / time_step_ / time_step_;
-    const double rho = (predicted < eps && actual < eps) ? 0.5 : actual / predicted;
-    if (!(dL_dq < std::numeric_limits<double>::epsilon()))
-      throw std::runtime_error("step is not a descent direction (TO.cc:2531)");
-    const double g_norm = std::sqrt(gg), h_norm = std::sqrt(hh), q_norm = std::sqrt(qq), dqH_norm = std::sqrt(ww);
-    last_accepted = rho > eta;
-    const double cost_k = cost;
-    if (last_accepted) {   // :2550-2553
+    const internal::TrustRatioScalars t = internal::CalcTrustRatioScalars(S, d.a, d.b, Tr[1], L->cost, cost_trial, time_step_);
+    if (!t.descent) throw std::runtime_error("step is not a descent direction (TO.cc:2531)");
+    const double g_norm = std::sqrt(S[0]), h_norm = std::sqrt(S[7]), q_norm = std::sqrt(S[6]), dqH_norm = std::sqrt(S[2]);
+    L->last_accepted = t.rho > args.eta;
+    const double cost_k = L->cost;
+    if (L->last_accepted) {   // :2550-2553
       Check(idto_hip_tr_accept(dev()));
-      cost = cost_trial;
+      L->cost = cost_trial;
       have = false;
     } else {
       Check(idto_hip_tr_reject(dev()));
@@ -1388,49 +1286,77 @@ SolverFlag TO::SolveOnDevice(WarmStart* ws, TrajectoryOptimizerSolution<T>* solu
     const double iter_time = std::chrono::duration<double>(clock::now() - iter_start).count();
     iter_start = clock::now();
     if (params_.verbose)
-      std::printf("| %6d | %8.3g | %7.2g | %7.3g | %10.5g | %10.5g | %10.4g | %10.4g |\n", k, cost_k, Delta, rho, iter_time,
-                  g_norm / cost_k, dL_dq, h_norm);
-    stats->push_data(iter_time, cost_k, 0, std::numeric_limits<double>::quiet_NaN(), Delta, q_norm, dq_norm, dqH_norm, rho,
-                     g_norm, dL_dq, h_norm, cost_k);   // :2586-2598 (merit = cost without constraints)
-    if (rho < 0.25) Delta *= 0.25;                                                   // :2614-2617
-    else if (rho > 0.75 && active) Delta = std::min(2 * Delta, params_.Delta_max);   // :2618-2622
-    ++k;
+      std::printf("| %6d | %8.3g | %7.2g | %7.3g | %10.5g | %10.5g | %10.4g | %10.4g |\n", L->k, cost_k, Delta, t.rho, iter_time,
+                  g_norm / cost_k, t.dL_dq, h_norm);
+    stats->push_data(iter_time, cost_k, 0, std::numeric_limits<double>::quiet_NaN(), Delta, q_norm, dq_norm, dqH_norm, t.rho,
+                     g_norm, t.dL_dq, h_norm, cost_k);   // :2586-2598 (merit = cost without constraints)
+    if (t.rho < 0.25) Delta *= 0.25;                                                     // :2614-2617
+    else if (t.rho > 0.75 && d.active) Delta = std::min(2 * Delta, params_.Delta_max);   // :2618-2622
+    ++L->k;
   }
+}
+
+SolverFlag TO::SolveOnDevice(WarmStart* ws, TrajectoryOptimizerSolution<T>* solution,
+                             TrajectoryOptimizerStats<T>* stats, ConvergenceReason* reason_out) const {
+  DeviceLoop L;
+  L.start = std::chrono::high_resolution_clock::now();
+  TrajectoryOptimizerState<T>& state = ws->state;
+  // ---- prologue: q, the unactuated dofs, the first evaluation, the adaptive scalings' memory
+  {
+    const Vec q0 = Flatten(state.q());
+    Check(idto_hip_set_q(dev(), q0.data()));
+  }
+  Check(idto_hip_set_unactuated_dofs(dev(), unactuated_dofs_.data(), (int)unactuated_dofs_.size()));
+  idto_hip_trace_mark("opt: q and the unactuated dofs set");
+  // the stepwise phase alone serves IDTO_OPT_STEPWISE=1 (and the adaptive scalings with dense cost weights)
+  const bool resident = ResidentLoopEligible();
+  // (the resident loop starts with the partials of this q: one finite-difference launch for both)
+  Check(resident ? idto_hip_eval_tau_partials(dev()) : idto_hip_eval_tau(dev()));
+  // (the resident loop keeps the cost on the device and reports it in its rows: no fetch, no synchronisation here)
+  if (!resident) L.cost = Fetch(IDTO_ARR_COST)[0];
+  const BatchLoopArgs args = LoopArgs();
+  // the adaptive scalings' memory of D belongs to the state (TO.cc:1241-1255 reads the cached scale
+  // factors): ones for a fresh state, the last solve's for a warm start - never the context's leftovers
+  if (AdaptiveScaling()) {
+    const Vec& Dmem = state.cache_.scale_factors;
+    Check(idto_hip_tr_set_scale_memory(dev(), (int)Dmem.size() == num_vars() ? Dmem.data() : nullptr));
+  }
+  if (params_.verbose) {
+    std::printf("-------------------------------------------------------------------------------------\n");
+    std::printf("|  iter  |   cost   |    Δ    |    ρ    |  time (s)  |  |g|/cost  |    dL_dq   |    |h|     |\n");
+    std::printf("-------------------------------------------------------------------------------------\n");
+  }
+  if (resident && ResidentPhase(ws, args, solution, stats, reason_out, &L)) return L.handed_over;
+  StepwisePhase(args, &ws->Delta, stats, &L);
   idto_hip_trace_mark("opt: statistics rows taken in");
-  // the solution: q from the device; v, tau belong to it unless the last trial point was rejected
+  // ---- epilogue: q from the device; v, tau belong to it unless the last trial point was rejected
   int two_sets = 0;   // (diagonal cost weights: the trial point was evaluated into the set the iterate does not occupy)
-  if (fetched) Check(idto_hip_get_option(dev(), "weights_diagonal", &two_sets));
-  fetched = fetched && (two_sets != 0 || last_accepted);
-  if (!fetched && !last_accepted) Check(idto_hip_eval_tau(dev()));
+  if (L.fetched) Check(idto_hip_get_option(dev(), "weights_diagonal", &two_sets));
+  L.fetched = L.fetched && (two_sets != 0 || L.last_accepted);
+  if (!L.fetched && !L.last_accepted) Check(idto_hip_eval_tau(dev()));
   // (the solution's arrays: with the resident loop's own wait - idto_hip_tr_solve_fetch - or with one synchronisation,
   // idto_hip_get_many)
-  {
-    Vec qf, vf, tf, dq, dqh;
-    if (fetched) {
-      qf.swap(fq); vf.swap(fv); tf.swap(ft); dq.swap(fdq); dqh.swap(fw);
-    } else {
-      qf.resize((std::size_t)num_vars()); vf.resize((std::size_t)(num_steps() + 1) * nv_); tf.resize((std::size_t)num_steps() * nv_);
-      dq.resize((std::size_t)num_vars()); dqh.resize((std::size_t)num_vars());
-      const int what[5] = {IDTO_ARR_Q, IDTO_ARR_V, IDTO_ARR_TAU, IDTO_ARR_TR_DQ, IDTO_ARR_TR_W};
-      double* const dst[5] = {qf.data(), vf.data(), tf.data(), dq.data(), dqh.data()};
-      Check(idto_hip_get_many(dev(), k > 0 ? 5 : 3, what, dst));
-    }
-    UnflattenInto(qf, num_steps() + 1, nq_, &solution->q);
-    state.set_q(solution->q);
-    UnflattenInto(vf, num_steps() + 1, nv_, &solution->v);
-    UnflattenInto(tf, num_steps(), nv_, &solution->tau);
-    if (k > 0) {
-      ws->dq = dq;
-      ws->dqH = dqh;
-      for (double& x : ws->dqH) x = -x;   // dqH = Delta pH = -w (:2152)
-    }
+  if (!L.fetched) {
+    L.q.resize((std::size_t)num_vars()); L.v.resize((std::size_t)(num_steps() + 1) * nv_); L.tau.resize((std::size_t)num_steps() * nv_);
+    L.dq.resize((std::size_t)num_vars()); L.w.resize((std::size_t)num_vars());
+    const int what[5] = {IDTO_ARR_Q, IDTO_ARR_V, IDTO_ARR_TAU, IDTO_ARR_TR_DQ, IDTO_ARR_TR_W};
+    double* const dst[5] = {L.q.data(), L.v.data(), L.tau.data(), L.dq.data(), L.w.data()};
+    Check(idto_hip_get_many(dev(), L.k > 0 ? 5 : 3, what, dst));
+  }
+  UnflattenInto(L.q.data(), num_steps() + 1, nq_, &solution->q);
+  state.set_q(solution->q);
+  UnflattenInto(L.v.data(), num_steps() + 1, nv_, &solution->v);
+  UnflattenInto(L.tau.data(), num_steps(), nv_, &solution->tau);
+  if (L.k > 0) {
+    ws->dq.swap(L.dq);
+    ws->dqH.swap(L.w);
+    for (double& x : ws->dqH) x = -x;   // dqH = Delta pH = -w (:2152)
   }
   idto_hip_trace_mark("opt: solution unpacked");
-  if (adaptive && k > 0) state.cache_.scale_factors = Fetch(IDTO_ARR_TR_SCALE);   // (kept across set_q: invalidate_cache)
-  resident_ = nullptr;   // the device arrays were advanced without the host-side cache
-  device_level_ = 0;
-  stats->solve_time = std::chrono::duration<double>(clock::now() - start_time).count();
-  if (k == params_.max_iterations) return SolverFlag::kMaxIterationsReached;
+  if (AdaptiveScaling() && L.k > 0) state.cache_.scale_factors = Fetch(IDTO_ARR_TR_SCALE);   // (kept across set_q: invalidate_cache)
+  InvalidateDevice();   // the device arrays were advanced without the host-side cache
+  stats->solve_time = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - L.start).count();
+  if (L.k == params_.max_iterations) return SolverFlag::kMaxIterationsReached;
   return SolverFlag::kSuccess;
 }
 
@@ -1465,6 +1391,12 @@ void ClearStats(TrajectoryOptimizerStats<double>* s) {
   s->trust_ratios.clear(); s->dL_dqs.clear(); s->h_norms.clear(); s->merits.clear();
 }
 void ClearSolution(TrajectoryOptimizerSolution<double>* s) { s->q.clear(); s->v.clear(); s->tau.clear(); }
+// entry b as before its solve: nothing of an earlier call's stays (the vectors keep their storage)
+void ClearEntry(TO::BatchSolveResult* out, int b) {
+  ClearStats(&out->stats[b]);
+  ClearSolution(&out->solutions[b]);
+  out->errors[b].clear();
+}
 }  // namespace
 
 TO::BatchContext* TO::GetBatchContext(int B, const std::vector<const ProblemDefinition*>& probs, const BatchPhysics* physics) const {
@@ -1475,29 +1407,15 @@ TO::BatchContext* TO::GetBatchContext(int B, const std::vector<const ProblemDefi
     bc.Delta0.resize(B); bc.Delta_out.resize(B); bc.final_cost.resize(B); bc.status.resize(B);
     bc.sol_q.resize(B * nqa); bc.sol_v.resize(B * nva); bc.sol_tau.resize(B * nta);
     // (created from the optimizer's own problem in every slot: each call uploads its problems anyway)
-    const Vec qn = Flatten(prob_.q_nom), vn = Flatten(prob_.v_nom);
-    idto_problem_t p = {};
-    p.num_steps = num_steps(); p.time_step = time_step_;
-    p.q_init = prob_.q_init.data(); p.v_init = prob_.v_init.data();
-    p.Qq = prob_.Qq.data(); p.Qv = prob_.Qv.data(); p.Qf_q = prob_.Qf_q.data(); p.Qf_v = prob_.Qf_v.data();
-    p.R = prob_.R.data(); p.q_nom = qn.data(); p.v_nom = vn.data();
-    std::vector<idto_problem_t> ps((std::size_t)B, p);
+    const ProblemView view(prob_, num_steps(), time_step_);
+    std::vector<idto_problem_t> ps((std::size_t)B, view.p);
     Check(idto_hip_create_batch_like(hip_, ps.data(), B, &bc.ctx));
     if (!std::getenv("IDTO_OPT_BLOCKING_UPLOADS")) Check(idto_hip_set_option(bc.ctx, "async_uploads", 1));
   }
   if ((int)bc.rows.size() < B * params_.max_iterations * IDTO_TR_ROW) bc.rows.resize((std::size_t)B * params_.max_iterations * IDTO_TR_ROW);
   for (int b = 0; b < B; ++b) {
-    const ProblemDefinition& pd = *probs[b];
-    for (int t = 0; t <= num_steps(); ++t) {
-      std::copy(pd.q_nom[t].begin(), pd.q_nom[t].end(), bc.q_nom.begin() + (std::size_t)t * nq_);
-      std::copy(pd.v_nom[t].begin(), pd.v_nom[t].end(), bc.v_nom.begin() + (std::size_t)t * nv_);
-    }
-    idto_problem_t p = {};
-    p.num_steps = num_steps(); p.time_step = time_step_;
-    p.q_init = pd.q_init.data(); p.v_init = pd.v_init.data();
-    p.Qq = pd.Qq.data(); p.Qv = pd.Qv.data(); p.Qf_q = pd.Qf_q.data(); p.Qf_v = pd.Qf_v.data();
-    p.R = pd.R.data(); p.q_nom = bc.q_nom.data(); p.v_nom = bc.v_nom.data();
-    Check(idto_hip_set_problem_batch(bc.ctx, b, &p));
+    const ProblemView view(*probs[b], num_steps(), time_step_, &bc.q_nom, &bc.v_nom);   // (the context's buffers: no allocation per entry)
+    Check(idto_hip_set_problem_batch(bc.ctx, b, &view.p));
     if (physics) Check(idto_hip_set_model_batch(bc.ctx, b, physics->models[b], physics->contacts[b]));
   }
   return &bc;
@@ -1505,24 +1423,17 @@ TO::BatchContext* TO::GetBatchContext(int B, const std::vector<const ProblemDefi
 
 void TO::SolveBatchEntryAlone(const ProblemDefinition* prob, const std::vector<VectorXd>& q_guess, int b,
                               BatchSolveResult* out) const {
-  ClearStats(&out->stats[b]);
-  ClearSolution(&out->solutions[b]);
-  out->errors[b].clear();
+  ClearEntry(out, b);
   out->final_costs[b] = std::numeric_limits<double>::quiet_NaN();
   out->flags[b] = SolverFlag::kFactorizationFailed;
   try {
-    if (prob) {
-      UploadProblemDefinition(*prob);
-      resident_ = nullptr;
-      device_level_ = 0;
-    }
+    if (prob) UploadProblemDefinition(*prob);
     out->flags[b] = Solve(q_guess, &out->solutions[b], &out->stats[b]);
     if (Usable(out->flags[b])) {
       TrajectoryOptimizerState<T> state = CreateState();
       state.set_q(out->solutions[b].q);
       out->final_costs[b] = EvalCost(state);
-      resident_ = nullptr;   // (`state` goes out of scope)
-      device_level_ = 0;
+      InvalidateDevice();   // (`state` goes out of scope)
     } else if (out->flags[b] == SolverFlag::kFactorizationFailed) {
       out->errors[b] = "idto_hip: factorisation failed";
       ClearSolution(&out->solutions[b]);
@@ -1566,6 +1477,33 @@ std::string TO::LinesearchBatchRefusal(int B, const std::vector<const ProblemDef
   return "";
 }
 
+void TO::PackGuesses(BatchContext* bc, const std::vector<std::vector<VectorXd>>& q_guesses) const {
+  double* dst = bc->q.data();
+  for (const std::vector<VectorXd>& guess : q_guesses)
+    for (const VectorXd& qt : guess) dst = std::copy(qt.begin(), qt.end(), dst);
+  Check(idto_hip_set_q_batch(bc->ctx, bc->q.data()));
+}
+
+void TO::TakeEntry(int b, int slot, internal::RowsOutcome outcome, SolverFlag flag, const std::string& error, const BatchContext& bc,
+                   const BatchPhysics* physics, BatchSolveResult* out, std::vector<char>* alone) const {
+  using internal::RowsOutcome;
+  out->flags[b] = flag;
+  out->final_costs[b] = bc.final_cost[b];
+  if (outcome == RowsOutcome::kNeedsHostLoop && !physics) { (*alone)[b] = 1; return; }
+  if (outcome != RowsOutcome::kDone) {   // the entry's own failure (with per-entry models no context holds this entry's model alone)
+    out->flags[b] = SolverFlag::kFactorizationFailed;
+    out->errors[b] = outcome != RowsOutcome::kNeedsHostLoop ? error
+                         : "the batch loop left this entry to the host loop, which a batch with per-entry models does not have";
+    out->final_costs[b] = std::numeric_limits<double>::quiet_NaN();
+    return;
+  }
+  if (slot < 0) return;
+  const std::size_t nqa = (std::size_t)num_vars(), nva = (std::size_t)(num_steps() + 1) * nv_, nta = (std::size_t)num_steps() * nv_;
+  UnflattenInto(bc.sol_q.data() + slot * nqa, num_steps() + 1, nq_, &out->solutions[b].q);
+  UnflattenInto(bc.sol_v.data() + slot * nva, num_steps() + 1, nv_, &out->solutions[b].v);
+  UnflattenInto(bc.sol_tau.data() + slot * nta, num_steps(), nv_, &out->solutions[b].tau);
+}
+
 void TO::SolveBatchImpl(const std::vector<std::vector<VectorXd>>& q_guesses, const std::vector<ProblemDefinition>* problems,
                         const BatchPhysics* physics, BatchSolveResult* out, bool only_best) const {
   using clock = std::chrono::high_resolution_clock;
@@ -1585,90 +1523,60 @@ void TO::SolveBatchImpl(const std::vector<std::vector<VectorXd>>& q_guesses, con
   out->best = -1;
   const auto start_time = clock::now();
 
-  // which route: the device's batch loop serves what the resident single-problem loop serves, except ...
-  const bool constrained = params_.equality_constraints && num_equality_constraints() > 0;
-  const int scal = params_.scaling ? static_cast<int>(params_.scaling_method) : -1;
-  // ... the adaptive scalings (a batch context's memory of D cannot be set: idto_hip_tr_set_scale_memory serves
-  // single-problem contexts, and a context kept per B would start from the previous call's D instead of ones),
-  const bool adaptive = scal == static_cast<int>(kAdaptiveSqrt) || scal == static_cast<int>(kAdaptiveDoubleSqrt);
-  // ... dense cost weights (the batch loop runs on the two-set evaluation), several devices, and the per-iteration table
-  bool batch_route = B >= 2 && params_.method == kTrustRegion && shard_ctx_.empty() && !adaptive && !params_.verbose &&
-                     DeviceLoopEligible() && ResidentLoopEligible();
-  for (int b = 0; batch_route && b < B; ++b) batch_route = DiagonalWeights(*probs[b]);
+  // ---- which route.  The device's trust-region batch loop serves what the resident single-problem loop serves, except
+  // the adaptive scalings (a batch context's memory of D cannot be set: idto_hip_tr_set_scale_memory serves single-problem
+  // contexts, and a context kept per B would start from the previous call's D instead of ones), dense cost weights (the
+  // batch loop runs on the two-set evaluation), several devices, and the per-iteration table.
+  // Its batch linesearch loop (idto_hip_ls_solve_batch_fetch) serves what the single problem's device loop serves
+  // (LinesearchLoopEligible: scaling off, no enforced constraints, the banded solver, no debug switches, at most
+  // IDTO_LS_MAX_CANDIDATES linesearch iterations, no forced host loop) on one device with verbose off and diagonal weights
+  // in every entry.  Everything else: entry by entry.
+  bool batch = B >= 2 && shard_ctx_.empty() && !params_.verbose;
+  for (int b = 0; batch && b < B; ++b) batch = DiagonalWeights(*probs[b]);
+  const bool tr_route = batch && params_.method == kTrustRegion && !AdaptiveScaling() && DeviceLoopEligible() && ResidentLoopEligible();
+  const bool ls_route = batch && params_.method == kLinesearch && LinesearchLoopEligible();
   if (physics) {
     // per-entry models: no entry-by-entry route.  Every refusal here, before any device work, by name.
     const char* who = "SolveBatch with per-entry models has no entry-by-entry route and the batch loops do not serve ";
     std::string why = params_.method == kTrustRegion ? BatchLoopRefusal(B, probs) : LinesearchBatchRefusal(B, probs);
-    if (why.empty() && params_.method == kTrustRegion && !batch_route) why = "this configuration (the device's resident loop is not eligible)";
+    if (why.empty() && params_.method == kTrustRegion && !tr_route) why = "this configuration (the device's resident loop is not eligible)";
     if (!why.empty()) throw std::invalid_argument(who + why);
     for (int b = 0; b < B; ++b)
       if (idto_hip_check_model_batch(hip_, b, physics->models[b], physics->contacts[b]) != 0)
         throw std::invalid_argument(std::string("SolveBatch: ") + idto_hip_last_error());
   }
 
-  std::vector<char> alone((std::size_t)B, batch_route ? 0 : 1);
-  if (batch_route) {
+  // ---- the route.  A loop that ran takes every entry (loop_ran) but those it leaves to the host loop; a loop that timed
+  // out on a shared device leaves all of them alone.
+  std::vector<char> alone((std::size_t)B, 1);
+  bool loop_ran = false;
+  if (tr_route) {
     BatchContext* bc = GetBatchContext(B, probs, physics);
     int resident_ok = 1;
     Check(idto_hip_get_option(bc->ctx, "tr_resident_ok", &resident_ok));
-    const std::size_t nqa = (std::size_t)num_vars(), nva = (std::size_t)(num_steps() + 1) * nv_, nta = (std::size_t)num_steps() * nv_;
-    const int iters = params_.max_iterations;
+    const BatchLoopArgs a = LoopArgs();
     int rc = -1, best_dev = -1;
     if (resident_ok) {
-      for (int b = 0; b < B; ++b)
-        for (int t = 0; t <= num_steps(); ++t)
-          std::copy(q_guesses[b][t].begin(), q_guesses[b][t].end(), bc->q.begin() + b * nqa + (std::size_t)t * nq_);
-      Check(idto_hip_set_q_batch(bc->ctx, bc->q.data()));
+      PackGuesses(bc, q_guesses);
       Check(idto_hip_set_unactuated_dofs(bc->ctx, unactuated_dofs_.data(), (int)unactuated_dofs_.size()));
       Check(idto_hip_eval_tau(bc->ctx));
-      if (params_.check_convergence) {
-        const auto& t = params_.convergence_tolerances;
-        const double tol[6] = {t.rel_cost_reduction, t.abs_cost_reduction, t.rel_gradient_along_dq, t.abs_gradient_along_dq,
-                               t.rel_state_change, t.abs_state_change};
-        Check(idto_hip_tr_set_convergence(bc->ctx, tol));
-      } else {
-        Check(idto_hip_tr_set_convergence(bc->ctx, nullptr));
-      }
+      SetConvergence(bc->ctx);
       std::fill(bc->Delta0.begin(), bc->Delta0.end(), params_.Delta0);
-      rc = idto_hip_tr_solve_batch_fetch(bc->ctx, iters, scal, params_.scaling ? 1 : 0, params_.normalize_quaternions ? 1 : 0,
-                                         bc->Delta0.data(), params_.Delta_max, 0.0, constrained ? unactuated_dofs_.data() : nullptr,
-                                         constrained ? (int)unactuated_dofs_.size() : 0, bc->rows.data(), bc->Delta_out.data(),
+      rc = idto_hip_tr_solve_batch_fetch(bc->ctx, a.iterations, a.scaling_method, a.scaling, a.normalize_quaternions, bc->Delta0.data(),
+                                         a.Delta_max, a.eta, a.constrained_dofs, a.nu, bc->rows.data(), bc->Delta_out.data(),
                                          only_best ? 1 : 0, bc->sol_q.data(), bc->sol_v.data(), bc->sol_tau.data(), nullptr, nullptr,
                                          bc->final_cost.data(), bc->status.data(), &best_dev);
     }
     if (rc == 0 || rc == IDTO_HIP_FACTORIZATION_FAILED) {
+      loop_ran = true;
+      std::fill(alone.begin(), alone.end(), 0);
       const double total = std::chrono::duration<double>(clock::now() - start_time).count();
       for (int b = 0; b < B; ++b) {
-        ClearStats(&out->stats[b]);
-        ClearSolution(&out->solutions[b]);
-        out->errors[b].clear();
+        ClearEntry(out, b);
         internal::BatchRowsResult r;
-        internal::RowsToStats(bc->rows.data() + (std::size_t)b * iters * IDTO_TR_ROW, iters, bc->Delta_out[b], total, params_,
-                              &out->stats[b], &r);
-        out->flags[b] = r.flag;
-        out->final_costs[b] = bc->final_cost[b];
-        if (r.outcome == internal::RowsOutcome::kNeedsHostLoop && physics) {   // (no context holds this entry's model alone)
-          out->flags[b] = SolverFlag::kFactorizationFailed;
-          out->errors[b] = "the batch loop left this entry to the host loop, which a batch with per-entry models does not have";
-          out->final_costs[b] = std::numeric_limits<double>::quiet_NaN();
-          continue;
-        }
-        if (r.outcome == internal::RowsOutcome::kNeedsHostLoop) { alone[b] = 1; continue; }
-        if (r.outcome != internal::RowsOutcome::kDone) {
-          out->flags[b] = SolverFlag::kFactorizationFailed;
-          out->errors[b] = r.error;
-          out->final_costs[b] = std::numeric_limits<double>::quiet_NaN();
-          continue;
-        }
-        const int slot = only_best ? (b == best_dev ? 0 : -1) : b;
-        if (slot < 0) continue;
-        Vec tmp;
-        tmp.assign(bc->sol_q.begin() + slot * nqa, bc->sol_q.begin() + (slot + 1) * nqa);
-        UnflattenInto(tmp, num_steps() + 1, nq_, &out->solutions[b].q);
-        tmp.assign(bc->sol_v.begin() + slot * nva, bc->sol_v.begin() + (slot + 1) * nva);
-        UnflattenInto(tmp, num_steps() + 1, nv_, &out->solutions[b].v);
-        tmp.assign(bc->sol_tau.begin() + slot * nta, bc->sol_tau.begin() + (slot + 1) * nta);
-        UnflattenInto(tmp, num_steps(), nv_, &out->solutions[b].tau);
+        internal::RowsToStats(bc->rows.data() + (std::size_t)b * a.iterations * IDTO_TR_ROW, a.iterations, bc->Delta_out[b], total,
+                              params_, &out->stats[b], &r);
+        TakeEntry(b, only_best ? (b == best_dev ? 0 : -1) : b, r.outcome, r.flag, r.error, *bc, physics, out, &alone);
       }
     } else if (!resident_ok || rc == IDTO_HIP_SOLVER_TIMEOUT ||
                (rc == -1 && std::strstr(idto_hip_last_error(), "child-context route"))) {
@@ -1676,26 +1584,13 @@ void TO::SolveBatchImpl(const std::vector<std::vector<VectorXd>>& q_guesses, con
       if (physics) throw std::runtime_error(std::string("SolveBatch with per-entry models: the batch loop did not run (") +
                                             (resident_ok ? idto_hip_last_error() : "the context's resident loop is off after a time-out") +
                                             ") and there is no entry-by-entry route");
-      batch_route = false;
-      std::fill(alone.begin(), alone.end(), 1);
     } else {
       Check(rc);
     }
-  }
-  // The linesearch method: the device's batch linesearch loop (idto_hip_ls_solve_batch_fetch: every iteration of every entry
-  // enqueued at once, one wait) serves what the single problem's device loop serves (LinesearchLoopEligible: scaling off,
-  // no enforced constraints, the banded solver, no debug switches, at most IDTO_LS_MAX_CANDIDATES linesearch iterations, no
-  // forced host loop) on one device with verbose off and diagonal weights in every entry.
-  bool ls_route = B >= 2 && params_.method == kLinesearch && shard_ctx_.empty() && !params_.verbose && LinesearchLoopEligible();
-  for (int b = 0; ls_route && b < B; ++b) ls_route = DiagonalWeights(*probs[b]);
-  if (ls_route) {
+  } else if (ls_route) {
     BatchContext* bc = GetBatchContext(B, probs, physics);
-    const std::size_t nqa = (std::size_t)num_vars(), nva = (std::size_t)(num_steps() + 1) * nv_, nta = (std::size_t)num_steps() * nv_;
     const int iters = params_.max_iterations;
-    for (int b = 0; b < B; ++b)
-      for (int t = 0; t <= num_steps(); ++t)
-        std::copy(q_guesses[b][t].begin(), q_guesses[b][t].end(), bc->q.begin() + b * nqa + (std::size_t)t * nq_);
-    Check(idto_hip_set_q_batch(bc->ctx, bc->q.data()));
+    PackGuesses(bc, q_guesses);
     Check(idto_hip_set_unactuated_dofs(bc->ctx, unactuated_dofs_.data(), (int)unactuated_dofs_.size()));
     static_assert(IDTO_LS_ROW <= IDTO_TR_ROW, "GetBatchContext sizes the rows for the trust-region loop's");
     const int rc = idto_hip_ls_solve_batch_fetch(bc->ctx, iters, static_cast<int>(params_.linesearch_method),
@@ -1704,41 +1599,18 @@ void TO::SolveBatchImpl(const std::vector<std::vector<VectorXd>>& q_guesses, con
                                                  bc->final_cost.data(), bc->status.data());
     idto_hip_trace_mark("opt: idto_hip_ls_solve_batch_fetch returned");
     if (rc == 0 || rc == IDTO_HIP_FACTORIZATION_FAILED) {
+      loop_ran = true;
       std::fill(alone.begin(), alone.end(), 0);
       const double total = std::chrono::duration<double>(clock::now() - start_time).count();
       for (int b = 0; b < B; ++b) {
-        ClearStats(&out->stats[b]);
-        ClearSolution(&out->solutions[b]);
-        out->errors[b].clear();
+        ClearEntry(out, b);
         internal::LsRowsResult r;
         internal::LsRowsToStats(bc->rows.data() + (std::size_t)b * iters * IDTO_LS_ROW, iters, total, params_.linesearch_method,
                                 &out->stats[b], &r);
-        out->flags[b] = r.flag;
-        out->final_costs[b] = bc->final_cost[b];
-        // (backtracking undecided within the device's candidates: the entry is solved again alone, where the host loop takes over)
-        if (r.outcome == internal::LsRowsOutcome::kNeedsHostLoop && physics) {   // (no context holds this entry's model alone)
-          out->flags[b] = SolverFlag::kFactorizationFailed;
-          out->errors[b] = "the batch loop left this entry to the host loop, which a batch with per-entry models does not have";
-          out->final_costs[b] = std::numeric_limits<double>::quiet_NaN();
-          continue;
-        }
-        if (r.outcome == internal::LsRowsOutcome::kNeedsHostLoop) { alone[b] = 1; continue; }
-        if (r.outcome != internal::LsRowsOutcome::kDone) {   // the entry's own failure, with the host loop's text
-          out->flags[b] = SolverFlag::kFactorizationFailed;
-          out->errors[b] = r.error;
-          out->final_costs[b] = std::numeric_limits<double>::quiet_NaN();
-          continue;
-        }
+        // (kNeedsHostLoop here: backtracking undecided within the device's candidates - the entry is solved again alone)
+        TakeEntry(b, b, r.outcome, r.flag, r.error, *bc, physics, out, &alone);
         if (!Usable(r.flag)) out->final_costs[b] = std::numeric_limits<double>::quiet_NaN();   // (kLinesearchMaxIters: as the entry alone)
-        Vec tmp;
-        tmp.assign(bc->sol_q.begin() + b * nqa, bc->sol_q.begin() + (b + 1) * nqa);
-        UnflattenInto(tmp, num_steps() + 1, nq_, &out->solutions[b].q);
-        tmp.assign(bc->sol_v.begin() + b * nva, bc->sol_v.begin() + (b + 1) * nva);
-        UnflattenInto(tmp, num_steps() + 1, nv_, &out->solutions[b].v);
-        tmp.assign(bc->sol_tau.begin() + b * nta, bc->sol_tau.begin() + (b + 1) * nta);
-        UnflattenInto(tmp, num_steps(), nv_, &out->solutions[b].tau);
       }
-      batch_route = true;
     } else if (rc == IDTO_HIP_SOLVER_TIMEOUT) {
       // a solver launch's workgroups timed out on a shared device: every entry runs alone (alone[] says so already)
       if (physics) throw std::runtime_error(std::string("SolveBatch with per-entry models: the batch linesearch loop timed out (") +
@@ -1747,7 +1619,7 @@ void TO::SolveBatchImpl(const std::vector<std::vector<VectorXd>>& q_guesses, con
       Check(rc);
     }
   }
-  last_batch_route_ = batch_route ? 1 : 0;
+  last_batch_route_ = loop_ran ? 1 : 0;
   for (int b = 0; b < B; ++b)
     if (alone[b]) SolveBatchEntryAlone(problems ? probs[b] : nullptr, q_guesses[b], b, out);
 
@@ -1766,9 +1638,7 @@ void TO::SolveBatchImpl(const std::vector<std::vector<VectorXd>>& q_guesses, con
 std::string TO::BatchLoopRefusal(int B, const std::vector<const ProblemDefinition*>& probs) const {
   if (B < 2) return "B < 2 (a batch of fewer than two controllers)";
   if (params_.method != kTrustRegion) return "method = kLinesearch";
-  const int scal = params_.scaling ? static_cast<int>(params_.scaling_method) : -1;
-  if (scal == static_cast<int>(kAdaptiveSqrt) || scal == static_cast<int>(kAdaptiveDoubleSqrt))
-    return "adaptive scalings (scaling_method = kAdaptiveSqrt / kAdaptiveDoubleSqrt)";
+  if (AdaptiveScaling()) return "adaptive scalings (scaling_method = kAdaptiveSqrt / kAdaptiveDoubleSqrt)";
   if (!shard_ctx_.empty()) return "several devices";
   if (params_.verbose) return "verbose";
   if (DenseLinearSolver()) return "linear_solver = kDenseLdlt";
@@ -1777,7 +1647,7 @@ std::string TO::BatchLoopRefusal(int B, const std::vector<const ProblemDefinitio
   if (params_.max_iterations <= 0) return "max_iterations <= 0";
   for (const ProblemDefinition* p : probs)
     if (!DiagonalWeights(*p)) return "dense weights (a cost weight matrix that is not diagonal)";
-  if (params_.equality_constraints && num_equality_constraints() > 0) {
+  if (Constrained()) {
     const char* e = std::getenv("IDTO_CON_KKT");   // (what a context reads at creation: option "con_kkt")
     if ((e && e[0] != '1') || idto_host::SolverBlockSize(nq_ + (int)unactuated_dofs_.size(), true) > 30)
       return "the child-context constraint route (enforced constraints with nq + nu > 30, or option con_kkt = 0)";
@@ -1793,40 +1663,37 @@ idto_hip_ctx* TO::CreateBatchContext(const std::vector<const ProblemDefinition*>
   for (int b = 0; b < B; ++b) {
     const ProblemDefinition& pd = *probs[b];
     CheckBatchProblem(pd, b);
-    qn[b] = Flatten(pd.q_nom); vn[b] = Flatten(pd.v_nom);
-    idto_problem_t p = {};
-    p.num_steps = num_steps(); p.time_step = time_step_;
-    p.q_init = pd.q_init.data(); p.v_init = pd.v_init.data();
-    p.Qq = pd.Qq.data(); p.Qv = pd.Qv.data(); p.Qf_q = pd.Qf_q.data(); p.Qf_v = pd.Qf_v.data();
-    p.R = pd.R.data(); p.q_nom = qn[b].data(); p.v_nom = vn[b].data();
-    ps[b] = p;
+    ps[b] = ProblemView(pd, num_steps(), time_step_, &qn[b], &vn[b]).p;
   }
   idto_hip_ctx* ctx = nullptr;
   Check(idto_hip_create_batch_like(dev(), ps.data(), B, &ctx));
   return ctx;
 }
 
-TO::BatchLoopArgs TO::PrepareBatchLoop(idto_hip_ctx* ctx) const {
-  Check(idto_hip_set_unactuated_dofs(ctx, unactuated_dofs_.data(), (int)unactuated_dofs_.size()));
-  if (params_.check_convergence) {
-    const auto& t = params_.convergence_tolerances;
-    const double tol[6] = {t.rel_cost_reduction, t.abs_cost_reduction, t.rel_gradient_along_dq, t.abs_gradient_along_dq,
-                           t.rel_state_change, t.abs_state_change};
-    Check(idto_hip_tr_set_convergence(ctx, tol));
-  } else {
-    Check(idto_hip_tr_set_convergence(ctx, nullptr));
-  }
-  const bool constrained = params_.equality_constraints && num_equality_constraints() > 0;
+void TO::SetConvergence(idto_hip_ctx* ctx) const {
+  const auto& t = params_.convergence_tolerances;
+  const double tol[6] = {t.rel_cost_reduction, t.abs_cost_reduction, t.rel_gradient_along_dq, t.abs_gradient_along_dq,
+                         t.rel_state_change, t.abs_state_change};
+  Check(idto_hip_tr_set_convergence(ctx, params_.check_convergence ? tol : nullptr));
+}
+
+TO::BatchLoopArgs TO::LoopArgs() const {
   BatchLoopArgs a;
   a.iterations = params_.max_iterations;
   a.scaling_method = params_.scaling ? static_cast<int>(params_.scaling_method) : -1;
   a.scaling = params_.scaling ? 1 : 0;
   a.normalize_quaternions = params_.normalize_quaternions ? 1 : 0;
   a.Delta_max = params_.Delta_max;
-  a.eta = 0.0;
-  a.constrained_dofs = constrained ? unactuated_dofs_.data() : nullptr;
-  a.nu = constrained ? (int)unactuated_dofs_.size() : 0;
+  a.eta = 0.0;   // trust ratio threshold (TO.cc:2466)
+  a.constrained_dofs = Constrained() ? unactuated_dofs_.data() : nullptr;
+  a.nu = Constrained() ? (int)unactuated_dofs_.size() : 0;
   return a;
+}
+
+TO::BatchLoopArgs TO::PrepareBatchLoop(idto_hip_ctx* ctx) const {
+  Check(idto_hip_set_unactuated_dofs(ctx, unactuated_dofs_.data(), (int)unactuated_dofs_.size()));
+  SetConvergence(ctx);
+  return LoopArgs();
 }
 
 SolverFlag TO::SolveFromWarmStartImpl(WarmStart* ws, TrajectoryOptimizerSolution<T>* solution,

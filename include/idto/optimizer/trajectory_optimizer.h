@@ -29,6 +29,7 @@
 // the 2-DoF toy examples' figures, TO.cc:1650-1830) are not produced: the constructor throws if one is set.
 #pragma once
 
+#include <chrono>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -51,6 +52,7 @@ namespace internal {
 // S x = b for the symmetric positive (semi-)definite Schur complement of the multipliers
 // (column-major, lower triangle read, overwritten): LDL^T with diagonal pivoting (TO.cc:1395).
 void DenseLdltSolve(std::vector<double>* S, int n, double* b);
+enum class RowsOutcome;   // how a device loop's statistics rows ended (csrc/host/batch_rows.h)
 }  // namespace internal
 
 template <typename T>
@@ -203,6 +205,12 @@ class TrajectoryOptimizer<double> {
   BatchContext* GetBatchContext(int B, const std::vector<const ProblemDefinition*>& probs, const BatchPhysics* physics = nullptr) const;
   void SolveBatchImpl(const std::vector<std::vector<VectorXd>>& q_guesses, const std::vector<ProblemDefinition>* problems,
                       const BatchPhysics* physics, BatchSolveResult* out, bool only_best) const;
+  // the two batch loops' shared steps: the guesses into bc->q, and entry b of a loop that ran into `out` (its outcome as the
+  // rows unit reports it; slot: where its solution lies in bc's arrays, -1: not fetched; an entry left to the host loop is
+  // marked in `alone`, or fails by name when per-entry models leave no context to run it on)
+  void PackGuesses(BatchContext* bc, const std::vector<std::vector<VectorXd>>& q_guesses) const;
+  void TakeEntry(int b, int slot, internal::RowsOutcome outcome, SolverFlag flag, const std::string& error, const BatchContext& bc,
+                 const BatchPhysics* physics, BatchSolveResult* out, std::vector<char>* alone) const;
   std::string LinesearchBatchRefusal(int B, const std::vector<const ProblemDefinition*>& probs) const;
   void CheckBatchProblem(const ProblemDefinition& p, int b) const;
   // entry b of a batch solved alone on this optimizer's own context (the fallback of SolveBatch)
@@ -238,8 +246,31 @@ class TrajectoryOptimizer<double> {
                                      TrajectoryOptimizerStats<T>* stats) const;
   bool DeviceLoopEligible() const;
   bool ResidentLoopEligible() const;
+  // SolveOnDevice: prologue (q, first evaluation), ResidentPhase (every iteration enqueued at once), StepwisePhase (two
+  // returns to the host per iteration: IDTO_OPT_STEPWISE, or what a truncated resident run left over), epilogue (the
+  // solution's arrays).  What crosses between them:
+  struct DeviceLoop {
+    std::chrono::high_resolution_clock::time_point start;
+    int k = 0;                    // iterations completed
+    double cost = 0.0;            // L(q_k) (the stepwise phase's; the resident loop keeps it on the device)
+    bool last_accepted = true, converged = false;
+    bool fetched = false;         // q, v, tau, dq, w are the final iterate's, brought along by idto_hip_tr_solve_fetch
+    std::vector<double> q, v, tau, dq, w;
+    SolverFlag handed_over = SolverFlag::kSuccess;   // ResidentPhase returned true: what the host loop made of the rest
+  };
+  bool ResidentPhase(WarmStart* warm_start, const BatchLoopArgs& args, TrajectoryOptimizerSolution<T>* solution,
+                     TrajectoryOptimizerStats<T>* stats, ConvergenceReason* reason, DeviceLoop* loop) const;
+  void StepwisePhase(const BatchLoopArgs& args, double* Delta, TrajectoryOptimizerStats<T>* stats, DeviceLoop* loop) const;
   SolverFlag SolveOnDevice(WarmStart* warm_start, TrajectoryOptimizerSolution<T>* solution,
                            TrajectoryOptimizerStats<T>* stats, ConvergenceReason* reason) const;
+  // what the device's trust-region loops are told, in one place
+  bool AdaptiveScaling() const {
+    return params_.scaling && (params_.scaling_method == kAdaptiveSqrt || params_.scaling_method == kAdaptiveDoubleSqrt);
+  }
+  bool Constrained() const { return params_.equality_constraints && num_equality_constraints() > 0; }
+  BatchLoopArgs LoopArgs() const;
+  void SetConvergence(idto_hip_ctx* ctx) const;   // VerifyConvergenceCriteria's tolerances, or none (check_convergence off)
+  void InvalidateDevice() const { resident_ = nullptr; device_level_ = 0; }   // no state's results are on the device any more
   void AdoptTrialPoint(const TrajectoryOptimizerState<T>& scratch, TrajectoryOptimizerState<T>* state) const;
   ConvergenceReason VerifyConvergenceCriteria(const TrajectoryOptimizerState<T>& state, T previous_cost,
                                               const VectorXd& dq) const;

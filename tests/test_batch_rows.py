@@ -3,7 +3,10 @@ convergence reason, the radius to keep and a SolverFlag - on the CPU.
 
 tests/cpp/batch_rows_check.cc is a stand-alone program: compiled here together with the unit by g++ with the address and
 undefined-behaviour sanitizers, then run on hand-written rows (all accepted, a rejected last row, a converged row followed
-by idle rows, each flag, zero iterations).  The same file checks that the batch entry points exist at every layer:
+by idle rows, each flag, zero iterations; what the single problem's driver reads besides: whether a reason was reported, the
+cost of the iterate behind the last row) and holds the stepwise loop's scalars of the same unit - the dogleg step against a
+restatement on vectors in each of its three branches, the trust ratio with its eps rule and the descent test's boundary - to
+hand-computed values.  The same file checks that the batch entry points exist at every layer:
 idto_hip_tr_solve_batch_fetch, idto_opt_solve_batch, TrajectoryOptimizer.solve_batch.
 """
 import ctypes as C

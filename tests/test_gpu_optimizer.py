@@ -493,3 +493,42 @@ def test_convergence_criteria_inside_the_device_loop(name, tols, constrained, mo
         assert n_ref == sp.max_iterations and out[False][2] == "kMaxIterationsReached"
     assert np.array_equal(out[False][1].trust_region_radii, out[True][1].trust_region_radii) or \
         np.allclose(out[False][1].trust_region_radii, out[True][1].trust_region_radii, rtol=1e-12)
+
+
+def test_verbose_table_of_the_resident_loop_is_the_stats_series(capfd, monkeypatch):
+    """verbose on the device-resident loop (acrobot, N = 10, four iterations): one line per iteration between the rules, every
+    column but the time the corresponding TrajectoryOptimizerStats series in the driver's format - and the stepwise loop
+    (IDTO_OPT_STEPWISE=1), whose iterates are the same bits, prints the same lines apart from the time."""
+    import ctypes
+    libc = ctypes.CDLL(None)   # (the driver prints through C stdio, which buffers when stdout is not a terminal)
+    cfg, model = load_config("acrobot"), load_model("acrobot")
+    prob, sp, q_guess = make_problem(cfg, model, num_steps=10)
+    sp.equality_constraints = False
+    sp.max_iterations, sp.verbose = 4, True
+    tables = {}
+    for stepwise in (False, True):
+        if stepwise:
+            monkeypatch.setenv("IDTO_OPT_STEPWISE", "1")
+        else:
+            monkeypatch.delenv("IDTO_OPT_STEPWISE", raising=False)
+        opt = TrajectoryOptimizer(model, prob, sp)
+        libc.fflush(None)
+        capfd.readouterr()
+        sol, st, flag = solve(opt, q_guess)
+        libc.fflush(None)
+        lines = [ln for ln in capfd.readouterr().out.splitlines() if ln.strip()]
+        opt.close()
+        rules = [i for i, ln in enumerate(lines) if set(ln) == {"-"}]
+        assert len(rules) == 2 and rules[0] == 0 and rules[1] == 2 and "iter" in lines[1], lines
+        data = lines[3:]
+        assert len(data) == 4 and st.iteration_costs.size == 4 and flag == "kMaxIterationsReached", lines
+        cells = [[c for c in ln.strip().strip("|").split("|")] for ln in data]
+        for k, row in enumerate(cells):
+            expect = "| %6d | %8.3g | %7.2g | %7.3g | %10.5g | %10.5g | %10.4g | %10.4g |" % (
+                k, st.iteration_costs[k], st.trust_region_radii[k], st.trust_ratios[k], 0.0,
+                st.gradient_norms[k] / st.iteration_costs[k], st.dL_dqs[k], st.h_norms[k])
+            want = expect.strip().strip("|").split("|")
+            assert len(row) == 8 and row[:4] == want[:4] and row[5:] == want[5:], (k, data[k], expect)
+            assert float(row[4]) > 0
+        tables[stepwise] = [row[:4] + row[5:] for row in cells]
+    assert tables[False] == tables[True]

@@ -11,6 +11,7 @@
 #include "idto/examples/mpc_controller.h"
 #include "idto/optimizer/trajectory_optimizer.h"
 #include "mpc_spline.h"
+#include "plant_step.h"
 
 using namespace idto::optimizer;
 
@@ -424,6 +425,76 @@ int idto_mpc_batch_update(idto_mpc_batch* mpc, const double* times, const double
 static void CheckController(const idto_mpc_batch* mpc, int b) {
   if (b < 0 || b >= mpc->mpc->num_controllers()) throw std::runtime_error("mpc_batch: controller index outside the batch");
 }
+// the outputs of a tick, as idto_mpc_batch_update hands them out
+static void BatchTickOutputs(idto_mpc_batch* mpc, double* q_guess, double* sol_q, double* sol_v, double* sol_tau, idto_stats_t* stats,
+                             int* flags, double* radii) {
+  const idto_opt* o = mpc->opt;
+  const int B = mpc->mpc->num_controllers();
+  const size_t nqa = (size_t)(o->N + 1) * o->nq, nva = (size_t)(o->N + 1) * o->nv, nta = (size_t)o->N * o->nv;
+  for (int b = 0; b < B; ++b) {
+    if (q_guess) Flat(mpc->mpc->last_guess(b), q_guess + b * nqa);
+    const auto& sol = mpc->mpc->last_solution(b);
+    Flat(sol.q, sol_q ? sol_q + b * nqa : nullptr);
+    Flat(sol.v, sol_v ? sol_v + b * nva : nullptr);
+    Flat(sol.tau, sol_tau ? sol_tau + b * nta : nullptr);
+    if (stats) FillStats(mpc->mpc->last_stats(b), &stats[b]);
+    if (flags) flags[b] = (int)mpc->mpc->last_flag(b);
+    if (radii) radii[b] = mpc->mpc->trust_region_radius(b);
+  }
+}
+int idto_mpc_batch_plants_begin(idto_mpc_batch* mpc, double sim_time_step, const double* Kp, int kp_size, const double* Kd, int kd_size,
+                                int feed_forward, int record_capacity) {
+  return Guard([&] {
+    idto::examples::mpc::BatchModelPredictiveController::PlantParams p;
+    p.sim_time_step = sim_time_step; p.feed_forward = feed_forward != 0; p.record_capacity = record_capacity;
+    if (Kp && kp_size > 0) p.Kp.assign(Kp, Kp + kp_size);
+    if (Kd && kd_size > 0) p.Kd.assign(Kd, Kd + kd_size);
+    mpc->mpc->BeginPlants(p);
+  });
+}
+int idto_mpc_batch_plants_set_model(idto_mpc_batch* mpc, int b, const idto_model_t* model, const idto_contact_params_t* contact) {
+  return Guard([&] { mpc->mpc->SetPlantModel(b, model, contact); });
+}
+int idto_mpc_batch_plants_set_states(idto_mpc_batch* mpc, const double* times, const double* x) {
+  return Guard([&] {
+    if (!times || !x) throw std::runtime_error("mpc_batch_plants_set_states: times[B] and x[B][nq + nv] are required");
+    mpc->mpc->SetPlantStates(times, x);
+  });
+}
+int idto_mpc_batch_plants_step(idto_mpc_batch* mpc, int substeps) { return Guard([&] { mpc->mpc->StepPlants(substeps); }); }
+int idto_mpc_batch_plants_state(idto_mpc_batch* mpc, int b, double* time, double* x, int* status) {
+  return Guard([&] {
+    CheckController(mpc, b);
+    if (x) Flat(mpc->mpc->plant_state(b), x);
+    if (time) *time = mpc->mpc->plant_time(b);
+    if (status) *status = mpc->mpc->plant_status(b);
+  });
+}
+int idto_mpc_batch_plants_tick(idto_mpc_batch* mpc, int substeps, double* q_guess, double* sol_q, double* sol_v, double* sol_tau,
+                               idto_stats_t* stats, int* flags, double* radii, int* tick_ok) {
+  return Guard([&] {
+    const bool ok = mpc->mpc->TickWithPlants(substeps);
+    if (tick_ok) *tick_ok = ok ? 1 : 0;
+    BatchTickOutputs(mpc, q_guess, sol_q, sol_v, sol_tau, stats, flags, radii);
+  });
+}
+// the Plants view on an optimizer's own context (one plant)
+int idto_plant_forward_dynamics(idto_opt* opt, const double* x, const double* tau, double* a, double* M, double* bias) {
+  return Guard([&] { idto::examples::mpc::Plants(opt->to->device_context()).ForwardDynamics(x, tau, a, M, bias); });
+}
+int idto_plant_begin(idto_opt* opt, double sim_time_step, int record_capacity) {
+  return Guard([&] { idto::examples::mpc::Plants(opt->to->device_context()).Begin(sim_time_step, record_capacity); });
+}
+int idto_plant_set_state(idto_opt* opt, double time, const double* x) {
+  return Guard([&] { idto::examples::mpc::Plants(opt->to->device_context()).SetStates(&time, x); });
+}
+int idto_plant_get_state(idto_opt* opt, double* time, double* x) {
+  return Guard([&] { idto::examples::mpc::Plants(opt->to->device_context()).GetStates(time, x); });
+}
+int idto_plant_step(idto_opt* opt, int substeps, const double* tau_hold, int record_every, double* x_record, int* status) {
+  return Guard([&] { idto::examples::mpc::Plants(opt->to->device_context()).Step(substeps, tau_hold, record_every, x_record, status); });
+}
+
 int idto_mpc_batch_state(const idto_mpc_batch* mpc, int b, double time, double* x) {
   return Guard([&] { CheckController(mpc, b); Flat(idto::examples::mpc::Interpolator::State(mpc->mpc->stored_trajectory(b), time), x); });
 }
@@ -462,5 +533,23 @@ int idto_mpc_shift_reference(const double* breaks, const double* y_q, const doub
       for (int c = 0; c < nq; ++c)
         q_nom[(size_t)i * nq + c] = idto_spline::nominal_shift(q_nom[(size_t)i * nq + c], selector[c] != 0, q0[c], old0[(size_t)c]);
   });
+}
+
+// ---- csrc/plant_step.h on the host, for the tests that hold plant_kernel to it
+int idto_plant_solve_host(const double* M, const double* tau_applied, const double* bias, int n, double* a_out) {
+  if (n < 1) return 0;
+  std::vector<double> A(M, M + (size_t)n * n), work((size_t)n, 0.0);
+  for (int i = 0; i < n; ++i) a_out[i] = tau_applied[i] - bias[i];
+  return idto_plant::plant_ldlt_solve(A.data(), n, a_out, work.data());
+}
+void idto_plant_pd_plus_host(const double* Kp, const double* Kd, int nu, int nq, int nv, const int* actuated_dofs, const double* q,
+                             const double* v, const double* q_nom, const double* v_nom, int feed_forward, const double* u_nom,
+                             double* tau_out) {
+  idto_plant::plant_pd_plus(Kp, Kd, nu, nq, nv, actuated_dofs, q, v, q_nom, v_nom, feed_forward != 0, u_nom, tau_out);
+}
+void idto_plant_advance_host(int nbodies, const int* jtype, const int* qstart, const int* vstart, int nq, double h, double* q,
+                             double* v, const double* a) {
+  std::vector<double> qdot((size_t)(nq > 0 ? nq : 1), 0.0);
+  idto_plant::plant_advance(nbodies, jtype, qstart, vstart, h, q, v, a, qdot.data());
 }
 }  // extern "C"

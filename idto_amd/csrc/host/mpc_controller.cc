@@ -282,17 +282,102 @@ bool BatchModelPredictiveController::UpdateAll(const std::vector<double>& times,
   return UpdateAll(times.data(), x0_.data());
 }
 
-bool BatchModelPredictiveController::UpdateAll(const double* times, const double* x0s) {
+bool BatchModelPredictiveController::UpdateAll(const double* times, const double* x0s) { return Tick(times, x0s, -1); }
+
+// ---- the plants
+static void PlantOk(int rc, const char* who) {
+  if (rc != 0) throw std::runtime_error(std::string(who) + ": " + idto_hip_last_error());
+}
+void BatchModelPredictiveController::BeginPlants(const PlantParams& params) {
+  idto_plant_params_t p{};
+  p.h = params.sim_time_step; p.mode = IDTO_PLANT_PD_PLUS;
+  p.Kp = params.Kp.data(); p.kp_size = (int)params.Kp.size(); p.Kd = params.Kd.data(); p.kd_size = (int)params.Kd.size();
+  p.feed_forward = params.feed_forward ? 1 : 0; p.record_capacity = params.record_capacity;
+  PlantOk(idto_hip_plant_begin(ctx_, &p), "BeginPlants");
+  plants_ = true; plants_stale_ = true;
+  plant_times_.assign((size_t)B_, 0.0); plant_x_.assign((size_t)B_ * (nq_ + nv_), 0.0); plant_status_.assign((size_t)B_ * 2, 0);
+  plant_states_.assign((size_t)B_, VectorXd((size_t)(nq_ + nv_)));
+}
+void BatchModelPredictiveController::SetPlantModel(int b, const idto_model_t* model, const idto_contact_params_t* contact) {
+  PlantOk(idto_hip_plant_set_model(ctx_, b, model, contact), "SetPlantModel");
+}
+void BatchModelPredictiveController::SetPlantStates(const double* times, const double* x) {
+  PlantOk(idto_hip_plant_set_state(ctx_, times, x), "SetPlantStates");
+  plants_stale_ = true;
+}
+void BatchModelPredictiveController::SetPlantStates(const std::vector<double>& times, const std::vector<VectorXd>& x) {
+  if ((int)times.size() != B_ || (int)x.size() != B_) throw std::invalid_argument("SetPlantStates: one time and one state per plant");
+  std::vector<double> flat((size_t)B_ * (nq_ + nv_));
+  for (int b = 0; b < B_; ++b) {
+    if ((int)x[(size_t)b].size() != nq_ + nv_) throw std::invalid_argument("a plant's state must be [q; v]");
+    std::copy(x[(size_t)b].begin(), x[(size_t)b].end(), flat.begin() + (size_t)b * (nq_ + nv_));
+  }
+  SetPlantStates(times.data(), flat.data());
+}
+void BatchModelPredictiveController::StepPlants(int substeps) {
+  if (!plants_) throw std::runtime_error("StepPlants: call BeginPlants first");
+  PlantOk(idto_hip_plant_step(ctx_, substeps, nullptr, 0, nullptr, plant_status_.data()), "StepPlants");
+  plants_stale_ = true;
+}
+void BatchModelPredictiveController::FetchPlants() {
+  if (!plants_) throw std::runtime_error("the plants: call BeginPlants first");
+  if (!plants_stale_) return;
+  PlantOk(idto_hip_plant_get_state(ctx_, plant_times_.data(), plant_x_.data()), "plant_state");
+  for (int b = 0; b < B_; ++b)
+    std::copy(plant_x_.begin() + (size_t)b * (nq_ + nv_), plant_x_.begin() + (size_t)(b + 1) * (nq_ + nv_), plant_states_[(size_t)b].begin());
+  plants_stale_ = false;
+}
+const VectorXd& BatchModelPredictiveController::plant_state(int b) { FetchPlants(); return plant_states_.at((size_t)b); }
+double BatchModelPredictiveController::plant_time(int b) { FetchPlants(); return plant_times_.at((size_t)b); }
+int BatchModelPredictiveController::plant_status(int b) { FetchPlants(); return plant_status_.at((size_t)b * 2); }
+bool BatchModelPredictiveController::TickWithPlants(int substeps) {
+  if (!plants_) throw std::runtime_error("TickWithPlants: call BeginPlants first");
+  if (substeps < 0) throw std::runtime_error("TickWithPlants: substeps must not be negative");
+  return Tick(nullptr, nullptr, substeps);
+}
+
+Plants::Plants(idto_hip_ctx* context) : ctx_(context), B_(context ? idto_hip_batch_size(context) : 0) {
+  if (!context) throw std::invalid_argument("Plants: a device context is required");
+}
+void Plants::ForwardDynamics(const double* x, const double* tau, double* a, double* M, double* bias) {
+  PlantOk(idto_hip_forward_dynamics(ctx_, x, tau, a, M, bias), "Plants::ForwardDynamics");
+}
+void Plants::Begin(double sim_time_step, int record_capacity) {
+  idto_plant_params_t p{};
+  p.h = sim_time_step; p.mode = IDTO_PLANT_HOLD; p.record_capacity = record_capacity;
+  PlantOk(idto_hip_plant_begin(ctx_, &p), "Plants::Begin");
+}
+void Plants::SetModel(int b, const idto_model_t* model, const idto_contact_params_t* contact) {
+  PlantOk(idto_hip_plant_set_model(ctx_, b, model, contact), "Plants::SetModel");
+}
+void Plants::SetStates(const double* times, const double* x) { PlantOk(idto_hip_plant_set_state(ctx_, times, x), "Plants::SetStates"); }
+void Plants::GetStates(double* times, double* x) { PlantOk(idto_hip_plant_get_state(ctx_, times, x), "Plants::GetStates"); }
+void Plants::Step(int substeps, const double* tau_hold, int record_every, double* x_record, int* status) {
+  PlantOk(idto_hip_plant_step(ctx_, substeps, tau_hold, record_every, x_record, status), "Plants::Step");
+}
+
+// One tick of the B controllers: from times / x0s (substeps < 0: UpdateAll), or from the plants after `substeps` substeps of
+// theirs (TickWithPlants) - the same adoption of the device's results either way
+bool BatchModelPredictiveController::Tick(const double* times, const double* x0s, int substeps) {
   using clock = std::chrono::high_resolution_clock;
   idto_hip_trace_mark("mpc batch: UpdateAll begins");
   const auto start = clock::now();
   const int n = N_ + 1, iters = loop_.iterations;
   const size_t nqa = (size_t)n * nq_, nva = (size_t)n * nv_, nta = (size_t)N_ * nv_, len = IDTO_MPC_PLAN_LEN(n, nq_, nv_, nu_);
   int best = -1;
-  const int rc = idto_hip_mpc_batch_replan(ctx_, times, x0s, iters, loop_.scaling_method, loop_.scaling, loop_.normalize_quaternions,
-                                           Delta_.data(), loop_.Delta_max, loop_.eta, loop_.constrained_dofs, loop_.nu, rows_.data(),
-                                           Delta_out_.data(), q_.data(), v_.data(), tau_.data(), final_cost_.data(), status_.data(),
-                                           &best, guess_.data(), plans_.data());
+  int rc;
+  if (substeps < 0) {
+    rc = idto_hip_mpc_batch_replan(ctx_, times, x0s, iters, loop_.scaling_method, loop_.scaling, loop_.normalize_quaternions,
+                                   Delta_.data(), loop_.Delta_max, loop_.eta, loop_.constrained_dofs, loop_.nu, rows_.data(),
+                                   Delta_out_.data(), q_.data(), v_.data(), tau_.data(), final_cost_.data(), status_.data(),
+                                   &best, guess_.data(), plans_.data());
+  } else {
+    rc = idto_hip_mpc_batch_tick_plants(ctx_, substeps, iters, loop_.scaling_method, loop_.scaling, loop_.normalize_quaternions,
+                                        Delta_.data(), loop_.Delta_max, loop_.eta, loop_.constrained_dofs, loop_.nu, rows_.data(),
+                                        Delta_out_.data(), q_.data(), v_.data(), tau_.data(), final_cost_.data(), status_.data(),
+                                        &best, guess_.data(), plans_.data(), plant_x_.data(), plant_status_.data());
+    plants_stale_ = true;   // (the states came back with the tick; the times have not: plant_time fetches them)
+  }
   idto_hip_trace_mark("mpc batch: idto_hip_mpc_batch_replan returned");
   tick_error_.clear();
   if (rc == IDTO_HIP_SOLVER_TIMEOUT) {

@@ -39,6 +39,7 @@
 #include "kkt.h"
 #include "linesearch.h"
 #include "mpc_batch.h"
+#include "plant_launch.h"
 #include "host/context_layout.h"
 #include "host/model_batch.h"
 #include "host/model_tables.h"
@@ -207,11 +208,35 @@ struct MpcTickHook {
   const double* times; const double* x0;     // host: [B], [B][nq + nv]
   double* guess_out; double* plans_out;      // host, may be null
   size_t nguess, nplans;                     // doubles of the two parts
+  // idto_hip_mpc_batch_tick_plants: times and x0 are null - the plants' kernel wrote the tick buffer on the device -, and the
+  // plants' [t, q, v] come back under the tick's one wait: x_after_out [B][nq + nv], host, may be null
+  // plant_status_out [B][2], host, may be null: {code, substeps completed} of the tick's substeps; followed: the host copies of
+  // the problems have been moved with the plants' states (behind the wait; MpcReplanRun does it where the loop returned early)
+  struct PlantState* plant = nullptr; double* x_after_out = nullptr; int* plant_status_out = nullptr; mutable bool followed = false;
+};
+
+// idto_hip_plant_*: the plants' storage (plant.h), ONE allocation made by idto_hip_plant_begin and cut up here - the plants'
+// parameter records, their states [B][1 + nq + nv] (the layout of the controllers' tick buffer), the held torques, the state
+// record of a launch, forward dynamics' inputs and outputs, the PD+ gains, the status words
+struct PlantState {
+  double* base = nullptr;
+  double *records = nullptr, *state = nullptr, *tau = nullptr, *record = nullptr;
+  double *fd_x = nullptr, *fd_a = nullptr, *fd_M = nullptr, *fd_bias = nullptr, *Kp = nullptr, *Kd = nullptr;
+  int* status = nullptr;
+  size_t mstride = 0;
+  int record_capacity = 64, nu = 0;
+  unsigned mpc_generation = 0;               // (PD+) the idto_hip_mpc_batch_begin whose plans the LDS was sized for
+  double h = 0; int mode = 0, feed_forward = 0, block = 64, lds = 0;
+  bool begun = false;                         // idto_hip_plant_begin made it (idto_hip_forward_dynamics alone: not)
+  double* pin = nullptr; size_t pin_cap = 0;   // pinned staging of what comes back
+  double* tick_pin = nullptr; size_t tick_pin_cap = 0;   // ... of the plants' states behind a tick (idto_hip_mpc_batch_tick_plants)
 };
 
 struct idto_hip_ctx {
   int device = 0;
   MpcBatchState* mpc = nullptr;
+  unsigned mpc_generation = 0;   // calls of idto_hip_mpc_batch_begin so far
+  PlantState* plant = nullptr;
   // (batch contexts) what the context was created from, and one single-problem context per problem, made on first use
   std::unique_ptr<HostModelCopy> host_model;
   std::vector<std::unique_ptr<HostProblemCopy>> host_problems;
@@ -1024,6 +1049,11 @@ void idto_hip_destroy(idto_hip_ctx* c) {
   if (c->con_pin) (void)hipHostFree(c->con_pin);
   if (c->fetch_pin) (void)hipHostFree(c->fetch_pin);
   if (c->bstate_pin) (void)hipHostFree(c->bstate_pin);
+  if (c->plant) {   // (its device allocation is in c->allocs)
+    if (c->plant->pin) (void)hipHostFree(c->plant->pin);
+    if (c->plant->tick_pin) (void)hipHostFree(c->plant->tick_pin);
+    delete c->plant;
+  }
   if (c->mpc) {   // (its device buffers are in c->allocs)
     if (c->mpc->tick_pin) (void)hipHostFree(c->mpc->tick_pin);
     if (c->mpc->io_pin) (void)hipHostFree(c->mpc->io_pin);
@@ -2748,6 +2778,29 @@ int TrFoldSets(idto_hip_ctx* c) {
   HIP_OK(hipGetLastError());
   return 0;
 }
+// A tick from the plants, behind its wait: the plants' states and status words, which PlantState::tick_pin holds, go to the
+// caller, and the host copies of the problems follow the states (as MpcShiftEnqueue moves them for a tick from the host)
+void MpcPlantsBack(idto_hip_ctx* c, const MpcTickHook& hook) {
+  const int B = c->batch;
+  const size_t tick_w = (size_t)(1 + c->nq + c->nv);
+  const double* s = hook.plant->tick_pin;
+  MpcBatchState* m = hook.m;
+  if (hook.plant_status_out) std::memcpy(hook.plant_status_out, s + (size_t)B * tick_w, (size_t)B * 2 * sizeof(int));
+  for (int b = 0; b < B; ++b) {
+    const double* x0 = s + (size_t)b * tick_w + 1;
+    if (hook.x_after_out) std::memcpy(hook.x_after_out + (size_t)b * (tick_w - 1), x0, (tick_w - 1) * sizeof(double));
+    if (b < (int)c->host_problems.size()) {
+      HostProblemCopy& hp = *c->host_problems[(size_t)b];
+      const std::vector<double> old0(hp.q_nom.begin(), hp.q_nom.begin() + c->nq);
+      for (int t = 0; t < m->L.n; ++t)
+        for (int i = 0; i < c->nq; ++i)
+          hp.q_nom[(size_t)t * c->nq + i] = idto_spline::nominal_shift(hp.q_nom[(size_t)t * c->nq + i], m->selector[(size_t)i] != 0, x0[i], old0[(size_t)i]);
+      std::copy(x0, x0 + c->nq, hp.q_init.begin());
+      std::copy(x0 + c->nq, x0 + c->nq + c->nv, hp.v_init.begin());
+    }
+  }
+  hook.followed = true;
+}
 // idto_hip_tr_solve_batch_fetch: state words, rows and the iterates of every problem (only_best: of the best one) packed
 // by ONE launch, which also chooses the best problem; one copy, one wait (trust_region.h tr_gather_batch_kernel)
 int TrFinishBatchFetch(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt) {
@@ -2778,10 +2831,18 @@ int TrFinishBatchFetch(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt) 
     HIP_OK(hipGetLastError());
   }
   HIP_OK(hipMemcpyAsync(c->fetch_pin, c->fetch_dev, L.total() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  const size_t tick_w = (size_t)(1 + c->nq + c->nv);
+  if (hook && hook->plant) {   // one more copy back, the plants' states, in front of the tick's one wait
+    PlantState* pl = hook->plant;
+    if (int erc = EnsurePinned(&pl->tick_pin, &pl->tick_pin_cap, (size_t)B * (tick_w + 1))) return erc;   // (+ two status ints a plant)
+    HIP_OK(hipMemcpyAsync(pl->tick_pin, pl->state, (size_t)B * tick_w * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(pl->tick_pin + (size_t)B * tick_w, pl->status, (size_t)B * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  }
   // (behind the copy: the fold only makes the context's first set the iterate's for the calls that follow)
   if (int rc = TrFoldSets(c)) return rc;
   HIP_OK(hipStreamSynchronize(c->stream));
   TRACE("hip: tr_solve: waited for the device (every problem's state words, rows and solution back)");
+  if (hook && hook->plant) MpcPlantsBack(c, *hook);
   const double* p = c->fetch_pin;
   const int best = *bfetch->best = (int)p[L.header()];
   for (int b = 0; b < B; ++b) { bfetch->final_cost[b] = p[L.final_cost() + b]; bfetch->status[b] = (int)p[L.status() + b]; }
@@ -3062,6 +3123,7 @@ int idto_hip_mpc_batch_begin(idto_hip_ctx* c, const int* selector, const int* ac
   HIP_OK(hipHostMalloc((void**)&m->tick_pin, tick * sizeof(double), hipHostMallocDefault));
   HIP_OK(hipHostMalloc((void**)&m->io_pin, m->io_count * sizeof(double), hipHostMallocDefault));
   c->mpc = m.release();
+  ++c->mpc_generation;
   return 0;
 }
 
@@ -3108,12 +3170,14 @@ static int MpcShiftEnqueue(idto_hip_ctx* c, const double* times, const double* x
   c->fd_full = false; c->partials_ahead = false;
   c->con_ready = false; c->con_begun = false;
   const size_t w = (size_t)(1 + nq + nv);
-  for (int b = 0; b < B; ++b) {
-    double* t = m->tick_pin + (size_t)b * w;
-    t[0] = times[b];
-    std::memcpy(t + 1, x0 + (size_t)b * (nq + nv), (size_t)(nq + nv) * sizeof(double));
+  if (times) {   // (null: the plants' kernel, enqueued in front, writes the tick buffer - idto_hip_mpc_batch_tick_plants)
+    for (int b = 0; b < B; ++b) {
+      double* t = m->tick_pin + (size_t)b * w;
+      t[0] = times[b];
+      std::memcpy(t + 1, x0 + (size_t)b * (nq + nv), (size_t)(nq + nv) * sizeof(double));
+    }
+    HIP_OK(hipMemcpyAsync(m->tick_dev, m->tick_pin, (size_t)B * w * sizeof(double), hipMemcpyHostToDevice, c->stream));
   }
-  HIP_OK(hipMemcpyAsync(m->tick_dev, m->tick_pin, (size_t)B * w * sizeof(double), hipMemcpyHostToDevice, c->stream));
   MpcShiftArgs A{};
   A.L = m->L; A.breaks = m->breaks; A.selector = m->selector_dev; A.time_step = c->dt;
   A.plan = m->plan[m->cur]; A.tick = m->tick_dev;
@@ -3122,7 +3186,8 @@ static int MpcShiftEnqueue(idto_hip_ctx* c, const double* times, const double* x
   hipLaunchKernelGGL(mpc_shift_kernel, dim3(1, B), dim3(256), (size_t)nq * sizeof(double), c->stream, A);
   HIP_OK(hipGetLastError());
   // the host copies of the problems (what a child context would be made from) follow: the same arithmetic, mpc_spline.h
-  for (int b = 0; b < B && b < (int)c->host_problems.size(); ++b) {
+  // (a tick from the plants: behind the wait, when their states are on the host - MpcHostProblemsFollow)
+  for (int b = 0; times && b < B && b < (int)c->host_problems.size(); ++b) {
     HostProblemCopy& hp = *c->host_problems[(size_t)b];
     const double* q0 = x0 + (size_t)b * (nq + nv);
     const std::vector<double> old0(hp.q_nom.begin(), hp.q_nom.begin() + nq);
@@ -3180,25 +3245,66 @@ static int TrSolveBatchFetch(idto_hip_ctx* c, const TrRequest& rq) {
   return rc;
 }
 
+// A tick's arguments and outputs behind its source of [time, q0, v0]: idto_hip_mpc_batch_replan's, which
+// idto_hip_mpc_batch_tick_plants shares
+struct MpcReplanArgs {
+  int iterations, scaling_method, scaling, normalize_quaternions; const double* Delta0; double Delta_max, eta;
+  const int* constrained_dofs; int nu; double* rows_host; double* Delta_out; double *q_out, *v_out, *tau_out, *final_cost;
+  int *status, *best; double *guess_out, *plans_out;
+};
+static TrRequest MpcReplanRequest(const MpcReplanArgs& a) {
+  return TrRequest{a.iterations, a.scaling_method, a.scaling, a.normalize_quaternions, a.Delta0, a.Delta_max, a.eta, a.constrained_dofs, a.nu, a.rows_host, a.Delta_out};
+}
+// what a tick refuses, before any device work (from_plants: times and x0 are not arguments)
+static int MpcReplanCheck(idto_hip_ctx* c, const char* who, const MpcReplanArgs& a, bool from_plants, bool tick_missing) {
+  if (int rc = MpcReady(c, who)) return rc;
+  const bool missing = tick_missing || !a.Delta0 || !a.rows_host || !a.final_cost || !a.status || !a.best;
+  const char* need = from_plants ? "Delta0[batch], rows_host[batch][iterations][IDTO_TR_ROW], final_cost[batch], status[batch] and best"
+                                 : "times[batch], x0[batch][nq + nv], Delta0[batch], rows_host[batch][iterations][IDTO_TR_ROW], "
+                                   "final_cost[batch], status[batch] and best";
+  if (int rc = TrCheckArgs(who, MpcReplanRequest(a), missing ? need : nullptr)) return rc;
+  if (c->batch < 2) { g_err = std::string(who) + ": serves batches of more than one problem (one controller: idto_hip_tr_solve_fetch)"; return -1; }
+  return 0;
+}
+// the tick itself: the shift from times / x0 (null: from the tick buffer that the plants' kernel wrote), the loop, the store,
+// the copies back, the one wait
+static int MpcReplanRun(idto_hip_ctx* c, const double* times, const double* x0, const MpcReplanArgs& a, PlantState* plant, double* x_after_out,
+                        int* plant_status_out) {
+  TrRequest rq = MpcReplanRequest(a);
+  MpcBatchState* m = c->mpc;
+  MpcTickHook hook{m, times, x0, a.guess_out, a.plans_out, (size_t)c->batch * m->L.n * c->nq, (size_t)c->batch * m->L.len()};
+  hook.plant = plant; hook.x_after_out = x_after_out; hook.plant_status_out = plant_status_out;
+  TrBatchFetch bf{0, {a.q_out, a.v_out, a.tau_out, nullptr, nullptr}, a.final_cost, a.status, a.best, &hook}; rq.bfetch = &bf;
+  const int rc = TrSolveBatchFetch(c, rq);
+  if (plant && !hook.followed) {
+    // the loop returned before its gather (an error, a time-out): the plants have advanced and the device has been shifted all
+    // the same - fetch the plants' states and status now, so that the caller and the host copies of the problems have them
+    const size_t w = (size_t)(1 + c->nq + c->nv), B = (size_t)c->batch;
+    if (EnsurePinned(&plant->tick_pin, &plant->tick_pin_cap, B * (w + 1)) == 0 && hipStreamSynchronize(c->stream) == hipSuccess &&
+        hipMemcpy(plant->tick_pin, plant->state, B * w * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+        hipMemcpy(plant->tick_pin + B * w, plant->status, B * 2 * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess) {
+      const std::string err = g_err;
+      MpcPlantsBack(c, hook);
+      g_err = err;
+    }
+  }
+  // the plane the store wrote is in force once the tick counted; a loop that timed out, or a call that failed, leaves every plan
+  if (rc == 0 || rc == IDTO_HIP_FACTORIZATION_FAILED) m->cur ^= 1;
+  return rc;
+}
+
 int idto_hip_mpc_batch_replan(idto_hip_ctx* c, const double* times, const double* x0, int iterations, int scaling_method,
                               int scaling, int normalize_quaternions, const double* Delta0, double Delta_max, double eta,
                               const int* constrained_dofs, int nu, double* rows_host, double* Delta_out, double* q_out,
                               double* v_out, double* tau_out, double* final_cost, int* status, int* best, double* guess_out,
                               double* plans_out) {
-  if (int rc = MpcReady(c, "mpc_batch_replan")) return rc;
-  TrRequest rq{iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu, rows_host, Delta_out};
-  const bool missing = !times || !x0 || !Delta0 || !rows_host || !final_cost || !status || !best;
-  if (int rc = TrCheckArgs("mpc_batch_replan", rq, missing ? "times[batch], x0[batch][nq + nv], Delta0[batch], rows_host[batch][iterations][IDTO_TR_ROW], "
-                                                             "final_cost[batch], status[batch] and best" : nullptr)) return rc;
-  if (c->batch < 2) { g_err = "mpc_batch_replan: serves batches of more than one problem (one controller: idto_hip_tr_solve_fetch)"; return -1; }
-  MpcBatchState* m = c->mpc;
-  MpcTickHook hook{m, times, x0, guess_out, plans_out, (size_t)c->batch * m->L.n * c->nq, (size_t)c->batch * m->L.len()};
-  TrBatchFetch bf{0, {q_out, v_out, tau_out, nullptr, nullptr}, final_cost, status, best, &hook}; rq.bfetch = &bf;
-  const int rc = TrSolveBatchFetch(c, rq);
-  // the plane the store wrote is in force once the tick counted; a loop that timed out, or a call that failed, leaves every plan
-  if (rc == 0 || rc == IDTO_HIP_FACTORIZATION_FAILED) m->cur ^= 1;
-  return rc;
+  const MpcReplanArgs a{iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta, constrained_dofs, nu, rows_host,
+                        Delta_out, q_out, v_out, tau_out, final_cost, status, best, guess_out, plans_out};
+  if (int rc = MpcReplanCheck(c, "mpc_batch_replan", a, false, !times || !x0)) return rc;
+  return MpcReplanRun(c, times, x0, a, nullptr, nullptr, nullptr);
 }
+
+#include "plant_abi.inc"   // idto_hip_forward_dynamics, idto_hip_plant_*
 
 // The batch loop with everything a caller reads afterwards brought back under the loop's one wait, and the best problem
 // chosen on the device (trust_region.h tr_gather_batch_kernel).

@@ -1,0 +1,23 @@
+// plant_launch.h — how idto_hip.hip starts plant_kernel (plant.h): its instantiations live in csrc/plant_launch.hip, a
+// translation unit of their own, so that fd_launch.hip and idto_hip.hip compile to what they compiled to without it.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "plant.h"
+
+namespace idto_dev {
+
+struct PlantLaunch {
+  int plants, block, lds;
+  hipStream_t stream;
+  PlantArgs args;
+  int maxc;      // the model's longest chain: the generic evaluation for chains of up to 2, 3, 4 and 8 bodies
+  int nxb;       // DevModel's: shared pairs -> id_eval<8, true> (a stem below the common body has no instantiation: DESIGN.md section 14.2)
+};
+// enqueues plant_kernel<MAXC, XCH>; the caller checks hipGetLastError()
+void plant_launch(const PlantLaunch& a);
+// opt-in of every instantiation to `max_lds` bytes of dynamic LDS
+void plant_set_max_lds(int max_lds);
+
+}  // namespace idto_dev

@@ -23,6 +23,16 @@ ARR = dict(q=0, v=1, a=2, tau=3, nplus=4, dtau_dqm=5, dtau_dqt=6, dtau_dqp=7, gr
 
 _lib = None
 
+PLANT_HOLD, PLANT_PD_PLUS = 0, 1
+PLANT_MAX_SUBSTEPS = 4096
+
+
+class CPlantParams(C.Structure):
+    """idto_plant_params_t (include/idto_hip.h)"""
+    _fields_ = [("h", C.c_double), ("mode", C.c_int), ("Kp", C.POINTER(C.c_double)), ("kp_size", C.c_int),
+                ("Kd", C.POINTER(C.c_double)), ("kd_size", C.c_int), ("feed_forward", C.c_int),
+                ("record_capacity", C.c_int), ("block_threads", C.c_int)]
+
 
 class HipLibraryMissing(RuntimeError):
     pass
@@ -80,6 +90,14 @@ def lib():
         L.idto_hip_mpc_batch_shift.argtypes = [C.c_void_p, pd, pd, pd, pd]
         L.idto_hip_mpc_batch_replan.argtypes = ([C.c_void_p, pd, pd, C.c_int, C.c_int, C.c_int, C.c_int, pd, C.c_double, C.c_double,
                                                  pi, C.c_int, pd, pd, pd, pd, pd, pd, pi, pi, pd, pd])
+        L.idto_hip_forward_dynamics.argtypes = [C.c_void_p, pd, pd, pd, pd, pd]
+        L.idto_hip_plant_begin.argtypes = [C.c_void_p, C.POINTER(CPlantParams)]
+        L.idto_hip_plant_set_model.argtypes = [C.c_void_p, C.c_int, C.POINTER(CModel), C.POINTER(CContactParams)]
+        L.idto_hip_plant_set_state.argtypes = [C.c_void_p, pd, pd]
+        L.idto_hip_plant_get_state.argtypes = [C.c_void_p, pd, pd]
+        L.idto_hip_plant_step.argtypes = [C.c_void_p, C.c_int, pd, C.c_int, pd, pi]
+        L.idto_hip_mpc_batch_tick_plants.argtypes = ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, pd, C.c_double, C.c_double,
+                                                      pi, C.c_int, pd, pd, pd, pd, pd, pd, pi, pi, pd, pd, pd, pi])
         L.idto_hip_tr_reject.argtypes = [C.c_void_p]
         L.idto_hip_tr_set_scale_memory.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.idto_hip_tr_set_convergence.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -141,6 +159,8 @@ EXPORTED_SYMBOLS = [
     "idto_hip_set_q_batch", "idto_hip_gn_step_batch", "idto_hip_get_batch", "idto_hip_get_many", "idto_hip_solver_status_batch",
     "idto_hip_tr_prepare", "idto_hip_tr_trial", "idto_hip_tr_accept", "idto_hip_tr_reject", "idto_hip_tr_set_scale_memory", "idto_hip_tr_set_convergence", "idto_hip_tr_solve", "idto_hip_tr_solve_fetch", "idto_hip_tr_solve_batch", "idto_hip_tr_solve_batch_constrained", "idto_hip_tr_solve_batch_fetch", "idto_hip_set_unactuated_dofs",
     "idto_hip_mpc_batch_begin", "idto_hip_mpc_batch_store", "idto_hip_mpc_batch_shift", "idto_hip_mpc_batch_replan",
+    "idto_hip_forward_dynamics", "idto_hip_plant_begin", "idto_hip_plant_set_model", "idto_hip_plant_set_state",
+    "idto_hip_plant_get_state", "idto_hip_plant_step", "idto_hip_mpc_batch_tick_plants",
     "idto_hip_rccl_info", "idto_hip_comm_unique_id", "idto_hip_comm_init", "idto_hip_comm_init_all", "idto_hip_comm_destroy",
     "idto_hip_allgather_slab", "idto_hip_gn_step_sharded", "idto_hip_gn_step_multi", "idto_hip_eval_partials_multi",
     "idto_hip_trace_enable", "idto_hip_trace_mark", "idto_hip_trace_dump",
@@ -247,6 +267,62 @@ class HipPath:
         cc = params.contact_to_c() if params is not None else None
         _chk(lib().idto_hip_set_model_batch(self.h, int(b), C.byref(cm) if cm is not None else None,
                                             C.byref(cc) if cc is not None else None))
+
+    # ---- plants on the device (include/idto_hip.h idto_hip_forward_dynamics, idto_hip_plant_*)
+    def forward_dynamics(self, x, tau_applied):
+        """x: [batch, nq + nv], tau_applied: [batch, nv] -> (a [batch, nv], M [batch, nv, nv], bias [batch, nv])"""
+        B, nq, nv = self.batch, self.nq, self.nv
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(B, nq + nv))
+        tau = np.ascontiguousarray(np.asarray(tau_applied, dtype=np.float64).reshape(B, nv))
+        a, M, bias = np.zeros((B, nv)), np.zeros((B, nv, nv)), np.zeros((B, nv))
+        _chk(lib().idto_hip_forward_dynamics(self.h, dptr(x), dptr(tau), dptr(a), dptr(M), dptr(bias)))
+        return a, np.ascontiguousarray(M.transpose(0, 2, 1)), bias   # (column-major blocks -> [row, col])
+
+    def plant_begin(self, h: float, mode: int = PLANT_HOLD, Kp=None, Kd=None, feed_forward: bool = False,
+                    record_capacity: int = 0, block_threads: int = 0):
+        """idto_hip_plant_begin: B plants stepped with the substep h; PD+: Kp [nu, nq], Kd [nu, nv] on the stored plans"""
+        prm = CPlantParams()
+        prm.h, prm.mode, prm.feed_forward = float(h), int(mode), int(bool(feed_forward))
+        prm.record_capacity, prm.block_threads = int(record_capacity), int(block_threads)
+        keep = []
+        for name, K in (("Kp", Kp), ("Kd", Kd)):
+            if K is not None:
+                K = np.ascontiguousarray(np.asarray(K, dtype=np.float64))
+                keep.append(K)
+                setattr(prm, name, dptr(K))
+                setattr(prm, name.lower() + "_size", int(K.size))
+        _chk(lib().idto_hip_plant_begin(self.h, C.byref(prm)))
+
+    def plant_set_model(self, b: int, model: Model = None, params: SolverParameters = None):
+        """plant b gets `model` (the context's topology; None: the context's) and the contact parameters of `params`"""
+        cm, keep = model.to_c() if model is not None else (None, None)
+        cc = params.contact_to_c() if params is not None else None
+        _chk(lib().idto_hip_plant_set_model(self.h, int(b), C.byref(cm) if cm is not None else None,
+                                            C.byref(cc) if cc is not None else None))
+
+    def plant_set_state(self, times, x):
+        times = np.ascontiguousarray(np.broadcast_to(np.asarray(times, dtype=np.float64), (self.batch,)))
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(self.batch, self.nq + self.nv))
+        _chk(lib().idto_hip_plant_set_state(self.h, dptr(times), dptr(x)))
+
+    def plant_get_state(self):
+        """-> (times [batch], x [batch, nq + nv])"""
+        times, x = np.zeros(self.batch), np.zeros((self.batch, self.nq + self.nv))
+        _chk(lib().idto_hip_plant_get_state(self.h, dptr(times), dptr(x)))
+        return times, x
+
+    def plant_step(self, substeps: int, tau_hold=None, record_every: int = 0, status: bool = True):
+        """idto_hip_plant_step: `substeps` substeps of every plant in one launch.  -> (recorded states [batch,
+        substeps // record_every, nq + nv] or None, status [batch, 2] = (code, substeps completed) or None); with
+        record_every = 0 and status = False the launch is enqueued only, nothing is waited for"""
+        B = self.batch
+        tau = None if tau_hold is None else np.ascontiguousarray(np.asarray(tau_hold, dtype=np.float64).reshape(B, self.nv))
+        rec = np.zeros((B, int(substeps) // int(record_every), self.nq + self.nv)) if record_every else None
+        st = np.zeros((B, 2), dtype=np.int32) if status else None
+        _chk(lib().idto_hip_plant_step(self.h, int(substeps), dptr(tau) if tau is not None else None, int(record_every),
+                                       dptr(rec) if rec is not None else None,
+                                       st.ctypes.data_as(C.POINTER(C.c_int)) if st is not None else None))
+        return rec, st
 
     def solver_status_batch(self):
         out = (C.c_int * self.batch)()
@@ -424,6 +500,44 @@ class HipPath:
         guess, q_nom = np.zeros((B, self.N + 1, self.nq)), np.zeros((B, self.N + 1, self.nq))
         _chk(lib().idto_hip_mpc_batch_shift(self.h, dptr(times), dptr(x0), dptr(guess), dptr(q_nom)))
         return guess, q_nom
+
+    def _mpc_tick(self, substeps, times, x0, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta,
+                  constrained_dofs):
+        B, N, nq, nv = self.batch, self.N, self.nq, self.nv
+        out = dict(rows=np.zeros((B, int(iterations), 17)), Delta=np.zeros(B), q=np.zeros((B, N + 1, nq)), v=np.zeros((B, N + 1, nv)),
+                   tau=np.zeros((B, N, nv)), final_cost=np.zeros(B), status=np.zeros(B, dtype=np.int32), guess=np.zeros((B, N + 1, nq)),
+                   plans=np.zeros((B, self.mpc_plan_len())))
+        d0 = np.ascontiguousarray(np.broadcast_to(np.asarray(Delta0, dtype=np.float64), (B,)))
+        dofs = np.ascontiguousarray(np.asarray(constrained_dofs, dtype=np.int32))
+        best = C.c_int(-1)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        tail = [int(iterations), int(scaling_method), int(scaling), int(normalize_quaternions), dptr(d0), float(Delta_max), float(eta),
+                ip(dofs) if dofs.size else None, int(dofs.size), dptr(out["rows"]), dptr(out["Delta"]), dptr(out["q"]), dptr(out["v"]),
+                dptr(out["tau"]), dptr(out["final_cost"]), ip(out["status"]), C.byref(best), dptr(out["guess"]), dptr(out["plans"])]
+        if substeps is None:
+            times, x0 = (np.ascontiguousarray(np.asarray(a, dtype=np.float64)) for a in (times, x0))
+            assert times.size == B and x0.size == B * (nq + nv)
+            rc = lib().idto_hip_mpc_batch_replan(self.h, dptr(times), dptr(x0), *tail)
+        else:
+            out["x_after"], out["plant_status"] = np.zeros((B, nq + nv)), np.zeros((B, 2), dtype=np.int32)
+            rc = lib().idto_hip_mpc_batch_tick_plants(self.h, int(substeps), *tail, dptr(out["x_after"]), ip(out["plant_status"]))
+        if rc != FACTORIZATION_FAILED:   # (a controller whose factorisation failed keeps its plan: its status says so)
+            _chk(rc)
+        out["best"] = best.value
+        return out
+
+    def mpc_batch_replan(self, times, x0, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta=0.0,
+                         constrained_dofs=()):
+        """idto_hip_mpc_batch_replan: one tick of the B controllers from times [B] and x0 [B, nq + nv]; a dict of its outputs"""
+        return self._mpc_tick(None, times, x0, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta,
+                              constrained_dofs)
+
+    def mpc_batch_tick_plants(self, substeps, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max, eta=0.0,
+                              constrained_dofs=()):
+        """idto_hip_mpc_batch_tick_plants: `substeps` PD+ substeps of the plants, then the re-plan from their states, under one
+        wait; the re-plan's outputs and x_after [B, nq + nv]"""
+        return self._mpc_tick(int(substeps), None, None, iterations, scaling_method, scaling, normalize_quaternions, Delta0, Delta_max,
+                              eta, constrained_dofs)
 
     def tr_set_convergence(self, tolerances=None):
         """[rel_cost, abs_cost, rel_gradient_along_dq, abs_gradient_along_dq, rel_state, abs_state] or None (no checks)"""

@@ -280,16 +280,60 @@ class BatchDeviceModelPredictiveController:
             b = self._buf = (times, x0, g, q, v, tau, stats, cst, flags, radii, ok, ptrs, O.lib().idto_mpc_batch_update)
         return b
 
+    # ---- B plants beside the controllers (BeginPlants ... TickWithPlants; include/idto_opt.h idto_mpc_batch_plants_*)
+    def begin_plants(self, sim_time_step, Kp, Kd, feed_forward=False, record_capacity=0):
+        """plant b: simulated on the device at sim_time_step under PD+ on controller b's stored plan; Kp [nu, nq], Kd [nu, nv]
+        (idto_amd.problem.mpc_parameters reads them from an example's configuration)"""
+        O = self._O
+        Kp, Kd = O._d(Kp), O._d(Kd)
+        self._chk(O.lib().idto_mpc_batch_plants_begin(self._h, float(sim_time_step), O.dptr(Kp), int(Kp.size), O.dptr(Kd), int(Kd.size),
+                                                      int(bool(feed_forward)), int(record_capacity)))
+
+    def set_plant_model(self, b, model=None, params=None):
+        """plant b gets `model` (the controllers' topology) and the contact parameters of `params`; None: the controllers'"""
+        C = self._C
+        cm, keep = model.to_c() if model is not None else (None, None)
+        cc = params.contact_to_c() if params is not None else None
+        self._chk(self._O.lib().idto_mpc_batch_plants_set_model(self._h, int(b), C.byref(cm) if cm is not None else None,
+                                                                C.byref(cc) if cc is not None else None))
+
+    def set_plant_states(self, times, x):
+        O = self._O
+        times = O._d(np.broadcast_to(np.asarray(times, float), (self.B,)))
+        x = O._d(np.asarray(x, float).reshape(self.B, self.nq + self.nv))
+        self._chk(O.lib().idto_mpc_batch_plants_set_states(self._h, O.dptr(times), O.dptr(x)))
+
+    def step_plants(self, substeps):
+        """`substeps` substeps of every plant in one launch"""
+        self._chk(self._O.lib().idto_mpc_batch_plants_step(self._h, int(substeps)))
+
+    def plant_state(self, b):
+        """(time, [q; v], status of the last step) of plant b"""
+        C, O = self._C, self._O
+        t, x, st = np.zeros(1), np.zeros(self.nq + self.nv), C.c_int()
+        self._chk(O.lib().idto_mpc_batch_plants_state(self._h, int(b), O.dptr(t), O.dptr(x), C.byref(st)))
+        return float(t[0]), x, st.value
+
+    def tick_with_plants(self, substeps, copy=True, strict=None):
+        """step_plants(substeps), then update(the plants' times, the plants' states), as ONE device pass waited for once: what
+        update returns"""
+        return self._tick(self._O.lib().idto_mpc_batch_plants_tick, (int(substeps),), copy, strict)
+
     def update(self, times, x0s, copy=True, strict=None):
         """UpdateAll: controller b re-plans at times[b] from x0s[b] = [q0; v0].  Returns (q_guess, q, v, tau), each
         [B, ...]; a controller whose re-plan failed keeps its previous plan and solution.  strict: raise when any
         controller's re-plan failed or the tick did not count (strict=False: `last_flags[b] == 2` / `last_tick_ok`
         say so, `error(b)` why).  copy=False: the controllers' own output buffers, overwritten by the next update."""
-        strict = self.strict if strict is None else bool(strict)
-        times_b, x0_b, g, q, v, tau, stats, cst, flags, radii, ok, ptrs, fn = self._buffers()
+        times_b, x0_b = self._buffers()[:2]
         times_b[:] = times
         x0_b[:] = np.asarray(x0s, float).reshape(self.B, self.nq + self.nv)
-        if fn(self._h, *ptrs):
+        return self._tick(self._buffers()[-1], self._buffers()[-2][:2], copy, strict)
+
+    def _tick(self, fn, head, copy, strict):
+        """one tick through `fn(handle, *head, the output pointers)` and the bookkeeping behind it"""
+        strict = self.strict if strict is None else bool(strict)
+        times_b, x0_b, g, q, v, tau, stats, cst, flags, radii, ok, ptrs, _ = self._buffers()
+        if fn(self._h, *head, *ptrs[2:]):
             raise RuntimeError(self._O.lib().idto_opt_last_error().decode())
         for b in range(self.B):
             stats[b].c = cst[b]

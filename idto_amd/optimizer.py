@@ -86,6 +86,22 @@ def lib():
         L.idto_mpc_batch_error.restype = C.c_char_p
         L.idto_mpc_spline_fit.argtypes = [P, P, C.c_int, C.c_int, P]
         L.idto_mpc_shift_reference.argtypes = [P, P, P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, P, I, P, P]
+        L.idto_mpc_batch_plants_begin.argtypes = [C.c_void_p, C.c_double, P, C.c_int, P, C.c_int, C.c_int, C.c_int]
+        L.idto_mpc_batch_plants_set_model.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.idto_mpc_batch_plants_set_states.argtypes = [C.c_void_p, P, P]
+        L.idto_mpc_batch_plants_step.argtypes = [C.c_void_p, C.c_int]
+        L.idto_mpc_batch_plants_state.argtypes = [C.c_void_p, C.c_int, P, P, I]
+        L.idto_mpc_batch_plants_tick.argtypes = [C.c_void_p, C.c_int, P, P, P, P, C.POINTER(CStats), I, P, I]
+        L.idto_plant_forward_dynamics.argtypes = [C.c_void_p, P, P, P, P, P]
+        L.idto_plant_begin.argtypes = [C.c_void_p, C.c_double, C.c_int]
+        L.idto_plant_set_state.argtypes = [C.c_void_p, C.c_double, P]
+        L.idto_plant_get_state.argtypes = [C.c_void_p, P, P]
+        L.idto_plant_step.argtypes = [C.c_void_p, C.c_int, P, C.c_int, P, I]
+        L.idto_plant_solve_host.argtypes = [P, P, P, C.c_int, P]
+        L.idto_plant_pd_plus_host.argtypes = [P, P, C.c_int, C.c_int, C.c_int, I, P, P, P, P, C.c_int, P, P]
+        L.idto_plant_pd_plus_host.restype = None
+        L.idto_plant_advance_host.argtypes = [C.c_int, I, I, I, C.c_int, C.c_double, P, P, P]
+        L.idto_plant_advance_host.restype = None
         _lib = L
     return _lib
 
@@ -101,7 +117,9 @@ MPC_SYMBOLS = ["idto_mpc_create", "idto_mpc_destroy", "idto_mpc_num_actuators", 
                "idto_mpc_control", "idto_mpc_start_time", "idto_mpc_spline_eval", "idto_mpc_stats",
                "idto_mpc_batch_create", "idto_mpc_batch_destroy", "idto_mpc_batch_num_actuators", "idto_mpc_batch_update",
                "idto_mpc_batch_state", "idto_mpc_batch_control", "idto_mpc_batch_start_time", "idto_mpc_batch_flag",
-               "idto_mpc_batch_error", "idto_mpc_spline_fit", "idto_mpc_shift_reference"]
+               "idto_mpc_batch_error", "idto_mpc_spline_fit", "idto_mpc_shift_reference",
+               "idto_mpc_batch_plants_begin", "idto_mpc_batch_plants_set_model", "idto_mpc_batch_plants_set_states",
+               "idto_mpc_batch_plants_step", "idto_mpc_batch_plants_state", "idto_mpc_batch_plants_tick"]
 
 
 def _d(a):

@@ -199,6 +199,32 @@ def make_problem(cfg: dict, model: Model | None = None, num_steps: int | None = 
     return prob, sp, q_guess
 
 
+def mpc_parameters(cfg: dict, model: Model) -> dict:
+    """The closed-loop keys of an example's configuration (reference examples/yaml_config.h, example_base.cc:104-144):
+    sim_time_step, controller_frequency, feed_forward and the PD+ gains.  Kp (nq entries) and Kd (nv entries) are the
+    diagonals the reference multiplies the actuation matrix with: row r of Kp [nu, nq] / Kd [nu, nv] carries the gain at
+    the position / velocity of actuated dof r (absent: zeros, as the reference).  substeps_per_tick: plant substeps between
+    two re-plans, round(1 / (controller_frequency sim_time_step))."""
+    act = np.flatnonzero(np.asarray(model.actuated))
+    nq, nv, nu = model.nq, model.nv, len(act)
+    Kp, Kd = np.zeros((nu, nq)), np.zeros((nu, nv))
+    kp, kd = np.asarray(cfg.get("Kp", []), float), np.asarray(cfg.get("Kd", []), float)
+    if kp.size not in (0, nq) or kd.size not in (0, nv):
+        raise ValueError(f"Kp has nq = {nq} entries and Kd nv = {nv} (got {kp.size}, {kd.size})")
+    for r, j in enumerate(act):
+        body = [b for b in range(model.nbodies) if int(model.vstart[b]) <= j][-1]
+        if int(model.jtype[body]) == 3:
+            raise ValueError("an actuated floating joint has no PD+ position gain")
+        qi = int(model.qstart[body]) + (j - int(model.vstart[body]))
+        if kp.size:
+            Kp[r, qi] = kp[qi]
+        if kd.size:
+            Kd[r, j] = kd[j]
+    h, f = float(cfg.get("sim_time_step", 1e-3)), float(cfg.get("controller_frequency", 30))
+    return dict(sim_time_step=h, controller_frequency=f, feed_forward=bool(cfg.get("feed_forward", False)), Kp=Kp, Kd=Kd,
+                substeps_per_tick=int(round(1.0 / (f * h))))
+
+
 # ---- synthetic trajectories for parity tests and the bench (BASELINE.md §3) ----
 def _splitmix64(state):
     state = (state + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF

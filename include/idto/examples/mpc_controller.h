@@ -176,7 +176,36 @@ class BatchModelPredictiveController {
   const std::vector<VectorXd>& last_guess(int b) const { return guesses_[b]; }
   double trust_region_radius(int b) const { return Delta_[b]; }   // what the next tick starts controller b's loop from
 
+  // ---- B plants beside the B controllers (include/idto_hip.h idto_hip_plant_*, csrc/plant.h): plant b is simulated on the
+  // device with the optimizer's own contact model at `sim_time_step`, under the PD+ law of reference
+  // examples/pd_plus_controller.cc on controller b's stored plan; TickWithPlants is one closed-loop tick - the substeps,
+  // then every controller's re-plan from its plant's state - enqueued at once and waited for once, no state crossing the
+  // bus on the way in.  Kp [nu][nq] and Kd [nu][nv] row-major (nu = num_actuators()).
+  struct PlantParams {
+    double sim_time_step = 1e-3;
+    std::vector<double> Kp, Kd;
+    bool feed_forward = false;
+    int record_capacity = 0;   // states per plant that one step may record (0: the library's default)
+  };
+  void BeginPlants(const PlantParams& params);   // throws std::runtime_error with the library's refusal
+  // plant b gets physics of its own (null: the controllers'): the rules of idto_hip_set_model_batch; the controllers keep theirs
+  void SetPlantModel(int b, const idto_model_t* model, const idto_contact_params_t* contact);
+  void SetPlantStates(const double* times, const double* x);   // [B], [B][nq + nv]
+  void SetPlantStates(const std::vector<double>& times, const std::vector<VectorXd>& x);
+  void StepPlants(int substeps);                 // one launch, one wait (the status words come back); plant_state / plant_time fetch
+  // StepPlants(substeps) + UpdateAll(plant times, plant states) as one device pass; its outputs are UpdateAll's
+  bool TickWithPlants(int substeps);
+  const VectorXd& plant_state(int b);            // [q; v]
+  double plant_time(int b);
+  int plant_status(int b);                       // of the last StepPlants / TickWithPlants: 0 ok, 1 a failed pivot, 2 a non-finite state or input
+
  private:
+  bool Tick(const double* times, const double* x0s, int substeps);
+  void FetchPlants();
+  bool plants_ = false, plants_stale_ = true;
+  std::vector<double> plant_times_, plant_x_;
+  std::vector<int> plant_status_;
+  std::vector<VectorXd> plant_states_;
   void AdoptPlan(int b, const double* plan);
   TrajectoryOptimizer<double>* optimizer_;
   idto_hip_ctx* ctx_ = nullptr;             // the controllers' batch context (owned)
@@ -192,6 +221,26 @@ class BatchModelPredictiveController {
   std::vector<double> Delta_, Delta_out_, rows_, q_, v_, tau_, guess_, plans_, final_cost_, x0_;
   std::vector<int> status_;
   std::string tick_error_;
+};
+
+// Plants on any optimizer's context, without controllers: forward dynamics a = M^-1 (tau - ID(q, v, 0)) and rollouts under
+// a held torque (include/idto_hip.h idto_hip_forward_dynamics, idto_hip_plant_* in hold mode), one plant per problem of the
+// context - the optimizer's own context has one.  A view: it owns nothing but the plants' storage inside the context.
+class Plants {
+ public:
+  explicit Plants(idto_hip_ctx* context);   // e.g. optimizer.device_context()
+  int num_plants() const { return B_; }
+  // x [B][nq + nv], tau [B][nv] -> a [B][nv]; M [B][nv * nv] column-major and bias [B][nv] may be null
+  void ForwardDynamics(const double* x, const double* tau, double* a, double* M = nullptr, double* bias = nullptr);
+  void Begin(double sim_time_step, int record_capacity = 0);
+  void SetModel(int b, const idto_model_t* model, const idto_contact_params_t* contact);
+  void SetStates(const double* times, const double* x);
+  void GetStates(double* times, double* x);
+  // `substeps` under tau_hold [B][nv]; x_record [B][substeps / record_every][nq + nv] and status [B][2] may be null
+  void Step(int substeps, const double* tau_hold, int record_every = 0, double* x_record = nullptr, int* status = nullptr);
+ private:
+  idto_hip_ctx* ctx_;
+  int B_;
 };
 
 // reference examples/mpc_controller.h:155-214: x(t) = [q(t); v(t)] and u(t) of a stored trajectory

@@ -497,6 +497,71 @@ int idto_hip_mpc_batch_replan(idto_hip_ctx* ctx, const double* times, const doub
                               double* v_out, double* tau_out, double* final_cost, int* status, int* best, double* guess_out,
                               double* plans_out);
 
+/* ---- Plants on the device (csrc/plant.h, csrc/plant_step.h): forward dynamics a = M(q)^-1 (tau_applied - ID(q, v, 0)) from
+ * the optimizer's own inverse dynamics and compliant contact model, and semi-implicit Euler substeps of it, one workgroup
+ * per plant.  A context of batch B has B plants.  Plant b's physics is the context's model - the context's record b where
+ * idto_hip_set_model_batch gave it one - until idto_hip_plant_set_model gives it its own.  The plants' storage (parameter
+ * records, states, torques, the state record, status words) is one allocation of the context's, made by
+ * idto_hip_plant_begin (by the first idto_hip_forward_dynamics on a context that never began a plant, with default
+ * parameters); a context that calls neither runs exactly the launches it ran before.
+ * The plants' records are a SNAPSHOT taken when the storage is made: a later idto_hip_set_model_batch on the context does
+ * not reach the plants (call idto_hip_plant_begin again, or idto_hip_plant_set_model).
+ * Every entry returns 0, or a negative value with idto_hip_last_error. */
+
+/* a[B][nv] = the forward dynamics at x[B][nq + nv] = [q; v] under tau_applied[B][nv]; M_out[B][nv * nv] (column-major) and
+ * bias_out[B][nv] (either may be NULL): the mass matrix' columns ID(q, 0, e_j) and the bias ID(q, v, 0) as evaluated.  One
+ * launch, one wait.  A plant whose M has a pivot of its LDL^T that is not > 0 and finite, or whose input is not finite, makes
+ * the call fail, naming the plant (the other plants' outputs are valid). */
+int idto_hip_forward_dynamics(idto_hip_ctx* ctx, const double* x, const double* tau_applied, double* a_out, double* M_out,
+                              double* bias_out);
+
+#define IDTO_PLANT_HOLD 0     /* tau_applied = idto_hip_plant_step's tau_hold, held over the launch */
+#define IDTO_PLANT_PD_PLUS 1  /* tau_applied = Kp (q_nom - q) + Kd (v_nom - v) [+ u_nom] on the actuated dofs, the nominal values
+                                 from the plant's stored plan (idto_hip_mpc_batch_*) at the substep's time */
+typedef struct {
+  double h;                  /* the substep, > 0 */
+  int mode;                  /* IDTO_PLANT_HOLD / IDTO_PLANT_PD_PLUS */
+  /* PD+ only: Kp[nu][nq] and Kd[nu][nv] row-major with their sizes in doubles (checked against the context's nu, nq, nv),
+   * feed_forward != 0 adds the plan's control; the actuated dofs are idto_hip_mpc_batch_begin's */
+  const double* Kp; int kp_size;
+  const double* Kd; int kd_size;
+  int feed_forward;
+  int record_capacity;       /* states per plant that one idto_hip_plant_step may record (0: 64) */
+  int block_threads;         /* 0: from the model's size; 64, 128, 192 or 256: the workgroup (a test aid: a small one makes
+                                the nv + 1 evaluations of a substep go in rounds) */
+} idto_plant_params_t;
+#define IDTO_PLANT_MAX_SUBSTEPS 4096   /* of one launch: a single launch stays short on a shared device */
+/* Refused by name before any device work: a context with child contexts, h <= 0, an unknown mode, PD+ before
+ * idto_hip_mpc_batch_begin, gains of the wrong size or not finite, nv > 64 (the solve runs a lane per row on one
+ * wavefront), a model with a stem below the common body (idto_hip_forward_dynamics refuses the last two as well).  May be called again: new storage, every plant the context's model again, states zero. */
+int idto_hip_plant_begin(idto_hip_ctx* ctx, const idto_plant_params_t* params);
+/* Plant b gets `model` (the context's topology; NULL: the context's model) and `contact` (NULL: the context's): the
+ * checks, the record and the refusal texts are idto_hip_set_model_batch's.  The context's own model is untouched. */
+int idto_hip_plant_set_model(idto_hip_ctx* ctx, int b, const idto_model_t* model, const idto_contact_params_t* contact);
+/* times[B], x[B][nq + nv] = [q; v] */
+int idto_hip_plant_set_state(idto_hip_ctx* ctx, const double* times, const double* x);
+int idto_hip_plant_get_state(idto_hip_ctx* ctx, double* times_out, double* x_out);
+/* `substeps` substeps of every plant in ONE launch (1 <= substeps <= IDTO_PLANT_MAX_SUBSTEPS).  tau_hold[B][nv]: hold mode
+ * only (PD+: NULL).  x_record_out[B][substeps / record_every][nq + nv] (may be NULL; then record_every is ignored): the
+ * state behind every record_every-th substep.  status_out[B][2] (may be NULL): {0 ok | 1 failed pivot | 2 non-finite state
+ * or input, substeps completed}: a plant that fails stops and keeps the state from before the failing substep, the
+ * others are unaffected.  One wait if an output pointer is given; none otherwise - the launch is enqueued only. */
+int idto_hip_plant_step(idto_hip_ctx* ctx, int substeps, const double* tau_hold, int record_every, double* x_record_out,
+                        int* status_out);
+/* One closed-loop tick of B plants and B controllers, enqueued at once and waited for ONCE, no state crossing the bus on the
+ * way in: `substeps` substeps of every plant under PD+ on the current plans (idto_hip_plant_begin with IDTO_PLANT_PD_PLUS);
+ * the kernel's last act writes every plant's [t, q, v] into the tick buffer that mpc_shift_kernel reads; then the body of
+ * idto_hip_mpc_batch_replan (shared code: its arguments without times and x0, its outputs, its return value), the tick
+ * re-planning at the plants' times from the plants' states; one more copy back, x_after_out[B][nq + nv] (may be NULL): the
+ * plants' states behind the substeps, i.e. the x0 of this tick; plant_status_out[B][2] (may be NULL): idto_hip_plant_step's
+ * status words of the tick's substeps - a plant that stopped re-plans from the state it stopped in.  Refused by name before any device work: everything
+ * idto_hip_mpc_batch_replan and idto_hip_plant_step refuse, and plants that are not in PD+ mode. */
+int idto_hip_mpc_batch_tick_plants(idto_hip_ctx* ctx, int substeps, int iterations, int scaling_method, int scaling,
+                                   int normalize_quaternions, const double* Delta0, double Delta_max, double eta,
+                                   const int* constrained_dofs, int nu, double* rows_host, double* Delta_out, double* q_out,
+                                   double* v_out, double* tau_out, double* final_cost, int* status, int* best, double* guess_out,
+                                   double* plans_out, double* x_after_out, int* plant_status_out);
+
 /* Options: "gradients_method" = 0 forward differences (default), 1 / 2 central differences of
  * 2nd / 4th order (SolverParameters::gradients_method, reference solver_parameters.h:26-50,
  * trajectory_optimizer.cc:565-885); 3 (autodiff) is refused.  "reference_solver" = 1 selects the bit-exact restatement of the reference's

@@ -158,6 +158,45 @@ int idto_mpc_spline_fit(const double* breaks, const double* knots, int n, int di
 int idto_mpc_shift_reference(const double* breaks, const double* y_q, const double* m_q, int n, int nq, double start_time, double time,
                              double time_step, const double* q0, const int* selector, double* q_nom, double* guess_out);
 
+/* ---- B plants beside the B controllers of a batch controller: BatchModelPredictiveController::BeginPlants ... TickWithPlants,
+ * include/idto/examples/mpc_controller.h; the device side: include/idto_hip.h idto_hip_plant_*, idto_hip_mpc_batch_tick_plants.
+ * Plant b is simulated on the device with the optimizer's own contact model at sim_time_step under the PD+ law on controller
+ * b's stored plan: Kp[nu][nq], Kd[nu][nv] row-major with their sizes in doubles, feed_forward != 0 adds the plan's control. */
+int idto_mpc_batch_plants_begin(idto_mpc_batch* mpc, double sim_time_step, const double* Kp, int kp_size, const double* Kd, int kd_size,
+                                int feed_forward, int record_capacity);
+/* plant b gets physics of its own (NULL: the controllers'); the controllers keep theirs */
+int idto_mpc_batch_plants_set_model(idto_mpc_batch* mpc, int b, const idto_model_t* model, const idto_contact_params_t* contact);
+int idto_mpc_batch_plants_set_states(idto_mpc_batch* mpc, const double* times, const double* x);   /* [B], [B][nq + nv] */
+int idto_mpc_batch_plants_step(idto_mpc_batch* mpc, int substeps);   /* one launch, one wait */
+/* plant b's time, state [q; v] and the status of its last step (0 ok, 1 failed pivot, 2 non-finite); any may be NULL */
+int idto_mpc_batch_plants_state(idto_mpc_batch* mpc, int b, double* time, double* x, int* status);
+/* One closed-loop tick: idto_mpc_batch_plants_step(substeps), then idto_mpc_batch_update from the plants' times and states, as
+ * ONE device pass waited for once, no state crossing the bus on the way in.  Outputs: idto_mpc_batch_update's. */
+int idto_mpc_batch_plants_tick(idto_mpc_batch* mpc, int substeps, double* q_guess, double* sol_q, double* sol_v, double* sol_tau,
+                               idto_stats_t* stats, int* flags, double* radii, int* tick_ok);
+
+/* ---- One plant on an optimizer's own context (idto::examples::mpc::Plants): forward dynamics a[nv] = M^-1 (tau - ID(q, v, 0)) at
+ * x = [q; v] (M[nv * nv] column-major and bias[nv] may be NULL), and rollouts under a held torque: begin, set / get the state,
+ * `substeps` substeps in one launch (x_record[substeps / record_every][nq + nv] and status[2] may be NULL). */
+int idto_plant_forward_dynamics(idto_opt* opt, const double* x, const double* tau, double* a, double* M, double* bias);
+int idto_plant_begin(idto_opt* opt, double sim_time_step, int record_capacity);
+int idto_plant_set_state(idto_opt* opt, double time, const double* x);
+int idto_plant_get_state(idto_opt* opt, double* time, double* x);
+int idto_plant_step(idto_opt* opt, int substeps, const double* tau_hold, int record_every, double* x_record, int* status);
+
+/* csrc/plant_step.h on the host (exported for the tests that hold the device's plant_kernel to it; include/idto_hip.h
+ * idto_hip_plant_*).  idto_plant_solve_host: a = M^-1 (tau_applied - bias) by the un-pivoted LDL^T, M[n][n] column-major (its
+ * lower triangle is read); returns -1, or the index of the first pivot that is not > 0 and finite.  idto_plant_pd_plus_host:
+ * tau_out[nv] = the PD+ law's u (Kp[nu][nq], Kd[nu][nv] row-major; u_nom[nu] is read only with feed_forward) on the actuated
+ * dofs, 0 elsewhere.  idto_plant_advance_host: one semi-implicit Euler substep in place, v += h a, q += h N(q) v, the
+ * quaternions of floating joints normalised (jtype, qstart, vstart: the model's tables). */
+int idto_plant_solve_host(const double* M, const double* tau_applied, const double* bias, int n, double* a_out);
+void idto_plant_pd_plus_host(const double* Kp, const double* Kd, int nu, int nq, int nv, const int* actuated_dofs, const double* q,
+                             const double* v, const double* q_nom, const double* v_nom, int feed_forward, const double* u_nom,
+                             double* tau_out);
+void idto_plant_advance_host(int nbodies, const int* jtype, const int* qstart, const int* vstart, int nq, double h, double* q,
+                             double* v, const double* a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,8 @@ usage: check_resources.py [--compile] [remarks files ...]     (--compile: produc
 import os, re, subprocess, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REMARKS = [os.path.join(ROOT, "build", "fd_launch.remarks"), os.path.join(ROOT, "build", "idto_hip.remarks")]
+REMARKS = [os.path.join(ROOT, "build", "fd_launch.remarks"), os.path.join(ROOT, "build", "idto_hip.remarks"),
+           os.path.join(ROOT, "build", "plant_launch.remarks")]
 
 # kernel (demangled, without "idto_dev::" and arguments) -> (max spilled VGPRs, max scratch bytes per lane, max spilled SGPRs)
 # Values: what profiles/r05_isa_resources.txt records, the SGPR figure with a margin of 24 (it moves by a few with every
@@ -110,6 +111,16 @@ LIMITS = {
     "fd_along_models_kernel<8, 6>": (0, 20, 71 + 24),
     "fd_along_models_kernel<8, 7>": (0, 0, 120 + 24),
     "fd_along_models_kernel<8, 8>": (0, 0, 127 + 24),
+    # (the plants' kernel, csrc/plant.h: the GENERIC evaluation id_eval<MAXC> for every model - the tree shapes' straight-line
+    # evaluation is not in it.  The figures are of the same kind as the generic fd_kernel<MAXC, 0>'s (24 / 28 / 69 / 564 spilled
+    # vector registers in this build: the chain's state in registers over the contact loop): up to MAXC = 3 the spills go to
+    # accumulation registers, no scratch; MAXC = 4 and 8 spill to scratch as fd_kernel<4, 0> and fd_kernel<8, 0> do
+    # (DESIGN.md section 14.2).  The exchange form keeps the chain in LDS and spills no vector register.)
+    "plant_kernel<2, false>": (24, 0, 171 + 24),
+    "plant_kernel<3, false>": (28, 0, 182 + 24),
+    "plant_kernel<4, false>": (87, 264, 162 + 24),
+    "plant_kernel<8, false>": (600, 1412, 201 + 24),
+    "plant_kernel<8, true>": (0, 0, 147 + 24),
     "ls_gather_batch_kernel": (0, 0, 0 + 24),
     "ls_trial_kernel": (0, 0, 0 + 24),
     "ls_cost_kernel": (0, 0, 0 + 24),
@@ -120,13 +131,14 @@ LIMITS = {
 
 
 def compile_remarks():
-    """The two translation units with the remark pass on (device code only, no object files kept)."""
+    """The three translation units with the remark pass on (device code only, no object files kept)."""
     os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Iinclude", "-Iidto_amd/csrc", "-S",
              "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     jobs = [([hipcc] + flags + ["idto_amd/csrc/fd_launch.hip", "-o", "/dev/null"], REMARKS[0]),
-            ([hipcc] + flags + ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "idto_amd/csrc/idto_hip.hip", "-o", "/dev/null"], REMARKS[1])]
+            ([hipcc] + flags + ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "idto_amd/csrc/idto_hip.hip", "-o", "/dev/null"], REMARKS[1]),
+            ([hipcc] + flags + ["idto_amd/csrc/plant_launch.hip", "-o", "/dev/null"], REMARKS[2])]
     procs = [(subprocess.Popen(cmd, cwd=ROOT, stderr=open(out, "w")), out) for cmd, out in jobs]
     for p, out in procs:
         if p.wait() != 0:

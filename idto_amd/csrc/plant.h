@@ -15,8 +15,8 @@
 // The applied torque is either held over the launch or the PD+ law on the plant's stored plan (mpc_batch.h: the MPC
 // context's current plane, staged into LDS with the gains): the nominal [q, v, u] at the substep's time is mpc_spline.h's
 // evaluation at t - start_time, clamped to the plan's range as the host's Interpolator clamps.
-// Instantiated: the generic evaluation for chains of up to 2, 3, 4 and 8 bodies and the exchange form id_eval<8, true> for
-// models with shared pairs; a stem below the common body has no instantiation (idto_hip_plant_begin refuses it).
+// Instantiated: the generic evaluation for chains of up to 2, 3, 4 and 8 bodies, the exchange form id_eval<8, true> for
+// models with shared pairs and id_eval<8, true, true> for a stem below the common body.
 // Status per plant: 0 ok; 1 a pivot that is not > 0 and finite; 2 a non-finite state or input - each with the substep.  A
 // plant that fails stops and keeps the state from before the failing substep.
 #pragma once
@@ -61,7 +61,7 @@ __host__ __device__ inline int plant_lds_doubles(int nq, int nv, int blob_n, int
   return 3 * nq + 7 * nv + (2 * nv - 1) + (nv + 1) * nv + 2 + blob_n + (threads / npaths) * xch_eval_doubles(nxb, nstem);
 }
 
-template <int MAXC, bool XCH>
+template <int MAXC, bool XCH, bool STEM = false>
 IDTO_DEV void plant_body(const DevModel& M, const DevContact& cp, const PlantArgs& A, const int b) {
   extern __shared__ double lds[];
   const int tid = threadIdx.x, nt = blockDim.x;
@@ -138,7 +138,7 @@ IDTO_DEV void plant_body(const DevModel& M, const DevContact& cp, const PlantArg
       double* dst = (el < E) ? etau + ee * nv : edump;
       const double* ev = full ? v : zero;
       const double* ea = full ? zero : ramp + (nv - ee);
-      if constexpr (XCH) id_eval<MAXC, true>(Ml, cp, path, full, q, ev, ea, dst, xch + (tid / K) * xeval);
+      if constexpr (XCH) id_eval<MAXC, true, STEM>(Ml, cp, path, full, q, ev, ea, dst, xch + (tid / K) * xeval);
       else id_eval<MAXC>(Ml, cp, path, full, q, ev, ea, dst);
     }
     __syncthreads();
@@ -220,10 +220,10 @@ IDTO_DEV void plant_body(const DevModel& M, const DevContact& cp, const PlantArg
 
 // The plant's DevModel and DevContact are read from its parameter record through the constant address space, as
 // fd_models_kernel reads its problem's (id_eval.h record_at).
-template <int MAXC, bool XCH = false>
+template <int MAXC, bool XCH = false, bool STEM = false>
 __global__ void __launch_bounds__(256) plant_kernel(PlantArgs A) {
   const RecordPtr rec = record_at(A.records, (size_t)blockIdx.x * A.mstride);
-  plant_body<MAXC, XCH>(*(const DevModel*)(rec + A.rec_model), *(const DevContact*)(rec + A.rec_contact), A, (int)blockIdx.x);
+  plant_body<MAXC, XCH, STEM>(*(const DevModel*)(rec + A.rec_model), *(const DevContact*)(rec + A.rec_contact), A, (int)blockIdx.x);
 }
 
 }  // namespace idto_dev

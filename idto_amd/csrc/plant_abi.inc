@@ -19,16 +19,9 @@ static int PlantBlock(const idto_hip_ctx* c, int forced, bool pd) {
   return t;
 }
 
-// The classes of model that plant_kernel serves.  A stem below the common body (id_eval<8, true, true>) is not among them: its
-// instantiation returned mass-matrix columns that differ from the oracle's far beyond round-off, reading the code did not
-// find the cause, and the bar is ==, not a tolerance (DESIGN.md section 14.2).
+// The classes of model that plant_kernel serves
 static int PlantServes(const idto_hip_ctx* c, const char* who) {
   if (c->nv > 64) { g_err = std::string(who) + ": nv > 64 (the solve of M a = tau - c runs a lane per row on one wavefront)"; return -1; }
-  if (c->M.nstem > 1) {
-    g_err = std::string(who) + ": models with a stem below the common body are not served by the plants' kernel (its instantiation "
-            "did not equal the oracle bit for bit and is left out)";
-    return -1;
-  }
   return 0;
 }
 
@@ -88,8 +81,13 @@ static int PlantAllocate(idto_hip_ctx* c, const idto_plant_params_t& prm) {
   if (ok && pd) ok = hipMemcpy(p->Kp, prm.Kp, (size_t)nu * nq * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
                      hipMemcpy(p->Kd, prm.Kd, (size_t)nu * nv * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) { g_err = "plant_begin: hipMemcpy (parameter records, gains) failed"; Release(c, &p->base); return -2; }
-  plant_set_max_lds(160 * 1024);
-  (void)hipGetLastError();
+  // (a launch above 64 KiB of dynamic LDS needs the opt-in: an instantiation that did not get it would fail at its launch)
+  if (const hipError_t e = plant_set_max_lds(160 * 1024); e != hipSuccess) {
+    (void)hipGetLastError();
+    g_err = std::string("plant_begin: hipFuncSetAttribute (160 KiB of dynamic LDS for plant_kernel) failed: ") + hipGetErrorString(e);
+    Release(c, &p->base);
+    return -2;
+  }
   c->plant = p.release();
   return 0;
 }
@@ -184,7 +182,7 @@ static PlantArgs PlantCommonArgs(const idto_hip_ctx* c) {
 static int PlantEnqueue(idto_hip_ctx* c, const PlantArgs& A, int lds) {
   PlantLaunch L{};
   L.plants = c->batch; L.block = c->plant->block; L.lds = lds; L.stream = c->stream; L.args = A;
-  L.maxc = c->maxc; L.nxb = c->M.nxb;
+  L.maxc = c->maxc; L.nxb = c->M.nxb; L.nstem = c->M.nstem;
   plant_launch(L);
   HIP_OK(hipGetLastError());
   return 0;

@@ -13,11 +13,12 @@ struct PlantLaunch {
   hipStream_t stream;
   PlantArgs args;
   int maxc;      // the model's longest chain: the generic evaluation for chains of up to 2, 3, 4 and 8 bodies
-  int nxb;       // DevModel's: shared pairs -> id_eval<8, true> (a stem below the common body has no instantiation: DESIGN.md section 14.2)
+  int nxb;       // DevModel's: shared pairs -> id_eval<8, true>
+  int nstem;     // DevModel's: a stem below the common body -> id_eval<8, true, true>
 };
-// enqueues plant_kernel<MAXC, XCH>; the caller checks hipGetLastError()
+// enqueues plant_kernel<MAXC, XCH, STEM>; the caller checks hipGetLastError()
 void plant_launch(const PlantLaunch& a);
-// opt-in of every instantiation to `max_lds` bytes of dynamic LDS
-void plant_set_max_lds(int max_lds);
+// opt-in of every instantiation to `max_lds` bytes of dynamic LDS: hipSuccess, or the first instantiation's error
+hipError_t plant_set_max_lds(int max_lds);
 
 }  // namespace idto_dev

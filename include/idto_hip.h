@@ -533,7 +533,7 @@ typedef struct {
 #define IDTO_PLANT_MAX_SUBSTEPS 4096   /* of one launch: a single launch stays short on a shared device */
 /* Refused by name before any device work: a context with child contexts, h <= 0, an unknown mode, PD+ before
  * idto_hip_mpc_batch_begin, gains of the wrong size or not finite, nv > 64 (the solve runs a lane per row on one
- * wavefront), a model with a stem below the common body (idto_hip_forward_dynamics refuses the last two as well).  May be called again: new storage, every plant the context's model again, states zero. */
+ * wavefront; idto_hip_forward_dynamics refuses it as well).  May be called again: new storage, every plant the context's model again, states zero. */
 int idto_hip_plant_begin(idto_hip_ctx* ctx, const idto_plant_params_t* params);
 /* Plant b gets `model` (the context's topology; NULL: the context's model) and `contact` (NULL: the context's): the
  * checks, the record and the refusal texts are idto_hip_set_model_batch's.  The context's own model is untouched. */

@@ -115,12 +115,16 @@ LIMITS = {
     # evaluation is not in it.  The figures are of the same kind as the generic fd_kernel<MAXC, 0>'s (24 / 28 / 69 / 564 spilled
     # vector registers in this build: the chain's state in registers over the contact loop): up to MAXC = 3 the spills go to
     # accumulation registers, no scratch; MAXC = 4 and 8 spill to scratch as fd_kernel<4, 0> and fd_kernel<8, 0> do
-    # (DESIGN.md section 14.2).  The exchange form keeps the chain in LDS and spills no vector register.)
-    "plant_kernel<2, false>": (24, 0, 171 + 24),
-    "plant_kernel<3, false>": (28, 0, 182 + 24),
-    "plant_kernel<4, false>": (87, 264, 162 + 24),
-    "plant_kernel<8, false>": (600, 1412, 201 + 24),
-    "plant_kernel<8, true>": (0, 0, 147 + 24),
+    # (DESIGN.md section 14.2).  The exchange form keeps the chain in LDS and spills no vector register.  The third template
+    # argument, STEM, came with plant_kernel<8, true, true>: the five rows before it are the same code under a longer name.)
+    "plant_kernel<2, false, false>": (24, 0, 171 + 24),
+    "plant_kernel<3, false, false>": (28, 0, 182 + 24),
+    "plant_kernel<4, false, false>": (87, 264, 162 + 24),
+    "plant_kernel<8, false, false>": (600, 1412, 201 + 24),
+    "plant_kernel<8, true, false>": (0, 0, 147 + 24),
+    # (a stem below the common body, id_eval<8, true, true>: the exchange form again - no vector register spilled, no scratch; the
+    # stem walk's loop state makes it the instantiation with the most scalar registers spilled to lanes beside <8, false, false>)
+    "plant_kernel<8, true, true>": (0, 0, 196 + 24),
     "ls_gather_batch_kernel": (0, 0, 0 + 24),
     "ls_trial_kernel": (0, 0, 0 + 24),
     "ls_cost_kernel": (0, 0, 0 + 24),

@@ -201,6 +201,23 @@ int idto_opt_solve(idto_opt* o, const double* q_guess, double* sol_q, double* so
   });
 }
 
+int idto_opt_scene_sizes(idto_opt* o, int* nbodies, int* npairs, int* body_doubles, int* pair_doubles) {
+  return Guard([&] {
+    if (idto_hip_scene_sizes(o->to->device_context(), nbodies, npairs, body_doubles, pair_doubles))
+      throw std::runtime_error(idto_hip_last_error());
+  });
+}
+int idto_opt_scene_report(idto_opt* o, int nstates, const double* q, const double* v, double* bodies_out, double* pairs_out,
+                          double* tau_contact_out, double* tau_pairs_out) {
+  return Guard([&] {
+    if (nstates < 1 || !q || !v) throw std::runtime_error("scene_report: nstates >= 1 states q[nstates][nq], v[nstates][nv] are required");
+    if (!bodies_out && !pairs_out && !tau_contact_out && !tau_pairs_out) throw std::runtime_error("scene_report: every output is NULL: nothing to report");
+    const SceneReport r = o->to->EvalScene(Rows(q, nstates, o->nq), Rows(v, nstates, o->nv), tau_pairs_out != nullptr);
+    auto out = [](const std::vector<double>& from, double* to) { if (to) std::copy(from.begin(), from.end(), to); };
+    out(r.bodies, bodies_out); out(r.pairs, pairs_out); out(r.tau_contact, tau_contact_out); out(r.tau_pairs, tau_pairs_out);
+  });
+}
+
 int idto_opt_solve_batch(idto_opt* o, int B, const idto_problem_t* problems, const double* q_guesses, int only_best,
                          double* sol_q, double* sol_v, double* sol_tau, idto_stats_t* stats, int* flags, int* reasons,
                          double* final_costs, int* best) {

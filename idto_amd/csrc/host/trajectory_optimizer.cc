@@ -505,6 +505,19 @@ const std::vector<VectorXd>& TO::EvalA(const TrajectoryOptimizerState<T>& s) con
 const std::vector<VectorXd>& TO::EvalTau(const TrajectoryOptimizerState<T>& s) const { CalcTrajectoryData(s); return s.cache_.tau; }
 const std::vector<MatrixXd>& TO::EvalNplus(const TrajectoryOptimizerState<T>& s) const { CalcKinematics(s); return s.cache_.nplus; }
 double TO::EvalCost(const TrajectoryOptimizerState<T>& s) const { CalcTrajectoryData(s); return s.cache_.cost; }
+
+SceneReport TO::EvalScene(const std::vector<VectorXd>& q, const std::vector<VectorXd>& v, bool pair_rows) const {
+  if (q.empty() || q.size() != v.size()) throw std::runtime_error("EvalScene: as many velocities as positions, at least one");
+  const std::size_t w = (std::size_t)nq_ + nv_;
+  std::vector<double> x(q.size() * w);
+  for (std::size_t t = 0; t < q.size(); ++t) {
+    if ((int)q[t].size() != nq_ || (int)v[t].size() != nv_) throw std::runtime_error("EvalScene: a state of the wrong size");
+    std::copy(q[t].begin(), q[t].end(), x.begin() + t * w);
+    std::copy(v[t].begin(), v[t].end(), x.begin() + t * w + nq_);
+  }
+  return Scene(dev()).Report((int)q.size(), x.data(), nv_, IDTO_SCENE_MODELS_PROBLEMS, pair_rows);
+}
+
 const VelocityPartials<double>& TO::EvalVelocityPartials(const TrajectoryOptimizerState<T>& s) const {
   CalcVelocityPartials(s);
   return s.cache_.v_partials;

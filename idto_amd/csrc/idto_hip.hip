@@ -40,6 +40,7 @@
 #include "linesearch.h"
 #include "mpc_batch.h"
 #include "plant_launch.h"
+#include "scene_launch.h"
 #include "host/context_layout.h"
 #include "host/model_batch.h"
 #include "host/model_tables.h"
@@ -232,11 +233,21 @@ struct PlantState {
   double* tick_pin = nullptr; size_t tick_pin_cap = 0;   // ... of the plants' states behind a tick (idto_hip_mpc_batch_tick_plants)
 };
 
+// idto_hip_scene_report: the report's storage (scene_abi.inc SceneEnsure), made at the first report - the body of every
+// geometry, the states and the outputs of a call on the device, their pinned staging
+struct SceneState {
+  int* geom_body = nullptr;
+  double* in = nullptr; size_t in_cap = 0;
+  double* out = nullptr; size_t out_cap = 0;
+  double* pin = nullptr; size_t pin_cap = 0;
+};
+
 struct idto_hip_ctx {
   int device = 0;
   MpcBatchState* mpc = nullptr;
   unsigned mpc_generation = 0;   // calls of idto_hip_mpc_batch_begin so far
   PlantState* plant = nullptr;
+  SceneState* scene = nullptr;
   // (batch contexts) what the context was created from, and one single-problem context per problem, made on first use
   std::unique_ptr<HostModelCopy> host_model;
   std::vector<std::unique_ptr<HostProblemCopy>> host_problems;
@@ -1053,6 +1064,10 @@ void idto_hip_destroy(idto_hip_ctx* c) {
     if (c->plant->pin) (void)hipHostFree(c->plant->pin);
     if (c->plant->tick_pin) (void)hipHostFree(c->plant->tick_pin);
     delete c->plant;
+  }
+  if (c->scene) {   // (its device buffers are in c->allocs)
+    if (c->scene->pin) (void)hipHostFree(c->scene->pin);
+    delete c->scene;
   }
   if (c->mpc) {   // (its device buffers are in c->allocs)
     if (c->mpc->tick_pin) (void)hipHostFree(c->mpc->tick_pin);
@@ -3305,6 +3320,7 @@ int idto_hip_mpc_batch_replan(idto_hip_ctx* c, const double* times, const double
 }
 
 #include "plant_abi.inc"   // idto_hip_forward_dynamics, idto_hip_plant_*
+#include "scene_abi.inc"   // idto_hip_scene_sizes, idto_hip_scene_report
 
 // The batch loop with everything a caller reads afterwards brought back under the loop's one wait, and the best problem
 // chosen on the device (trust_region.h tr_gather_batch_kernel).

@@ -27,6 +27,27 @@ PLANT_HOLD, PLANT_PD_PLUS = 0, 1
 PLANT_MAX_SUBSTEPS = 4096
 
 
+SCENE_MODELS_PROBLEMS, SCENE_MODELS_PLANTS = 0, 1
+SCENE_BODY_DOUBLES, SCENE_PAIR_DOUBLES = 18, 20
+
+
+class SceneReport:
+    """What idto_hip_scene_report returns, as named views of its arrays (include/idto_hip.h IDTO_SCENE_PAIR_*).  Leading axes:
+    [batch, nstates] (a single problem: [nstates]), then the body or the pair.
+      bodies [..., nbodies, 18]: X_WB [..., 12] = R_WB row-major, p;  V_WB [..., 6] = w, v of the body origin
+      pairs [..., npairs, 20]: active (bool), phi, normal (A towards B), Ca, Cb, vn, vt, fn, force (on body B at (Ca + Cb) / 2)
+      tau_contact [..., nv]: the generalised force that contact applies;  tau_pairs [..., npairs, nv] or None: its rows"""
+
+    def __init__(self, bodies, pairs, tau_contact, tau_pairs):
+        self.bodies, self.pairs, self.tau_contact, self.tau_pairs = bodies, pairs, tau_contact, tau_pairs
+        self.X_WB, self.V_WB = bodies[..., 0:12], bodies[..., 12:18]
+        self.active = pairs[..., 0] != 0.0
+        self.phi = pairs[..., 1]
+        self.normal, self.Ca, self.Cb = pairs[..., 2:5], pairs[..., 5:8], pairs[..., 8:11]
+        self.vn, self.vt = pairs[..., 11], pairs[..., 12:15]
+        self.fn, self.force = pairs[..., 15], pairs[..., 16:19]
+
+
 class CPlantParams(C.Structure):
     """idto_plant_params_t (include/idto_hip.h)"""
     _fields_ = [("h", C.c_double), ("mode", C.c_int), ("Kp", C.POINTER(C.c_double)), ("kp_size", C.c_int),
@@ -98,6 +119,8 @@ def lib():
         L.idto_hip_plant_step.argtypes = [C.c_void_p, C.c_int, pd, C.c_int, pd, pi]
         L.idto_hip_mpc_batch_tick_plants.argtypes = ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, pd, C.c_double, C.c_double,
                                                       pi, C.c_int, pd, pd, pd, pd, pd, pd, pi, pi, pd, pd, pd, pi])
+        L.idto_hip_scene_sizes.argtypes = [C.c_void_p, pi, pi, pi, pi]
+        L.idto_hip_scene_report.argtypes = [C.c_void_p, C.c_int, pd, C.c_int, pd, pd, pd, pd]
         L.idto_hip_tr_reject.argtypes = [C.c_void_p]
         L.idto_hip_tr_set_scale_memory.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.idto_hip_tr_set_convergence.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -161,6 +184,7 @@ EXPORTED_SYMBOLS = [
     "idto_hip_mpc_batch_begin", "idto_hip_mpc_batch_store", "idto_hip_mpc_batch_shift", "idto_hip_mpc_batch_replan",
     "idto_hip_forward_dynamics", "idto_hip_plant_begin", "idto_hip_plant_set_model", "idto_hip_plant_set_state",
     "idto_hip_plant_get_state", "idto_hip_plant_step", "idto_hip_mpc_batch_tick_plants",
+    "idto_hip_scene_sizes", "idto_hip_scene_report",
     "idto_hip_rccl_info", "idto_hip_comm_unique_id", "idto_hip_comm_init", "idto_hip_comm_init_all", "idto_hip_comm_destroy",
     "idto_hip_allgather_slab", "idto_hip_gn_step_sharded", "idto_hip_gn_step_multi", "idto_hip_eval_partials_multi",
     "idto_hip_trace_enable", "idto_hip_trace_mark", "idto_hip_trace_dump",
@@ -323,6 +347,30 @@ class HipPath:
                                        dptr(rec) if rec is not None else None,
                                        st.ctypes.data_as(C.POINTER(C.c_int)) if st is not None else None))
         return rec, st
+
+    # ---- the scene report (include/idto_hip.h idto_hip_scene_report)
+    def scene_sizes(self):
+        """-> (nbodies, npairs, doubles per body, doubles per pair)"""
+        out = [C.c_int() for _ in range(4)]
+        _chk(lib().idto_hip_scene_sizes(self.h, *[C.byref(o) for o in out]))
+        return tuple(o.value for o in out)
+
+    def scene_report(self, x, models: int = SCENE_MODELS_PROBLEMS, pair_rows: bool = False) -> SceneReport:
+        """x: [batch, nstates, nq + nv] (a single problem: [nstates, nq + nv]) = [q; v] per state -> SceneReport.  models:
+        SCENE_MODELS_PROBLEMS (problem b's physics) or SCENE_MODELS_PLANTS (plant b's); pair_rows: tau_pairs as well"""
+        B, w = self.batch, self.nq + self.nv
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+        squeeze = B == 1 and x.ndim == 2
+        x = x.reshape(B, -1, w)
+        S = x.shape[1]
+        nb, npairs, bd, pdn = self.scene_sizes()
+        bodies, pairs = np.zeros((B, S, nb, bd)), np.zeros((B, S, npairs, pdn))
+        tau, rows = np.zeros((B, S, self.nv)), (np.zeros((B, S, npairs, self.nv)) if pair_rows else None)
+        _chk(lib().idto_hip_scene_report(self.h, int(S), dptr(x), int(models), dptr(bodies), dptr(pairs), dptr(tau),
+                                         dptr(rows) if rows is not None else None))
+        if squeeze:   # (a single problem given as [nstates, nq + nv])
+            bodies, pairs, tau, rows = bodies[0], pairs[0], tau[0], (rows[0] if rows is not None else None)
+        return SceneReport(bodies, pairs, tau, rows)
 
     def solver_status_batch(self):
         out = (C.c_int * self.batch)()

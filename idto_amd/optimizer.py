@@ -48,6 +48,8 @@ def lib():
                                                   C.POINTER(C.c_int), C.POINTER(C.c_int), P, C.POINTER(C.c_int)]
         L.idto_opt_solve_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(CProblem), P, C.c_int, P, P, P, C.POINTER(CStats),
                                            C.POINTER(C.c_int), C.POINTER(C.c_int), P, C.POINTER(C.c_int)]
+        L.idto_opt_scene_sizes.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
+        L.idto_opt_scene_report.argtypes = [C.c_void_p, C.c_int, P, P, P, P, P, P]
         L.idto_opt_batch_error.argtypes = [C.c_void_p, C.c_int]
         L.idto_opt_batch_error.restype = C.c_char_p
         L.idto_opt_last_batch_route.argtypes = [C.c_void_p]
@@ -112,6 +114,7 @@ EXPORTED_SYMBOLS = [
     "idto_opt_ws_set_q", "idto_opt_ws_get", "idto_opt_ws_solve", "idto_opt_reset_initial_conditions",
     "idto_opt_update_nominal_trajectory", "idto_opt_eval", "idto_opt_dogleg", "idto_opt_trust_ratio",
     "idto_opt_solve_batch", "idto_opt_solve_batch_models", "idto_opt_batch_error", "idto_opt_last_batch_route",
+    "idto_opt_scene_sizes", "idto_opt_scene_report",
 ]
 MPC_SYMBOLS = ["idto_mpc_create", "idto_mpc_destroy", "idto_mpc_num_actuators", "idto_mpc_update", "idto_mpc_state",
                "idto_mpc_control", "idto_mpc_start_time", "idto_mpc_spline_eval", "idto_mpc_stats",
@@ -280,6 +283,27 @@ class TrajectoryOptimizer:
         solution.q, solution.v, solution.tau = q, v, tau
         self.last_convergence_reason = reason.value
         return SOLVER_FLAGS[flag.value]
+
+    def scene_report(self, solution_or_q, v=None, pair_rows: bool = False):
+        """TrajectoryOptimizer::EvalScene, what replaces the reference's EvalPlantContext: body poses and spatial velocities,
+        per-pair signed distances, witness points and contact forces and the generalised force of contact at the states of a
+        solution - `scene_report(solution)` - or at `scene_report(q, v)` with q [S, nq], v [S, nv].  -> hip.SceneReport; one
+        launch of the device, one wait.  The contact inside solution.tau[t] is -tau_contact[t + 1]."""
+        from .hip import SceneReport
+        q = solution_or_q.q if v is None else solution_or_q
+        v = solution_or_q.v if v is None else v
+        q, v = np.ascontiguousarray(_d(q)).reshape(-1, self.nq), np.ascontiguousarray(_d(v)).reshape(-1, self.nv)
+        if len(q) != len(v):
+            raise RuntimeError("scene_report: as many velocities as positions")
+        S = len(q)
+        sizes = [C.c_int() for _ in range(4)]
+        self._chk(lib().idto_opt_scene_sizes(self._h, *[C.byref(s) for s in sizes]))
+        nb, npairs, bd, pdn = (s.value for s in sizes)
+        bodies, pairs, tau = np.zeros((S, nb, bd)), np.zeros((S, npairs, pdn)), np.zeros((S, self.nv))
+        rows = np.zeros((S, npairs, self.nv)) if pair_rows else None
+        self._chk(lib().idto_opt_scene_report(self._h, S, dptr(q), dptr(v), dptr(bodies), dptr(pairs), dptr(tau),
+                                              dptr(rows) if rows is not None else None))
+        return SceneReport(bodies, pairs, tau, rows)
 
     def solve_batch(self, q_guesses, problems=None, only_best: bool = False, models=None, contacts=None) -> BatchSolveResult:
         """TrajectoryOptimizer::SolveBatch: entry b is `Solve(q_guesses[b])` on an optimizer made with `problems[b]` (None:

@@ -39,6 +39,7 @@
 
 #include "idto/optimizer/penta_diagonal_matrix.h"
 #include "idto/optimizer/problem_definition.h"
+#include "idto/optimizer/scene_report.h"
 #include "idto/optimizer/solver_parameters.h"
 #include "idto/optimizer/trajectory_optimizer_solution.h"
 #include "idto/optimizer/trajectory_optimizer_state.h"
@@ -188,6 +189,15 @@ class TrajectoryOptimizer<double> {
                    TrajectoryOptimizerState<T>* scratch_state) const;
 
   idto_hip_ctx* device_context() const { return dev(); }
+
+  // What replaces the reference's EvalPlantContext(state, t) (optimizer/trajectory_optimizer.h:452): body poses and spatial
+  // velocities, per-pair signed distances, witness points and contact forces, and the generalised force of contact at the
+  // states (q[t], v[t]) - every t in ONE launch of the device and one wait (idto/optimizer/scene_report.h, include/idto_hip.h
+  // idto_hip_scene_report).  The contact inside solution.tau[t] is -tau_contact of state t + 1.
+  SceneReport EvalScene(const std::vector<VectorXd>& q, const std::vector<VectorXd>& v, bool pair_rows = false) const;
+  SceneReport EvalScene(const TrajectoryOptimizerSolution<T>& solution, bool pair_rows = false) const {
+    return EvalScene(solution.q, solution.v, pair_rows);
+  }
 
  private:
   int num_vars() const { return (num_steps() + 1) * nq_; }

@@ -562,6 +562,47 @@ int idto_hip_mpc_batch_tick_plants(idto_hip_ctx* ctx, int substeps, int iteratio
                                    double* v_out, double* tau_out, double* final_cost, int* status, int* best, double* guess_out,
                                    double* plans_out, double* x_after_out, int* plant_status_out);
 
+/* ---- Scene report (csrc/scene_report.h): where every body is and what every candidate contact pair does at the states
+ * [q; v] of a trajectory - an optimizer's solution (q_t, v_t) or the rows that idto_hip_plant_step recorded.  It stands
+ * where the reference's EvalPlantContext stands: body poses, spatial velocities, signed-distance pairs and contact results,
+ * without a plant's context.  One workgroup per state and problem, one launch.  The table the kernel needs beside the
+ * model (the body of every geometry) is storage the context allocates at the first report; a context that never asks for
+ * a report runs exactly the launches it ran before, and a report changes none of the context's state: the iterate, the
+ * prefetches and the trust-region sets are as they were.
+ *
+ * The contact inside tau_t (IDTO_ARR_TAU, row t) is the report's tau_contact row for (q_{t+1}, v_{t+1}) with a minus sign:
+ * tau_contact is the generalised force that contact applies to the system, and inverse dynamics at (q_{t+1}, v_{t+1}, a_t)
+ * subtracts it. */
+#define IDTO_SCENE_MODELS_PROBLEMS 0   /* problem b's physics: the context's model, or its record b after idto_hip_set_model_batch */
+#define IDTO_SCENE_MODELS_PLANTS 1     /* plant b's physics (idto_hip_plant_begin, idto_hip_plant_set_model) */
+#define IDTO_SCENE_BODY_DOUBLES 18     /* a body: R_WB row-major [0, 9), p [9, 12), w [12, 15), v of the body origin [15, 18); world frame */
+#define IDTO_SCENE_PAIR_DOUBLES 20     /* a candidate pair, the entries at these offsets: */
+#define IDTO_SCENE_PAIR_ACTIVE 0       /* 1.0 or 0.0: phi <= the contact threshold */
+#define IDTO_SCENE_PAIR_PHI 1          /* signed distance */
+#define IDTO_SCENE_PAIR_N 2            /* [3] unit normal from A towards B */
+#define IDTO_SCENE_PAIR_CA 5           /* [3] witness point on A, world */
+#define IDTO_SCENE_PAIR_CB 8           /* [3] witness point on B, world */
+#define IDTO_SCENE_PAIR_VN 11          /* normal velocity of B relative to A at pC = (Ca + Cb) / 2 */
+#define IDTO_SCENE_PAIR_VT 12          /* [3] tangential part of that velocity */
+#define IDTO_SCENE_PAIR_FN 15          /* normal force */
+#define IDTO_SCENE_PAIR_F 16           /* [3] the force on body B at pC, world frame; body A gets -f */
+#define IDTO_SCENE_PAIR_PAD 19         /* 0.0 */
+/* An inactive pair keeps its geometry and velocities and has fn and f exactly zero; an active pair that separates at twice
+ * the dissipation velocity or faster is active with an exactly zero force. */
+
+/* nbodies, npairs, IDTO_SCENE_BODY_DOUBLES, IDTO_SCENE_PAIR_DOUBLES (each pointer may be NULL) */
+int idto_hip_scene_sizes(idto_hip_ctx* ctx, int* nbodies, int* npairs, int* body_doubles, int* pair_doubles);
+/* x[batch][nstates][nq + nv]: the layout of a plant's record rows and of a solution's (q_t, v_t).  models:
+ * IDTO_SCENE_MODELS_PROBLEMS or IDTO_SCENE_MODELS_PLANTS.  Outputs, each may be NULL (not all):
+ *   bodies_out[batch][nstates][nbodies][18], pairs_out[batch][nstates][npairs][20],
+ *   tau_contact_out[batch][nstates][nv], tau_pairs_out[batch][nstates][npairs][nv] (a pair's row of tau_contact; the rows
+ *   sum to it in ascending pair index from +0).
+ * One upload, one launch, one copy back through pinned staging, one wait.  Refused by name before any device work: x NULL,
+ * nstates < 1, all outputs NULL, an entry of x that is not finite (named by problem, state and index), an unknown `models`,
+ * the plants' models on a context without a begun plant. */
+int idto_hip_scene_report(idto_hip_ctx* ctx, int nstates, const double* x, int models, double* bodies_out, double* pairs_out,
+                          double* tau_contact_out, double* tau_pairs_out);
+
 /* Options: "gradients_method" = 0 forward differences (default), 1 / 2 central differences of
  * 2nd / 4th order (SolverParameters::gradients_method, reference solver_parameters.h:26-50,
  * trajectory_optimizer.cc:565-885); 3 (autodiff) is refused.  "reference_solver" = 1 selects the bit-exact restatement of the reference's

@@ -46,6 +46,15 @@ int idto_opt_num_equality_constraints(const idto_opt* opt);
 int idto_opt_solve(idto_opt* opt, const double* q_guess, double* sol_q, double* sol_v, double* sol_tau,
                    idto_stats_t* stats, int* flag, int* reason);
 
+/* TrajectoryOptimizer::EvalScene (what replaces the reference's EvalPlantContext; include/idto_hip.h idto_hip_scene_report,
+ * whose layouts these are): the sizes - nbodies, npairs, doubles per body (18) and per pair (20), each may be NULL - and the
+ * report at nstates states q[nstates][nq], v[nstates][nv], e.g. a solution's sol_q, sol_v with nstates = N + 1.  Outputs, each
+ * may be NULL (not all): bodies_out[nstates][nbodies][18], pairs_out[nstates][npairs][20], tau_contact_out[nstates][nv],
+ * tau_pairs_out[nstates][npairs][nv].  One launch, one wait. */
+int idto_opt_scene_sizes(idto_opt* opt, int* nbodies, int* npairs, int* body_doubles, int* pair_doubles);
+int idto_opt_scene_report(idto_opt* opt, int nstates, const double* q, const double* v, double* bodies_out, double* pairs_out,
+                          double* tau_contact_out, double* tau_pairs_out);
+
 /* TrajectoryOptimizer::SolveBatch (include/idto/optimizer/trajectory_optimizer.h): B problems of the optimizer's model,
  * horizon, solver and contact parameters; entry b is idto_opt_solve of q_guesses[b] on an optimizer created with problems[b]
  * (NULL: the optimizer's own problem for every entry).  q_guesses: [B][(N+1)*nq]; sol_q / sol_v / sol_tau: [B][...] (any may

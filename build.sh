@@ -9,7 +9,8 @@ cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -Iinclude -Iidto_amd/csrc"
 mkdir -p build
-# four HIP translation units, compiled side by side: the finite-difference kernel, the plants' kernel, the scene report's and everything else.
+# five HIP translation units, compiled side by side: the finite-difference kernel, the plants' kernel, the scene report's, the
+# linearisation's and everything else.
 # -Rpass-analysis=kernel-resource-usage: the compiler's register / scratch / spill figures per kernel go to
 # build/*.remarks, and tools/check_resources.py FAILS THE BUILD when a production kernel spills vector registers or
 # exceeds its scratch / SGPR-spill limit (fd_kernel once computed wrong partials after an edit
@@ -20,6 +21,8 @@ REM="-Rpass-analysis=kernel-resource-usage"
 ( $HIPCC $FLAGS $REM -c idto_amd/csrc/plant_launch.hip -o build/plant_launch.o "$@" 2> build/plant_launch.remarks || { grep -v "remark:" build/plant_launch.remarks >&2; exit 1; } ) &
 # the scene report's kernel (csrc/scene_report.h): a unit of its own for the same reason
 ( $HIPCC $FLAGS $REM -c idto_amd/csrc/scene_launch.hip -o build/scene_launch.o "$@" 2> build/scene_launch.remarks || { grep -v "remark:" build/scene_launch.remarks >&2; exit 1; } ) &
+# the linearisation's and the Riccati recursion's kernels (csrc/plant_lin.h): a unit of their own for the same reason
+( $HIPCC $FLAGS $REM -c idto_amd/csrc/lin_launch.hip -o build/lin_launch.o "$@" 2> build/lin_launch.remarks || { grep -v "remark:" build/lin_launch.remarks >&2; exit 1; } ) &
 # the model's checks and tables: host-only C++ (no HIP include), so that the unit also builds for the CPU under sanitizers.
 # -ffp-contract=off, no fast-math: its gathered records use explicit std::fma and a deliberate 0.0 + x.
 ( g++ -O2 -std=c++17 -fPIC -ffp-contract=off -Wall -Wextra -Iinclude -Iidto_amd/csrc -c idto_amd/csrc/host/model_tables.cc -o build/model_tables.o ) &
@@ -38,12 +41,18 @@ wait %4
 wait %5
 wait %6
 wait %7
-grep -h -A3 "warning:" build/fd_launch.remarks build/idto_hip.remarks build/plant_launch.remarks build/scene_launch.remarks >&2 || true
-if [ -z "$IDTO_SKIP_RESOURCE_CHECK" ]; then python3 tools/check_resources.py build/fd_launch.remarks build/idto_hip.remarks build/plant_launch.remarks build/scene_launch.remarks > build/resource_check.txt || { cat build/resource_check.txt >&2; exit 1; }; fi
-$HIPCC --offload-arch=gfx950 -fPIC -shared build/fd_launch.o build/plant_launch.o build/scene_launch.o build/idto_hip.o build/model_tables.o build/solver_plan.o build/model_batch.o build/context_layout.o -o idto_amd/libidto_hip.so -ldl
+wait %8
+grep -h -A3 "warning:" build/fd_launch.remarks build/idto_hip.remarks build/plant_launch.remarks build/scene_launch.remarks build/lin_launch.remarks >&2 || true
+if [ -z "$IDTO_SKIP_RESOURCE_CHECK" ]; then python3 tools/check_resources.py build/fd_launch.remarks build/idto_hip.remarks build/plant_launch.remarks build/scene_launch.remarks build/lin_launch.remarks > build/resource_check.txt || { cat build/resource_check.txt >&2; exit 1; }; fi
+$HIPCC --offload-arch=gfx950 -fPIC -shared build/fd_launch.o build/plant_launch.o build/scene_launch.o build/lin_launch.o build/idto_hip.o build/model_tables.o build/solver_plan.o build/model_batch.o build/context_layout.o -o idto_amd/libidto_hip.so -ldl
 # libidto_opt.so: the host-side TrajectoryOptimizer (C++) + its C-ABI, on top of libidto_hip.so
 g++ -O3 -std=c++17 -fPIC -shared -Wall -Iinclude -Iidto_amd/csrc idto_amd/csrc/host/trajectory_optimizer.cc \
   idto_amd/csrc/host/batch_rows.cc idto_amd/csrc/host/ls_rows.cc idto_amd/csrc/host/mpc_controller.cc idto_amd/csrc/host/idto_opt_c.cc -o idto_amd/libidto_opt.so -Lidto_amd -lidto_hip -Wl,-rpath,'$ORIGIN'
 
 # a C++ consumer of the boundary with no Python in the process (tests/test_gpu_cpp_consumer.py runs it on the GPU box)
 g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/solve_acrobot.cc -o build/solve_acrobot -Lidto_amd -lidto_opt -lidto_hip -Wl,-rpath,'$ORIGIN/../idto_amd'
+# ... and one of TrajectoryOptimizer::Tvlqr (tests/test_gpu_tvlqr_cpp.py)
+g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/tvlqr_acrobot.cc -o build/tvlqr_acrobot -Lidto_amd -lidto_opt -lidto_hip -Wl,-rpath,'$ORIGIN/../idto_amd'
+
+# csrc/plant_tangent.h and csrc/tvlqr_step.h compiled for the host, as a program the tests drive through files (tests/lin_cases.py)
+g++ -O1 -std=c++17 -ffp-contract=off -Wall -Wextra -Iinclude -Iidto_amd/csrc tests/cpp/lin_host.cc -o build/lin_host

@@ -218,6 +218,50 @@ int idto_opt_scene_report(idto_opt* o, int nstates, const double* q, const doubl
   });
 }
 
+int idto_opt_actuated_dofs(idto_opt* o, int* actuated_out) {
+  const std::vector<int> dofs = o->to->actuated_dofs();
+  if (actuated_out) std::copy(dofs.begin(), dofs.end(), actuated_out);
+  return (int)dofs.size();
+}
+
+// a linearisation's arrays into the caller's (each may be NULL)
+static void LinOut(const PlantLinearization& l, double* x_next_out, double* A_out, double* B_out, int* status_out) {
+  const size_t w = (size_t)l.nq + l.nv, n = 2 * (size_t)l.nv;
+  for (size_t k = 0; k < l.x_next.size(); ++k) {
+    if (x_next_out) std::copy(l.x_next[k].begin(), l.x_next[k].end(), x_next_out + k * w);
+    if (A_out) std::copy(l.A[k].data(), l.A[k].data() + n * n, A_out + k * n * n);
+    if (B_out) std::copy(l.B[k].data(), l.B[k].data() + n * l.nv, B_out + k * n * l.nv);
+  }
+  if (status_out) std::copy(l.status.begin(), l.status.end(), status_out);
+}
+
+int idto_opt_plant_linearize(idto_opt* o, int nstates, const double* q, const double* v, const double* tau, double h, int substeps,
+                             double* x_next_out, double* A_out, double* B_out, int* status_out) {
+  return Guard([&] {
+    if (nstates < 1 || !q || !v || !tau) throw std::runtime_error("plant_linearize: nstates >= 1 states q[nstates][nq], v[nstates][nv] and torques tau[nstates][nv] are required");
+    LinOut(o->to->LinearizePlant(Rows(q, nstates, o->nq), Rows(v, nstates, o->nv), Rows(tau, nstates, o->nv), h, substeps), x_next_out,
+           A_out, B_out, status_out);
+  });
+}
+
+int idto_opt_tvlqr(idto_opt* o, const double* sol_q, const double* sol_v, const double* sol_tau, double h, const double* Qtheta,
+                   const double* Qv, const double* R, const double* Qf_theta, const double* Qf_v, double* x_next_out, double* A_out,
+                   double* B_out, int* status_out, double* K_out, double* P_out, int* lqr_status_out) {
+  return Guard([&] {
+    if (!sol_q || !sol_v || !sol_tau || !Qtheta || !Qv || !R || !Qf_theta || !Qf_v)
+      throw std::runtime_error("tvlqr: the solution's q, v, tau and the weights Qtheta, Qv, R, Qf_theta, Qf_v are required");
+    const int nv = o->nv, nu = (int)o->to->actuated_dofs().size(), n = 2 * nv;
+    auto mat = [](const double* p, int m) { MatrixXd M(m, m); std::copy(p, p + (size_t)m * m, M.data()); return M; };
+    TrajectoryOptimizerSolution<double> sol;
+    sol.q = Rows(sol_q, o->N + 1, o->nq); sol.v = Rows(sol_v, o->N + 1, nv); sol.tau = Rows(sol_tau, o->N, nv);
+    const TvlqrGains g = o->to->Tvlqr(sol, h, mat(Qtheta, nv), mat(Qv, nv), mat(R, nu), mat(Qf_theta, nv), mat(Qf_v, nv));
+    LinOut(g.lin, x_next_out, A_out, B_out, status_out);
+    for (size_t t = 0; K_out && t < g.K.size(); ++t) std::copy(g.K[t].data(), g.K[t].data() + (size_t)nu * n, K_out + t * nu * n);
+    for (size_t t = 0; P_out && t < g.P.size(); ++t) std::copy(g.P[t].data(), g.P[t].data() + (size_t)n * n, P_out + t * n * n);
+    if (lqr_status_out) *lqr_status_out = g.status[0];
+  });
+}
+
 int idto_opt_solve_batch(idto_opt* o, int B, const idto_problem_t* problems, const double* q_guesses, int only_best,
                          double* sol_q, double* sol_v, double* sol_tau, idto_stats_t* stats, int* flags, int* reasons,
                          double* final_costs, int* best) {

@@ -518,6 +518,46 @@ SceneReport TO::EvalScene(const std::vector<VectorXd>& q, const std::vector<Vect
   return Scene(dev()).Report((int)q.size(), x.data(), nv_, IDTO_SCENE_MODELS_PROBLEMS, pair_rows);
 }
 
+// the states [q; v] of `count` steps as the device's rows, and the torques beside them
+static void PackStates(const std::vector<VectorXd>& q, const std::vector<VectorXd>& v, const std::vector<VectorXd>& tau, std::size_t count,
+                       int nq, int nv, const char* who, std::vector<double>* x, std::vector<double>* u) {
+  if (count < 1 || q.size() < count || v.size() < count || tau.size() < count)
+    throw std::runtime_error(std::string(who) + ": as many positions, velocities and torques as states, at least one");
+  const std::size_t w = (std::size_t)nq + nv;
+  x->resize(count * w); u->resize(count * nv);
+  for (std::size_t t = 0; t < count; ++t) {
+    if ((int)q[t].size() != nq || (int)v[t].size() != nv || (int)tau[t].size() != nv) throw std::runtime_error(std::string(who) + ": a state or torque of the wrong size");
+    std::copy(q[t].begin(), q[t].end(), x->begin() + t * w);
+    std::copy(v[t].begin(), v[t].end(), x->begin() + t * w + nq);
+    std::copy(tau[t].begin(), tau[t].end(), u->begin() + t * nv);
+  }
+}
+
+PlantLinearization TO::LinearizePlant(const std::vector<VectorXd>& q, const std::vector<VectorXd>& v, const std::vector<VectorXd>& tau,
+                                      double h, int substeps) const {
+  if (q.size() != v.size() || q.size() != tau.size()) throw std::runtime_error("LinearizePlant: as many velocities and torques as positions");
+  std::vector<double> x, u;
+  PackStates(q, v, tau, q.size(), nq_, nv_, "LinearizePlant", &x, &u);
+  return Linearizer(dev()).Linearize((int)q.size(), x.data(), u.data(), nq_, nv_, h, substeps);
+}
+
+std::vector<int> TO::actuated_dofs() const {
+  std::vector<int> dofs;
+  for (int j = 0; j < nv_; ++j)
+    if (std::find(unactuated_dofs_.begin(), unactuated_dofs_.end(), j) == unactuated_dofs_.end()) dofs.push_back(j);
+  return dofs;
+}
+
+TvlqrGains TO::Tvlqr(const TrajectoryOptimizerSolution<T>& solution, double h, const MatrixXd& Qtheta, const MatrixXd& Qv, const MatrixXd& R,
+                     const MatrixXd& Qf_theta, const MatrixXd& Qf_v) const {
+  const int substeps = SubstepsPerStep(time_step_, h);
+  if (Qtheta.rows() != nv_ || Qf_theta.rows() != nv_) throw std::invalid_argument("Tvlqr: the weights' blocks are nv x nv (tangent coordinates)");
+  std::vector<double> x, u;
+  PackStates(solution.q, solution.v, solution.tau, (std::size_t)num_steps(), nq_, nv_, "Tvlqr", &x, &u);
+  return Linearizer(dev()).Gains(num_steps(), x.data(), u.data(), nq_, nv_, h, substeps, actuated_dofs(), TangentWeight(Qtheta, Qv), R,
+                                 TangentWeight(Qf_theta, Qf_v));
+}
+
 const VelocityPartials<double>& TO::EvalVelocityPartials(const TrajectoryOptimizerState<T>& s) const {
   CalcVelocityPartials(s);
   return s.cache_.v_partials;

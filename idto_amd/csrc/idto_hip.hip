@@ -41,6 +41,7 @@
 #include "mpc_batch.h"
 #include "plant_launch.h"
 #include "scene_launch.h"
+#include "lin_launch.h"
 #include "host/context_layout.h"
 #include "host/model_batch.h"
 #include "host/model_tables.h"
@@ -242,12 +243,22 @@ struct SceneState {
   double* pin = nullptr; size_t pin_cap = 0;
 };
 
+// idto_hip_plant_linearize, idto_hip_plant_tvlqr: the feature's storage (lin_abi.inc LinEnsure), made at the first call - the
+// context's own parameter record, then one device buffer (a call's inputs, the columns' plants, the outputs) and its pinned
+// staging, grown on demand
+struct LinState {
+  double* record = nullptr;
+  double* dev = nullptr; size_t dev_cap = 0;
+  double* pin = nullptr; size_t pin_cap = 0;
+};
+
 struct idto_hip_ctx {
   int device = 0;
   MpcBatchState* mpc = nullptr;
   unsigned mpc_generation = 0;   // calls of idto_hip_mpc_batch_begin so far
   PlantState* plant = nullptr;
   SceneState* scene = nullptr;
+  LinState* lin = nullptr;
   // (batch contexts) what the context was created from, and one single-problem context per problem, made on first use
   std::unique_ptr<HostModelCopy> host_model;
   std::vector<std::unique_ptr<HostProblemCopy>> host_problems;
@@ -1068,6 +1079,10 @@ void idto_hip_destroy(idto_hip_ctx* c) {
   if (c->scene) {   // (its device buffers are in c->allocs)
     if (c->scene->pin) (void)hipHostFree(c->scene->pin);
     delete c->scene;
+  }
+  if (c->lin) {   // (its device buffers are in c->allocs)
+    if (c->lin->pin) (void)hipHostFree(c->lin->pin);
+    delete c->lin;
   }
   if (c->mpc) {   // (its device buffers are in c->allocs)
     if (c->mpc->tick_pin) (void)hipHostFree(c->mpc->tick_pin);
@@ -3321,6 +3336,7 @@ int idto_hip_mpc_batch_replan(idto_hip_ctx* c, const double* times, const double
 
 #include "plant_abi.inc"   // idto_hip_forward_dynamics, idto_hip_plant_*
 #include "scene_abi.inc"   // idto_hip_scene_sizes, idto_hip_scene_report
+#include "lin_abi.inc"     // idto_hip_lin_sizes, idto_hip_plant_linearize, idto_hip_plant_tvlqr
 
 // The batch loop with everything a caller reads afterwards brought back under the loop's one wait, and the best problem
 // chosen on the device (trust_region.h tr_gather_batch_kernel).

@@ -48,6 +48,20 @@ class SceneReport:
         self.fn, self.force = pairs[..., 15], pairs[..., 16:19]
 
 
+LIN_EPS_DEFAULT = 6.0554544523933395e-06   # cbrt(2^-52), IDTO_LIN_EPS_DEFAULT
+
+
+class Tvlqr:
+    """What idto_hip_plant_tvlqr returns (include/idto_hip.h).  Leading axes [batch, nstates] (a single problem given without the
+    batch axis: [nstates]); matrices as [row, col], deviations in tangent coordinates [dtheta (nv); dv (nv)], n = 2 nv.
+      x_next [..., nq + nv], A [..., n, n], B [..., n, nv], lin_status [..., 2]: the linearisation (HipPath.plant_linearize)
+      K [..., nu, n]: u = u_nom - K_t dx;  P [batch, nstates + 1, n, n]: the cost-to-go, P[..., -1] = Qf
+      status [batch]: 0, or 1 + t for the first step t whose R + Bu^T P Bu has a bad pivot (K, P NaN from t downward)"""
+
+    def __init__(self, x_next, A, B, lin_status, K, P, status):
+        self.x_next, self.A, self.B, self.lin_status, self.K, self.P, self.status = x_next, A, B, lin_status, K, P, status
+
+
 class CPlantParams(C.Structure):
     """idto_plant_params_t (include/idto_hip.h)"""
     _fields_ = [("h", C.c_double), ("mode", C.c_int), ("Kp", C.POINTER(C.c_double)), ("kp_size", C.c_int),
@@ -121,6 +135,11 @@ def lib():
                                                       pi, C.c_int, pd, pd, pd, pd, pd, pd, pi, pi, pd, pd, pd, pi])
         L.idto_hip_scene_sizes.argtypes = [C.c_void_p, pi, pi, pi, pi]
         L.idto_hip_scene_report.argtypes = [C.c_void_p, C.c_int, pd, C.c_int, pd, pd, pd, pd]
+        pl = C.POINTER(C.c_long)
+        L.idto_hip_lin_sizes.argtypes = [C.c_void_p, C.c_int, C.c_int, pi, pi, pl, pl, pl, pl, pl]
+        L.idto_hip_plant_linearize.argtypes = [C.c_void_p, C.c_int, pd, pd, C.c_double, C.c_int, C.c_double, C.c_int, pd, pd, pd, pi]
+        L.idto_hip_plant_tvlqr.argtypes = ([C.c_void_p, C.c_int, pd, pd, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, pi, pd, pd, pd,
+                                            pd, pd, pd, pi, pd, pd, pi])
         L.idto_hip_tr_reject.argtypes = [C.c_void_p]
         L.idto_hip_tr_set_scale_memory.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.idto_hip_tr_set_convergence.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -185,6 +204,7 @@ EXPORTED_SYMBOLS = [
     "idto_hip_forward_dynamics", "idto_hip_plant_begin", "idto_hip_plant_set_model", "idto_hip_plant_set_state",
     "idto_hip_plant_get_state", "idto_hip_plant_step", "idto_hip_mpc_batch_tick_plants",
     "idto_hip_scene_sizes", "idto_hip_scene_report",
+    "idto_hip_lin_sizes", "idto_hip_plant_linearize", "idto_hip_plant_tvlqr",
     "idto_hip_rccl_info", "idto_hip_comm_unique_id", "idto_hip_comm_init", "idto_hip_comm_init_all", "idto_hip_comm_destroy",
     "idto_hip_allgather_slab", "idto_hip_gn_step_sharded", "idto_hip_gn_step_multi", "idto_hip_eval_partials_multi",
     "idto_hip_trace_enable", "idto_hip_trace_mark", "idto_hip_trace_dump",
@@ -371,6 +391,57 @@ class HipPath:
         if squeeze:   # (a single problem given as [nstates, nq + nv])
             bodies, pairs, tau, rows = bodies[0], pairs[0], tau[0], (rows[0] if rows is not None else None)
         return SceneReport(bodies, pairs, tau, rows)
+
+    # ---- the plants' linearisation and the LQR gains about it (include/idto_hip.h idto_hip_plant_linearize, idto_hip_plant_tvlqr)
+    def _lin_inputs(self, x, tau):
+        B, w = self.batch, self.nq + self.nv
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+        squeeze = B == 1 and x.ndim == 2
+        x = x.reshape(B, -1, w)
+        S = x.shape[1]
+        tau = np.ascontiguousarray(np.asarray(tau, dtype=np.float64).reshape(B, S, self.nv))
+        return x, tau, S, squeeze
+
+    def lin_sizes(self, nstates: int, nu: int = 0):
+        """idto_hip_lin_sizes -> (n = 2 nv, columns per state, the doubles of x_next, A, B, K, P for nstates states and nu controls)"""
+        n, cols = C.c_int(), C.c_int()
+        counts = [C.c_long() for _ in range(5)]
+        _chk(lib().idto_hip_lin_sizes(self.h, int(nstates), int(nu), C.byref(n), C.byref(cols), *[C.byref(c) for c in counts]))
+        return (n.value, cols.value) + tuple(c.value for c in counts)
+
+    def plant_linearize(self, x, tau, h: float, substeps: int, eps: float = LIN_EPS_DEFAULT, models: int = SCENE_MODELS_PROBLEMS):
+        """x: [batch, nstates, nq + nv] (a single problem: [nstates, nq + nv]), tau: [batch, nstates, nv] the held torques ->
+        (x_next [batch, nstates, nq + nv], A [batch, nstates, n, n], B [batch, nstates, n, nv], status [batch, nstates, 2]) about
+        the map of `substeps` substeps of h, in tangent coordinates, as [row, col]"""
+        x, tau, S, squeeze = self._lin_inputs(x, tau)
+        B, nv, n = self.batch, self.nv, 2 * self.nv
+        xn, A, Bm = np.zeros((B, S, self.nq + nv)), np.zeros((B, S, n, n)), np.zeros((B, S, nv, n))
+        st = np.zeros((B, S, 2), dtype=np.int32)
+        _chk(lib().idto_hip_plant_linearize(self.h, int(S), dptr(x), dptr(tau), float(h), int(substeps), float(eps), int(models),
+                                            dptr(xn), dptr(A), dptr(Bm), st.ctypes.data_as(C.POINTER(C.c_int))))
+        A, Bm = np.ascontiguousarray(A.swapaxes(-1, -2)), np.ascontiguousarray(Bm.swapaxes(-1, -2))   # (column-major -> [row, col])
+        return (xn[0], A[0], Bm[0], st[0]) if squeeze else (xn, A, Bm, st)
+
+    def plant_tvlqr(self, x, tau, h: float, substeps: int, actuated, Q, R, Qf, eps: float = LIN_EPS_DEFAULT,
+                    models: int = SCENE_MODELS_PROBLEMS) -> Tvlqr:
+        """plant_linearize's inputs, the actuated velocity indices [nu] and the weights Q, Qf [n, n], R [nu, nu] in tangent
+        coordinates -> Tvlqr"""
+        x, tau, S, squeeze = self._lin_inputs(x, tau)
+        B, nv, n = self.batch, self.nv, 2 * self.nv
+        act = np.ascontiguousarray(np.asarray(actuated, dtype=np.int32).ravel())
+        nu = act.size
+        Q, Qf = (np.ascontiguousarray(np.asarray(M, dtype=np.float64).reshape(n, n).T) for M in (Q, Qf))
+        R = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(nu, nu).T)
+        xn, A, Bm = np.zeros((B, S, self.nq + nv)), np.zeros((B, S, n, n)), np.zeros((B, S, nv, n))
+        st, lst = np.zeros((B, S, 2), dtype=np.int32), np.zeros(B, dtype=np.int32)
+        K, P = np.zeros((B, S, n, nu)), np.zeros((B, S + 1, n, n))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        _chk(lib().idto_hip_plant_tvlqr(self.h, int(S), dptr(x), dptr(tau), float(h), int(substeps), float(eps), int(models), int(nu),
+                                        ip(act), dptr(Q), dptr(R), dptr(Qf), dptr(xn), dptr(A), dptr(Bm), ip(st), dptr(K), dptr(P), ip(lst)))
+        A, Bm, K, P = (np.ascontiguousarray(M.swapaxes(-1, -2)) for M in (A, Bm, K, P))
+        if squeeze:
+            xn, A, Bm, st, K = xn[0], A[0], Bm[0], st[0], K[0]
+        return Tvlqr(xn, A, Bm, st, K, P, lst)
 
     def solver_status_batch(self):
         out = (C.c_int * self.batch)()

@@ -50,6 +50,9 @@ def lib():
                                            C.POINTER(C.c_int), C.POINTER(C.c_int), P, C.POINTER(C.c_int)]
         L.idto_opt_scene_sizes.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
         L.idto_opt_scene_report.argtypes = [C.c_void_p, C.c_int, P, P, P, P, P, P]
+        L.idto_opt_actuated_dofs.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.idto_opt_plant_linearize.argtypes = [C.c_void_p, C.c_int, P, P, P, C.c_double, C.c_int, P, P, P, C.POINTER(C.c_int)]
+        L.idto_opt_tvlqr.argtypes = [C.c_void_p, P, P, P, C.c_double, P, P, P, P, P, P, P, P, C.POINTER(C.c_int), P, P, C.POINTER(C.c_int)]
         L.idto_opt_batch_error.argtypes = [C.c_void_p, C.c_int]
         L.idto_opt_batch_error.restype = C.c_char_p
         L.idto_opt_last_batch_route.argtypes = [C.c_void_p]
@@ -115,6 +118,7 @@ EXPORTED_SYMBOLS = [
     "idto_opt_update_nominal_trajectory", "idto_opt_eval", "idto_opt_dogleg", "idto_opt_trust_ratio",
     "idto_opt_solve_batch", "idto_opt_solve_batch_models", "idto_opt_batch_error", "idto_opt_last_batch_route",
     "idto_opt_scene_sizes", "idto_opt_scene_report",
+    "idto_opt_actuated_dofs", "idto_opt_plant_linearize", "idto_opt_tvlqr",
 ]
 MPC_SYMBOLS = ["idto_mpc_create", "idto_mpc_destroy", "idto_mpc_num_actuators", "idto_mpc_update", "idto_mpc_state",
                "idto_mpc_control", "idto_mpc_start_time", "idto_mpc_spline_eval", "idto_mpc_stats",
@@ -304,6 +308,45 @@ class TrajectoryOptimizer:
         self._chk(lib().idto_opt_scene_report(self._h, S, dptr(q), dptr(v), dptr(bodies), dptr(pairs), dptr(tau),
                                               dptr(rows) if rows is not None else None))
         return SceneReport(bodies, pairs, tau, rows)
+
+    def actuated_dofs(self):
+        """the velocity indices of the controls (every dof of a model without an actuator)"""
+        out = np.zeros(self.nv, dtype=np.int32)
+        nu = lib().idto_opt_actuated_dofs(self._h, out.ctypes.data_as(C.POINTER(C.c_int)))
+        return out[:nu].copy()
+
+    def linearize_plant(self, q, v, tau, h: float, substeps: int):
+        """TrajectoryOptimizer::LinearizePlant: q [S, nq], v [S, nv], tau [S, nv] (the held torques) -> (x_next [S, nq + nv],
+        A [S, n, n], B [S, n, nv], status [S, 2]) about the map of `substeps` substeps of h, in tangent coordinates (n = 2 nv)"""
+        q, v, tau = (np.ascontiguousarray(_d(a)).reshape(-1, w) for a, w in ((q, self.nq), (v, self.nv), (tau, self.nv)))
+        if not len(q) == len(v) == len(tau):
+            raise RuntimeError("linearize_plant: as many velocities and torques as positions")
+        S, nv, n = len(q), self.nv, 2 * self.nv
+        xn, A, B, st = np.zeros((S, self.nq + nv)), np.zeros((S, n, n)), np.zeros((S, nv, n)), np.zeros((S, 2), dtype=np.int32)
+        self._chk(lib().idto_opt_plant_linearize(self._h, S, dptr(q), dptr(v), dptr(tau), float(h), int(substeps), dptr(xn), dptr(A),
+                                                 dptr(B), st.ctypes.data_as(C.POINTER(C.c_int))))
+        return xn, np.ascontiguousarray(A.swapaxes(1, 2)), np.ascontiguousarray(B.swapaxes(1, 2)), st
+
+    def tvlqr(self, solution, h: float, Qtheta, Qv, R, Qf_theta, Qf_v):
+        """TrajectoryOptimizer::Tvlqr: the time-varying LQR gains about `solution` - its states (q_t, v_t), t = 0 ... N - 1, the held
+        torque solution.tau[t], the map of one time step in substeps of h (time_step / h a whole number) - with the weights
+        Q = blkdiag(Qtheta, Qv), R [nu, nu], Qf = blkdiag(Qf_theta, Qf_v) in tangent coordinates; the controls are actuated_dofs().
+        -> hip.Tvlqr with the leading axis [N] (P: [N + 1]); u = solution.tau[t][actuated] - K[t] @ [q (-) q_t; v - v_t]"""
+        from .hip import Tvlqr
+        N, nv, n = self.N, self.nv, 2 * self.nv
+        nu = len(self.actuated_dofs())
+        q, v, tau = (np.ascontiguousarray(_d(a)) for a in (solution.q, solution.v, solution.tau))
+        if q.size != (N + 1) * self.nq or v.size != (N + 1) * nv or tau.size != N * nv:
+            raise RuntimeError("tvlqr: a solution of this optimizer's horizon is required")
+        blocks = [np.ascontiguousarray(_d(M).reshape(nv, nv).T) for M in (Qtheta, Qv, Qf_theta, Qf_v)]
+        Rm = np.ascontiguousarray(_d(R).reshape(nu, nu).T)
+        xn, A, B, st = np.zeros((N, self.nq + nv)), np.zeros((N, n, n)), np.zeros((N, nv, n)), np.zeros((N, 2), dtype=np.int32)
+        K, P, lst = np.zeros((N, n, nu)), np.zeros((N + 1, n, n)), C.c_int()
+        self._chk(lib().idto_opt_tvlqr(self._h, dptr(q), dptr(v), dptr(tau), float(h), dptr(blocks[0]), dptr(blocks[1]), dptr(Rm),
+                                       dptr(blocks[2]), dptr(blocks[3]), dptr(xn), dptr(A), dptr(B),
+                                       st.ctypes.data_as(C.POINTER(C.c_int)), dptr(K), dptr(P), C.byref(lst)))
+        A, B, K, P = (np.ascontiguousarray(M.swapaxes(1, 2)) for M in (A, B, K, P))
+        return Tvlqr(xn, A, B, st, K, P, np.array([lst.value], dtype=np.int32))
 
     def solve_batch(self, q_guesses, problems=None, only_best: bool = False, models=None, contacts=None) -> BatchSolveResult:
         """TrajectoryOptimizer::SolveBatch: entry b is `Solve(q_guesses[b])` on an optimizer made with `problems[b]` (None:

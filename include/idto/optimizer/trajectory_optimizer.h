@@ -43,6 +43,7 @@
 #include "idto/optimizer/solver_parameters.h"
 #include "idto/optimizer/trajectory_optimizer_solution.h"
 #include "idto/optimizer/trajectory_optimizer_state.h"
+#include "idto/optimizer/tvlqr.h"
 #include "idto/optimizer/warm_start.h"
 #include "idto_hip.h"
 
@@ -189,6 +190,20 @@ class TrajectoryOptimizer<double> {
                    TrajectoryOptimizerState<T>* scratch_state) const;
 
   idto_hip_ctx* device_context() const { return dev(); }
+
+  // The local model of the plant about given states (idto/optimizer/tvlqr.h, include/idto_hip.h idto_hip_plant_linearize):
+  // x+ ~ f(x_s, tau_s) + A_s dx + B_s du for the map f of `substeps` substeps of h under the held torque tau[s] (all nv
+  // components), with this optimizer's model and contact parameters, in tangent coordinates.  One pass of the device, one wait.
+  PlantLinearization LinearizePlant(const std::vector<VectorXd>& q, const std::vector<VectorXd>& v, const std::vector<VectorXd>& tau,
+                                    double h, int substeps) const;
+  // The time-varying LQR gains about a solution: the states (q_t, v_t), t = 0 ... N - 1, the held torque solution.tau[t], the map
+  // of one time step in substeps of h (time_step / h must be a whole number to 1e-9: std::invalid_argument otherwise), the
+  // weights Q = blkdiag(Qtheta, Qv), R [nu x nu] and Qf = blkdiag(Qf_theta, Qf_v) in tangent coordinates, time-invariant; the
+  // controls are the model's actuated dofs (actuated_dofs(): every dof of a model without an actuator).  K[t] (nu x n) gives
+  // u = solution.tau[t][actuated] - K[t] [q (-) q_t; v - v_t]; P[t], t = 0 ... N, is the cost-to-go.
+  TvlqrGains Tvlqr(const TrajectoryOptimizerSolution<T>& solution, double h, const MatrixXd& Qtheta, const MatrixXd& Qv, const MatrixXd& R,
+                   const MatrixXd& Qf_theta, const MatrixXd& Qf_v) const;
+  std::vector<int> actuated_dofs() const;
 
   // What replaces the reference's EvalPlantContext(state, t) (optimizer/trajectory_optimizer.h:452): body poses and spatial
   // velocities, per-pair signed distances, witness points and contact forces, and the generalised force of contact at the

@@ -603,6 +603,46 @@ int idto_hip_scene_sizes(idto_hip_ctx* ctx, int* nbodies, int* npairs, int* body
 int idto_hip_scene_report(idto_hip_ctx* ctx, int nstates, const double* x, int models, double* bodies_out, double* pairs_out,
                           double* tau_contact_out, double* tau_pairs_out);
 
+/* ---- Plant linearisation and time-varying LQR gains (csrc/plant_lin.h, csrc/plant_tangent.h, csrc/tvlqr_step.h): the local
+ * model x+ ~ f(x*, u*) + A dx + B du of the plants' own map f of `substeps` substeps of h under a held torque, about the
+ * states of a trajectory, and the gains K_t of the finite-horizon LQR problem along them.  Deviations are in TANGENT
+ * coordinates: dx = [dtheta (nv); dv (nv)], n = 2 nv - a floating joint's quaternion deviates by three angular components in
+ * the world frame (the convention of the velocities), every other joint's positions by themselves.  A and B are central
+ * differences of step eps over plant_kernel's rollouts, P = 1 + 6 nv columns per state (column 0 the nominal, then +eps, -eps
+ * along each component of dtheta, dv and tau); the storage is an allocation of the feature's own, made at the first call
+ * and grown on demand: a context that never calls these runs exactly the launches it ran before, and a call changes none
+ * of the context's state nor the plants'.  Matrices are column-major.  `models` is the scene report's selector. */
+#define IDTO_LIN_EPS_DEFAULT 6.0554544523933395e-06   /* cbrt(2^-52): the step of a central difference */
+/* n = 2 nv, the columns per state P, and the number of doubles of every output for `nstates` states and `nu` controls
+ * (each pointer may be NULL) */
+int idto_hip_lin_sizes(idto_hip_ctx* ctx, int nstates, int nu, int* n, int* columns, long* x_next_count, long* A_count,
+                       long* B_count, long* K_count, long* P_count);
+/* x[batch][nstates][nq + nv] = [q; v], tau[batch][nstates][nv] the held torque (all nv components).  Outputs, each may be
+ * NULL and is then not fetched:
+ *   x_next_out[batch][nstates][nq + nv]: f(x, tau), the nominal column's final state
+ *   A_out[batch][nstates][n * n], B_out[batch][nstates][n * nv]
+ *   status_out[batch][nstates][2]: {0, 0}, or {plant_kernel's code, the column} of the first column whose rollout did not end
+ *   well - A, B and x_next of that state are then NaN, the other states are unaffected.
+ * Everything is enqueued at once (the perturbation, one plant_kernel launch per problem, the difference) and waited for
+ * once.  Refused by name before any device work: x or tau NULL or not finite, nstates < 1, substeps outside
+ * [1, IDTO_PLANT_MAX_SUBSTEPS], h or eps not > 0 and finite, nstates * P > 65536, an unknown `models`, the plants' models on
+ * a context without a begun plant, nv > 64, a context with child contexts. */
+int idto_hip_plant_linearize(idto_hip_ctx* ctx, int nstates, const double* x, const double* tau, double h, int substeps,
+                             double eps, int models, double* x_next_out, double* A_out, double* B_out, int* status_out);
+/* The same, and behind it on the device the Riccati recursion over the problem's nstates linearisations, one workgroup per
+ * problem, A and B read where the difference left them: actuated[nu] the velocity indices whose columns of B are Bu;
+ * Q[n * n], R[nu * nu], Qf[n * n] symmetric, time-invariant, in tangent coordinates.  With S = nstates, P_S = Qf and for
+ * t = S - 1 ... 0: G = R + Bu^T P Bu, K_t = G^-1 Bu^T P A (un-pivoted LDL^T), P_t = Q + K_t^T R K_t + (A - Bu K_t)^T P (A - Bu K_t).
+ *   K_out[batch][nstates][nu * n], P_out[batch][nstates + 1][n * n]
+ *   lqr_status_out[batch]: 0, or 1 + t for the first step t whose G has a pivot that is not > 0 and finite: K and P from t
+ *   downward are NaN.  A state whose linearisation failed ends the recursion there in the same way.
+ * Refused by name as well: nu outside [1, nv], an index of actuated outside [0, nv), Q, R or Qf NULL or not finite, matrices
+ * that do not fit the 160 KiB of LDS (5 n^2 + 4 n nu + 2 nu^2 + nu doubles). */
+int idto_hip_plant_tvlqr(idto_hip_ctx* ctx, int nstates, const double* x, const double* tau, double h, int substeps, double eps,
+                         int models, int nu, const int* actuated, const double* Q, const double* R, const double* Qf,
+                         double* x_next_out, double* A_out, double* B_out, int* status_out, double* K_out, double* P_out,
+                         int* lqr_status_out);
+
 /* Options: "gradients_method" = 0 forward differences (default), 1 / 2 central differences of
  * 2nd / 4th order (SolverParameters::gradients_method, reference solver_parameters.h:26-50,
  * trajectory_optimizer.cc:565-885); 3 (autodiff) is refused.  "reference_solver" = 1 selects the bit-exact restatement of the reference's

@@ -55,6 +55,23 @@ int idto_opt_scene_sizes(idto_opt* opt, int* nbodies, int* npairs, int* body_dou
 int idto_opt_scene_report(idto_opt* opt, int nstates, const double* q, const double* v, double* bodies_out, double* pairs_out,
                           double* tau_contact_out, double* tau_pairs_out);
 
+/* TrajectoryOptimizer::LinearizePlant and ::Tvlqr (include/idto/optimizer/tvlqr.h; include/idto_hip.h idto_hip_plant_linearize,
+ * idto_hip_plant_tvlqr, whose layouts these are: matrices column-major, deviations in tangent coordinates, n = 2 nv).
+ * idto_opt_actuated_dofs: the velocity indices of the controls, actuated_out[nv] filled from the front (may be NULL); returns nu.
+ * idto_opt_plant_linearize: about nstates states q[nstates][nq], v[nstates][nv] under the held torques tau[nstates][nv], the map
+ * of `substeps` substeps of h; outputs, each may be NULL: x_next_out[nstates][nq + nv], A_out[nstates][n * n],
+ * B_out[nstates][n * nv], status_out[nstates][2].
+ * idto_opt_tvlqr: about a solution's (sol_q[t], sol_v[t]), t = 0 ... N - 1, under sol_tau[t], the map of one time step in
+ * substeps of h (time_step / h a whole number to 1e-9, or the call fails); Qtheta, Qv, Qf_theta, Qf_v [nv * nv] and R [nu * nu]
+ * symmetric; outputs, each may be NULL: idto_opt_plant_linearize's with nstates = N, K_out[N][nu * n], P_out[N + 1][n * n],
+ * *lqr_status_out (0, or 1 + t: K and P from t downward are NaN). */
+int idto_opt_actuated_dofs(idto_opt* opt, int* actuated_out);
+int idto_opt_plant_linearize(idto_opt* opt, int nstates, const double* q, const double* v, const double* tau, double h, int substeps,
+                             double* x_next_out, double* A_out, double* B_out, int* status_out);
+int idto_opt_tvlqr(idto_opt* opt, const double* sol_q, const double* sol_v, const double* sol_tau, double h, const double* Qtheta,
+                   const double* Qv, const double* R, const double* Qf_theta, const double* Qf_v, double* x_next_out, double* A_out,
+                   double* B_out, int* status_out, double* K_out, double* P_out, int* lqr_status_out);
+
 /* TrajectoryOptimizer::SolveBatch (include/idto/optimizer/trajectory_optimizer.h): B problems of the optimizer's model,
  * horizon, solver and contact parameters; entry b is idto_opt_solve of q_guesses[b] on an optimizer created with problems[b]
  * (NULL: the optimizer's own problem for every entry).  q_guesses: [B][(N+1)*nq]; sol_q / sol_v / sol_tau: [B][...] (any may

@@ -14,7 +14,8 @@ import os, re, subprocess, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REMARKS = [os.path.join(ROOT, "build", "fd_launch.remarks"), os.path.join(ROOT, "build", "idto_hip.remarks"),
-           os.path.join(ROOT, "build", "plant_launch.remarks"), os.path.join(ROOT, "build", "scene_launch.remarks")]
+           os.path.join(ROOT, "build", "plant_launch.remarks"), os.path.join(ROOT, "build", "scene_launch.remarks"),
+           os.path.join(ROOT, "build", "lin_launch.remarks")]
 
 # kernel (demangled, without "idto_dev::" and arguments) -> (max spilled VGPRs, max scratch bytes per lane, max spilled SGPRs)
 # Values: what profiles/r05_isa_resources.txt records, the SGPR figure with a margin of 24 (it moves by a few with every
@@ -130,6 +131,11 @@ LIMITS = {
     # parameter record, <false> from the kernel's arguments: 10 / 3 scalar registers spilled to lanes)
     "scene_kernel<false>": (0, 0, 3 + 24),
     "scene_kernel<true>": (0, 0, 10 + 24),
+    # (the linearisation's and the Riccati recursion's kernels, csrc/plant_lin.h: a lane per column and joint, a lane per entry of
+    # a product with the matrices in LDS - no vector register spilled, no scratch; tvlqr_kernel spills 11 scalar registers to lanes)
+    "lin_perturb_kernel": (0, 0, 0 + 24),
+    "lin_difference_kernel": (0, 0, 0 + 24),
+    "tvlqr_kernel": (0, 0, 11 + 24),
     "ls_gather_batch_kernel": (0, 0, 0 + 24),
     "ls_trial_kernel": (0, 0, 0 + 24),
     "ls_cost_kernel": (0, 0, 0 + 24),
@@ -140,7 +146,7 @@ LIMITS = {
 
 
 def compile_remarks():
-    """The four translation units with the remark pass on (device code only, no object files kept)."""
+    """The five translation units with the remark pass on (device code only, no object files kept)."""
     os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Iinclude", "-Iidto_amd/csrc", "-S",
              "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"]
@@ -148,7 +154,8 @@ def compile_remarks():
     jobs = [([hipcc] + flags + ["idto_amd/csrc/fd_launch.hip", "-o", "/dev/null"], REMARKS[0]),
             ([hipcc] + flags + ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "idto_amd/csrc/idto_hip.hip", "-o", "/dev/null"], REMARKS[1]),
             ([hipcc] + flags + ["idto_amd/csrc/plant_launch.hip", "-o", "/dev/null"], REMARKS[2]),
-            ([hipcc] + flags + ["idto_amd/csrc/scene_launch.hip", "-o", "/dev/null"], REMARKS[3])]
+            ([hipcc] + flags + ["idto_amd/csrc/scene_launch.hip", "-o", "/dev/null"], REMARKS[3]),
+            ([hipcc] + flags + ["idto_amd/csrc/lin_launch.hip", "-o", "/dev/null"], REMARKS[4])]
     procs = [(subprocess.Popen(cmd, cwd=ROOT, stderr=open(out, "w")), out) for cmd, out in jobs]
     for p, out in procs:
         if p.wait() != 0:

@@ -9,8 +9,8 @@ cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -Iinclude -Iidto_amd/csrc"
 mkdir -p build
-# five HIP translation units, compiled side by side: the finite-difference kernel, the plants' kernel, the scene report's, the
-# linearisation's and everything else.
+# six HIP translation units, compiled side by side: the finite-difference kernel, the plants' kernel, the scene report's, the
+# linearisation's, the tracked rollouts' and everything else.
 # -Rpass-analysis=kernel-resource-usage: the compiler's register / scratch / spill figures per kernel go to
 # build/*.remarks, and tools/check_resources.py FAILS THE BUILD when a production kernel spills vector registers or
 # exceeds its scratch / SGPR-spill limit (fd_kernel once computed wrong partials after an edit
@@ -23,6 +23,8 @@ REM="-Rpass-analysis=kernel-resource-usage"
 ( $HIPCC $FLAGS $REM -c idto_amd/csrc/scene_launch.hip -o build/scene_launch.o "$@" 2> build/scene_launch.remarks || { grep -v "remark:" build/scene_launch.remarks >&2; exit 1; } ) &
 # the linearisation's and the Riccati recursion's kernels (csrc/plant_lin.h): a unit of their own for the same reason
 ( $HIPCC $FLAGS $REM -c idto_amd/csrc/lin_launch.hip -o build/lin_launch.o "$@" 2> build/lin_launch.remarks || { grep -v "remark:" build/lin_launch.remarks >&2; exit 1; } ) &
+# the plants under the time-varying LQR law (csrc/plant.h track_kernel): a unit of its own for the same reason
+( $HIPCC $FLAGS $REM -c idto_amd/csrc/track_launch.hip -o build/track_launch.o "$@" 2> build/track_launch.remarks || { grep -v "remark:" build/track_launch.remarks >&2; exit 1; } ) &
 # the model's checks and tables: host-only C++ (no HIP include), so that the unit also builds for the CPU under sanitizers.
 # -ffp-contract=off, no fast-math: its gathered records use explicit std::fma and a deliberate 0.0 + x.
 ( g++ -O2 -std=c++17 -fPIC -ffp-contract=off -Wall -Wextra -Iinclude -Iidto_amd/csrc -c idto_amd/csrc/host/model_tables.cc -o build/model_tables.o ) &
@@ -42,9 +44,10 @@ wait %5
 wait %6
 wait %7
 wait %8
-grep -h -A3 "warning:" build/fd_launch.remarks build/idto_hip.remarks build/plant_launch.remarks build/scene_launch.remarks build/lin_launch.remarks >&2 || true
-if [ -z "$IDTO_SKIP_RESOURCE_CHECK" ]; then python3 tools/check_resources.py build/fd_launch.remarks build/idto_hip.remarks build/plant_launch.remarks build/scene_launch.remarks build/lin_launch.remarks > build/resource_check.txt || { cat build/resource_check.txt >&2; exit 1; }; fi
-$HIPCC --offload-arch=gfx950 -fPIC -shared build/fd_launch.o build/plant_launch.o build/scene_launch.o build/lin_launch.o build/idto_hip.o build/model_tables.o build/solver_plan.o build/model_batch.o build/context_layout.o -o idto_amd/libidto_hip.so -ldl
+wait %9
+grep -h -A3 "warning:" build/fd_launch.remarks build/idto_hip.remarks build/plant_launch.remarks build/scene_launch.remarks build/lin_launch.remarks build/track_launch.remarks >&2 || true
+if [ -z "$IDTO_SKIP_RESOURCE_CHECK" ]; then python3 tools/check_resources.py build/fd_launch.remarks build/idto_hip.remarks build/plant_launch.remarks build/scene_launch.remarks build/lin_launch.remarks build/track_launch.remarks > build/resource_check.txt || { cat build/resource_check.txt >&2; exit 1; }; fi
+$HIPCC --offload-arch=gfx950 -fPIC -shared build/fd_launch.o build/plant_launch.o build/scene_launch.o build/lin_launch.o build/track_launch.o build/idto_hip.o build/model_tables.o build/solver_plan.o build/model_batch.o build/context_layout.o -o idto_amd/libidto_hip.so -ldl
 # libidto_opt.so: the host-side TrajectoryOptimizer (C++) + its C-ABI, on top of libidto_hip.so
 g++ -O3 -std=c++17 -fPIC -shared -Wall -Iinclude -Iidto_amd/csrc idto_amd/csrc/host/trajectory_optimizer.cc \
   idto_amd/csrc/host/batch_rows.cc idto_amd/csrc/host/ls_rows.cc idto_amd/csrc/host/mpc_controller.cc idto_amd/csrc/host/idto_opt_c.cc -o idto_amd/libidto_opt.so -Lidto_amd -lidto_hip -Wl,-rpath,'$ORIGIN'
@@ -53,6 +56,8 @@ g++ -O3 -std=c++17 -fPIC -shared -Wall -Iinclude -Iidto_amd/csrc idto_amd/csrc/h
 g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/solve_acrobot.cc -o build/solve_acrobot -Lidto_amd -lidto_opt -lidto_hip -Wl,-rpath,'$ORIGIN/../idto_amd'
 # ... and one of TrajectoryOptimizer::Tvlqr (tests/test_gpu_tvlqr_cpp.py)
 g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/tvlqr_acrobot.cc -o build/tvlqr_acrobot -Lidto_amd -lidto_opt -lidto_hip -Wl,-rpath,'$ORIGIN/../idto_amd'
+# ... and one of TrajectoryOptimizer::Track (tests/test_gpu_plant_track.py)
+g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/track_pendulum.cc -o build/track_pendulum -Lidto_amd -lidto_opt -lidto_hip -Wl,-rpath,'$ORIGIN/../idto_amd'
 
 # csrc/plant_tangent.h and csrc/tvlqr_step.h compiled for the host, as a program the tests drive through files (tests/lin_cases.py)
 g++ -O1 -std=c++17 -ffp-contract=off -Wall -Wextra -Iinclude -Iidto_amd/csrc tests/cpp/lin_host.cc -o build/lin_host

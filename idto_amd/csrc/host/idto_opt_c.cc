@@ -262,6 +262,32 @@ int idto_opt_tvlqr(idto_opt* o, const double* sol_q, const double* sol_v, const 
   });
 }
 
+int idto_opt_track(idto_opt* o, const double* sol_q, const double* sol_v, const double* sol_tau, double h, const double* Qtheta,
+                   const double* Qv, const double* R, const double* Qf_theta, const double* Qf_v, int nrollouts, const double* x0,
+                   int zero_unactuated, double* x_next_out, double* A_out, double* B_out, int* status_out, double* K_out, double* P_out,
+                   int* lqr_status_out, double* x_out, double* u_out, double* dx_out, int* track_status_out) {
+  return Guard([&] {
+    if (!sol_q || !sol_v || !sol_tau || !Qtheta || !Qv || !R || !Qf_theta || !Qf_v || !x0 || nrollouts < 1)
+      throw std::runtime_error("track: the solution's q, v, tau, the weights Qtheta, Qv, R, Qf_theta, Qf_v and nrollouts >= 1 initial states x0 are required");
+    const int nv = o->nv, nu = (int)o->to->actuated_dofs().size(), n = 2 * nv;
+    auto mat = [](const double* p, int m) { MatrixXd M(m, m); std::copy(p, p + (size_t)m * m, M.data()); return M; };
+    TrajectoryOptimizerSolution<double> sol;
+    sol.q = Rows(sol_q, o->N + 1, o->nq); sol.v = Rows(sol_v, o->N + 1, nv); sol.tau = Rows(sol_tau, o->N, nv);
+    const TrackedRollouts r = o->to->Track(sol, h, mat(Qtheta, nv), mat(Qv, nv), mat(R, nu), mat(Qf_theta, nv), mat(Qf_v, nv),
+                                           Rows(x0, nrollouts, o->nq + nv), zero_unactuated != 0);
+    const TvlqrGains& g = r.gains;
+    LinOut(g.lin, x_next_out, A_out, B_out, status_out);
+    for (size_t t = 0; K_out && t < g.K.size(); ++t) std::copy(g.K[t].data(), g.K[t].data() + (size_t)nu * n, K_out + t * nu * n);
+    for (size_t t = 0; P_out && t < g.P.size(); ++t) std::copy(g.P[t].data(), g.P[t].data() + (size_t)n * n, P_out + t * n * n);
+    if (lqr_status_out) *lqr_status_out = g.status[0];
+    auto flat = [](const std::vector<VectorXd>& rows, double* out) {
+      for (size_t k = 0; out && k < rows.size(); ++k) std::copy(rows[k].begin(), rows[k].end(), out + k * rows[k].size());
+    };
+    flat(r.x, x_out); flat(r.u, u_out); flat(r.dx, dx_out);
+    if (track_status_out) std::copy(r.status.begin(), r.status.end(), track_status_out);
+  });
+}
+
 int idto_opt_solve_batch(idto_opt* o, int B, const idto_problem_t* problems, const double* q_guesses, int only_best,
                          double* sol_q, double* sol_v, double* sol_tau, idto_stats_t* stats, int* flags, int* reasons,
                          double* final_costs, int* best) {

@@ -558,6 +558,30 @@ TvlqrGains TO::Tvlqr(const TrajectoryOptimizerSolution<T>& solution, double h, c
                                  TangentWeight(Qf_theta, Qf_v));
 }
 
+TrackedRollouts TO::Track(const TrajectoryOptimizerSolution<T>& solution, double h, const MatrixXd& Qtheta, const MatrixXd& Qv, const MatrixXd& R,
+                          const MatrixXd& Qf_theta, const MatrixXd& Qf_v, const std::vector<VectorXd>& x0s, bool zero_unactuated) const {
+  const int substeps = SubstepsPerStep(time_step_, h);
+  if (Qtheta.rows() != nv_ || Qf_theta.rows() != nv_) throw std::invalid_argument("Track: the weights' blocks are nv x nv (tangent coordinates)");
+  const std::size_t N = (std::size_t)num_steps(), w = (std::size_t)nq_ + nv_;
+  if (solution.q.size() < N + 1 || solution.v.size() < N + 1) throw std::runtime_error("Track: the solution's states (q_t, v_t), t = 0 ... N, are required");
+  std::vector<double> x, u;
+  PackStates(solution.q, solution.v, solution.tau, N, nq_, nv_, "Track", &x, &u);
+  if ((int)solution.q[N].size() != nq_ || (int)solution.v[N].size() != nv_) throw std::runtime_error("Track: a state of the wrong size");
+  x.insert(x.end(), solution.q[N].begin(), solution.q[N].end());   // (the last row: what the final deviation is against)
+  x.insert(x.end(), solution.v[N].begin(), solution.v[N].end());
+  if (zero_unactuated)
+    for (int j : unactuated_dofs_)
+      for (std::size_t t = 0; t < N; ++t) u[t * nv_ + j] = 0.0;
+  if (x0s.empty()) throw std::runtime_error("Track: at least one initial state is required");
+  std::vector<double> x0(x0s.size() * w);
+  for (std::size_t r = 0; r < x0s.size(); ++r) {
+    if (x0s[r].size() != w) throw std::runtime_error("Track: an initial state is [q; v], nq + nv entries");
+    std::copy(x0s[r].begin(), x0s[r].end(), x0.begin() + r * w);
+  }
+  return Tracker(dev()).Track((int)N, x.data(), u.data(), nq_, nv_, h, substeps, actuated_dofs(), TangentWeight(Qtheta, Qv), R,
+                              TangentWeight(Qf_theta, Qf_v), (int)x0s.size(), x0.data());
+}
+
 const VelocityPartials<double>& TO::EvalVelocityPartials(const TrajectoryOptimizerState<T>& s) const {
   CalcVelocityPartials(s);
   return s.cache_.v_partials;

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <initializer_list>
 #include <limits>
 #include <memory>
@@ -42,6 +43,7 @@
 #include "plant_launch.h"
 #include "scene_launch.h"
 #include "lin_launch.h"
+#include "track_launch.h"
 #include "host/context_layout.h"
 #include "host/model_batch.h"
 #include "host/model_tables.h"
@@ -252,6 +254,13 @@ struct LinState {
   double* pin = nullptr; size_t pin_cap = 0;
 };
 
+// idto_hip_plant_track, idto_hip_plant_tvlqr_track: the feature's storage (track_abi.inc TrackEnsure), made at the first call -
+// one device buffer (a call's inputs, the rollouts' states and status words, the outputs) and its pinned staging, grown on demand
+struct TrackState {
+  double* dev = nullptr; size_t dev_cap = 0;
+  double* pin = nullptr; size_t pin_cap = 0;
+};
+
 struct idto_hip_ctx {
   int device = 0;
   MpcBatchState* mpc = nullptr;
@@ -259,6 +268,7 @@ struct idto_hip_ctx {
   PlantState* plant = nullptr;
   SceneState* scene = nullptr;
   LinState* lin = nullptr;
+  TrackState* track = nullptr;
   // (batch contexts) what the context was created from, and one single-problem context per problem, made on first use
   std::unique_ptr<HostModelCopy> host_model;
   std::vector<std::unique_ptr<HostProblemCopy>> host_problems;
@@ -1083,6 +1093,10 @@ void idto_hip_destroy(idto_hip_ctx* c) {
   if (c->lin) {   // (its device buffers are in c->allocs)
     if (c->lin->pin) (void)hipHostFree(c->lin->pin);
     delete c->lin;
+  }
+  if (c->track) {   // (its device buffer is in c->allocs)
+    if (c->track->pin) (void)hipHostFree(c->track->pin);
+    delete c->track;
   }
   if (c->mpc) {   // (its device buffers are in c->allocs)
     if (c->mpc->tick_pin) (void)hipHostFree(c->mpc->tick_pin);
@@ -3337,6 +3351,7 @@ int idto_hip_mpc_batch_replan(idto_hip_ctx* c, const double* times, const double
 #include "plant_abi.inc"   // idto_hip_forward_dynamics, idto_hip_plant_*
 #include "scene_abi.inc"   // idto_hip_scene_sizes, idto_hip_scene_report
 #include "lin_abi.inc"     // idto_hip_lin_sizes, idto_hip_plant_linearize, idto_hip_plant_tvlqr
+#include "track_abi.inc"   // idto_hip_plant_track, idto_hip_plant_tvlqr_track
 
 // The batch loop with everything a caller reads afterwards brought back under the loop's one wait, and the best problem
 // chosen on the device (trust_region.h tr_gather_batch_kernel).

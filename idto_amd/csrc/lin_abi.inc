@@ -69,9 +69,16 @@ static int LinFinite(const std::string& who, const char* what, const double* p, 
   return 0;
 }
 
-static int LinRun(idto_hip_ctx* c, const std::string& who, int nstates, const double* x, const double* tau, double h, int substeps, double eps,
-                  int models, const LinTv* tv, double* x_next_out, double* A_out, double* B_out, int* status_out) {
-  // ---- every refusal, before any device work
+// What a caller enqueues behind LinRun's launches and in front of its one wait (track_abi.inc: the rollouts under the gains):
+// enqueue gets the device's K [B][S][nu * n] where tvlqr_kernel leaves it, finish runs behind the wait
+struct LinThen {
+  std::function<int(const double* K_dev)> enqueue;
+  std::function<void()> finish;
+};
+
+// every refusal of LinRun, before any device work
+static int LinCheck(idto_hip_ctx* c, const std::string& who, int nstates, const double* x, const double* tau, double h, int substeps, double eps,
+                    int models, const LinTv* tv) {
   if (!x || !tau) { g_err = who + ": x[batch][nstates][nq + nv] and tau[batch][nstates][nv] are required"; return -1; }
   if (nstates < 1) { g_err = who + ": nstates must be >= 1"; return -1; }
   if (substeps < 1 || substeps > IDTO_PLANT_MAX_SUBSTEPS) { g_err = who + ": substeps must be in [1, 4096] (a single launch stays short on a shared device)"; return -1; }
@@ -91,7 +98,7 @@ static int LinRun(idto_hip_ctx* c, const std::string& who, int nstates, const do
     g_err = who + ": nstates * (1 + 6 nv) = " + std::to_string((long long)nstates * P) + " columns, more than " + std::to_string(IDTO_LIN_MAX_COLUMNS) + " in one call";
     return -1;
   }
-  const size_t B = (size_t)c->batch, S = (size_t)nstates, nq = (size_t)c->nq, nv = (size_t)c->nv, w = nq + nv, n = 2 * nv, SP = S * (size_t)P;
+  const size_t B = (size_t)c->batch, S = (size_t)nstates, nq = (size_t)c->nq, nv = (size_t)c->nv, w = nq + nv, n = 2 * nv;
   const size_t nu = tv ? (size_t)tv->nu : 0;
   if (tv) {
     if (tv->nu < 1 || tv->nu > c->nv) { g_err = who + ": nu must be in [1, nv]"; return -1; }
@@ -107,8 +114,17 @@ static int LinRun(idto_hip_ctx* c, const std::string& who, int nstates, const do
   }
   if (int rc = LinFinite(who, "x", x, B * S * w)) return rc;
   if (int rc = LinFinite(who, "tau", tau, B * S * nv)) return rc;
+  if (PlantLdsBytes(c, PlantBlock(c, 0, false), false) > 160 * 1024) { g_err = who + ": the model and a substep's evaluations do not fit the 160 KiB of LDS"; return -1; }
+  return 0;
+}
+
+static int LinRun(idto_hip_ctx* c, const std::string& who, int nstates, const double* x, const double* tau, double h, int substeps, double eps,
+                  int models, const LinTv* tv, double* x_next_out, double* A_out, double* B_out, int* status_out, const LinThen* then = nullptr) {
+  if (int rc = LinCheck(c, who, nstates, x, tau, h, substeps, eps, models, tv)) return rc;
+  const int P = lin_columns(c->nv);
+  const size_t B = (size_t)c->batch, S = (size_t)nstates, nq = (size_t)c->nq, nv = (size_t)c->nv, w = nq + nv, n = 2 * nv, SP = S * (size_t)P;
+  const size_t nu = tv ? (size_t)tv->nu : 0;
   const int block = PlantBlock(c, 0, false), plant_lds = PlantLdsBytes(c, block, false);
-  if (plant_lds > 160 * 1024) { g_err = who + ": the model and a substep's evaluations do not fit the 160 KiB of LDS"; return -1; }
 
   HIP_OK(hipSetDevice(c->device));
   // one device buffer: [inputs | the columns' plants | outputs], each part on a 64-byte boundary
@@ -171,6 +187,8 @@ static int LinRun(idto_hip_ctx* c, const std::string& who, int nstates, const do
     tvlqr_launch(t, c->batch, (int)(tvlqr_lds_doubles((int)n, (int)nu) * sizeof(double)), c->stream);
     if (int rc = launched("tvlqr_kernel")) return rc;
   }
+  if (then)
+    if (int rc = then->enqueue(L->dev + o_K)) { (void)hipStreamSynchronize(c->stream); return rc; }
   // (the inputs' copy is in front of the launches on the stream: the staging is free again) - only what was asked for comes back
   auto fetch = [&](bool on, size_t o, size_t count) {
     return on && count ? hipMemcpyAsync(L->pin + (o - out0), L->dev + o, count * sizeof(double), hipMemcpyDeviceToHost, c->stream) : hipSuccess;
@@ -186,6 +204,7 @@ static int LinRun(idto_hip_ctx* c, const std::string& who, int nstates, const do
   }
   HIP_OK(hipStreamSynchronize(c->stream));
   TRACE("hip: plant_linearize: waited for the device");
+  if (then) then->finish();
   auto back = [&](size_t o) { return L->pin + (o - out0); };
   if (x_next_out) std::memcpy(x_next_out, back(o_xn), n_xn * sizeof(double));
   if (A_out) std::memcpy(A_out, back(o_A), n_A * sizeof(double));

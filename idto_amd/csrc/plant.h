@@ -14,7 +14,9 @@
 //   3. plant_advance_body, a lane of wavefront 0 per body, into a candidate state that is committed only if it is finite.
 // The applied torque is either held over the launch or the PD+ law on the plant's stored plan (mpc_batch.h: the MPC
 // context's current plane, staged into LDS with the gains): the nominal [q, v, u] at the substep's time is mpc_spline.h's
-// evaluation at t - start_time, clamped to the plan's range as the host's Interpolator clamps.
+// evaluation at t - start_time, clamped to the plan's range as the host's Interpolator clamps.  A third controller, the
+// time-varying LQR law about a nominal (tvlqr_step.h tvlqr_control), is the compile-time LAW of plant_body: TrackArgs and
+// track_kernel below.
 // Instantiated: the generic evaluation for chains of up to 2, 3, 4 and 8 bodies, the exchange form id_eval<8, true> for
 // models with shared pairs and id_eval<8, true, true> for a stem below the common body.
 // Status per plant: 0 ok; 1 a pivot that is not > 0 and finite; 2 a non-finite state or input - each with the substep.  A
@@ -26,6 +28,7 @@
 #include "id_eval.h"
 #include "mpc_spline.h"
 #include "plant_step.h"
+#include "tvlqr_step.h"
 
 namespace idto_dev {
 
@@ -56,13 +59,33 @@ __host__ __device__ inline size_t plant_pd_doubles(int nq, int nv, int nu, int n
   return plan_len + (size_t)n + (size_t)nu * (nq + nv) + (size_t)(nq + nv + nu) + (size_t)(nu + 1) / 2;
 }
 
+// The time-varying LQR law (LAW; track_kernel below, include/idto_hip.h idto_hip_plant_track): R rollouts per problem, the plant
+// blockIdx.x and its problem blockIdx.x / R, of S control steps of m substeps each.  At the start of step t the block stages
+// K_t, x*_t and tau*_t into LDS, and wavefront 0 forms tvlqr_step.h's tvlqr_control - a lane per body tangent_sub, a lane per
+// velocity v - v*, then a lane per control row ONE sum left to right - into the torque that is held over the step's substeps:
+// the map that A_t, B_t linearise.  A launch runs the steps [first_step, first_step + steps); PlantArgs' substeps is S * m, the
+// whole rollout's, so that the substep count, the status word and the record's rows (record_every = m) are the rollout's.
+struct TrackArgs {
+  int R, S, m, first_step, steps, nu;
+  const int* actuated;     // [nu] velocity indices
+  const double* x_nom;     // [B][S + 1][nq + nv]
+  const double* tau_nom;   // [B][S][nv]: every component, the unactuated ones are applied as they are
+  const double* K;         // [B][S][nu * n] column-major, n = 2 nv
+  double* u_out;           // [B * R][S][nu]
+  double* dx_out;          // [B * R][S + 1][n]: row t the deviation in front of step t, row S behind the last
+};
+// what the law adds to the LDS, in doubles: K_t, x*_t, tau*_t, dx, the actuated dofs (u_t goes straight into tau_app)
+__host__ __device__ inline size_t plant_law_doubles(int nq, int nv, int nu) {
+  return (size_t)nu * 2 * nv + (size_t)(nq + nv) + (size_t)nv + (size_t)2 * nv + (size_t)(nu + 1) / 2;
+}
+
 // dynamic LDS of plant_kernel in doubles, for a block of `threads`
 __host__ __device__ inline int plant_lds_doubles(int nq, int nv, int blob_n, int nxb, int nstem, int npaths, int threads) {
   return 3 * nq + 7 * nv + (2 * nv - 1) + (nv + 1) * nv + 2 + blob_n + (threads / npaths) * xch_eval_doubles(nxb, nstem);
 }
 
-template <int MAXC, bool XCH, bool STEM = false>
-IDTO_DEV void plant_body(const DevModel& M, const DevContact& cp, const PlantArgs& A, const int b) {
+template <int MAXC, bool XCH, bool STEM = false, bool LAW = false>
+IDTO_DEV void plant_body(const DevModel& M, const DevContact& cp, const PlantArgs& A, const int b, const TrackArgs* T = nullptr) {
   extern __shared__ double lds[];
   const int tid = threadIdx.x, nt = blockDim.x;
   const int nq = M.nq, nv = M.nv, K = M.npaths, E = nv + 1;
@@ -89,6 +112,20 @@ IDTO_DEV void plant_body(const DevModel& M, const DevContact& cp, const PlantArg
   double* Kd = Kp + A.nu * nq;                       // [nu][nv]
   double* nom = Kd + A.nu * nv;                      // [nq | nv | nu] the nominal state and control
   int* act = reinterpret_cast<int*>(nom + nq + nv + A.nu);   // [nu]
+  // (LAW) in the same place: there is no plan
+  double *Kt = nullptr, *xs = nullptr, *taus = nullptr, *dx = nullptr;
+  int* lact = nullptr;
+  int nu = 0, n = 0, prob = 0;
+  if constexpr (LAW) {
+    if (A.status[2 * b] != PLANT_OK) return;   // (ended in an earlier launch of the same call: its words and rows stand)
+    nu = T->nu; n = 2 * nv; prob = b / T->R;
+    Kt = plan;                 // [nu x n] column-major
+    xs = Kt + nu * n;          // [nq | nv]
+    taus = xs + nq + nv;       // [nv]
+    dx = taus + nv;            // [n]
+    lact = reinterpret_cast<int*>(dx + n);   // [nu]
+    for (int i = tid; i < nu; i += nt) lact[i] = T->actuated[i];
+  }
 
   double* state = A.state + (size_t)b * ((A.fd ? 0 : 1) + nq + nv);
   for (int i = tid; i < M.blob_n; i += nt) mblob[i] = M.blob[i];
@@ -99,7 +136,7 @@ IDTO_DEV void plant_body(const DevModel& M, const DevContact& cp, const PlantArg
     for (int i = tid; i < nq; i += nt) q[i] = state[1 + i];
     for (int i = tid; i < nv; i += nt) v[i] = state[1 + nq + i];
   }
-  for (int i = tid; i < nv; i += nt) { tau_app[i] = A.pd ? 0.0 : A.tau[(size_t)b * nv + i]; zero[i] = 0.0; }
+  for (int i = tid; i < nv; i += nt) { tau_app[i] = (LAW || A.pd) ? 0.0 : A.tau[(size_t)b * nv + i]; zero[i] = 0.0; }
   const double t0 = A.fd ? 0.0 : state[0];
   if (A.pd) {
     for (size_t i = tid; i < A.plan_len; i += nt) plan[i] = A.plan[(size_t)b * A.plan_len + i];
@@ -119,9 +156,37 @@ IDTO_DEV void plant_body(const DevModel& M, const DevContact& cp, const PlantArg
   }
   __syncthreads();
   int code = flag[0] ? PLANT_NONFINITE : PLANT_OK, done = 0;
-  const int nsub = A.fd ? 1 : A.substeps;
+  int nsub = A.fd ? 1 : A.substeps, s0 = 0;
+  if constexpr (LAW) {   // substeps of the rollout, not of the launch
+    s0 = T->first_step * T->m; nsub = (T->first_step + T->steps) * T->m; done = s0;
+  }
   const int groups = nt / K, xeval = xch_eval_doubles(Ml.nxb, Ml.nstem);
-  for (int s = 0; s < nsub && code == PLANT_OK; ++s) {
+  for (int s = s0; s < nsub && code == PLANT_OK; ++s) {
+    if constexpr (LAW) {
+      if (s % T->m == 0) {   // a control step begins: tau_app = tau*_t with u_t = tau*_t[act] - K_t dx on the actuated dofs
+        const int t = s / T->m;
+        const double* Kg = T->K + ((size_t)prob * T->S + t) * (size_t)(nu * n);
+        const double* xg = T->x_nom + ((size_t)prob * (T->S + 1) + t) * (size_t)(nq + nv);
+        const double* tg = T->tau_nom + ((size_t)prob * T->S + t) * (size_t)nv;
+        for (int i = tid; i < nu * n; i += nt) Kt[i] = Kg[i];
+        for (int i = tid; i < nq + nv; i += nt) xs[i] = xg[i];
+        for (int i = tid; i < nv; i += nt) taus[i] = tg[i];
+        __syncthreads();
+        if (tid < 64) {   // (q, v are only read here, as the evaluations read them; tau_app and flag[0] are read behind their barrier)
+          const int lane = tid;
+          for (int body = lane; body < Ml.nb; body += 64) idto_plant::tangent_sub(Ml.jtype[body], Ml.qstart[body], Ml.vstart[body], q, xs, dx);
+          if (lane < nv) { dx[nv + lane] = v[lane] - xs[nq + lane]; tau_app[lane] = taus[lane]; }
+          wave_exchange_point();
+          if (lane < nu) {
+            const double u = taus[lact[lane]] - idto_plant::tvlqr_dot(Kt + lane, nu, dx, 1, n);
+            if (!idto_plant::plant_finite(u)) flag[0] = 1;
+            tau_app[lact[lane]] = u;
+            T->u_out[((size_t)b * T->S + t) * (size_t)nu + lane] = u;
+          }
+          for (int i = lane; i < n; i += 64) T->dx_out[((size_t)b * (T->S + 1) + t) * (size_t)n + i] = dx[i];   // (n = 2 nv: up to 128)
+        }
+      }
+    }
     if (A.pd) {   // the nominal [q, v, u] at this substep's time, a thread per component (read behind the evaluations' barrier)
       const double t = idto_plant::plant_time(t0, s, A.h) - plan[0];
       for (int j = tid; j < nq + nv + A.nu; j += nt) {
@@ -205,12 +270,26 @@ IDTO_DEV void plant_body(const DevModel& M, const DevContact& cp, const PlantArg
     done = s + 1;
     __syncthreads();
   }
+  if constexpr (LAW) {
+    if (code == PLANT_OK && done == T->S * T->m) {   // the rollout is complete: the last row of dx, against x*_S
+      const double* xg = T->x_nom + ((size_t)prob * (T->S + 1) + T->S) * (size_t)(nq + nv);
+      for (int i = tid; i < nq + nv; i += nt) xs[i] = xg[i];
+      __syncthreads();
+      if (tid < 64) {
+        const int lane = tid;
+        for (int body = lane; body < Ml.nb; body += 64) idto_plant::tangent_sub(Ml.jtype[body], Ml.qstart[body], Ml.vstart[body], q, xs, dx);
+        if (lane < nv) dx[nv + lane] = v[lane] - xs[nq + lane];
+        wave_exchange_point();
+        for (int i = lane; i < n; i += 64) T->dx_out[((size_t)b * (T->S + 1) + T->S) * (size_t)n + i] = dx[i];
+      }
+    }
+  }
   if (A.fd) {
     if (code == PLANT_OK)
       for (int i = tid; i < nv; i += nt) A.a_out[(size_t)b * nv + i] = rhs[i];
   } else {
     double* tick = A.tick_out ? A.tick_out + (size_t)b * (1 + nq + nv) : nullptr;
-    const double t_end = idto_plant::plant_time(t0, done, A.h);
+    const double t_end = idto_plant::plant_time(t0, done - s0, A.h);
     if (tid == 0) { state[0] = t_end; if (tick) tick[0] = t_end; }
     for (int i = tid; i < nq; i += nt) { state[1 + i] = q[i]; if (tick) tick[1 + i] = q[i]; }
     for (int i = tid; i < nv; i += nt) { state[1 + nq + i] = v[i]; if (tick) tick[1 + nq + i] = v[i]; }
@@ -224,6 +303,14 @@ template <int MAXC, bool XCH = false, bool STEM = false>
 __global__ void __launch_bounds__(256) plant_kernel(PlantArgs A) {
   const RecordPtr rec = record_at(A.records, (size_t)blockIdx.x * A.mstride);
   plant_body<MAXC, XCH, STEM>(*(const DevModel*)(rec + A.rec_model), *(const DevContact*)(rec + A.rec_contact), A, (int)blockIdx.x);
+}
+
+// The law's kernel: plant_body with LAW.  The plant is blockIdx.x; its problem blockIdx.x / R selects the parameter record, K,
+// x* and tau*.
+template <int MAXC, bool XCH = false, bool STEM = false>
+__global__ void __launch_bounds__(256) track_kernel(PlantArgs A, TrackArgs T) {
+  const RecordPtr rec = record_at(A.records, (size_t)((int)blockIdx.x / T.R) * A.mstride);
+  plant_body<MAXC, XCH, STEM, true>(*(const DevModel*)(rec + A.rec_model), *(const DevContact*)(rec + A.rec_contact), A, (int)blockIdx.x, &T);
 }
 
 }  // namespace idto_dev

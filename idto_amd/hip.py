@@ -62,6 +62,18 @@ class Tvlqr:
         self.x_next, self.A, self.B, self.lin_status, self.K, self.P, self.status = x_next, A, B, lin_status, K, P, status
 
 
+class Track:
+    """What idto_hip_plant_track / idto_hip_plant_tvlqr_track return (include/idto_hip.h).  Leading axes [batch, nrollouts] (a
+    single problem given without the batch axis: [nrollouts]); S control steps, n = 2 nv.
+      x [..., S, nq + nv]: the state behind every step;  u [..., S, nu], dx [..., S + 1, n]: the law's control and deviation
+      in front of step t, dx[..., S, :] the final state's;  status [..., 2]: {code, substeps completed} - the rows of a rollout
+      behind its last completed step are NaN
+      tvlqr: the Tvlqr of idto_hip_plant_tvlqr_track, else None"""
+
+    def __init__(self, x, u, dx, status, tvlqr=None):
+        self.x, self.u, self.dx, self.status, self.tvlqr = x, u, dx, status, tvlqr
+
+
 class CPlantParams(C.Structure):
     """idto_plant_params_t (include/idto_hip.h)"""
     _fields_ = [("h", C.c_double), ("mode", C.c_int), ("Kp", C.POINTER(C.c_double)), ("kp_size", C.c_int),
@@ -140,6 +152,10 @@ def lib():
         L.idto_hip_plant_linearize.argtypes = [C.c_void_p, C.c_int, pd, pd, C.c_double, C.c_int, C.c_double, C.c_int, pd, pd, pd, pi]
         L.idto_hip_plant_tvlqr.argtypes = ([C.c_void_p, C.c_int, pd, pd, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, pi, pd, pd, pd,
                                             pd, pd, pd, pi, pd, pd, pi])
+        L.idto_hip_plant_track.argtypes = ([C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, pi, pd, pd, pd, C.c_int, pd, C.c_int,
+                                            pd, pd, pd, pi])
+        L.idto_hip_plant_tvlqr_track.argtypes = ([C.c_void_p, C.c_int, pd, pd, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, pi, pd, pd,
+                                                  pd, C.c_int, pd, C.c_int, pd, pd, pd, pi, pd, pd, pi, pd, pd, pd, pi])
         L.idto_hip_tr_reject.argtypes = [C.c_void_p]
         L.idto_hip_tr_set_scale_memory.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.idto_hip_tr_set_convergence.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -205,6 +221,7 @@ EXPORTED_SYMBOLS = [
     "idto_hip_plant_get_state", "idto_hip_plant_step", "idto_hip_mpc_batch_tick_plants",
     "idto_hip_scene_sizes", "idto_hip_scene_report",
     "idto_hip_lin_sizes", "idto_hip_plant_linearize", "idto_hip_plant_tvlqr",
+    "idto_hip_plant_track", "idto_hip_plant_tvlqr_track",
     "idto_hip_rccl_info", "idto_hip_comm_unique_id", "idto_hip_comm_init", "idto_hip_comm_init_all", "idto_hip_comm_destroy",
     "idto_hip_allgather_slab", "idto_hip_gn_step_sharded", "idto_hip_gn_step_multi", "idto_hip_eval_partials_multi",
     "idto_hip_trace_enable", "idto_hip_trace_mark", "idto_hip_trace_dump",
@@ -442,6 +459,61 @@ class HipPath:
         if squeeze:
             xn, A, Bm, st, K = xn[0], A[0], Bm[0], st[0], K[0]
         return Tvlqr(xn, A, Bm, st, K, P, lst)
+
+    # ---- the plants under the time-varying LQR law (include/idto_hip.h idto_hip_plant_track, idto_hip_plant_tvlqr_track)
+    def _track_inputs(self, x_nom, tau_nom, x0):
+        B, w = self.batch, self.nq + self.nv
+        x_nom = np.ascontiguousarray(np.asarray(x_nom, dtype=np.float64))
+        squeeze = B == 1 and x_nom.ndim == 2
+        x_nom = x_nom.reshape(B, -1, w)
+        S = x_nom.shape[1] - 1
+        tau_nom = np.ascontiguousarray(np.asarray(tau_nom, dtype=np.float64).reshape(B, S, self.nv))
+        x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).reshape(B, -1, w))
+        return x_nom, tau_nom, x0, S, x0.shape[1], squeeze
+
+    def _track_outputs(self, S, R, nu):
+        B, n = self.batch, 2 * self.nv
+        return np.zeros((B, R, S, self.nq + self.nv)), np.zeros((B, R, S, nu)), np.zeros((B, R, S + 1, n)), np.zeros((B, R, 2), dtype=np.int32)
+
+    def plant_track(self, x_nom, tau_nom, K, x0, h: float, substeps: int, actuated, models: int = SCENE_MODELS_PROBLEMS,
+                    max_launch_substeps: int = 0) -> Track:
+        """x_nom: [batch, S + 1, nq + nv] (a single problem: [S + 1, nq + nv]), tau_nom: [batch, S, nv], K: [batch, S, nu, n] as
+        [row, col], x0: [batch, nrollouts, nq + nv] -> Track: the rollouts of S steps of `substeps` substeps of h under
+        u_t = tau_nom_t[actuated] - K_t [q (-) q*_t; v - v*_t], held over a step"""
+        x_nom, tau_nom, x0, S, R, squeeze = self._track_inputs(x_nom, tau_nom, x0)
+        B, n = self.batch, 2 * self.nv
+        act = np.ascontiguousarray(np.asarray(actuated, dtype=np.int32).ravel())
+        nu = act.size
+        K = np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(B, S, nu, n).swapaxes(-1, -2))   # ([row, col] -> column-major)
+        x, u, dx, st = self._track_outputs(S, R, nu)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        _chk(lib().idto_hip_plant_track(self.h, int(S), int(substeps), float(h), int(models), int(nu), ip(act), dptr(x_nom), dptr(tau_nom),
+                                        dptr(K), int(R), dptr(x0), int(max_launch_substeps), dptr(x), dptr(u), dptr(dx), ip(st)))
+        return Track(x[0], u[0], dx[0], st[0]) if squeeze else Track(x, u, dx, st)
+
+    def plant_tvlqr_track(self, x, tau, x0, h: float, substeps: int, actuated, Q, R, Qf, eps: float = LIN_EPS_DEFAULT,
+                          models: int = SCENE_MODELS_PROBLEMS, max_launch_substeps: int = 0) -> Track:
+        """plant_tvlqr about the first S of x's S + 1 states, and behind it on the device plant_track about x and tau with the
+        gains where the recursion left them: one wait -> Track with .tvlqr"""
+        x, tau, x0, S, nroll, squeeze = self._track_inputs(x, tau, x0)
+        B, nv, n = self.batch, self.nv, 2 * self.nv
+        act = np.ascontiguousarray(np.asarray(actuated, dtype=np.int32).ravel())
+        nu = act.size
+        Q, Qf = (np.ascontiguousarray(np.asarray(M, dtype=np.float64).reshape(n, n).T) for M in (Q, Qf))
+        R = np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(nu, nu).T)
+        xn, A, Bm = np.zeros((B, S, self.nq + nv)), np.zeros((B, S, n, n)), np.zeros((B, S, nv, n))
+        st, lst = np.zeros((B, S, 2), dtype=np.int32), np.zeros(B, dtype=np.int32)
+        K, P = np.zeros((B, S, n, nu)), np.zeros((B, S + 1, n, n))
+        xo, u, dx, tst = self._track_outputs(S, nroll, nu)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        _chk(lib().idto_hip_plant_tvlqr_track(self.h, int(S), dptr(x), dptr(tau), float(h), int(substeps), float(eps), int(models), int(nu),
+                                              ip(act), dptr(Q), dptr(R), dptr(Qf), int(nroll), dptr(x0), int(max_launch_substeps), dptr(xn),
+                                              dptr(A), dptr(Bm), ip(st), dptr(K), dptr(P), ip(lst), dptr(xo), dptr(u), dptr(dx), ip(tst)))
+        A, Bm, K, P = (np.ascontiguousarray(M.swapaxes(-1, -2)) for M in (A, Bm, K, P))
+        if squeeze:
+            xn, A, Bm, st, K = xn[0], A[0], Bm[0], st[0], K[0]
+            xo, u, dx, tst = xo[0], u[0], dx[0], tst[0]
+        return Track(xo, u, dx, tst, Tvlqr(xn, A, Bm, st, K, P, lst))
 
     def solver_status_batch(self):
         out = (C.c_int * self.batch)()

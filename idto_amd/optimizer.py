@@ -53,6 +53,8 @@ def lib():
         L.idto_opt_actuated_dofs.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.idto_opt_plant_linearize.argtypes = [C.c_void_p, C.c_int, P, P, P, C.c_double, C.c_int, P, P, P, C.POINTER(C.c_int)]
         L.idto_opt_tvlqr.argtypes = [C.c_void_p, P, P, P, C.c_double, P, P, P, P, P, P, P, P, C.POINTER(C.c_int), P, P, C.POINTER(C.c_int)]
+        L.idto_opt_track.argtypes = [C.c_void_p, P, P, P, C.c_double, P, P, P, P, P, C.c_int, P, C.c_int, P, P, P, C.POINTER(C.c_int), P, P,
+                                     C.POINTER(C.c_int), P, P, P, C.POINTER(C.c_int)]
         L.idto_opt_batch_error.argtypes = [C.c_void_p, C.c_int]
         L.idto_opt_batch_error.restype = C.c_char_p
         L.idto_opt_last_batch_route.argtypes = [C.c_void_p]
@@ -118,7 +120,7 @@ EXPORTED_SYMBOLS = [
     "idto_opt_update_nominal_trajectory", "idto_opt_eval", "idto_opt_dogleg", "idto_opt_trust_ratio",
     "idto_opt_solve_batch", "idto_opt_solve_batch_models", "idto_opt_batch_error", "idto_opt_last_batch_route",
     "idto_opt_scene_sizes", "idto_opt_scene_report",
-    "idto_opt_actuated_dofs", "idto_opt_plant_linearize", "idto_opt_tvlqr",
+    "idto_opt_actuated_dofs", "idto_opt_plant_linearize", "idto_opt_tvlqr", "idto_opt_track",
 ]
 MPC_SYMBOLS = ["idto_mpc_create", "idto_mpc_destroy", "idto_mpc_num_actuators", "idto_mpc_update", "idto_mpc_state",
                "idto_mpc_control", "idto_mpc_start_time", "idto_mpc_spline_eval", "idto_mpc_stats",
@@ -347,6 +349,31 @@ class TrajectoryOptimizer:
                                        st.ctypes.data_as(C.POINTER(C.c_int)), dptr(K), dptr(P), C.byref(lst)))
         A, B, K, P = (np.ascontiguousarray(M.swapaxes(1, 2)) for M in (A, B, K, P))
         return Tvlqr(xn, A, B, st, K, P, np.array([lst.value], dtype=np.int32))
+
+    def track(self, solution, h: float, Qtheta, Qv, R, Qf_theta, Qf_v, x0s, zero_unactuated: bool = False):
+        """TrajectoryOptimizer::Track: tvlqr's gains about `solution`, and behind them on the device one rollout per row of x0s
+        [R, nq + nv] under u_t = solution.tau[t][actuated] - K[t] @ [q (-) q_t; v - v_t], held over a time step (zero_unactuated:
+        solution.tau is zeroed on the unactuated dofs first) - one pass of the device, one wait.
+        -> hip.Track with the leading axis [R]: x [R, N, nq + nv], u [R, N, nu], dx [R, N + 1, n], status [R, 2], .tvlqr as tvlqr returns"""
+        from .hip import Track, Tvlqr
+        N, nv, n = self.N, self.nv, 2 * self.nv
+        nu = len(self.actuated_dofs())
+        q, v, tau = (np.ascontiguousarray(_d(a)) for a in (solution.q, solution.v, solution.tau))
+        if q.size != (N + 1) * self.nq or v.size != (N + 1) * nv or tau.size != N * nv:
+            raise RuntimeError("track: a solution of this optimizer's horizon is required")
+        x0 = np.ascontiguousarray(_d(x0s)).reshape(-1, self.nq + nv)
+        nr = len(x0)
+        blocks = [np.ascontiguousarray(_d(M).reshape(nv, nv).T) for M in (Qtheta, Qv, Qf_theta, Qf_v)]
+        Rm = np.ascontiguousarray(_d(R).reshape(nu, nu).T)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        xn, A, B, st = np.zeros((N, self.nq + nv)), np.zeros((N, n, n)), np.zeros((N, nv, n)), np.zeros((N, 2), dtype=np.int32)
+        K, P, lst = np.zeros((N, n, nu)), np.zeros((N + 1, n, n)), C.c_int()
+        x, u, dx, tst = np.zeros((nr, N, self.nq + nv)), np.zeros((nr, N, nu)), np.zeros((nr, N + 1, n)), np.zeros((nr, 2), dtype=np.int32)
+        self._chk(lib().idto_opt_track(self._h, dptr(q), dptr(v), dptr(tau), float(h), dptr(blocks[0]), dptr(blocks[1]), dptr(Rm),
+                                       dptr(blocks[2]), dptr(blocks[3]), nr, dptr(x0), int(bool(zero_unactuated)), dptr(xn), dptr(A), dptr(B),
+                                       ip(st), dptr(K), dptr(P), C.byref(lst), dptr(x), dptr(u), dptr(dx), ip(tst)))
+        A, B, K, P = (np.ascontiguousarray(M.swapaxes(1, 2)) for M in (A, B, K, P))
+        return Track(x, u, dx, tst, Tvlqr(xn, A, B, st, K, P, np.array([lst.value], dtype=np.int32)))
 
     def solve_batch(self, q_guesses, problems=None, only_best: bool = False, models=None, contacts=None) -> BatchSolveResult:
         """TrajectoryOptimizer::SolveBatch: entry b is `Solve(q_guesses[b])` on an optimizer made with `problems[b]` (None:

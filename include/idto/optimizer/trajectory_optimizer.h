@@ -43,6 +43,7 @@
 #include "idto/optimizer/solver_parameters.h"
 #include "idto/optimizer/trajectory_optimizer_solution.h"
 #include "idto/optimizer/trajectory_optimizer_state.h"
+#include "idto/optimizer/tracking.h"
 #include "idto/optimizer/tvlqr.h"
 #include "idto/optimizer/warm_start.h"
 #include "idto_hip.h"
@@ -204,6 +205,12 @@ class TrajectoryOptimizer<double> {
   TvlqrGains Tvlqr(const TrajectoryOptimizerSolution<T>& solution, double h, const MatrixXd& Qtheta, const MatrixXd& Qv, const MatrixXd& R,
                    const MatrixXd& Qf_theta, const MatrixXd& Qf_v) const;
   std::vector<int> actuated_dofs() const;
+  // Tvlqr's gains about a solution, and on the device behind them one rollout per entry of x0s ([q; v] each) under
+  // u_t = tau*_t[actuated] - K_t [q (-) q_t; v - v_t] held over a time step, tau* = solution.tau[t] (with zero_unactuated: zero on the
+  // unactuated dofs, where a solution carries the constraint's residual), against the states (q_t, v_t), t = 0 ... N: one pass of
+  // the device, one wait (idto/optimizer/tracking.h, include/idto_hip.h idto_hip_plant_tvlqr_track).  time_step / h as in Tvlqr.
+  TrackedRollouts Track(const TrajectoryOptimizerSolution<T>& solution, double h, const MatrixXd& Qtheta, const MatrixXd& Qv, const MatrixXd& R,
+                        const MatrixXd& Qf_theta, const MatrixXd& Qf_v, const std::vector<VectorXd>& x0s, bool zero_unactuated = false) const;
 
   // What replaces the reference's EvalPlantContext(state, t) (optimizer/trajectory_optimizer.h:452): body poses and spatial
   // velocities, per-pair signed distances, witness points and contact forces, and the generalised force of contact at the

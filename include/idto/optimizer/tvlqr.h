@@ -73,7 +73,7 @@ class Linearizer {
     return g;
   }
 
- private:
+ protected:   // (idto/optimizer/tracking.h Tracker lays its call's arrays out with the same helpers)
   struct Raw { int batch = 0; std::vector<double> xn, A, B, K, P; std::vector<int> status; };
   Raw Sized(int nstates, int nq, int nv, int nu) const {
     Raw r;

@@ -643,6 +643,41 @@ int idto_hip_plant_tvlqr(idto_hip_ctx* ctx, int nstates, const double* x, const 
                          double* x_next_out, double* A_out, double* B_out, int* status_out, double* K_out, double* P_out,
                          int* lqr_status_out);
 
+/* ---- Plants under the time-varying LQR law (csrc/plant.h plant_body with LAW, track_kernel): `nrollouts` rollouts per
+ * problem of nsteps control steps, each `substeps` substeps of h under the torque
+ *   tau_t = tau*_t, with u_t = tau*_t[actuated] - K_t [q (-) q*_t ; v - v*_t] on the actuated dofs (tvlqr_step.h tvlqr_control),
+ * formed at the start of the step and HELD over it: the map that idto_hip_plant_linearize's A_t, B_t linearise.  With
+ * S = nsteps, R = nrollouts, n = 2 nv:
+ *   x_nom[batch][S + 1][nq + nv], tau_nom[batch][S][nv] (all nv components), K[batch][S][nu * n] column-major,
+ *   x0[batch][R][nq + nv] the rollouts' initial states.
+ * Outputs, each may be NULL and is then not fetched:
+ *   x_out[batch][R][S][nq + nv]: the state behind every step
+ *   u_out[batch][R][S][nu], dx_out[batch][R][S + 1][n]: the law's control and deviation in front of step t; row S of dx the
+ *   deviation of the final state from x*_S
+ *   status_out[batch][R][2]: idto_hip_plant_step's {code, substeps completed}; a non-finite u_t (a NaN in K_t, say) ends the
+ *   rollout with code 2 at that substep.  The rows of a rollout behind its last completed step are NaN (x and u from row
+ *   completed / substeps on, dx behind that row); the other rollouts are unaffected.
+ * The steps are cut into launches of whole steps of at most max_launch_substeps substeps (0: IDTO_PLANT_MAX_SUBSTEPS; a
+ * smaller figure is a test aid), all enqueued at once and waited for once; a rollout that ended in one launch is skipped by
+ * the later ones.  The storage is an allocation of the feature's own, made at the first call and grown on demand; a call
+ * changes none of the context's state nor the plants'.  `models` is the scene report's selector.  Refused by name before any
+ * device work: what idto_hip_plant_linearize refuses of its kind (an unknown `models`, the plants' models without a begun
+ * plant, nv > 64, child contexts, h not > 0 and finite, substeps outside [1, IDTO_PLANT_MAX_SUBSTEPS]), nsteps < 1,
+ * nrollouts < 1, batch * nrollouts > 65536, max_launch_substeps neither 0 nor in [substeps, IDTO_PLANT_MAX_SUBSTEPS], nu outside [1, nv], an index of
+ * actuated outside [0, nv), an input NULL, an entry of x_nom, tau_nom or x0 that is not finite (named by array and index; K may
+ * hold NaN: that is a status), a block whose LDS would exceed 160 KiB. */
+int idto_hip_plant_track(idto_hip_ctx* ctx, int nsteps, int substeps, double h, int models, int nu, const int* actuated,
+                         const double* x_nom, const double* tau_nom, const double* K, int nrollouts, const double* x0,
+                         int max_launch_substeps, double* x_out, double* u_out, double* dx_out, int* status_out);
+/* idto_hip_plant_tvlqr about x[batch][nsteps + 1][nq + nv] (the linearisations of its first nsteps rows) and
+ * tau[batch][nsteps][nv], and behind it on the same stream the rollouts of idto_hip_plant_track about the same x and tau, K read
+ * where the recursion left it on the device: one wait for everything.  Refuses what either refuses. */
+int idto_hip_plant_tvlqr_track(idto_hip_ctx* ctx, int nsteps, const double* x, const double* tau, double h, int substeps, double eps,
+                               int models, int nu, const int* actuated, const double* Q, const double* R, const double* Qf,
+                               int nrollouts, const double* x0, int max_launch_substeps, double* x_next_out, double* A_out,
+                               double* B_out, int* status_out, double* K_out, double* P_out, int* lqr_status_out, double* x_out,
+                               double* u_out, double* dx_out, int* track_status_out);
+
 /* Options: "gradients_method" = 0 forward differences (default), 1 / 2 central differences of
  * 2nd / 4th order (SolverParameters::gradients_method, reference solver_parameters.h:26-50,
  * trajectory_optimizer.cc:565-885); 3 (autodiff) is refused.  "reference_solver" = 1 selects the bit-exact restatement of the reference's

@@ -72,6 +72,16 @@ int idto_opt_tvlqr(idto_opt* opt, const double* sol_q, const double* sol_v, cons
                    const double* Qv, const double* R, const double* Qf_theta, const double* Qf_v, double* x_next_out, double* A_out,
                    double* B_out, int* status_out, double* K_out, double* P_out, int* lqr_status_out);
 
+/* TrajectoryOptimizer::Track (include/idto/optimizer/tracking.h; include/idto_hip.h idto_hip_plant_tvlqr_track, whose layouts these
+ * are): idto_opt_tvlqr's gains about the solution, and behind them on the device nrollouts rollouts from x0[nrollouts][nq + nv] under
+ * u_t = sol_tau[t][actuated] - K_t [q (-) sol_q[t]; v - sol_v[t]], held over a time step; zero_unactuated != 0 zeroes sol_tau on the
+ * unactuated dofs first.  Outputs, each may be NULL: idto_opt_tvlqr's, then x_out[nrollouts][N][nq + nv], u_out[nrollouts][N][nu],
+ * dx_out[nrollouts][N + 1][n], track_status_out[nrollouts][2] ({code, substeps completed}). */
+int idto_opt_track(idto_opt* opt, const double* sol_q, const double* sol_v, const double* sol_tau, double h, const double* Qtheta,
+                   const double* Qv, const double* R, const double* Qf_theta, const double* Qf_v, int nrollouts, const double* x0,
+                   int zero_unactuated, double* x_next_out, double* A_out, double* B_out, int* status_out, double* K_out, double* P_out,
+                   int* lqr_status_out, double* x_out, double* u_out, double* dx_out, int* track_status_out);
+
 /* TrajectoryOptimizer::SolveBatch (include/idto/optimizer/trajectory_optimizer.h): B problems of the optimizer's model,
  * horizon, solver and contact parameters; entry b is idto_opt_solve of q_guesses[b] on an optimizer created with problems[b]
  * (NULL: the optimizer's own problem for every entry).  q_guesses: [B][(N+1)*nq]; sol_q / sol_v / sol_tau: [B][...] (any may

@@ -15,7 +15,7 @@ import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REMARKS = [os.path.join(ROOT, "build", "fd_launch.remarks"), os.path.join(ROOT, "build", "idto_hip.remarks"),
            os.path.join(ROOT, "build", "plant_launch.remarks"), os.path.join(ROOT, "build", "scene_launch.remarks"),
-           os.path.join(ROOT, "build", "lin_launch.remarks")]
+           os.path.join(ROOT, "build", "lin_launch.remarks"), os.path.join(ROOT, "build", "track_launch.remarks")]
 
 # kernel (demangled, without "idto_dev::" and arguments) -> (max spilled VGPRs, max scratch bytes per lane, max spilled SGPRs)
 # Values: what profiles/r05_isa_resources.txt records, the SGPR figure with a margin of 24 (it moves by a few with every
@@ -136,6 +136,17 @@ LIMITS = {
     "lin_perturb_kernel": (0, 0, 0 + 24),
     "lin_difference_kernel": (0, 0, 0 + 24),
     "tvlqr_kernel": (0, 0, 11 + 24),
+    # (the plants under the time-varying LQR law, csrc/plant.h: plant_kernel's body with the law at the start of every control
+    # step - six more pointers and six more integers live over the substep loop.  Against plant_kernel's rows: 31 to 87 more
+    # scalar registers spilled to lanes; <2> and <8, true, false> spill what plant_kernel spills of vector registers, <3> 4 more
+    # (now past the accumulation registers: 68 B of scratch), <4> and <8> 25 / 37 more to 100 B more of scratch, and
+    # <8, true, true> spills ONE vector register to 8 B of scratch where plant_kernel spills none.  Recorded)
+    "track_kernel<2, false, false>": (24, 0, 202 + 24),
+    "track_kernel<3, false, false>": (32, 68, 214 + 24),
+    "track_kernel<4, false, false>": (112, 364, 229 + 24),
+    "track_kernel<8, false, false>": (637, 1512, 265 + 24),
+    "track_kernel<8, true, false>": (0, 0, 214 + 24),
+    "track_kernel<8, true, true>": (1, 8, 283 + 24),
     "ls_gather_batch_kernel": (0, 0, 0 + 24),
     "ls_trial_kernel": (0, 0, 0 + 24),
     "ls_cost_kernel": (0, 0, 0 + 24),
@@ -146,7 +157,7 @@ LIMITS = {
 
 
 def compile_remarks():
-    """The five translation units with the remark pass on (device code only, no object files kept)."""
+    """The six translation units with the remark pass on (device code only, no object files kept)."""
     os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Iinclude", "-Iidto_amd/csrc", "-S",
              "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"]
@@ -155,7 +166,8 @@ def compile_remarks():
             ([hipcc] + flags + ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "idto_amd/csrc/idto_hip.hip", "-o", "/dev/null"], REMARKS[1]),
             ([hipcc] + flags + ["idto_amd/csrc/plant_launch.hip", "-o", "/dev/null"], REMARKS[2]),
             ([hipcc] + flags + ["idto_amd/csrc/scene_launch.hip", "-o", "/dev/null"], REMARKS[3]),
-            ([hipcc] + flags + ["idto_amd/csrc/lin_launch.hip", "-o", "/dev/null"], REMARKS[4])]
+            ([hipcc] + flags + ["idto_amd/csrc/lin_launch.hip", "-o", "/dev/null"], REMARKS[4]),
+            ([hipcc] + flags + ["idto_amd/csrc/track_launch.hip", "-o", "/dev/null"], REMARKS[5])]
     procs = [(subprocess.Popen(cmd, cwd=ROOT, stderr=open(out, "w")), out) for cmd, out in jobs]
     for p, out in procs:
         if p.wait() != 0:

@@ -5,7 +5,7 @@ tools/make_design.py.  The numbers in DESIGN.md are therefore the ones in profil
 KNOWN DRIFT, to be settled before the next regeneration: the committed DESIGN.md carries text on the pipelined solver's tail
 behind the separator (section 5.1's penta_pipe row, 5.2's "Joiners" / "Producers: closed form" items, its timeline and bound,
 the numbers table's closed_tail row, item 8 of section 10) that was written into DESIGN.md alone; tools/design/DESIGN.in.md and
-this script do not produce it, so a regeneration drops it.  Section 14.4 is in both."""
+this script do not produce it, so a regeneration drops it.  Sections 14.4 and 14.5 are in both."""
 import csv
 import json
 import os
@@ -144,6 +144,8 @@ vals["SOLVE_BATCH_FIGURES"] = ("Measured (`tools/solve_batch_bench.py` → `prof
                                + "\n".join("    " + l for l in sb[1:]))
 # §14.4: the time-varying LQR gains, profiles/tvlqr.txt (tools/tvlqr_bench.py; not a round's file)
 vals["TVLQR_TABLE"] = "\n".join("    " + l.strip() for l in open(os.path.join(ROOT, "profiles", "tvlqr.txt")) if l.startswith("  "))
+# §14.5: rollouts under the law, profiles/track.txt (tools/track_bench.py; not a round's file)
+vals["TRACK_TABLE"] = "\n".join("    " + l.strip() for l in open(os.path.join(ROOT, "profiles", "track.txt")) if l.startswith("  "))
 src = os.path.join(ROOT, "tools", "design", "DESIGN.in.md")
 text = open(src).read()
 subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_design.py")])

@@ -317,7 +317,9 @@ __host__ __device__ inline int fd_xch_doubles(int nxb, int threads, int npaths, 
   return (threads / npaths) * xch_eval_doubles(nxb, nstem);
 }
 
-template <int MAXC, int SHAPE = 0>
+// DD: forward differences on the lane map without the redundant path lanes (model_layout.h tree_shape_dedup) -
+// the kernels fd_dedup_kernel and fd_dedup_models_kernel below, so that fd_kernel's own code is what it was.
+template <int MAXC, int SHAPE = 0, bool DD = false>
 IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem& P, const double* __restrict__ q,
                       double* __restrict__ slab, int slab_stride, double* __restrict__ v_out,
                       double* __restrict__ a_out, double* __restrict__ nplus_out, const int k, int mode,
@@ -325,6 +327,7 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
   extern __shared__ double lds[];
   constexpr bool FAST = SHAPE != 0 && SHAPE != SHAPE_XCH && SHAPE != SHAPE_STEM;   // id_fast.h's straight-line evaluation
   const int tid = threadIdx.x, nt = blockDim.x;
+  if constexpr (DD) mode = 1;   // (launched for forward differences only)
   if (stop_after == 10) return;   // (profiling aid: the launch alone)
 #ifdef IDTO_FD_STAMPS
   long long st_arr[IDTO_FD_NSTAMPS] = {};
@@ -628,6 +631,54 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
     FT.body = Ml.f_body; FT.cbody = Ml.f_cbody; FT.pairs = Ml.f_pairs; FT.seg = Ml.f_seg; FT.maxpp = Ml.f_maxpp;
     FT.gslots = Ml.gslots; FT.gcommon = Ml.gcommon;
     const int grp = tid / FS::NP, path = tid % FS::NP;
+    (void)grp; (void)path;
+    if constexpr (DD) {
+      static_assert(tree_shape_dedup(SHAPE), "model_layout.h: the shapes with the lane map");
+      // The lane map without the redundant path lanes (model_layout.h tree_shape_dedup): the block's first
+      // half are main lanes - a lane word names each one's evaluation and path -, the second half evaluates their pairs with
+      // the world.  The two roles meet at four workgroup barriers; the branch between them is a scalar one.
+      {
+        const int* lanes = Ml.f_seg + FS::NP * (FS::MAXC + 2);   // (model_layout.h: the lane words follow the segment words)
+        double* xfoot = xch;
+        double* xcbs = xfoot + kFdMainLanes * FDX_STATE;
+        double* fres = xcbs + (kFdMainLanes / 4) * FDX_STATE;
+        double* bres = fres + kFdMainLanes * FDX_RES;
+        double* pub = bres + (kFdMainLanes / 4) * FDX_RES;
+        if (__builtin_amdgcn_readfirstlane(tid >> 7) == 0) {
+          const int word = lanes[tid], el = word & 255;
+          InFwd in;
+          in.q1 = q1; in.v1 = v1; in.a0 = a0; in.N1 = N1; in.N0 = N0; in.nv = nv;
+          in.kind = (el == 0) ? 0 : ((el < 1 + nP) ? 1 : ((el < 1 + nP + nT) ? 2 : 3));
+          in.col = (el == 0) ? 0 : ((el < 1 + nP) ? el - 1 : ((el < 1 + nP + nT) ? el - 1 - nP : el - 1 - nP - nT));
+          in.dq = edq[el];
+          in.sdv = (in.kind == 2) ? -edv[el] : ((in.kind == 1) ? edv[el] : 0.0);
+          in.sda = (in.kind == 2) ? -eda[el] : ((in.kind == 1) ? eda[el] : 0.0);
+          in.keep = (in.kind == 3) ? 0ull : ~0ull;
+          in.keep0 = (in.kind == 2) ? ~0ull : 0ull;
+          FdLane dl;
+          dl.word = word;
+          dl.foot = xfoot + tid * FDX_STATE; dl.cbs = xcbs + (tid >> 2) * FDX_STATE;
+          dl.foot_res = fres + tid * FDX_RES; dl.body_res = bres + ((word & FDL_BODY_OWN) ? (tid >> 2) : 0) * FDX_RES;
+          dl.pub = pub; dl.tau0 = etau;
+          id_eval_fast<FS::MAXC, FS::NP, FS::CJ, FS::J0, FS::K0, FS::W2, FS::GS, true>(
+              FT, Ml.gravity, cp, (word >> 8) & 3, (word & FDL_FULL) != 0, in, (word & FDL_VALID) ? etau + el * nv : edump,
+#ifdef IDTO_FD_STAMPS
+              idto_fd_st,
+#else
+              nullptr,
+#endif
+              &dl);
+        } else {
+          // (v, a, N+ leave from the last wavefront before its first wait)
+          if (late_outputs && tid >= nt - 64) trajectory_outputs(tid - (nt - 64), 64);
+          fd_helper_lane(FT.pairs, cp, lanes[tid], xfoot, xcbs, fres, bres
+#ifdef IDTO_FD_STAMPS
+                         , idto_fd_st
+#endif
+          );
+        }
+      }
+    } else {
     for (int e0 = 0; e0 < ce; e0 += groups) {
       const int el = (e0 == 0) ? grp : e0 + (groups - 1 - grp);
       if (el < ce) {
@@ -655,6 +706,7 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
       }
     }
     if (late_outputs && tid >= nt - 64) trajectory_outputs(tid - (nt - 64), 64);
+    }
   } else {
   for (int e0 = 0; e0 < ce; e0 += groups) {
     const int el = e0 + tid / K;
@@ -954,6 +1006,33 @@ __global__ void __launch_bounds__(256) fd_along_models_kernel(const double* __re
   fd_body<MAXC, SHAPE>(*(const DevModel*)(rec + mat), *(const DevContact*)(rec + cat), at_problem(P, (size_t)blockIdx.z * pstride),
                        at_problem(q, w), at_problem(slab, w), slab_stride, at_problem(v_out, w), at_problem(a_out, w),
                        at_problem(nplus_out, w), k_begin + (int)blockIdx.x, 0, stop_after, echunk, nullptr);
+}
+
+// fd_kernel and fd_models_kernel for forward differences on the lane map without the redundant path lanes (fd_body's
+// DD; blocks of kFdMainLanes + kFdHelperLanes threads).  Kernels of their own, so that the two above keep their text and
+// their code: the context's option fd_dedup chooses between them at the launch.
+template <int MAXC, int SHAPE>
+__global__ void __launch_bounds__(256) fd_dedup_kernel(DevModel M, DevContact cp, DevProblem P, const double* __restrict__ q,
+                          double* __restrict__ slab, int slab_stride, double* __restrict__ v_out,
+                          double* __restrict__ a_out, double* __restrict__ nplus_out, int k_begin,
+                          int stop_after, int echunk, size_t pstride, double* __restrict__ terms, AltSel alt) {
+  const size_t o = (size_t)blockIdx.y * pstride;
+  const size_t w = o + (size_t)alt_offset(alt, o);
+  fd_body<MAXC, SHAPE, true>(M, cp, at_problem(P, o), at_problem(q, o), at_problem(slab, w), slab_stride, at_problem(v_out, w),
+                                  at_problem(a_out, w), at_problem(nplus_out, w), k_begin + (int)blockIdx.x, 1, stop_after, echunk,
+                                  terms ? at_problem(terms, w) : nullptr);
+}
+template <int MAXC, int SHAPE>
+__global__ void __launch_bounds__(256) fd_dedup_models_kernel(const double* __restrict__ records, size_t mstride, size_t cat, size_t mat,
+                          DevProblem P, const double* __restrict__ q, double* __restrict__ slab, int slab_stride,
+                          double* __restrict__ v_out, double* __restrict__ a_out, double* __restrict__ nplus_out, int k_begin,
+                          int stop_after, int echunk, size_t pstride, double* __restrict__ terms, AltSel alt) {
+  const size_t o = (size_t)blockIdx.y * pstride;
+  const size_t w = o + (size_t)alt_offset(alt, o);
+  const RecordPtr rec = record_at(records, (size_t)blockIdx.y * mstride);
+  fd_body<MAXC, SHAPE, true>(*(const DevModel*)(rec + mat), *(const DevContact*)(rec + cat), at_problem(P, o), at_problem(q, o),
+                                  at_problem(slab, w), slab_stride, at_problem(v_out, w), at_problem(a_out, w), at_problem(nplus_out, w),
+                                  k_begin + (int)blockIdx.x, 1, stop_after, echunk, terms ? at_problem(terms, w) : nullptr);
 }
 
 }  // namespace idto_dev

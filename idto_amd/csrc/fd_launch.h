@@ -34,6 +34,9 @@ struct FdLaunch {
   const double* records = nullptr; size_t mstride = 0, rec_contact = 0, rec_model = 0;
   int shape;   // id_fast.h: the model's instantiated tree shape, 0: id_eval<MAXC>, SHAPE_XCH: id_eval<8, true> (shared pairs), SHAPE_STEM: id_eval<8, true, true>
   int maxc;
+  // forward differences on the lane map without the redundant path lanes (fd_dedup_kernel / fd_dedup_models_kernel): a shape
+  // with model_layout.h's tree_shape_dedup, mode 1, a block of kFdMainLanes + kFdHelperLanes threads, no candidates
+  bool dedup = false;
 };
 // enqueues fd_kernel<MAXC, SHAPE>; the caller checks hipGetLastError()
 void fd_launch(const FdLaunch& a);

@@ -15,6 +15,17 @@ static void go(const FdLaunch& a) {
                        a.bstride, a.gstride);
     return;
   }
+  if constexpr (tree_shape_dedup(SH)) {
+    if (a.dedup && !a.cstride) {   // forward differences on the lane map without the redundant path lanes (LaunchFd: mode 1, 256 threads)
+      if (a.records)
+        hipLaunchKernelGGL((fd_dedup_models_kernel<MC, SH>), a.grid, a.block, a.lds, a.stream, a.records, a.mstride, a.rec_contact, a.rec_model,
+                           a.P, a.q, a.slab, a.slab_stride, a.v, a.a, a.nplus, a.k_begin, a.stop_after, a.echunk, a.pstride, a.terms, a.alt);
+      else
+        hipLaunchKernelGGL((fd_dedup_kernel<MC, SH>), a.grid, a.block, a.lds, a.stream, a.M, a.cp, a.P, a.q, a.slab, a.slab_stride, a.v,
+                           a.a, a.nplus, a.k_begin, a.stop_after, a.echunk, a.pstride, a.terms, a.alt);
+      return;
+    }
+  }
   if (a.records) {   // a batch with per-problem parameter records (fd_models_kernel)
     hipLaunchKernelGGL((fd_models_kernel<MC, SH>), a.grid, a.block, a.lds, a.stream, a.records, a.mstride, a.rec_contact, a.rec_model,
                        a.P, a.q, a.slab, a.slab_stride, a.v, a.a, a.nplus, a.k_begin, a.mode, a.stop_after, a.echunk, a.pstride, a.terms, a.alt);
@@ -41,6 +52,10 @@ static void allow(int max_lds) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fd_along_batch_kernel<MC, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fd_models_kernel<MC, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fd_along_models_kernel<MC, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+  if constexpr (tree_shape_dedup(SH)) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fd_dedup_kernel<MC, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fd_dedup_models_kernel<MC, SH>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+  }
 }
 using Shapes = std::make_integer_sequence<int, SHAPE_STEM>;   // (shape = 1 + the index)
 

@@ -351,6 +351,93 @@ FastOrder OrderFastPairs(const idto_model_t* m, const Star& star, const PairList
   return o;
 }
 
+// ---- 8b. fd_kernel's forward-difference lane map without the redundant path lanes (model_layout.h tree_shape_dedup,
+// DESIGN.md 3.1).  A column of q, or a mass column, of a chain joint touches that chain's path only: in such an
+// evaluation the other paths' lanes repeat the baseline's path (exact zeros in a mass column).  Main lanes: four per
+// evaluation of the baseline and of the common body's columns, one per single-path evaluation; helper lane h evaluates
+// pairs for main lane h.  Refused - `on` false, the lane map of every evaluation on all its paths stays - when
+//   - the shape's kernel has no such path, or a pair touches two chains,
+//   - N+'s column for a chain joint is not a unit column (the perturbed v and a would reach other joints),
+//   - the pairs are not laid out as that path walks them: per path nothing before the last slot, on the last slot one pair
+//     with the common body then one with the world, behind it at most one pair of the common body with the world and
+//     that on one path only,
+//   - the tasks do not fit kFdMainLanes.
+struct FdDedup {
+  bool on = false;
+  std::vector<int> qpaths, vpaths, lanes;
+};
+FdDedup BuildFdDedup(const idto_model_t* m, const Stem& stem, const Star& star, const PairLists& l, const NPlus& nplus,
+                     const FastShapeOf& fast, const FastOrder& o, int f_maxpp) {
+  const int K = m->npaths, maxc = star.maxc, nq = m->nq, nv = m->nv, all = (1 << K) - 1;
+  FdDedup d;
+  d.qpaths.assign(nq, all);
+  d.vpaths.assign(nv, all);
+  bool unit = true;
+  for (int b = 0; b < m->nbodies; ++b) {
+    if (b == m->common_body || stem.has(b)) continue;
+    const int jn = m->jtype[b] == IDTO_JOINT_PLANAR ? 3 : 1;   // (a chain body's joint: revolute, prismatic or planar)
+    for (int e = 0; e < jn; ++e) {
+      const int c = m->qstart[b] + e, j = m->vstart[b] + e;
+      d.qpaths[c] = 1 << m->body_path[b];
+      d.vpaths[j] = 1 << m->body_path[b];
+      unit = unit && nplus.colinfo[c] == (j | 1 << 16) && nplus.constant[(size_t)c * nv + j] == 1.0;
+    }
+  }
+  if (!tree_shape_dedup(fast.shape) || l.shared || !unit || m->common_body < 0 || K != 4) return d;
+  // ---- the pairs, as id_eval_fast<..., DD> walks them
+  int body_path = -1, body_rec = 0;
+  std::vector<int> foot_rec(K, 0);
+  for (int p = 0; p < K; ++p) {
+    const int* seg = o.seg.data() + (size_t)p * (maxc + 2);
+    for (int gi = 0; gi < maxc; ++gi)
+      if (seg[gi] >> 16) return d;
+    const int s0 = seg[maxc] & 0xffff, tail = seg[maxc + 1] >> 16;
+    if ((seg[maxc] >> 16) != 2 || tail > 1) return d;
+    auto other = [&](int pi) { return l.sa[pi] >= 0 ? l.sb[pi] : l.sa[pi]; };
+    if (other(o.order[p][s0]) != -1 || other(o.order[p][s0 + 1]) != -2) return d;
+    foot_rec[p] = p * f_maxpp + s0 + 1;
+    if (tail) {
+      if (body_path >= 0) return d;
+      const int pi = o.order[p][seg[maxc + 1] & 0xffff];
+      if (std::max(l.sa[pi], l.sb[pi]) != -1 || std::min(l.sa[pi], l.sb[pi]) != -2) return d;
+      body_path = p;
+      body_rec = p * f_maxpp + (seg[maxc + 1] & 0xffff);
+    }
+  }
+  if (K * f_maxpp > 255) return d;
+  // ---- the main lanes: the evaluations on all paths first (their four lanes aligned), then the single-path ones, each
+  // in the order of fd_body's evaluation index e = 0 | 1 + c (P) | 1 + nq + c (T) | 1 + 2 nq + j (M)
+  const int E = 1 + 2 * nq + nv;
+  auto paths_of = [&](int e) { return e == 0 ? all : (e < 1 + 2 * nq ? d.qpaths[(e - 1) % nq] : d.vpaths[e - 1 - 2 * nq]); };
+  std::vector<int> main;
+  for (int e = 0; e < E; ++e) {
+    if (paths_of(e) != all) continue;
+    const int full = e < 1 + 2 * nq ? FDL_FULL : 0;
+    for (int p = 0; p < K; ++p)
+      main.push_back(e | p << 8 | FDL_WHOLE | FDL_VALID | full | ((full && p == body_path) ? FDL_BODY_OWN : 0));
+  }
+  for (int e = 0; e < E; ++e) {
+    const int ps = paths_of(e);
+    if (ps == all) continue;
+    if (ps & (ps - 1)) return d;
+    int p = 0;
+    while (!(ps >> p & 1)) ++p;
+    const int full = e < 1 + 2 * nq ? FDL_FULL : 0;
+    main.push_back(e | p << 8 | FDL_VALID | full | ((full && p == body_path) ? FDL_BODY_BASE : 0));
+  }
+  if ((int)main.size() > kFdMainLanes || E > 255) return d;
+  // (the baseline's lanes are lanes 0 .. K - 1: FDL_BODY_BASE reads the result of lane body_path's helper)
+  for (int p = (int)main.size(); p < kFdMainLanes; ++p) main.push_back(0 | (p % K) << 8);
+  d.lanes = main;
+  for (int h = 0; h < kFdHelperLanes; ++h) {
+    const int w = main[h], p = w >> 8 & 3;
+    const bool foot = (w & FDL_VALID) && (w & FDL_FULL), body = (w & FDL_BODY_OWN) != 0;
+    d.lanes.push_back((foot ? FDH_FOOT : 0) | (body ? FDH_BODY : 0) | h << 8 | foot_rec[p] << 16 | body_rec << 24);
+  }
+  d.on = true;
+  return d;
+}
+
 // ---- 9. id_fast.h's records: one of constants per (path, slot), one for the common body, one per contact pair in
 // walking order
 struct FastRecords {
@@ -452,10 +539,12 @@ int BuildModelTables(const idto_model_t* m, ModelTables* out, std::string* err) 
     t.at.f_body = k.d(rec.body); t.at.f_cbody = k.d(rec.cbody); t.at.f_pairs = k.d(rec.pairs);
     t.f_maxpp = rec.f_maxpp;
   }
+  const FdDedup dedup = BuildFdDedup(m, stem, star, lists, nplus, fast, order, t.f_maxpp);
   // the int tables, those fd_kernel needs beside the gathered records first: with a fast shape it stages only
   // [fast_lo, fast_lo + fast_n) of the blob in LDS
   t.at.jtype = k.i(m->jtype, nb); t.at.qstart = k.i(m->qstart, nb); t.at.vstart = k.i(m->vstart, nb);
   t.at.colinfo = k.i(nplus.colinfo); t.at.rowinfo = k.i(nplus.rowinfo); t.at.f_seg = k.i(order.seg);
+  const size_t lanes_at = k.i(dedup.lanes);   // (no table of DevModel's: the kernel finds the words behind f_seg's)
   const size_t fast_end = k.ints.size();
   t.at.parent = k.i(m->parent, nb); t.at.geom_type = k.i(m->geom_type, ng); t.at.chain = k.i(star.chain);
   t.at.nchain = k.i(star.nchain); t.at.pkind = k.i(star.pkind); t.at.path_npairs = k.i(lists.path_npairs);
@@ -479,6 +568,7 @@ int BuildModelTables(const idto_model_t* m, ModelTables* out, std::string* err) 
   t.fast_n = (int)(nd + (fast_end + 1) / 2) - t.fast_lo;
   t.nxb = xch.nxb; t.nstem = stem.n(); t.gslots = star.gslots; t.gcommon = star.gcommon; t.gstem = star.gstem;
   t.maxc = star.maxc; t.capsules = capsules;
+  t.fd_dedup = dedup.on; t.fd_lanes_at = lanes_at + 2 * nd; t.fd_qpaths = dedup.qpaths; t.fd_vpaths = dedup.vpaths;
   return 0;
 }
 

@@ -28,6 +28,13 @@ struct ModelTables {
   // the context's: the longest chain, and whether the model has a capsule
   int maxc = 1;
   bool capsules = false;
+  // fd_kernel's forward-difference lane map without the redundant path lanes (model_layout.h tree_shape_dedup): whether the
+  // model takes it (then the blob read as int[] holds kFdMainLanes + kFdHelperLanes lane words from fd_lanes_at on, right
+  // behind f_seg's words and inside the part a shape's kernel stages; else none), and what it was
+  // derived from - the paths (bit p) that column c of q / mass column j touches, all of them for a column of the common body
+  bool fd_dedup = false;
+  size_t fd_lanes_at = 0;
+  std::vector<int> fd_qpaths, fd_vpaths;
 };
 
 // 0, or -1 with the refusal in *err.  The checks run in a fixed order - geometry, stem, then paths, joints, gravity

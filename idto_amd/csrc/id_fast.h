@@ -33,7 +33,7 @@
 #ifndef IDTO_FD_STAMP_TID
 #define IDTO_FD_STAMP_TID 192
 #endif
-#define IDTO_FD_NSTAMPS 24   // slots per stamping lane (tools/fd_stamps.py names them)
+#define IDTO_FD_NSTAMPS 26   // slots per stamping lane (tools/fd_stamps.py names them)
 #define FD_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); asm volatile("" ::: "memory"); if (idto_fd_st) idto_fd_st[i] = (long long)__builtin_readcyclecounter(); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
 #define FD_STAMP(i) do { } while (0)
@@ -335,6 +335,69 @@ struct InFwd {
   IDTO_DEV InFwd laundered() const { InFwd o = *this; o.v1 = lds_launder(v1); o.N1 = lds_launder(N1); return o; }
 };
 
+// ---- the forward-difference lane map without the redundant path lanes (model_layout.h tree_shape_dedup):
+// what main and helper lanes hand each other through LDS.  Every value is stored and read back as it is - an exact copy.
+enum { FDX_STATE = 19, FDX_RES = 9 };   // doubles per body state (18 used) and per pair result (fc, nc, hit); odd strides: no bank conflicts
+constexpr int fd_dedup_doubles() {
+  return kFdMainLanes * FDX_STATE + (kFdMainLanes / 4) * FDX_STATE + kFdMainLanes * FDX_RES + (kFdMainLanes / 4) * FDX_RES + 4 * 12;
+}
+IDTO_DEV void st_state(double* x, const BodyState& b) {
+#pragma unroll
+  for (int i = 0; i < 9; ++i) x[i] = b.R.m[i];
+  x[9] = b.p.x; x[10] = b.p.y; x[11] = b.p.z; x[12] = b.w.x; x[13] = b.w.y; x[14] = b.w.z; x[15] = b.v.x; x[16] = b.v.y; x[17] = b.v.z;
+}
+IDTO_DEV BodyState ld_state(const double* x) {
+  BodyState b;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) b.R.m[i] = x[i];
+  b.p = ldv3(x + 9); b.w = ldv3(x + 12); b.v = ldv3(x + 15);
+  return b;
+}
+struct FdLane {             // one main lane's part
+  int word;                 // FDL_*
+  double* foot;             // [FDX_STATE] the last slot's state, for the lane's helper
+  double* cbs;              // [FDX_STATE] the common body's state, for the helper of the lane that adds its pair
+  const double* foot_res;   // [FDX_RES] the helper's result: the last slot's pair with the world
+  const double* body_res;   // [FDX_RES] ... the common body's pair with the world (FDL_BODY_BASE: the baseline's)
+  double* pub;              // [NP][12] the baseline's cfe, cne, root_f, root_n per path
+  const double* tau0;       // the baseline's tau row
+};
+// A helper lane: the pairs with the world of main lane `hword >> 8`, the common body's when its state is there (behind the
+// first barrier), the last slot's when that is (behind the second) - box against box and sphere against box never in one
+// wait.  pair_eval<false> is what pair_group<false> runs for the common body's pair, and for a pair of a chain body with
+// the world pair_eval<true> selects, value by value, what <false> computes.  The barriers are the main lanes' four.
+IDTO_DEV void fd_helper_lane(const double* pairs, const DevContact& cp, int hword, const double* xfoot, const double* xcbs,
+                             double* fres, double* bres, long long* idto_fd_st = nullptr) {
+  (void)idto_fd_st;
+  const int m = (hword >> 8) & 255;
+#pragma unroll 1
+  for (int ph = 0; ph < 2; ++ph) {
+    __syncthreads();
+    if (hword & (ph ? FDH_FOOT : FDH_BODY)) {
+      const BodyState C = ld_state(ph ? xfoot + m * FDX_STATE : xcbs + (m >> 2) * FDX_STATE);
+      double* res = ph ? fres + m * FDX_RES : bres + (m >> 2) * FDX_RES;
+      V3 fc, nc, fo, no;
+      const bool hit = pair_eval<false>(pairs + ((hword >> (ph ? 16 : 24)) & 255) * FP_STRIDE, cp, C, C, &fc, &nc, &fo, &no);
+      res[6] = hit ? 1.0 : 0.0;
+      if (hit) { res[0] = fc.x; res[1] = fc.y; res[2] = fc.z; res[3] = nc.x; res[4] = nc.y; res[5] = nc.z; }
+    }
+    if (ph) FD_STAMP(25);
+  }
+  __syncthreads();
+  __syncthreads();
+}
+// the sum over the paths of a single-path lane: its own value in its own place, the baseline's (zeros in a mass column) in
+// the others, in the association of tree_sum_fast<4> on path 0
+IDTO_DEV V3 fd_path_sum(const double* pub, int off, int path, V3 own, bool full) {
+  V3 t[4];
+#pragma unroll
+  for (int pp = 0; pp < 4; ++pp) {
+    const V3 b = ldv3(pub + pp * 12 + off);
+    t[pp] = mk(pp == path ? own.x : (full ? b.x : 0.0), pp == path ? own.y : (full ? b.y : 0.0), pp == path ? own.z : (full ? b.z : 0.0));
+  }
+  return (t[0] + t[1]) + (t[2] + t[3]);
+}
+
 // GS: the shape's bodies may have their weight switched off (DevModel::gslots, gcommon); the shapes without it are built
 // only for models whose every body has gravity, and their code is what it was without the switch.
 // tau = ID(q, v, a) for the lane's path: id_eval<MAXC> for a model of shape (CJ, J0, K0).
@@ -342,9 +405,15 @@ struct InFwd {
 // pairs of its group touch slot W2 - 1 as their other body (pair_eval's "common" argument is that slot's state; the
 // force on it is taken out of its wrench after the group - the slot has no pairs of its own, host/model_tables.cc checks, so the
 // order of the generic sum, fin - (0 + f), is kept).
-template <int MAXC, int NP, int CJ, int J0, int K0, int W2, int GS = 0, class In>
+// DD: a main lane of the lane map without the redundant path lanes (`dl`, FdLane above; the caller is the whole block's
+// first half, every lane of it, and the second half runs fd_helper_lane: four workgroup barriers).  The lane's own
+// expressions are the ones below, unchanged; what differs is who evaluates the pairs with the world (the lane's helper;
+// their wrenches are added at their place in the walking order) and, for a single-path lane, where the other paths' terms
+// of the common body's sums come from (the baseline's lanes, through LDS).
+template <int MAXC, int NP, int CJ, int J0, int K0, int W2, int GS = 0, bool DD = false, class In>
 IDTO_DEV void id_eval_fast(const FastTab& T, const double* gravity, const DevContact& cp, int path, bool full,
-                           const In& in_fwd, double* tau, long long* idto_fd_st = nullptr) {
+                           const In& in_fwd, double* tau, long long* idto_fd_st = nullptr, const FdLane* dl = nullptr) {
+  static_assert(!DD || (CJ == IDTO_JOINT_FLOATING && K0 == PK_COMMON && W2 < 0 && NP == 4), "the lane map's shapes");
   const In& in = in_fwd;
   constexpr bool HAS_COMMON = (CJ == IDTO_JOINT_FLOATING);
   const V3 zero = mk(0, 0, 0);
@@ -415,7 +484,11 @@ IDTO_DEV void id_eval_fast(const FastTab& T, const double* gravity, const DevCon
     cb_a = zero + a_rel;
     inertial_wrench_rec(ct, cb.R, cb.w, cb_al, cb_a, GS ? body_gravity(T.gcommon != 0, g) : g, &cb_fin, &cb_nin);
     pin(cb_fin); pin(cb_nin);
-    if (full) pair_group<false>(plist, seg[0], cp, cb, cb, &cfe, &cne, &cfe, &cne);
+    if (!DD && full) pair_group<false>(plist, seg[0], cp, cb, cb, &cfe, &cne, &cfe, &cne);   // (DD: the host found no such pair)
+  }
+  if constexpr (DD) {
+    if (dl->word & FDL_BODY_OWN) st_state(dl->cbs, cb);
+    __syncthreads();
   }
 
   FD_STAMP(6);
@@ -489,6 +562,25 @@ IDTO_DEV void id_eval_fast(const FastTab& T, const double* gravity, const DevCon
       ft[W2 - 1] = ft[W2 - 1] - ofe;
       nt[W2 - 1] = nt[W2 - 1] - one;
       pin(ft[W2 - 1]); pin(nt[W2 - 1]);
+    } else if constexpr (DD) {
+      // (the host found pairs on the last slot only: one with the common body, evaluated here while the helper evaluates the
+      // one with the world that follows it in the list)
+      if (s == MAXC - 1) {
+        if (full) st_state(dl->foot, bs);
+        __syncthreads();
+        FD_STAMP(23);
+        if (full) {
+          V3 fc, nc, fo, no;
+          if (pair_eval<true>(plist + (seg[1 + s] & 0xffff) * FP_STRIDE, cp, bs, cb, &fc, &nc, &fo, &no)) {
+            fext = fext + fc; next = next + nc;
+            cfe = cfe + fo; cne = cne + no;
+          }
+        }
+        __syncthreads();
+        if (full && dl->foot_res[6] != 0.0) {
+          fext = fext + ldv3(dl->foot_res); next = next + ldv3(dl->foot_res + 3);
+        }
+      }
     } else if (full) {
       pair_group<HAS_COMMON>(plist, seg[1 + s], cp, bs, cb, &fext, &next, &cfe, &cne);
     }
@@ -500,7 +592,11 @@ IDTO_DEV void id_eval_fast(const FastTab& T, const double* gravity, const DevCon
     if (s == 0) FD_STAMP(7);
     if (s == MAXC - 1) FD_STAMP(9);
   }
-  if (HAS_COMMON && full) pair_group<false>(plist, seg[MAXC + 1], cp, cb, cb, &cfe, &cne, &cfe, &cne);
+  if constexpr (DD) {
+    if ((dl->word & (FDL_BODY_OWN | FDL_BODY_BASE)) && dl->body_res[6] != 0.0) {
+      cfe = cfe + ldv3(dl->body_res); cne = cne + ldv3(dl->body_res + 3);
+    }
+  } else if (HAS_COMMON && full) pair_group<false>(plist, seg[MAXC + 1], cp, cb, cb, &cfe, &cne, &cfe, &cne);
 
   FD_STAMP(10);
   // ---- backward pass along the chain, joint torques
@@ -533,13 +629,38 @@ IDTO_DEV void id_eval_fast(const FastTab& T, const double* gravity, const DevCon
   FD_STAMP(11);
   // ---- common body: butterfly sums over the lanes of this evaluation
   if (HAS_COMMON) {
-    const V3 ext_f = tree_sum_fast<NP>(cfe);
-    const V3 ext_n = tree_sum_fast<NP>(cne);
-    const V3 ch_f = tree_sum_fast<NP>(root_f);
-    const V3 ch_n = tree_sum_fast<NP>(root_n);
+    V3 ext_f = tree_sum_fast<NP>(cfe);
+    V3 ext_n = tree_sum_fast<NP>(cne);
+    V3 ch_f = tree_sum_fast<NP>(root_f);
+    V3 ch_n = tree_sum_fast<NP>(root_n);
+    bool base_tau = path == 0;
+    if constexpr (DD) {
+      const int word = dl->word;
+      const bool whole = (word & FDL_WHOLE) != 0;
+      if ((word & 255) == 0 && (word & FDL_VALID)) {   // the baseline's lanes
+        double* pb = dl->pub + path * 12;
+        pb[0] = cfe.x; pb[1] = cfe.y; pb[2] = cfe.z; pb[3] = cne.x; pb[4] = cne.y; pb[5] = cne.z;
+        pb[6] = root_f.x; pb[7] = root_f.y; pb[8] = root_f.z; pb[9] = root_n.x; pb[10] = root_n.y; pb[11] = root_n.z;
+      }
+      __syncthreads();
+      FD_STAMP(24);
+      if (!whole) {
+        ext_f = fd_path_sum(dl->pub, 0, path, cfe, full); ext_n = fd_path_sum(dl->pub, 3, path, cne, full);
+        ch_f = fd_path_sum(dl->pub, 6, path, root_f, full); ch_n = fd_path_sum(dl->pub, 9, path, root_n, full);
+        base_tau = true;
+        // the other chains' torques are the baseline's (exact zeros in a mass column)
+#pragma unroll
+        for (int pp = 0; pp < NP; ++pp)
+#pragma unroll
+          for (int s = 0; s < MAXC; ++s) {
+            const int j = reinterpret_cast<const int*>(T.body + (pp * MAXC + s) * FB_STRIDE + FB_IDX)[1];
+            if (pp != path) tau[j] = full ? dl->tau0[j] : 0.0;
+          }
+      }
+    }
     const V3 f = (cb_fin - ext_f) + ch_f;
     const V3 n = (cb_nin - ext_n) + ch_n;
-    if (path == 0) {
+    if (base_tau) {
       const double* ctb = lds_launder(ct);
       const M3 R_WF = ldm3(ctb + FB_XPF);
       const V3 nF = tmul(R_WF, n), fF = tmul(R_WF, f);

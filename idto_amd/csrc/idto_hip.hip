@@ -334,6 +334,11 @@ struct idto_hip_ctx {
   int fd_stop = 0;                        // same for the finite-difference kernel
   int nd_min_rows = 16;                   // option "nd_min_rows": systems of at least this many block rows take the five-workgroup / band kernels
   bool fd_fast = true;                    // option "fd_fast": id_fast.h's evaluation when the model has an instantiated shape
+  // option "fd_dedup": forward differences on the lane map without the redundant path lanes, where the model has it
+  // (model_has_fd_dedup: host/model_tables.cc BuildFdDedup; any other model ignores the option).  0: every evaluation on all its paths.
+  bool fd_dedup = true;
+  bool model_has_fd_dedup = false;
+  bool last_fd_dedup = false;             // the most recent finite-difference launch ran on that lane map (fd_dedup_kernel)
   int asm_stop = 0;                       // profiling aid: truncate the assembly kernel after a phase
   bool two_sided = true;                  // solver: two workgroups eliminating from both ends
   bool fused = true;                      // gn_step: one persistent launch (fused.h) when eligible
@@ -503,9 +508,11 @@ enum { OPT_GET = 1, OPT_SET = 2, OPT_RW = 3 };
   X(asm_stop, OPT_INT, OPT_SET, nullptr, 0, 0) /* profiling aid */               \
   X(fd_stop, OPT_INT, OPT_SET, nullptr, 0, 0)  /* profiling aid */               \
   X(fd_fast, OPT_BOOL, OPT_RW, nullptr, 0, 1)                                    \
+  X(fd_dedup, OPT_BOOL, OPT_RW, "IDTO_FD_DEDUP", 0, 1)                           \
   X(gradients_method, OPT_INT, OPT_RW, nullptr, 0, 1)                            \
   X(last_solver, OPT_INT, OPT_GET, nullptr, 0, 0)                                \
   X(last_assembly, OPT_INT, OPT_GET, nullptr, 0, 0)                              \
+  X(last_fd_dedup, OPT_BOOL, OPT_GET, nullptr, 0, 0)                             \
   X(weights_diagonal, OPT_BOOL, OPT_GET, nullptr, 0, 0)                          \
   X(solver_timeouts, OPT_INT, OPT_GET, nullptr, 0, 0)                            \
   X(ls_solves, OPT_INT, OPT_GET, nullptr, 0, 0)                                  \
@@ -714,7 +721,7 @@ int UploadModel(idto_hip_ctx* c, const idto_model_t* m, const idto_host::ModelTa
   for (int i = 0; i < 4; ++i) { M.float_qs[i] = t.float_qs[i]; M.float_vs[i] = t.float_vs[i]; }
   M.fast_shape = t.fast_shape; M.fast_lo = t.fast_lo; M.fast_n = t.fast_n; M.f_maxpp = t.f_maxpp;
   M.gslots = t.gslots; M.gcommon = t.gcommon; M.gstem = t.gstem; M.nxb = t.nxb; M.nstem = t.nstem;
-  c->maxc = t.maxc; c->capsules = t.capsules;
+  c->maxc = t.maxc; c->capsules = t.capsules; c->model_has_fd_dedup = t.fd_dedup;
   return 0;
 }
 
@@ -733,7 +740,8 @@ int FdLds(const idto_hip_ctx* c, int mode, int ec, bool with_terms = false, bool
   const int blob_n = (fast && c->fd_fast && c->M.fast_shape) ? c->M.fast_n : c->M.blob_n;   // what fd_body stages of the model
   // (the exchange of shared pairs and of a stem, per concurrent evaluation: id_eval.h xch_eval_doubles)
   if (!threads) threads = mode >= 1 ? c->fd_threads : 64;
-  const int xch = fd_xch_doubles(c->M.nxb, threads, c->npaths, c->M.nstem);
+  // (... or, in its place, what the main and helper lanes of the lane map without the redundant path lanes hand each other)
+  const int xch = fd_xch_doubles(c->M.nxb, threads, c->npaths, c->M.nstem) + ((fast && c->model_has_fd_dedup && mode == 1) ? fd_dedup_doubles() : 0);
   return (int)sizeof(double) * (3 * nq + 2 * nv * nq + 3 * nv + 3 * E + E * nv + ec * (nq + 2 * nv) + nv + blob_n + 2 + nq / 2 + 2 + rec + xch);
 }
 
@@ -795,6 +803,9 @@ int LaunchFd(idto_hip_ctx* c, int mode, int kb, int ke, AltSel alt = AltSel{null
   if (c->M.nxb) fl.shape = SHAPE_XCH;             // shared pairs: the generic evaluation with the exchange (whatever fd_fast says)
   if (c->M.nstem > 1) fl.shape = SHAPE_STEM;      // a stem below the common body: ... and the walk along it
   fl.maxc = c->maxc;
+  fl.dedup = mode == 1 && !along && c->fd_dedup && c->fd_fast && c->model_has_fd_dedup && fl.shape == c->M.fast_shape &&
+             tree_shape_dedup(fl.shape) && (int)block.x == kFdMainLanes + kFdHelperLanes;
+  if (!along) c->last_fd_dedup = fl.dedup;
   fd_launch(fl);
   HIP_OK(hipGetLastError());
   return 0;

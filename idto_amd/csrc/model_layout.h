@@ -66,6 +66,27 @@ constexpr int SHAPE_STEM = kNumTreeShapes + 2;
 constexpr TreeShape tree_shape(int shape) {
   return shape >= 1 && shape <= kNumTreeShapes ? kTreeShapes[shape - 1] : TreeShape{0, 1, -1, 0, 0, -1, 0, 8};
 }
+// fd_kernel's forward-difference lane map without the redundant path lanes (id_fast.h id_eval_fast<..., DD>):
+// a column of q, or a mass column, that belongs to a joint of ONE chain leaves the common body and the other chains what
+// they are in the baseline evaluation, so that evaluation runs on one lane - its own path's - and the lanes this frees
+// evaluate contact pairs for the others.  The trait of the shapes whose kernel has that path (the host still refuses it
+// per model, host/model_tables.cc BuildFdDedup), and the lane budget: main lanes in the block's first half, one helper
+// lane behind each in the second.
+constexpr bool tree_shape_dedup(int shape) { return shape == 3; }
+constexpr int kFdMainLanes = 128, kFdHelperLanes = 128;
+// The lane words, in the blob right behind DevModel::f_seg's NP * (MAXC + 2) segment words (nothing there where the host
+// refused the map): [kFdMainLanes] main words, then [kFdHelperLanes] helper words
+//   main word:   evaluation | path << 8 | flags
+enum {
+  FDL_WHOLE = 1 << 12,      // four lanes, one per path, meet in the butterfly sums as they always did
+  FDL_FULL = 1 << 13,       // gravity, damping and contact (not a mass column)
+  FDL_VALID = 1 << 14,      // (a lane without a task runs the baseline into the dump row)
+  FDL_BODY_OWN = 1 << 15,   // the lane that adds the common body's own pair, evaluated by its helper
+  FDL_BODY_BASE = 1 << 16   // a single-path lane that adds it from the baseline's helper (the common body is the baseline's)
+};
+//   helper word: FDH_* | main lane << 8 | the chain pair's record (path * f_maxpp + place) << 16 | the common body's pair's << 24
+enum { FDH_FOOT = 1, FDH_BODY = 2 };
+
 // Shapes 1 ... kNumSizedShapes - the five example configurations - have the constants compiled into fd_kernel's tail.  The Jaco
 // shape (6) takes the g rows but keeps the run-time loops: no benchmark configuration has it, and the constants were never
 // measured on it.

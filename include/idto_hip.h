@@ -706,6 +706,10 @@ int idto_hip_plant_tvlqr_track(idto_hip_ctx* ctx, int nsteps, const double* x, c
  * having the gated assembly write it along, "decide_in_solver" = 0 keeps cost_kernel a launch of its own in front of the
  * pipelined solver's instead of one more workgroup of that launch; all of these leave every result bit for bit as it is (tests/test_gpu_small.py,
  * tests/test_gpu_trust_region.py);
+ * "fd_dedup" = 0 runs the forward differences of a model that has the lane map without the redundant path lanes (mini_cheetah:
+ * a column of a leg's joint evaluated on that leg's lane only, the freed lanes evaluating contact pairs) with every
+ * evaluation on all its paths again (default 1; IDTO_FD_DEDUP overrides it at creation; any other model ignores it; the results
+ * are equal value for value, tests/test_gpu_fd_dedup.py); "last_fd_dedup" reads back whether the last launch ran on that map;
  * "solver_debug" = 1 records per-phase cycle stamps (IDTO_ARR 15, tools/solver_phases.py);
  * "asm_stop" truncates the assembly kernel after a phase (tools/asm_phases.py). */
 int idto_hip_set_option(idto_hip_ctx* ctx, const char* name, int value);

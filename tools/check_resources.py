@@ -96,6 +96,11 @@ LIMITS = {
     # the DevContact read from the problem's parameter record through the constant address space instead of the kernel's
     # arguments - no vector register spilled, fd_kernel's 20 B of private segment; where the model's fields were argument
     # registers they are scalar loads' results now, and up to 49 more scalar registers are spilled to lanes)
+    # (forward differences on the lane map without the redundant path lanes, csrc/fd_kernel.h fd_body_impl's DD: main lanes and the
+    # helper lanes that evaluate their pairs with the world in one kernel.  Held to the limits of fd_kernel<3, 3> and
+    # fd_models_kernel<3, 3>, whose rows - the kernels the option fd_dedup = 0 launches - did not move.)
+    "fd_dedup_kernel<3, 3>": (0, 20, 105 + 24),
+    "fd_dedup_models_kernel<3, 3>": (0, 20, 109 + 24),
     "fd_models_kernel<2, 1>": (0, 20, 90 + 24),
     "fd_models_kernel<3, 2>": (0, 20, 92 + 24),
     "fd_models_kernel<3, 3>": (0, 20, 109 + 24),

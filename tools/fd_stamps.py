@@ -1,6 +1,7 @@
 """In-kernel clock stamps of fd_kernel (a library built with -DIDTO_FD_STAMPS: tools/fd_variants.sh stamps "-DIDTO_FD_STAMPS";
 run with IDTO_HIP_LIB=build/variants/stamps/libidto_hip.so).  Block k = 1, lanes tid 0 (the record's own evaluation,
-path 0) and tid 192 (a mass-matrix column): shader-clock cycles since the block's start."""
+path 0) and tid 192 (a mass-matrix column; a helper lane of the lane map without the redundant path lanes): shader-clock
+cycles since the block's start."""
 import os, re, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -11,7 +12,11 @@ NAMES = ["start", "loads issued", "barrier 1", "v/a/edq + barrier 2 + outputs is
          "eval: common body + its pairs", "eval: slot 0 done", "eval: last slot kinematics", "eval: last slot pairs",
          "eval: trailing pairs", "eval: backward pass", "evaluations + barrier", "record: reads landed", "record: divisions done",
          "record: stores issued", "barrier", "products: last tile decoded", "products: last tile, operand step 0",
-         "products: last tile, all operand steps", "products: last tile stored", "products: tiles done", "g rows + end"]
+         "products: last tile, all operand steps", "products: last tile stored", "products: tiles done", "g rows + end",
+         # (the lane map without the redundant path lanes, option fd_dedup - IDTO_FD_DEDUP=0 in the environment for the other map;
+         # out of sequence: 23 lies between 8 and 9, 24 behind 11, and 25 is the helper lane's, tid 192, between the main lanes' 23 and 9)
+         "lane map: last slot's state handed over + barrier", "lane map: baseline's sums published + barrier",
+         "lane map (helper): the pairs with the world done"]
 NS = int(re.search(r"#define IDTO_FD_NSTAMPS (\d+)", open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "idto_amd", "csrc", "id_fast.h")).read()).group(1))   # slots per stamping lane
 for name, N in ((sys.argv[1], int(sys.argv[2])),) if len(sys.argv) > 2 else (("mini_cheetah", 40), ("allegro_hand", 60)):
     cfg = load_config(name); model = load_model(name)
@@ -28,5 +33,9 @@ for name, N in ((sys.argv[1], int(sys.argv[2])),) if len(sys.argv) > 2 else (("m
     acc /= n
     print(name, "N =", N, "(cycles since the block's start; 100 MHz ticks if the counter is the constant one)")
     for i, nm in enumerate(NAMES):
+        if min(acc[i], acc[NS + i]) < 0:   # (a slot the lane did not take holds 0: minus the block's start here)
+            col = lambda x: f"{x:9.0f}" if x >= 0 else "        -"
+            print(f"  {i:2d} {nm:42s} tid0 {col(acc[i])}              tid192 {col(acc[NS+i])}")
+            continue
         print(f"  {i:2d} {nm:42s} tid0 {acc[i]:9.0f} (+{acc[i] - (acc[i-1] if i else 0):7.0f})   tid192 {acc[NS+i]:9.0f} (+{acc[NS+i] - (acc[NS+i-1] if i else 0):7.0f})")
     dev.close()

@@ -33,7 +33,7 @@
 #ifndef IDTO_FD_STAMP_TID
 #define IDTO_FD_STAMP_TID 192
 #endif
-#define IDTO_FD_NSTAMPS 26   // slots per stamping lane (tools/fd_stamps.py names them)
+#define IDTO_FD_NSTAMPS 30   // slots per stamping lane (tools/fd_stamps.py names them)
 #define FD_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); asm volatile("" ::: "memory"); if (idto_fd_st) idto_fd_st[i] = (long long)__builtin_readcyclecounter(); asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
 #define FD_STAMP(i) do { } while (0)
@@ -366,18 +366,34 @@ struct FdLane {             // one main lane's part
 // first barrier), the last slot's when that is (behind the second) - box against box and sphere against box never in one
 // wait.  pair_eval<false> is what pair_group<false> runs for the common body's pair, and for a pair of a chain body with
 // the world pair_eval<true> selects, value by value, what <false> computes.  The barriers are the main lanes' four.
+// The pair's record and the contact parameters are in registers before each wait - none of them depends on a main lane, and
+// behind the wait the helper is on the block's critical path (a helper lane holds little else: what cost a main lane
+// more than it hid, pair_group above, is free here); pair_eval runs on that copy, the same bits.
 IDTO_DEV void fd_helper_lane(const double* pairs, const DevContact& cp, int hword, const double* xfoot, const double* xcbs,
                              double* fres, double* bres, long long* idto_fd_st = nullptr) {
   (void)idto_fd_st;
   const int m = (hword >> 8) & 255;
+  DevContact cr = cp;
+  asm volatile("" : "+v"(cr.k), "+v"(cr.vd), "+v"(cr.vs), "+v"(cr.mu), "+v"(cr.sigma), "+v"(cr.threshold));
 #pragma unroll 1
   for (int ph = 0; ph < 2; ++ph) {
+    double rec[FP_STRIDE];
+    {
+      typedef __attribute__((address_space(3))) const volatile double lds_cvdouble;
+      lds_cvdouble* p = (lds_cvdouble*)(pairs + ((hword >> (ph ? 16 : 24)) & 255) * FP_STRIDE);
+#pragma unroll
+      for (int i = 0; i < FP_STRIDE; ++i) rec[i] = p[i];
+#pragma unroll
+      for (int i = 0; i < FP_STRIDE; ++i) asm volatile("" : "+v"(rec[i]));
+    }
     __syncthreads();
+    if (ph) FD_STAMP(29);
     if (hword & (ph ? FDH_FOOT : FDH_BODY)) {
       const BodyState C = ld_state(ph ? xfoot + m * FDX_STATE : xcbs + (m >> 2) * FDX_STATE);
+      if (ph) FD_STAMP(28);
       double* res = ph ? fres + m * FDX_RES : bres + (m >> 2) * FDX_RES;
       V3 fc, nc, fo, no;
-      const bool hit = pair_eval<false>(pairs + ((hword >> (ph ? 16 : 24)) & 255) * FP_STRIDE, cp, C, C, &fc, &nc, &fo, &no);
+      const bool hit = pair_eval<false>(rec, cr, C, C, &fc, &nc, &fo, &no);
       res[6] = hit ? 1.0 : 0.0;
       if (hit) { res[0] = fc.x; res[1] = fc.y; res[2] = fc.z; res[3] = nc.x; res[4] = nc.y; res[5] = nc.z; }
     }
@@ -387,15 +403,16 @@ IDTO_DEV void fd_helper_lane(const double* pairs, const DevContact& cp, int hwor
   __syncthreads();
 }
 // the sum over the paths of a single-path lane: its own value in its own place, the baseline's (zeros in a mass column) in
-// the others, in the association of tree_sum_fast<4> on path 0
-IDTO_DEV V3 fd_path_sum(const double* pub, int off, int path, V3 own, bool full) {
-  V3 t[4];
+// the others, in the association of tree_sum_fast<4> on path 0, (t0 + t1) + (t2 + t3).  pub: the baseline's published values
+// of the paths path ^ 1, path ^ 2, path ^ 3, already in registers: the lane's own term meets its partner's first and the
+// other pair's sum second, as in the butterfly - for the paths 1, 2, 3 that is the association above with the operands of
+// an addition exchanged, and a + b and b + a are the same bits.
+IDTO_DEV V3 fd_path_sum(const double (&pub)[36], int off, V3 own, bool full) {
+  V3 b[3];
 #pragma unroll
-  for (int pp = 0; pp < 4; ++pp) {
-    const V3 b = ldv3(pub + pp * 12 + off);
-    t[pp] = mk(pp == path ? own.x : (full ? b.x : 0.0), pp == path ? own.y : (full ? b.y : 0.0), pp == path ? own.z : (full ? b.z : 0.0));
-  }
-  return (t[0] + t[1]) + (t[2] + t[3]);
+  for (int k = 0; k < 3; ++k)
+    b[k] = mk(full ? pub[k * 12 + off] : 0.0, full ? pub[k * 12 + off + 1] : 0.0, full ? pub[k * 12 + off + 2] : 0.0);
+  return (own + b[0]) + (b[1] + b[2]);
 }
 
 // GS: the shape's bodies may have their weight switched off (DevModel::gslots, gcommon); the shapes without it are built
@@ -435,6 +452,20 @@ IDTO_DEV void id_eval_fast(const FastTab& T, const double* gravity, const DevCon
     const int2 ix = *reinterpret_cast<const int2*>(ct + FB_IDX);
     cqs = ix.x; cvs = ix.y;
   }
+  // (DD) where every chain joint's torque lies in a tau row: a single-path lane copies the other paths' from the baseline's
+  // row at the very end, and an index read there would be one more dependent LDS round trip on the block's critical path
+  // (the paths path ^ 1, path ^ 2, path ^ 3, a word each with a slot's index a byte - they are below nv <= E < 256, as the
+  // lane words' evaluation field has it: three registers)
+  constexpr int NJW = DD ? NP - 1 : 1;
+  int jw[NJW] = {};
+  if constexpr (DD) {
+    static_assert(MAXC <= 4, "a byte a slot");
+#pragma unroll
+    for (int k = 1; k < NP; ++k)
+#pragma unroll
+      for (int s = 0; s < MAXC; ++s)
+        jw[k - 1] |= reinterpret_cast<const int*>(T.body + ((path ^ k) * MAXC + s) * FB_STRIDE + FB_IDX)[1] << (8 * s);
+  }
   double qj[MAXC], vj[MAXC], aj[MAXC];       // the revolute coordinate of each slot (slot 0 planar: theta)
   double q0x = 0, q0y = 0, v0x = 0, v0y = 0, a0x = 0, a0y = 0;   // slot 0 planar: x, y
 #pragma unroll
@@ -453,6 +484,10 @@ IDTO_DEV void id_eval_fast(const FastTab& T, const double* gravity, const DevCon
     for (int i = 0; i < 7; ++i) cq[i] = in.Q(cqs + i);
 #pragma unroll
     for (int i = 0; i < 6; ++i) { cv[i] = in.V(cvs + i); ca[i] = in.A(cvs + i); }
+  }
+  if constexpr (DD) {   // (pinned in registers here, as fd_body pins qf0: the reads are not to sink to the use)
+#pragma unroll
+    for (int i = 0; i < NJW; ++i) asm volatile("" : "+v"(jw[i]));
   }
   FD_STAMP(4);
   double sn[MAXC], cs[MAXC];
@@ -550,6 +585,20 @@ IDTO_DEV void id_eval_fast(const FastTab& T, const double* gravity, const DevCon
         acc = ((P.a + cross(P.al, r[s])) + cross(P.w, cross(P.w, r[s]))) + zero;
       }
     }
+    if constexpr (DD) {
+      // (the last slot's state goes to the lane's helper before the slot's inertial wrench, not behind it: the pair needs
+      // R, p, w, v only, and the lane forms the wrench while the helper works)
+      if (s == MAXC - 1) {
+        if (full) st_state(dl->foot, bs);
+        __syncthreads();
+        FD_STAMP(23);
+        // (the wrench's constants - mass, centre of mass, inertia - are read again here, the same words: ten doubles
+        // fewer in registers across the wait, where the lane holds the most)
+        const double* rb = lds_launder(bt + s * FB_STRIDE);
+#pragma unroll
+        for (int i = FB_MASS; i < FB_PREFETCH; ++i) rec[i] = rb[i];
+      }
+    }
     V3 fin, nin;
     inertial_wrench_rec(rec, bs.R, bs.w, al, acc, GS ? body_gravity(slot_gravity(T.gslots, path, s), g) : g, &fin, &nin);
     pin(fin); pin(nin); pin(r[s]); pin(hW[s]);
@@ -566,9 +615,6 @@ IDTO_DEV void id_eval_fast(const FastTab& T, const double* gravity, const DevCon
       // (the host found pairs on the last slot only: one with the common body, evaluated here while the helper evaluates the
       // one with the world that follows it in the list)
       if (s == MAXC - 1) {
-        if (full) st_state(dl->foot, bs);
-        __syncthreads();
-        FD_STAMP(23);
         if (full) {
           V3 fc, nc, fo, no;
           if (pair_eval<true>(plist + (seg[1 + s] & 0xffff) * FP_STRIDE, cp, bs, cb, &fc, &nc, &fo, &no)) {
@@ -576,6 +622,7 @@ IDTO_DEV void id_eval_fast(const FastTab& T, const double* gravity, const DevCon
             cfe = cfe + fo; cne = cne + no;
           }
         }
+        FD_STAMP(26);
         __syncthreads();
         if (full && dl->foot_res[6] != 0.0) {
           fext = fext + ldv3(dl->foot_res); next = next + ldv3(dl->foot_res + 3);
@@ -645,18 +692,39 @@ IDTO_DEV void id_eval_fast(const FastTab& T, const double* gravity, const DevCon
       __syncthreads();
       FD_STAMP(24);
       if (!whole) {
-        ext_f = fd_path_sum(dl->pub, 0, path, cfe, full); ext_n = fd_path_sum(dl->pub, 3, path, cne, full);
-        ch_f = fd_path_sum(dl->pub, 6, path, root_f, full); ch_n = fd_path_sum(dl->pub, 9, path, root_n, full);
+        // Three phases, so that the lane waits for LDS once and not once per word (the pointers here may alias for all the
+        // compiler knows, and it would order every read behind the store before it): every read - the other paths'
+        // published sums and the baseline's torques of their joints, at the indices read in the prologue -, then the
+        // sums, then the stores.
+        typedef __attribute__((address_space(3))) const volatile double lds_cvdouble;
+        lds_cvdouble* tau0v = (lds_cvdouble*)dl->tau0;
+        double pb[(NP - 1) * 12], t0[(NP - 1) * MAXC];
+        int js[(NP - 1) * MAXC];
+#pragma unroll
+        for (int k = 0; k < NP - 1; ++k)
+#pragma unroll
+          for (int s = 0; s < MAXC; ++s) {
+            js[k * MAXC + s] = (jw[k] >> (8 * s)) & 255;
+            t0[k * MAXC + s] = tau0v[js[k * MAXC + s]];
+          }
+#pragma unroll
+        for (int k = 0; k < NP - 1; ++k) {
+          lds_cvdouble* pubv = (lds_cvdouble*)(dl->pub + (path ^ (k + 1)) * 12);
+#pragma unroll
+          for (int i = 0; i < 12; ++i) pb[k * 12 + i] = pubv[i];
+        }
+#pragma unroll
+        for (int i = 0; i < (NP - 1) * MAXC; ++i) asm volatile("" : "+v"(t0[i]));
+#pragma unroll
+        for (int i = 0; i < (NP - 1) * 12; ++i) asm volatile("" : "+v"(pb[i]));
+        ext_f = fd_path_sum(pb, 0, cfe, full); ext_n = fd_path_sum(pb, 3, cne, full);
+        ch_f = fd_path_sum(pb, 6, root_f, full); ch_n = fd_path_sum(pb, 9, root_n, full);
         base_tau = true;
         // the other chains' torques are the baseline's (exact zeros in a mass column)
 #pragma unroll
-        for (int pp = 0; pp < NP; ++pp)
-#pragma unroll
-          for (int s = 0; s < MAXC; ++s) {
-            const int j = reinterpret_cast<const int*>(T.body + (pp * MAXC + s) * FB_STRIDE + FB_IDX)[1];
-            if (pp != path) tau[j] = full ? dl->tau0[j] : 0.0;
-          }
+        for (int i = 0; i < (NP - 1) * MAXC; ++i) tau[js[i]] = full ? t0[i] : 0.0;
       }
+      FD_STAMP(27);
     }
     const V3 f = (cb_fin - ext_f) + ch_f;
     const V3 n = (cb_nin - ext_n) + ch_n;

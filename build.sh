@@ -35,6 +35,9 @@ REM="-Rpass-analysis=kernel-resource-usage"
 # where every per-problem array lies in a context's arena, and the launch sizes that are pure functions of the sizes: host-only
 # (tests/cpp/context_layout_check.cc holds it to tests/golden/context_layout.txt on the CPU)
 ( g++ -O2 -std=c++17 -fPIC -ffp-contract=off -Wall -Wextra -Iinclude -Iidto_amd/csrc -c idto_amd/csrc/host/context_layout.cc -o build/context_layout.o ) &
+# what the plant family's entries (csrc/*_abi.inc) refuse, the sizes of their launches and where a call's arrays lie: host-only
+# (tests/cpp/plant_calls_check.cc holds it to tests/golden/plant_call_layouts.txt and to every message on the CPU)
+( g++ -O2 -std=c++17 -fPIC -ffp-contract=off -Wall -Wextra -Iinclude -Iidto_amd/csrc -c idto_amd/csrc/host/plant_calls.cc -o build/plant_calls.o ) &
 $HIPCC $FLAGS -mllvm -amdgpu-mfma-vgpr-form=1 $MAIN_FLAGS $REM -c idto_amd/csrc/idto_hip.hip -o build/idto_hip.o "$@" 2> build/idto_hip.remarks || { grep -v "remark:" build/idto_hip.remarks >&2; exit 1; }
 wait %1
 wait %2
@@ -45,9 +48,10 @@ wait %6
 wait %7
 wait %8
 wait %9
+wait %10
 grep -h -A3 "warning:" build/fd_launch.remarks build/idto_hip.remarks build/plant_launch.remarks build/scene_launch.remarks build/lin_launch.remarks build/track_launch.remarks >&2 || true
 if [ -z "$IDTO_SKIP_RESOURCE_CHECK" ]; then python3 tools/check_resources.py build/fd_launch.remarks build/idto_hip.remarks build/plant_launch.remarks build/scene_launch.remarks build/lin_launch.remarks build/track_launch.remarks > build/resource_check.txt || { cat build/resource_check.txt >&2; exit 1; }; fi
-$HIPCC --offload-arch=gfx950 -fPIC -shared build/fd_launch.o build/plant_launch.o build/scene_launch.o build/lin_launch.o build/track_launch.o build/idto_hip.o build/model_tables.o build/solver_plan.o build/model_batch.o build/context_layout.o -o idto_amd/libidto_hip.so -ldl
+$HIPCC --offload-arch=gfx950 -fPIC -shared build/fd_launch.o build/plant_launch.o build/scene_launch.o build/lin_launch.o build/track_launch.o build/idto_hip.o build/model_tables.o build/solver_plan.o build/model_batch.o build/context_layout.o build/plant_calls.o -o idto_amd/libidto_hip.so -ldl
 # libidto_opt.so: the host-side TrajectoryOptimizer (C++) + its C-ABI, on top of libidto_hip.so
 g++ -O3 -std=c++17 -fPIC -shared -Wall -Iinclude -Iidto_amd/csrc idto_amd/csrc/host/trajectory_optimizer.cc \
   idto_amd/csrc/host/batch_rows.cc idto_amd/csrc/host/ls_rows.cc idto_amd/csrc/host/mpc_controller.cc idto_amd/csrc/host/idto_opt_c.cc -o idto_amd/libidto_opt.so -Lidto_amd -lidto_hip -Wl,-rpath,'$ORIGIN'

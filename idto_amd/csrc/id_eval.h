@@ -21,6 +21,7 @@
 #include "dev_math.h"
 #include "idto_model.h"
 #include "model_layout.h"
+#include "plant_sizes.h"
 
 namespace idto_dev {
 
@@ -146,13 +147,8 @@ struct BodyState {  // what later stages need of a body
   V3 p, w, v;
 };
 
-// A body's record in the exchange area of id_eval<MAXC, true>: R (row-major), p, w, v - the doubles contact_pair reads -,
-// then the contact force and moment on the body (XEXT: summed there by the lane that owns the body)
-constexpr int XREC = 24, XEXT = 18;
-// id_eval<MAXC, true, true>: behind the M.nxb records of an evaluation, one block per stem body below the common one with what the
-// backward pass needs of it: the joint axis hW, the inertial wrench (fin, nin) and the offset r of the NEXT stem body from it
-constexpr int SAUX = 12, SA_HW = 0, SA_FIN = 3, SA_NIN = 6, SA_RC = 9;
-__host__ __device__ inline int xch_eval_doubles(int nxb, int nstem) { return nxb * XREC + (nstem > 1 ? nstem - 1 : 0) * SAUX; }
+// (a body's record in the exchange area of id_eval<MAXC, true> - XREC, XEXT -, a stem body's block behind the records - SAUX,
+// SA_* - and xch_eval_doubles: plant_sizes.h, which the host-only units read as well)
 IDTO_DEV void put_v3(double* x, V3 a) { x[0] = a.x; x[1] = a.y; x[2] = a.z; }
 IDTO_DEV V3 get_v3(const double* x) { return mk(x[0], x[1], x[2]); }
 IDTO_DEV void put_state(double* x, const BodyState& b) {

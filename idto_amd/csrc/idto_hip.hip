@@ -47,6 +47,7 @@
 #include "host/context_layout.h"
 #include "host/model_batch.h"
 #include "host/model_tables.h"
+#include "host/plant_calls.h"
 #include "host/solver_plan.h"
 
 using namespace idto_dev;
@@ -233,33 +234,20 @@ struct PlantState {
   double h = 0; int mode = 0, feed_forward = 0, block = 64, lds = 0;
   bool begun = false;                         // idto_hip_plant_begin made it (idto_hip_forward_dynamics alone: not)
   double* pin = nullptr; size_t pin_cap = 0;   // pinned staging of what comes back
+  size_t fd_pinned = 0;                        // ... its doubles for idto_hip_forward_dynamics (the storage plan's)
   double* tick_pin = nullptr; size_t tick_pin_cap = 0;   // ... of the plants' states behind a tick (idto_hip_mpc_batch_tick_plants)
 };
 
-// idto_hip_scene_report: the report's storage (scene_abi.inc SceneEnsure), made at the first report - the body of every
-// geometry, the states and the outputs of a call on the device, their pinned staging
-struct SceneState {
-  int* geom_body = nullptr;
-  double* in = nullptr; size_t in_cap = 0;
-  double* out = nullptr; size_t out_cap = 0;
-  double* pin = nullptr; size_t pin_cap = 0;
-};
-
-// idto_hip_plant_linearize, idto_hip_plant_tvlqr: the feature's storage (lin_abi.inc LinEnsure), made at the first call - the
-// context's own parameter record, then one device buffer (a call's inputs, the columns' plants, the outputs) and its pinned
-// staging, grown on demand
-struct LinState {
-  double* record = nullptr;
+// A device buffer with its pinned mirror, both grown on demand (GrownEnsure): where a call of the scene report, the
+// linearisation or the tracked rollouts keeps its arrays, laid out by host/plant_calls.h's CallPlan
+struct GrownBuffer {
   double* dev = nullptr; size_t dev_cap = 0;
   double* pin = nullptr; size_t pin_cap = 0;
 };
-
-// idto_hip_plant_track, idto_hip_plant_tvlqr_track: the feature's storage (track_abi.inc TrackEnsure), made at the first call -
-// one device buffer (a call's inputs, the rollouts' states and status words, the outputs) and its pinned staging, grown on demand
-struct TrackState {
-  double* dev = nullptr; size_t dev_cap = 0;
-  double* pin = nullptr; size_t pin_cap = 0;
-};
+// idto_hip_scene_report, made at the first report: the body of every geometry, the states (in, whose mirror stages both ways) and the outputs
+struct SceneState { int* geom_body = nullptr; GrownBuffer in, out; };
+// idto_hip_plant_linearize, idto_hip_plant_tvlqr, made at the first call: the context's own parameter record, a call's arrays
+struct LinState { double* record = nullptr; GrownBuffer buf; };
 
 struct idto_hip_ctx {
   int device = 0;
@@ -268,7 +256,7 @@ struct idto_hip_ctx {
   PlantState* plant = nullptr;
   SceneState* scene = nullptr;
   LinState* lin = nullptr;
-  TrackState* track = nullptr;
+  GrownBuffer* track = nullptr;   // idto_hip_plant_track, idto_hip_plant_tvlqr_track: a call's arrays, made at the first call
   // (batch contexts) what the context was created from, and one single-problem context per problem, made on first use
   std::unique_ptr<HostModelCopy> host_model;
   std::vector<std::unique_ptr<HostProblemCopy>> host_problems;
@@ -860,6 +848,16 @@ int EnsurePinned(double** p, size_t* cap, size_t count) {
   *cap = count;
   return 0;
 }
+// (the stream is drained before a device buffer that a launch may still read is released)
+int GrownEnsure(idto_hip_ctx* c, GrownBuffer* b, size_t dev_count, size_t pin_count) {
+  if (b->dev_cap < dev_count) {
+    HIP_OK(hipStreamSynchronize(c->stream));
+    Release(c, &b->dev); b->dev_cap = 0;
+    if (Alloc(c, dev_count, &b->dev)) return -2;
+    b->dev_cap = dev_count;
+  }
+  return EnsurePinned(&b->pin, &b->pin_cap, pin_count);
+}
 int EnsureStage(idto_hip_ctx* c, size_t count) {
   if (count > c->stage_count) {  // staging buffers grow on demand and are reused
     double *a = nullptr, *b = nullptr;
@@ -1097,18 +1095,9 @@ void idto_hip_destroy(idto_hip_ctx* c) {
     if (c->plant->tick_pin) (void)hipHostFree(c->plant->tick_pin);
     delete c->plant;
   }
-  if (c->scene) {   // (its device buffers are in c->allocs)
-    if (c->scene->pin) (void)hipHostFree(c->scene->pin);
-    delete c->scene;
-  }
-  if (c->lin) {   // (its device buffers are in c->allocs)
-    if (c->lin->pin) (void)hipHostFree(c->lin->pin);
-    delete c->lin;
-  }
-  if (c->track) {   // (its device buffer is in c->allocs)
-    if (c->track->pin) (void)hipHostFree(c->track->pin);
-    delete c->track;
-  }
+  for (GrownBuffer* b : {c->scene ? &c->scene->in : nullptr, c->lin ? &c->lin->buf : nullptr, c->track})   // (the device side is in c->allocs)
+    if (b && b->pin) (void)hipHostFree(b->pin);
+  delete c->scene; delete c->lin; delete c->track;
   if (c->mpc) {   // (its device buffers are in c->allocs)
     if (c->mpc->tick_pin) (void)hipHostFree(c->mpc->tick_pin);
     if (c->mpc->io_pin) (void)hipHostFree(c->mpc->io_pin);
@@ -3358,6 +3347,63 @@ int idto_hip_mpc_batch_replan(idto_hip_ctx* c, const double* times, const double
   if (int rc = MpcReplanCheck(c, "mpc_batch_replan", a, false, !times || !x0)) return rc;
   return MpcReplanRun(c, times, x0, a, nullptr, nullptr, nullptr);
 }
+
+// ---- the plant family's entries (plant_abi.inc, scene_abi.inc, lin_abi.inc, track_abi.inc): what they refuse, the sizes of
+// their launches and where a call's arrays lie are host/plant_calls.h's answers about a PlantShape; here is what acts on them
+using idto_host::CallPlan;
+static idto_host::PlantShape PlantShapeOf(const idto_hip_ctx* c) {
+  idto_host::PlantShape s{};
+  s.batch = c->batch; s.nq = c->nq; s.nv = c->nv; s.nb = c->M.nb; s.npairs = c->M.npairs; s.ngeoms = c->M.ngeoms; s.blob_n = c->M.blob_n;
+  s.nxb = c->M.nxb; s.nstem = c->M.nstem; s.npaths = c->npaths; s.maxc = c->maxc;
+  for (const idto_hip_ctx* ch : c->children) s.children |= ch != nullptr;
+  s.model_records = c->model_records != nullptr; s.host_model = c->host_tables && c->host_model;
+  if (c->mpc) { s.mpc = true; s.mpc_nu = c->mpc->L.nu; s.mpc_n = c->mpc->L.n; s.mpc_len = c->mpc->L.len(); }
+  if (const PlantState* p = c->plant; p && p->begun) {
+    s.plants_begun = true; s.plant_mode = p->mode; s.plant_nu = p->nu; s.plant_block = p->block; s.plant_lds = p->lds;
+    s.plant_record_capacity = p->record_capacity; s.plant_mpc_current = c->mpc_generation == p->mpc_generation;
+  }
+  return s;
+}
+// a refusal becomes the entry's message and return code (the message is built only then)
+static int Refused(idto_host::Refusal r) {
+  if (r.rc) g_err = std::move(r.msg);
+  return r.rc;
+}
+// rec: a parameter record on the host; its DevModel becomes Mb with the tables moved to the record's device copy at `dev`
+static void RecordForDevice(const idto_hip_ctx* c, DevModel Mb, const double* dev, double* rec) {
+  shift_model(Mb, dev);
+  std::memcpy(rec + model_record_devmodel_at((size_t)c->M.blob_n), &Mb, sizeof(DevModel));
+}
+// Which parameter records a launch reads: the plants' where `models` asks for them, else the context's per-problem records,
+// else `own` - the context's own record, or null for a kernel that has the context's model among its arguments.
+// b >= 0: problem b's record for every workgroup of the launch (stride 0).
+extern "C++" template <class Args>   // (PlantArgs, SceneArgs)
+static void SelectRecords(const idto_hip_ctx* c, int models, const double* own, long b, Args* A) {
+  const bool plants = models == IDTO_SCENE_MODELS_PLANTS;
+  const double* records = plants ? c->plant->records : c->model_records;
+  const size_t stride = plants ? c->plant->mstride : c->mstride;
+  if (!records) { A->records = own; A->mstride = 0; }
+  else if (b >= 0) { A->records = at_problem(records, (size_t)b * stride); A->mstride = 0; }
+  else { A->records = records; A->mstride = stride; }
+  A->rec_contact = model_record_contact_at((size_t)c->M.blob_n) * sizeof(double);
+  A->rec_model = model_record_devmodel_at((size_t)c->M.blob_n) * sizeof(double);
+}
+// A call's arrays against its plan, in buffer b and its mirror.  PlanStage: an input into the mirror at its device offset;
+// PlanUpload: all of them in one copy; PlanFetch: entry e back to its place in the mirror if it was asked for (from: the entry
+// that holds it on the device, where e is in the mirror alone); PlanCopyOut, behind the wait: from the mirror to the caller.
+static void PlanStage(const CallPlan& p, const GrownBuffer& b, int e, const void* src, size_t bytes) { std::memcpy(b.pin + p.at(e), src, bytes); }
+static void PlanStage(const CallPlan& p, const GrownBuffer& b, int e, const double* src) { PlanStage(p, b, e, src, p.count(e) * sizeof(double)); }
+static int PlanUpload(idto_hip_ctx* c, const CallPlan& p, const GrownBuffer& b) {
+  HIP_OK(hipMemcpyAsync(b.dev, b.pin, p.in_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+static int PlanFetch(idto_hip_ctx* c, const CallPlan& p, const GrownBuffer& b, int e, const void* wanted, int from = -1) {
+  if (!wanted || !p.count(e)) return 0;
+  HIP_OK(hipMemcpyAsync(b.pin + p.Mirror(e), b.dev + p.at(from < 0 ? e : from), p.count(e) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  return 0;
+}
+static void PlanCopyOut(const CallPlan& p, const GrownBuffer& b, int e, void* out, size_t bytes) { if (out) std::memcpy(out, b.pin + p.Mirror(e), bytes); }
+static void PlanCopyOut(const CallPlan& p, const GrownBuffer& b, int e, double* out) { PlanCopyOut(p, b, e, out, p.count(e) * sizeof(double)); }
 
 #include "plant_abi.inc"   // idto_hip_forward_dynamics, idto_hip_plant_*
 #include "scene_abi.inc"   // idto_hip_scene_sizes, idto_hip_scene_report

@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "plant_sizes.h"
 #include "plant_tangent.h"
 
 namespace idto_dev {
@@ -37,10 +38,7 @@ struct TvlqrArgs {
   int* status;           // [B]
 };
 
-// dynamic LDS of tvlqr_kernel in doubles: P, A, W, Acl, Q [n x n]; Bu, PBu [n x nu]; K, RK [nu x n]; G, R [nu x nu]; col [nu]
-__host__ __device__ inline size_t tvlqr_lds_doubles(int n, int nu) {
-  return 5 * (size_t)n * n + 4 * (size_t)n * nu + 2 * (size_t)nu * nu + (size_t)nu;
-}
+// (dynamic LDS of tvlqr_kernel: plant_sizes.h tvlqr_lds_doubles)
 
 // each enqueues its kernel on `stream`; the caller checks hipGetLastError()
 void lin_perturb_launch(const LinArgs& a, int batch, hipStream_t stream);      // grid (S, batch)

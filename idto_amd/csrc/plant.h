@@ -27,6 +27,7 @@
 
 #include "id_eval.h"
 #include "mpc_spline.h"
+#include "plant_sizes.h"
 #include "plant_step.h"
 #include "tvlqr_step.h"
 
@@ -54,10 +55,7 @@ struct PlantArgs {
   const double* breaks; const double* plan; size_t plan_len, plan_y[3], plan_m[3];
   const double* Kp; const double* Kd; const int* actuated;
 };
-// what PD+ adds to plant_kernel's LDS, in doubles: the plan, the breaks, the gains, the nominal [q, v, u], the actuated dofs
-__host__ __device__ inline size_t plant_pd_doubles(int nq, int nv, int nu, int n, size_t plan_len) {
-  return plan_len + (size_t)n + (size_t)nu * (nq + nv) + (size_t)(nq + nv + nu) + (size_t)(nu + 1) / 2;
-}
+// (what PD+ adds to plant_kernel's LDS: plant_sizes.h plant_pd_doubles)
 
 // The time-varying LQR law (LAW; track_kernel below, include/idto_hip.h idto_hip_plant_track): R rollouts per problem, the plant
 // blockIdx.x and its problem blockIdx.x / R, of S control steps of m substeps each.  At the start of step t the block stages
@@ -74,15 +72,7 @@ struct TrackArgs {
   double* u_out;           // [B * R][S][nu]
   double* dx_out;          // [B * R][S + 1][n]: row t the deviation in front of step t, row S behind the last
 };
-// what the law adds to the LDS, in doubles: K_t, x*_t, tau*_t, dx, the actuated dofs (u_t goes straight into tau_app)
-__host__ __device__ inline size_t plant_law_doubles(int nq, int nv, int nu) {
-  return (size_t)nu * 2 * nv + (size_t)(nq + nv) + (size_t)nv + (size_t)2 * nv + (size_t)(nu + 1) / 2;
-}
-
-// dynamic LDS of plant_kernel in doubles, for a block of `threads`
-__host__ __device__ inline int plant_lds_doubles(int nq, int nv, int blob_n, int nxb, int nstem, int npaths, int threads) {
-  return 3 * nq + 7 * nv + (2 * nv - 1) + (nv + 1) * nv + 2 + blob_n + (threads / npaths) * xch_eval_doubles(nxb, nstem);
-}
+// (what the law adds to the LDS, and the dynamic LDS of plant_kernel for a block: plant_sizes.h plant_law_doubles, plant_lds_doubles)
 
 template <int MAXC, bool XCH, bool STEM = false, bool LAW = false>
 IDTO_DEV void plant_body(const DevModel& M, const DevContact& cp, const PlantArgs& A, const int b, const TrackArgs* T = nullptr) {

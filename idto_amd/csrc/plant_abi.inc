@@ -1,29 +1,8 @@
 // plant_abi.inc — the C-ABI of the plants on the device (include/idto_hip.h idto_hip_forward_dynamics, idto_hip_plant_*):
 // host code only, included by idto_hip.hip inside its extern "C" block, where idto_hip_ctx and the helpers it uses
-// (Alloc, Release, EnsurePinned, UploadStage, HIP_OK, TRACE) are defined.  The kernel is plant.h's, its instantiations
-// plant_launch.hip's.
-
-// ---- plants on the device (plant.h, plant_launch.hip): the storage, its parameter records and the launches
-
-static int PlantLdsBytes(const idto_hip_ctx* c, int threads, bool pd) {
-  size_t d = (size_t)plant_lds_doubles(c->nq, c->nv, c->M.blob_n, c->M.nxb, c->M.nstem, c->npaths, threads);
-  if (pd) d += plant_pd_doubles(c->nq, c->nv, c->mpc->L.nu, c->mpc->L.n, c->mpc->L.len());
-  return d > (size_t)1 << 24 ? 1 << 27 : (int)(d * sizeof(double));
-}
-// Threads of plant_kernel's block, beside FdBlock: a wavefront per 64 lanes of the (nv + 1) * npaths that a substep's
-// evaluations want, up to 256; the block shrinks by a wavefront at a time where the exchange areas of its concurrent
-// evaluations do not fit the 160 KB of LDS beside the rest (the evaluations then go in rounds)
-static int PlantBlock(const idto_hip_ctx* c, int forced, bool pd) {
-  int t = forced ? forced : std::min(256, (((c->nv + 1) * c->npaths + 63) / 64) * 64);
-  while (t > 64 && PlantLdsBytes(c, t, pd) > 160 * 1024) t -= 64;
-  return t;
-}
-
-// The classes of model that plant_kernel serves
-static int PlantServes(const idto_hip_ctx* c, const char* who) {
-  if (c->nv > 64) { g_err = std::string(who) + ": nv > 64 (the solve of M a = tau - c runs a lane per row on one wavefront)"; return -1; }
-  return 0;
-}
+// (PlantShapeOf, Refused, RecordForDevice, SelectRecords; Alloc, Release, EnsurePinned, UploadStage, HIP_OK, TRACE) are defined.
+// What an entry refuses, the block and LDS of a launch and the storage's layout are host/plant_calls.h's.  The kernel is
+// plant.h's, its instantiations plant_launch.hip's.
 
 static void PlantRelease(idto_hip_ctx* c) {
   if (!c->plant) return;
@@ -36,32 +15,29 @@ static void PlantRelease(idto_hip_ctx* c) {
 
 // The plants' one allocation, every plant's parameter record the context's (the base model's, or the context's record b)
 static int PlantAllocate(idto_hip_ctx* c, const idto_plant_params_t& prm) {
-  if (!c->host_tables || !c->host_model) { g_err = "plant_begin: the context keeps no host copy of its model"; return -1; }
+  const idto_host::PlantShape s = PlantShapeOf(c);
   const bool pd = prm.mode == IDTO_PLANT_PD_PLUS;
+  if (int rc = Refused(idto_host::RefusePlantStorage(s, prm.block_threads, pd))) return rc;
+  const size_t beside = pd ? idto_host::PlantPdDoubles(s) : 0;
   const int B = c->batch, nq = c->nq, nv = c->nv, nu = pd ? c->mpc->L.nu : 0;
-  const int block = PlantBlock(c, prm.block_threads, pd), lds = PlantLdsBytes(c, block, pd);
-  if (lds > 160 * 1024) { g_err = "plant_begin: the model, a substep's evaluations and the plan do not fit the 160 KiB of LDS"; return -1; }
   HIP_OK(hipSetDevice(c->device));
   HIP_OK(hipStreamSynchronize(c->stream));   // (a record upload of the context's may be in flight; the old storage may be in use)
   PlantRelease(c);
   auto p = std::make_unique<PlantState>();
-  p->nu = nu; p->mpc_generation = c->mpc_generation; p->h = prm.h; p->mode = prm.mode; p->feed_forward = prm.feed_forward; p->block = block; p->lds = lds;
-  p->record_capacity = prm.record_capacity > 0 ? prm.record_capacity : 64;
-  const idto_model_t* base = &c->host_model->m;
-  const std::vector<double> base_record = idto_host::ModelRecord(base, *c->host_tables, c->host_contact);
-  const size_t rec_n = base_record.size(), al = 8;
+  p->nu = nu; p->mpc_generation = c->mpc_generation; p->h = prm.h; p->mode = prm.mode; p->feed_forward = prm.feed_forward;
+  p->block = idto_host::PlantBlock(s, prm.block_threads, beside); p->lds = idto_host::PlantLdsBytes(s, p->block, beside);
+  p->record_capacity = idto_host::PlantRecordCapacity(prm.record_capacity);
+  const std::vector<double> base_record = idto_host::ModelRecord(&c->host_model->m, *c->host_tables, c->host_contact);
+  const size_t rec_n = base_record.size();
   if (c->model_records && c->mstride != rec_n * sizeof(double)) { g_err = "plant_begin: the context's parameter records have another size"; return -1; }
   p->mstride = rec_n * sizeof(double);
-  size_t at = 0;
-  auto take = [&](size_t count) { const size_t o = at; at += (count + al - 1) / al * al; return o; };
-  const size_t o_rec = take((size_t)B * rec_n), o_state = take((size_t)B * (1 + nq + nv)), o_tau = take((size_t)B * nv),
-               o_record = take((size_t)B * p->record_capacity * (nq + nv)), o_fdx = take((size_t)B * (nq + nv)),
-               o_fda = take((size_t)B * nv), o_fdM = take((size_t)B * nv * nv), o_fdb = take((size_t)B * nv),
-               o_kp = take((size_t)nu * nq), o_kd = take((size_t)nu * nv), o_status = take((size_t)B);   // (two ints a plant)
-  if (Alloc(c, at, &p->base)) return -2;
-  p->records = p->base + o_rec; p->state = p->base + o_state; p->tau = p->base + o_tau; p->record = p->base + o_record;
-  p->fd_x = p->base + o_fdx; p->fd_a = p->base + o_fda; p->fd_M = p->base + o_fdM; p->fd_bias = p->base + o_fdb;
-  p->Kp = p->base + o_kp; p->Kd = p->base + o_kd; p->status = reinterpret_cast<int*>(p->base + o_status);
+  const CallPlan L = idto_host::PlanPlantStorage(s, rec_n, prm.record_capacity, nu);
+  if (Alloc(c, L.total, &p->base)) return -2;
+  namespace ps = idto_host::plant_storage;
+  p->records = p->base + L.at(ps::records); p->state = p->base + L.at(ps::state); p->tau = p->base + L.at(ps::tau); p->record = p->base + L.at(ps::record);
+  p->fd_x = p->base + L.at(ps::fd_x); p->fd_a = p->base + L.at(ps::fd_a); p->fd_M = p->base + L.at(ps::fd_M); p->fd_bias = p->base + L.at(ps::fd_bias);
+  p->Kp = p->base + L.at(ps::Kp); p->Kd = p->base + L.at(ps::Kd); p->status = reinterpret_cast<int*>(p->base + L.at(ps::status));
+  p->fd_pinned = L.pinned;
   std::vector<double> all((size_t)B * rec_n);
   if (c->model_records) {
     if (hipMemcpy(all.data(), c->model_records, all.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
@@ -74,15 +50,14 @@ static int PlantAllocate(idto_hip_ctx* c, const idto_plant_params_t& prm) {
     DevModel Mb = c->M;
     if (c->model_records) std::memcpy(&Mb, rec + mat, sizeof(DevModel));   // (its tables: the context's record b - moved below)
     else std::copy(base_record.begin(), base_record.end(), rec);
-    shift_model(Mb, p->records + (size_t)b * rec_n);
-    std::memcpy(rec + mat, &Mb, sizeof(DevModel));
+    RecordForDevice(c, Mb, p->records + (size_t)b * rec_n, rec);
   }
   bool ok = hipMemcpy(p->records, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
   if (ok && pd) ok = hipMemcpy(p->Kp, prm.Kp, (size_t)nu * nq * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
                      hipMemcpy(p->Kd, prm.Kd, (size_t)nu * nv * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) { g_err = "plant_begin: hipMemcpy (parameter records, gains) failed"; Release(c, &p->base); return -2; }
   // (a launch above 64 KiB of dynamic LDS needs the opt-in: an instantiation that did not get it would fail at its launch)
-  if (const hipError_t e = plant_set_max_lds(160 * 1024); e != hipSuccess) {
+  if (const hipError_t e = plant_set_max_lds(idto_host::kPlantMaxLds); e != hipSuccess) {
     (void)hipGetLastError();
     g_err = std::string("plant_begin: hipFuncSetAttribute (160 KiB of dynamic LDS for plant_kernel) failed: ") + hipGetErrorString(e);
     Release(c, &p->base);
@@ -93,35 +68,14 @@ static int PlantAllocate(idto_hip_ctx* c, const idto_plant_params_t& prm) {
 }
 
 int idto_hip_plant_begin(idto_hip_ctx* c, const idto_plant_params_t* prm) {
-  if (!prm) { g_err = "plant_begin: parameters are required"; return -1; }
-  for (idto_hip_ctx* ch : c->children)
-    if (ch) { g_err = "plant_begin: this context has child contexts (the child-context route of idto_hip_tr_solve_batch_constrained made them)"; return -1; }
-  if (!(prm->h > 0.0) || !std::isfinite(prm->h)) { g_err = "plant_begin: the substep h must be > 0"; return -1; }
-  if (prm->mode != IDTO_PLANT_HOLD && prm->mode != IDTO_PLANT_PD_PLUS) { g_err = "plant_begin: mode is IDTO_PLANT_HOLD or IDTO_PLANT_PD_PLUS"; return -1; }
-  if (int rc = PlantServes(c, "plant_begin")) return rc;
-  if (prm->block_threads != 0 && (prm->block_threads % 64 != 0 || prm->block_threads < 64 || prm->block_threads > 256)) {
-    g_err = "plant_begin: block_threads is 0, 64, 128, 192 or 256"; return -1;
-  }
-  if (prm->record_capacity < 0) { g_err = "plant_begin: record_capacity must not be negative"; return -1; }
-  if (prm->mode == IDTO_PLANT_PD_PLUS) {
-    if (!c->mpc) { g_err = "plant_begin: PD+ needs the stored plans: call idto_hip_mpc_batch_begin (and idto_hip_mpc_batch_store) on the context first"; return -1; }
-    const int nu = c->mpc->L.nu;
-    if (!prm->Kp || !prm->Kd || prm->kp_size != nu * c->nq || prm->kd_size != nu * c->nv) {
-      g_err = "plant_begin: gains of the wrong size: Kp is [nu][nq] = " + std::to_string(nu * c->nq) + " and Kd [nu][nv] = " +
-              std::to_string(nu * c->nv) + " doubles";
-      return -1;
-    }
-    for (int i = 0; i < prm->kp_size; ++i) if (!std::isfinite(prm->Kp[i])) { g_err = "plant_begin: a gain in Kp is not finite"; return -1; }
-    for (int i = 0; i < prm->kd_size; ++i) if (!std::isfinite(prm->Kd[i])) { g_err = "plant_begin: a gain in Kd is not finite"; return -1; }
-  }
+  if (int rc = Refused(idto_host::RefusePlantBegin(PlantShapeOf(c), prm))) return rc;
   const int rc = PlantAllocate(c, *prm);
   if (rc == 0) c->plant->begun = true;
   return rc;
 }
 
 int idto_hip_plant_set_model(idto_hip_ctx* c, int b, const idto_model_t* model, const idto_contact_params_t* contact) {
-  if (!c->plant || !c->plant->begun) { g_err = "plant_set_model: call idto_hip_plant_begin on the context first"; return -1; }
-  if (b < 0 || b >= c->batch) { g_err = "plant_set_model: plant index outside the batch"; return -1; }
+  if (int rc = Refused(idto_host::RefusePlantSetModel(PlantShapeOf(c), b))) return rc;
   const idto_model_t* base = &c->host_model->m;
   std::vector<double> record;
   if (int rc = idto_host::BuildModelVariant(base, *c->host_tables, b, model ? model : base, contact ? *contact : c->host_contact, &record, &g_err))
@@ -131,9 +85,8 @@ int idto_hip_plant_set_model(idto_hip_ctx* c, int b, const idto_model_t* model, 
   HIP_OK(hipSetDevice(c->device));
   double* dev = at_problem(p->records, (size_t)b * p->mstride);
   DevModel Mb = c->M;
-  shift_model(Mb, dev);
   for (int i = 0; i < 3; ++i) Mb.gravity[i] = (model ? model : base)->gravity[i];
-  std::memcpy(record.data() + model_record_devmodel_at((size_t)c->M.blob_n), &Mb, sizeof(DevModel));
+  RecordForDevice(c, Mb, dev, record.data());
   // (behind whatever the context has enqueued: a launch in flight keeps the record it started with)
   HIP_OK(hipMemcpyAsync(dev, record.data(), p->mstride, hipMemcpyHostToDevice, c->stream));
   HIP_OK(hipStreamSynchronize(c->stream));
@@ -141,8 +94,7 @@ int idto_hip_plant_set_model(idto_hip_ctx* c, int b, const idto_model_t* model, 
 }
 
 int idto_hip_plant_set_state(idto_hip_ctx* c, const double* times, const double* x) {
-  if (!c->plant || !c->plant->begun) { g_err = "plant_set_state: call idto_hip_plant_begin on the context first"; return -1; }
-  if (!times || !x) { g_err = "plant_set_state: times[batch] and x[batch][nq + nv] are required"; return -1; }
+  if (int rc = Refused(idto_host::RefusePlantSetState(PlantShapeOf(c), times, x))) return rc;
   HIP_OK(hipSetDevice(c->device));
   const size_t w = (size_t)(1 + c->nq + c->nv);
   std::vector<double> s((size_t)c->batch * w);
@@ -156,7 +108,7 @@ int idto_hip_plant_set_state(idto_hip_ctx* c, const double* times, const double*
 }
 
 int idto_hip_plant_get_state(idto_hip_ctx* c, double* times_out, double* x_out) {
-  if (!c->plant || !c->plant->begun) { g_err = "plant_get_state: call idto_hip_plant_begin on the context first"; return -1; }
+  if (int rc = Refused(idto_host::RefusePlantsBegun(PlantShapeOf(c), "plant_get_state"))) return rc;
   HIP_OK(hipSetDevice(c->device));
   const size_t w = (size_t)(1 + c->nq + c->nv);
   std::vector<double> s((size_t)c->batch * w);
@@ -169,14 +121,11 @@ int idto_hip_plant_get_state(idto_hip_ctx* c, double* times_out, double* x_out) 
   return 0;
 }
 
-// plant_kernel's arguments that every launch shares, and the launch
+// plant_kernel's arguments that every launch on the plants' records shares, and the launch
 static PlantArgs PlantCommonArgs(const idto_hip_ctx* c) {
-  const PlantState* p = c->plant;
   PlantArgs A{};
-  A.records = p->records; A.mstride = p->mstride;
-  A.rec_contact = model_record_contact_at((size_t)c->M.blob_n) * sizeof(double);
-  A.rec_model = model_record_devmodel_at((size_t)c->M.blob_n) * sizeof(double);
-  A.status = p->status; A.h = p->h;
+  SelectRecords(c, IDTO_SCENE_MODELS_PLANTS, nullptr, -1, &A);
+  A.status = c->plant->status; A.h = c->plant->h;
   return A;
 }
 static int PlantEnqueue(idto_hip_ctx* c, const PlantArgs& A, int lds) {
@@ -189,8 +138,8 @@ static int PlantEnqueue(idto_hip_ctx* c, const PlantArgs& A, int lds) {
 }
 
 int idto_hip_forward_dynamics(idto_hip_ctx* c, const double* x, const double* tau_applied, double* a_out, double* M_out, double* bias_out) {
-  if (!x || !tau_applied || !a_out) { g_err = "forward_dynamics: x[batch][nq + nv], tau_applied[batch][nv] and a_out[batch][nv] are required"; return -1; }
-  if (int rc = PlantServes(c, "forward_dynamics")) return rc;
+  const idto_host::PlantShape s = PlantShapeOf(c);
+  if (int rc = Refused(idto_host::RefuseForwardDynamics(s, x, tau_applied, a_out))) return rc;
   if (!c->plant) {   // (a context that never began a plant: the storage with default parameters)
     idto_plant_params_t prm{};
     prm.h = 1.0; prm.mode = IDTO_PLANT_HOLD;
@@ -200,8 +149,8 @@ int idto_hip_forward_dynamics(idto_hip_ctx* c, const double* x, const double* ta
   PlantState* p = c->plant;
   const size_t B = (size_t)c->batch, nq = (size_t)c->nq, nv = (size_t)c->nv;
   // (fd_a, fd_M, fd_bias lie next to each other, each padded to 64 bytes: one copy back, then the status words)
-  const size_t in = B * (nq + 2 * nv), span = (size_t)(p->fd_bias + B * nv - p->fd_a);
-  if (int rc = EnsurePinned(&p->pin, &p->pin_cap, std::max(in, span + B))) return rc;
+  const size_t span = (size_t)(p->fd_bias + B * nv - p->fd_a);
+  if (int rc = EnsurePinned(&p->pin, &p->pin_cap, p->fd_pinned)) return rc;
   std::memcpy(p->pin, x, B * (nq + nv) * sizeof(double));
   std::memcpy(p->pin + B * (nq + nv), tau_applied, B * nv * sizeof(double));
   HIP_OK(hipMemcpyAsync(p->fd_x, p->pin, B * (nq + nv) * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -209,7 +158,7 @@ int idto_hip_forward_dynamics(idto_hip_ctx* c, const double* x, const double* ta
   PlantArgs A = PlantCommonArgs(c);
   A.state = p->fd_x; A.tau = p->tau; A.fd = 1; A.substeps = 1;
   A.a_out = p->fd_a; A.M_out = p->fd_M; A.bias_out = p->fd_bias;
-  if (int rc = PlantEnqueue(c, A, PlantLdsBytes(c, p->block, false))) { (void)hipStreamSynchronize(c->stream); return rc; }
+  if (int rc = PlantEnqueue(c, A, idto_host::PlantLdsBytes(s, p->block, 0))) { (void)hipStreamSynchronize(c->stream); return rc; }
   const double* back = p->pin;   // (the inputs' copies are in front of the launch on the stream: the staging is free again)
   const int* status = reinterpret_cast<const int*>(p->pin + span);
   HIP_OK(hipMemcpyAsync(p->pin, p->fd_a, span * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -225,28 +174,6 @@ int idto_hip_forward_dynamics(idto_hip_ctx* c, const double* x, const double* ta
                                                                                               : ": a non-finite state or torque") + " (its a_out is not valid)";
       return -1;
     }
-  return 0;
-}
-
-// what a step of the plants refuses (who: the entry's name); *nrec: the states it records
-static int PlantStepCheck(idto_hip_ctx* c, const std::string& who, int substeps, const double* tau_hold, int record_every, bool record, int* nrec) {
-  if (!c->plant || !c->plant->begun) { g_err = who + ": call idto_hip_plant_begin on the context first"; return -1; }
-  PlantState* p = c->plant;
-  if (substeps < 1 || substeps > IDTO_PLANT_MAX_SUBSTEPS) { g_err = who + ": substeps must be in [1, 4096] (a single launch stays short on a shared device)"; return -1; }
-  const bool pd = p->mode == IDTO_PLANT_PD_PLUS;
-  if (!pd && !tau_hold) { g_err = who + ": hold mode needs tau_hold[batch][nv]"; return -1; }
-  if (pd && tau_hold) { g_err = who + ": PD+ forms the torque itself: tau_hold must be NULL"; return -1; }
-  // (the plans the LDS was sized for at idto_hip_plant_begin: the same idto_hip_mpc_batch_begin, not only the same sizes)
-  if (pd && (!c->mpc || c->mpc_generation != p->mpc_generation || c->mpc->L.nu != p->nu || PlantLdsBytes(c, p->block, true) != p->lds)) {
-    g_err = who + ": PD+: idto_hip_mpc_batch_begin was called again after idto_hip_plant_begin (call idto_hip_plant_begin again)";
-    return -1;
-  }
-  *nrec = 0;
-  if (record) {
-    if (record_every < 1) { g_err = who + ": record_every must be >= 1 with x_record_out"; return -1; }
-    *nrec = substeps / record_every;
-    if (*nrec > p->record_capacity) { g_err = who + ": more recorded states than idto_hip_plant_begin's record_capacity"; return -1; }
-  }
   return 0;
 }
 
@@ -278,7 +205,7 @@ static int PlantStepEnqueue(idto_hip_ctx* c, int substeps, const double* tau_hol
 
 int idto_hip_plant_step(idto_hip_ctx* c, int substeps, const double* tau_hold, int record_every, double* x_record_out, int* status_out) {
   int nrec = 0;
-  if (int rc = PlantStepCheck(c, "plant_step", substeps, tau_hold, record_every, x_record_out != nullptr, &nrec)) return rc;
+  if (int rc = Refused(idto_host::RefusePlantStep(PlantShapeOf(c), "plant_step", substeps, tau_hold, record_every, x_record_out != nullptr, &nrec))) return rc;
   HIP_OK(hipSetDevice(c->device));
   PlantState* p = c->plant;
   const size_t B = (size_t)c->batch, nq = (size_t)c->nq, nv = (size_t)c->nv;
@@ -304,11 +231,7 @@ int idto_hip_mpc_batch_tick_plants(idto_hip_ctx* c, int substeps, int iterations
                         Delta_out, q_out, v_out, tau_out, final_cost, status, best, guess_out, plans_out};
   // every refusal first: the tick's (idto_hip_mpc_batch_replan's own), then the step's
   if (int rc = MpcReplanCheck(c, "mpc_batch_tick_plants", a, true, false)) return rc;
-  int nrec = 0;
-  if (int rc = PlantStepCheck(c, "mpc_batch_tick_plants", substeps, nullptr, 0, false, &nrec)) {
-    if (c->plant && c->plant->begun && c->plant->mode != IDTO_PLANT_PD_PLUS) g_err = "mpc_batch_tick_plants: the plants track the stored plans: idto_hip_plant_begin with IDTO_PLANT_PD_PLUS";
-    return rc;
-  }
+  if (int rc = Refused(idto_host::RefuseTickPlantsStep(PlantShapeOf(c), substeps))) return rc;
   HIP_OK(hipSetDevice(c->device));
   // the plants' substeps under PD+ on the current plans; the kernel's last act writes the tick buffer that mpc_shift_kernel reads
   if (int rc = PlantStepEnqueue(c, substeps, nullptr, 0, 0, c->mpc->tick_dev)) return rc;

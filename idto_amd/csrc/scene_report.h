@@ -26,8 +26,7 @@
 
 namespace idto_dev {
 
-// a body's record in LDS: put_state's 18 doubles, then hW (the axis of a revolute / prismatic joint in the world)
-constexpr int SREC = 21, SR_HW = 18;
+// (a body's record in LDS - SREC, SR_HW -, scene_row_stride, scene_lds_doubles and scene_block: plant_sizes.h)
 constexpr int SCENE_BODY = IDTO_SCENE_BODY_DOUBLES, SCENE_PAIR = IDTO_SCENE_PAIR_DOUBLES;
 
 struct SceneArgs {
@@ -44,18 +43,6 @@ struct SceneArgs {
   double* tau_contact;      // [batch][nstates][nv]
   double* tau_pairs;        // [batch][nstates][npairs][nv]
 };
-
-__host__ __device__ inline int scene_row_stride(int nv) { return nv | 1; }
-// dynamic LDS of scene_kernel in doubles
-__host__ __device__ inline size_t scene_lds_doubles(int nb, int nq, int nv, int npairs, int blob_n) {
-  return (size_t)blob_n + nq + nv + (size_t)nb * SREC + (size_t)npairs * scene_row_stride(nv);
-}
-// threads of its block: a lane per body, pair (in rounds beyond 256) and DoF
-__host__ __device__ inline int scene_block(int nb, int nv, int npairs) {
-  const int want = nb > nv ? (nb > npairs ? nb : npairs) : (nv > npairs ? nv : npairs);
-  const int t = (want + 63) / 64 * 64;
-  return t < 64 ? 64 : (t > 256 ? 256 : t);
-}
 
 struct ScenePair {
   bool active;

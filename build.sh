@@ -38,6 +38,9 @@ REM="-Rpass-analysis=kernel-resource-usage"
 # what the plant family's entries (csrc/*_abi.inc) refuse, the sizes of their launches and where a call's arrays lie: host-only
 # (tests/cpp/plant_calls_check.cc holds it to tests/golden/plant_call_layouts.txt and to every message on the CPU)
 ( g++ -O2 -std=c++17 -fPIC -ffp-contract=off -Wall -Wextra -Iinclude -Iidto_amd/csrc -c idto_amd/csrc/host/plant_calls.cc -o build/plant_calls.o ) &
+# every finite-difference launch - block, evaluations per pass, fold, LDS, grid, kernel: host-only (tests/cpp/fd_plan_check.cc
+# holds it to tests/golden/fd_plans.txt and the LDS formula to the kernel's carve-up on the CPU)
+( g++ -O2 -std=c++17 -fPIC -ffp-contract=off -Wall -Wextra -Iinclude -Iidto_amd/csrc -c idto_amd/csrc/host/fd_plan.cc -o build/fd_plan.o ) &
 $HIPCC $FLAGS -mllvm -amdgpu-mfma-vgpr-form=1 $MAIN_FLAGS $REM -c idto_amd/csrc/idto_hip.hip -o build/idto_hip.o "$@" 2> build/idto_hip.remarks || { grep -v "remark:" build/idto_hip.remarks >&2; exit 1; }
 wait %1
 wait %2
@@ -49,9 +52,10 @@ wait %7
 wait %8
 wait %9
 wait %10
+wait %11
 grep -h -A3 "warning:" build/fd_launch.remarks build/idto_hip.remarks build/plant_launch.remarks build/scene_launch.remarks build/lin_launch.remarks build/track_launch.remarks >&2 || true
 if [ -z "$IDTO_SKIP_RESOURCE_CHECK" ]; then python3 tools/check_resources.py build/fd_launch.remarks build/idto_hip.remarks build/plant_launch.remarks build/scene_launch.remarks build/lin_launch.remarks build/track_launch.remarks > build/resource_check.txt || { cat build/resource_check.txt >&2; exit 1; }; fi
-$HIPCC --offload-arch=gfx950 -fPIC -shared build/fd_launch.o build/plant_launch.o build/scene_launch.o build/lin_launch.o build/track_launch.o build/idto_hip.o build/model_tables.o build/solver_plan.o build/model_batch.o build/context_layout.o build/plant_calls.o -o idto_amd/libidto_hip.so -ldl
+$HIPCC --offload-arch=gfx950 -fPIC -shared build/fd_launch.o build/plant_launch.o build/scene_launch.o build/lin_launch.o build/track_launch.o build/idto_hip.o build/model_tables.o build/solver_plan.o build/model_batch.o build/context_layout.o build/plant_calls.o build/fd_plan.o -o idto_amd/libidto_hip.so -ldl
 # libidto_opt.so: the host-side TrajectoryOptimizer (C++) + its C-ABI, on top of libidto_hip.so
 g++ -O3 -std=c++17 -fPIC -shared -Wall -Iinclude -Iidto_amd/csrc idto_amd/csrc/host/trajectory_optimizer.cc \
   idto_amd/csrc/host/batch_rows.cc idto_amd/csrc/host/ls_rows.cc idto_amd/csrc/host/mpc_controller.cc idto_amd/csrc/host/idto_opt_c.cc -o idto_amd/libidto_opt.so -Lidto_amd -lidto_hip -Wl,-rpath,'$ORIGIN'

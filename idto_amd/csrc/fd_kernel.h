@@ -8,6 +8,7 @@
 
 #include "arena_sizes.h"
 #include "batch.h"
+#include "fd_sizes.h"
 #include "id_eval.h"
 #include "id_fast.h"
 
@@ -311,11 +312,7 @@ template <int SHAPE> struct FastShape {
   static constexpr TreeShape T = tree_shape(SHAPE);
   static constexpr int MAXC = T.MAXC, NP = T.NP, CJ = T.CJ, J0 = T.J0, K0 = T.K0, W2 = T.W2, GS = T.GS;
 };
-// the part of fd_body's LDS that id_eval<MAXC, true> exchanges the chain states through: a record per chain body that a
-// pair touches, for each of the block's concurrent evaluations
-__host__ __device__ inline int fd_xch_doubles(int nxb, int threads, int npaths, int nstem = 0) {
-  return (threads / npaths) * xch_eval_doubles(nxb, nstem);
-}
+// (fd_xch_doubles, the part of fd_body's LDS that id_eval<MAXC, true> exchanges the chain states through: fd_sizes.h)
 
 // DD: forward differences on the lane map without the redundant path lanes (model_layout.h tree_shape_dedup) -
 // the kernels fd_dedup_kernel and fd_dedup_models_kernel below, so that fd_kernel's own code is what it was.
@@ -349,6 +346,9 @@ IDTO_DEV void fd_body(const DevModel& M, const DevContact& cp, const DevProblem&
   const int nM = (mode == 1) ? nv : (central ? NM * nq : 0);
   const int E = 1 + nP + nT + nM;
 
+  // (the walk from here to xch is restated, as offsets, by fd_sizes.h fd_carve - the host holds the launch's LDS bytes to it,
+  // tests/cpp/fd_plan_check.cc; a change here is a change there.  Taking the pointers from fd_carve was tried: the kernels
+  // compile to other register allocations, so the text stays.)
   double* qm1 = lds;            // q_{k-1}
   double* q0 = qm1 + nq;        // q_k
   double* q1 = q0 + nq;         // q_{k+1}

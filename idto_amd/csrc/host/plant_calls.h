@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "fd_sizes.h"
 #include "idto_hip.h"
 
 namespace idto_host {
@@ -34,11 +35,11 @@ struct Refusal {
 
 // ---- the block and the dynamic LDS of plant_kernel / track_kernel; beside: the doubles that lie in LDS beside the block's
 // own (PlantPdDoubles, plant_sizes.h plant_law_doubles, or 0)
-constexpr int kPlantMaxLds = 160 * 1024;
+constexpr int kPlantMaxLds = idto_dev::kMaxDynamicLds;
 size_t PlantPdDoubles(const PlantShape& s);
 // bytes; 1 << 27 where the count of doubles is beyond 2^24 (no int overflow, and past every bound)
 int PlantLdsBytes(const PlantShape& s, int threads, size_t beside);
-// Threads of the block, beside FdBlock: a wavefront per 64 lanes of the (nv + 1) * npaths that a substep's evaluations want,
+// Threads of the block, beside host/fd_plan.cc's: a wavefront per 64 lanes of the (nv + 1) * npaths that a substep's evaluations want,
 // up to 256 (or `forced`); the block shrinks by a wavefront at a time where the exchange areas of its concurrent evaluations do
 // not fit the 160 KiB of LDS beside the rest (the evaluations then go in rounds)
 int PlantBlock(const PlantShape& s, int forced, size_t beside);

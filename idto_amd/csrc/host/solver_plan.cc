@@ -4,13 +4,14 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "fd_sizes.h"
 #include "solver_layout.h"
 
 namespace idto_host {
 using namespace idto_dev;
 
 namespace {
-constexpr int kMaxLds = 160 * 1024;
+constexpr int kMaxLds = kMaxDynamicLds;   // (fd_sizes.h: the one limit of every kernel of the library)
 
 int Fail(std::string* err, const char* what) {
   if (err) *err = what;

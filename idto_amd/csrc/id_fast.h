@@ -25,6 +25,7 @@
 // with the same fused expressions.
 #pragma once
 
+#include "fd_sizes.h"
 #include "id_eval.h"
 
 // profiling build (tools/fd_variants.sh, -DIDTO_FD_STAMPS): shader-clock stamps of the phases of fd_kernel and of the
@@ -336,11 +337,8 @@ struct InFwd {
 };
 
 // ---- the forward-difference lane map without the redundant path lanes (model_layout.h tree_shape_dedup):
-// what main and helper lanes hand each other through LDS.  Every value is stored and read back as it is - an exact copy.
-enum { FDX_STATE = 19, FDX_RES = 9 };   // doubles per body state (18 used) and per pair result (fc, nc, hit); odd strides: no bank conflicts
-constexpr int fd_dedup_doubles() {
-  return kFdMainLanes * FDX_STATE + (kFdMainLanes / 4) * FDX_STATE + kFdMainLanes * FDX_RES + (kFdMainLanes / 4) * FDX_RES + 4 * 12;
-}
+// what main and helper lanes hand each other through LDS (FDX_STATE, FDX_RES, fd_dedup_doubles: fd_sizes.h).  Every value
+// is stored and read back as it is - an exact copy.
 IDTO_DEV void st_state(double* x, const BodyState& b) {
 #pragma unroll
   for (int i = 0; i < 9; ++i) x[i] = b.R.m[i];

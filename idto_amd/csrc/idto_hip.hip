@@ -45,6 +45,7 @@
 #include "lin_launch.h"
 #include "track_launch.h"
 #include "host/context_layout.h"
+#include "host/fd_plan.h"
 #include "host/model_batch.h"
 #include "host/model_tables.h"
 #include "host/plant_calls.h"
@@ -308,7 +309,7 @@ struct idto_hip_ctx {
   int last_assembly = 0;                  // 1 assemble_terms_kernel, 2 assemble_diag_kernel (also inside the fused launch), 3 assemble_kernel,
                                           // 4 inside the solver's launch, 5 inside gn_small_kernel
   // launch geometry
-  int fd_threads = 256, fd_lds = 0, asm_lds = 0, penta_lds = 0, solve_lds = 0, cost_lds = 0;
+  int asm_lds = 0, penta_lds = 0, solve_lds = 0, cost_lds = 0;
   // timing
   bool timing = false;
   int timing_stride = 1;     // record events on every timing_stride-th launch of each kernel
@@ -714,39 +715,16 @@ int UploadModel(idto_hip_ctx* c, const idto_model_t* m, const idto_host::ModelTa
 }
 
 
-int FdEvals(const idto_hip_ctx* c, int mode) {
-  return (mode == 0) ? 1 : ((mode == 1) ? 1 + 2 * c->nq + c->nv : 1 + ((mode == 2) ? 2 : 4) * 3 * c->nq);
+// what host/fd_plan.cc reads of a context
+static idto_host::FdShape FdShapeOf(const idto_hip_ctx* c) {
+  idto_host::FdShape s;
+  s.nq = c->nq; s.nv = c->nv; s.npaths = c->npaths; s.batch = c->batch;
+  s.blob_n = c->M.blob_n; s.fast_n = c->M.fast_n; s.fast_shape = c->M.fast_shape; s.maxc = c->maxc; s.nxb = c->M.nxb; s.nstem = c->M.nstem;
+  s.lane_map = c->model_has_fd_dedup; s.model_records = c->model_records != nullptr;
+  s.fd_fast = c->fd_fast; s.fd_dedup = c->fd_dedup; s.asm_fold = c->asm_fold; s.weights_diagonal = c->weights_diagonal;
+  s.gradients_method = c->gradients_method;
+  return s;
 }
-
-// dynamic LDS of fd_kernel when it builds the inputs of `ec` evaluations per pass
-// (fast: fd_kernel<MAXC, SHAPE != 0>, which stages only the shape's records of the model; the fused launch runs the
-// generic evaluation and stages the whole blob)
-// threads: of the block (0: the context's fd_threads, 64 for a launch of tau alone)
-int FdLds(const idto_hip_ctx* c, int mode, int ec, bool with_terms = false, bool fast = true, int threads = 0) {
-  const int nq = c->nq, nv = c->nv, E = FdEvals(c, mode), nvp = (nv + 1) & ~1;
-  const int rec = with_terms ? 6 * nvp * nq + 2 * nvp + 1 : 0;   // the record, its weighted copy, diag R', tau R' (+1: 16-byte alignment)
-  const int blob_n = (fast && c->fd_fast && c->M.fast_shape) ? c->M.fast_n : c->M.blob_n;   // what fd_body stages of the model
-  // (the exchange of shared pairs and of a stem, per concurrent evaluation: id_eval.h xch_eval_doubles)
-  if (!threads) threads = mode >= 1 ? c->fd_threads : 64;
-  // (... or, in its place, what the main and helper lanes of the lane map without the redundant path lanes hand each other)
-  const int xch = fd_xch_doubles(c->M.nxb, threads, c->npaths, c->M.nstem) + ((fast && c->model_has_fd_dedup && mode == 1) ? fd_dedup_doubles() : 0);
-  return (int)sizeof(double) * (3 * nq + 2 * nv * nq + 3 * nv + 3 * E + E * nv + ec * (nq + 2 * nv) + nv + blob_n + 2 + nq / 2 + 2 + rec + xch);
-}
-
-// Threads of fd_kernel's block.  A stem model keeps a record per touched body and concurrent evaluation in LDS (punyo: 1.8 KB
-// an evaluation): where the carve-up of one round does not fit beside them, the block shrinks by a wavefront at a time and
-// the launch goes in rounds (punyo, forward differences: 48 concurrent evaluations - the 43 with contact and 5 mass-matrix
-// columns in the first round, the other 15 columns, which have no contact, in the second).
-static int FdBlock(const idto_hip_ctx* c, int mode) {
-  if (mode == 0) return 64;
-  int t = c->fd_threads;
-  while (c->M.nstem > 1 && t > 64 && FdLds(c, mode, t / c->npaths, false, true, t) > 160 * 1024) t -= 64;
-  return t;
-}
-
-// fd_kernel also forms the single-record products of the Gauss-Newton assembly (diagonal weights,
-// derivatives requested): grad_hess then only combines them
-static bool FoldTerms(const idto_hip_ctx* c, int mode) { return c->asm_fold && c->weights_diagonal && mode >= 1; }
 
 // along (idto_hip_costs_along, mode 0): the launch evaluates `m` candidate points of the context's one problem instead
 // of the resident q - grid.y = candidate, q and the outputs in arenas of their own (linesearch.h LsArena), nothing of the
@@ -756,23 +734,17 @@ struct FdAlong { const double* q; double *slab, *v, *a, *nplus; int slab_stride;
 int LaunchFd(idto_hip_ctx* c, int mode, int kb, int ke, AltSel alt = AltSel{nullptr, 0, 0}, const FdAlong* along = nullptr) {
   if (!along) c->partials_ahead = false;   // (whatever idto_hip_eval_tau_partials left is about to be overwritten; it sets the flag after its own launch)
   if (ke <= kb) return 0;
-  if (mode >= 1) mode = 1 + c->gradients_method;  // 1 forward, 2 central, 3 central (4th order)
-  dim3 grid(ke - kb, along ? along->m : c->batch), block(FdBlock(c, mode));
-  // evaluations per pass: all of them if they fit in LDS, otherwise the largest multiple of
-  // the number of evaluations the block runs concurrently
-  const int E = FdEvals(c, mode), groups = (int)block.x / c->npaths;
-  int ec = E;
-  bool fold = FoldTerms(c, mode);
-  if (fold && FdLds(c, mode, std::min(ec, groups), true, true, block.x) > 160 * 1024) fold = false;
-  while (ec > groups && FdLds(c, mode, ec, fold, true, block.x) > 160 * 1024) ec = ((ec - 1) / groups) * groups;
-  const int lds = FdLds(c, mode, ec, fold, true, block.x);
-  if (lds > 160 * 1024) { g_err = "finite-difference evaluation set does not fit in LDS"; return -1; }
-  double* terms = fold ? c->terms : nullptr;
-  if (mode >= 1) c->terms_valid = fold && kb == 0 && ke == c->N;
+  // the block, the evaluations per pass, the fold, the LDS, the grid, the shape and the kernel: host/fd_plan.cc
+  idto_host::FdRequest rq;
+  rq.kind = along ? idto_host::FdRequest::CANDIDATES : idto_host::FdRequest::RESIDENT;
+  rq.mode = mode; rq.kb = kb; rq.ke = ke; rq.m = along ? along->m : 0;
   FdLaunch fl;
-  fl.grid = grid; fl.block = block; fl.lds = lds; fl.stream = c->stream; fl.M = c->M; fl.cp = c->cp; fl.P = c->P;
+  if (idto_host::PlanFd(FdShapeOf(c), rq, &fl.plan, &g_err)) return -1;
+  const idto_host::FdPlan& p = fl.plan;
+  if (p.mode >= 1) c->terms_valid = p.fold && kb == 0 && ke == c->N;
+  fl.stream = c->stream; fl.M = c->M; fl.cp = c->cp; fl.P = c->P;
   fl.q = c->q; fl.slab = c->slab; fl.slab_stride = c->slab_stride; fl.v = c->v; fl.a = c->a; fl.nplus = c->nplus;
-  fl.k_begin = kb; fl.mode = mode; fl.stop_after = c->fd_stop; fl.echunk = ec; fl.pstride = c->pstride; fl.terms = terms;
+  fl.k_begin = kb; fl.stop_after = c->fd_stop; fl.pstride = c->pstride; fl.terms = p.fold ? c->terms : nullptr;
   fl.alt = alt;
   if (c->model_records) {   // (a batch: idto_hip_set_model_batch)
     fl.records = c->model_records; fl.mstride = c->mstride;
@@ -782,18 +754,9 @@ int LaunchFd(idto_hip_ctx* c, int mode, int kb, int ke, AltSel alt = AltSel{null
   if (along) {
     fl.q = along->q; fl.slab = along->slab; fl.slab_stride = along->slab_stride; fl.v = along->v; fl.a = along->a;
     fl.nplus = along->nplus; fl.cstride = along->cstride; fl.gate = along->gate;
-    if (c->batch > 1) {
-      fl.grid = dim3(ke - kb, along->m, c->batch);
-      fl.along_batch = true; fl.bstride = along->bstride; fl.gstride = along->gstride;
-    }
+    if (c->batch > 1) { fl.bstride = along->bstride; fl.gstride = along->gstride; }
   }
-  fl.shape = c->fd_fast ? c->M.fast_shape : 0;   // id_fast.h: the straight-line evaluation of the model's tree shape
-  if (c->M.nxb) fl.shape = SHAPE_XCH;             // shared pairs: the generic evaluation with the exchange (whatever fd_fast says)
-  if (c->M.nstem > 1) fl.shape = SHAPE_STEM;      // a stem below the common body: ... and the walk along it
-  fl.maxc = c->maxc;
-  fl.dedup = mode == 1 && !along && c->fd_dedup && c->fd_fast && c->model_has_fd_dedup && fl.shape == c->M.fast_shape &&
-             tree_shape_dedup(fl.shape) && (int)block.x == kFdMainLanes + kFdHelperLanes;
-  if (!along) c->last_fd_dedup = fl.dedup;
+  if (!along) c->last_fd_dedup = p.dedup;
   fd_launch(fl);
   HIP_OK(hipGetLastError());
   return 0;
@@ -1003,22 +966,15 @@ int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* probl
   if (AllocStatusWords(c, "hipHostMalloc (solver status) failed")) { idto_hip_destroy(c); return -2; }
   c->k_begin = 0; c->k_end = N;
 
-  // launch geometry
-  const int K = c->npaths;
-  const int E = 1 + 2 * nq + nv;
-  int threads = ((E * K + 63) / 64) * 64;
-  if (threads > 256) threads = 256;  // one wave per SIMD: the evaluation keeps its bodies in up to 512 VGPRs
-  c->fd_threads = threads;
-  threads = FdBlock(c, 1);   // (a stem model: fewer where the exchange records leave no room, LaunchFd decides per mode)
-  // smallest LDS carve-up of the finite-difference kernel: the inputs of one round of concurrent
-  // evaluations per pass (LaunchFd uses more when they fit)
-  c->fd_lds = FdLds(c, 1, threads / K, false, true, threads);
+  // launch geometry: the widest block of the finite-difference kernel and its smallest LDS carve-up (host/fd_plan.cc;
+  // LaunchFd uses more when it fits)
+  const int fd_lds = idto_host::FdCreateGeometry(FdShapeOf(c)).fd_lds;
   // (the launches whose sizes are a pure function of nq, nv, N: host/context_layout.cc)
   const idto_host::LaunchSizes ls = idto_host::PlanLaunchSizes(nq, nv, N);
   c->asm_lds = ls.asm_lds; c->asm_diag_lds = ls.asm_diag_lds; c->asm_terms_lds = ls.asm_terms_lds; c->asm_terms_threads = ls.asm_terms_threads;
   c->penta_lds = ls.penta_lds; c->solve_lds = ls.solve_lds; c->cost_lds = ls.cost_lds;
-  const int max_lds = 160 * 1024;
-  if (c->fd_lds > max_lds || c->asm_lds > max_lds || c->penta_lds > max_lds || c->cost_lds > max_lds ||
+  const int max_lds = kMaxDynamicLds;
+  if (fd_lds > max_lds || c->asm_lds > max_lds || c->penta_lds > max_lds || c->cost_lds > max_lds ||
       ls.apply_lds > max_lds) {
     g_err = "problem too large for the 160 KiB LDS carve-up of the v1 kernels (fd / assemble / solver / cost / "
             "multi-rhs substitution)";
@@ -1842,11 +1798,10 @@ static int LaunchLdl(idto_hip_ctx* c, const SolverPlan& p, const double* b, doub
 }
 
 // ---- one persistent launch for the whole Gauss-Newton iteration (fused.h)
-static int FusedMaxc(const idto_hip_ctx* c) { return c->maxc <= 2 ? 2 : (c->maxc <= 3 ? 3 : (c->maxc <= 4 ? 4 : 8)); }
 static int FusedVariant(const idto_hip_ctx* c) {  // instantiated (MAXC, K) combinations: the reference's example models
   if (c->M.nxb || c->M.nstem > 1) return 0;   // (gn_fused_kernel embeds id_eval without the exchange of shared pairs / the stem)
   if (c->capsules) return 0;   // (capsule models: the three-launch path only)
-  const int mc = FusedMaxc(c);
+  const int mc = idto_host::FdChainBound(c->maxc);   // (what a FUSED plan names)
   int variant = 0, i = 0;
 #define FUSED_IS(MC, KM, PD, GW) ++i; if (mc == MC && c->nq == KM) variant = i;
   IDTO_FUSED_KERNELS(FUSED_IS)
@@ -1872,17 +1827,15 @@ static int LaunchFused(idto_hip_ctx* c) {
   }
   SolverPlan p;   // (the chains' geometry: r0, n, m_split and lds_full are the same whichever kernel the plan names)
   if (int rc = Plan(c, true, SolveRequest{}, &p)) return rc;
-  const int mode = 1 + c->gradients_method;
-  const int E = FdEvals(c, mode), groups = 256 / c->npaths;
-  int ec = E;
-  while (ec > groups && FdLds(c, mode, ec, false, false) > 160 * 1024) ec = ((ec - 1) / groups) * groups;
-  const int fd_lds = FdLds(c, mode, ec, false, false);
-  if (fd_lds > 160 * 1024) { g_err = "finite-difference evaluation set does not fit in LDS"; return -1; }
-  const int lds = std::max(std::max(fd_lds, c->asm_diag_lds), std::max(p.lds_full, 84 * 1024));
+  idto_host::FdRequest rq;   // the embedded evaluation's mode, chunk, LDS term and chain bound: host/fd_plan.cc
+  rq.kind = idto_host::FdRequest::FUSED; rq.mode = 1;
+  idto_host::FdPlan fd;
+  if (idto_host::PlanFd(FdShapeOf(c), rq, &fd, &g_err)) return -1;
+  const int lds = std::max(std::max(fd.lds, c->asm_diag_lds), std::max(p.lds_full, 84 * 1024));
   FusedArgs A;
   A.M = c->M; A.cp = c->cp; A.P = c->P;
   A.q = c->q; A.slab = c->slab; A.slab_stride = c->slab_stride; A.v = c->v; A.a = c->a; A.nplus = c->nplus;
-  A.fd_mode = mode; A.fd_echunk = ec; A.nfd = c->N;
+  A.fd_mode = fd.mode; A.fd_echunk = fd.echunk; A.nfd = c->N;
   A.g = c->g; A.HA = c->HA; A.HB = c->HB; A.HC = c->HC; A.nrows = c->N + 1;
   A.n = p.n; A.k = p.k;
   A.sHA = c->HA + p.qq0; A.sHB = c->HB + p.qq0; A.sHC = c->HC + p.qq0;
@@ -1905,7 +1858,7 @@ static int LaunchFused(idto_hip_ctx* c) {
 #define FUSED_LAUNCH(MC, KM, PD, GW) \
   if (mc == MC && c->nq == KM) { hipLaunchKernelGGL((gn_fused_kernel<MC, KM, PD, GW>), grid, dim3(256), lds, c->stream, A); launched = true; }
   {
-    const int mc = FusedMaxc(c);
+    const int mc = fd.maxc;
     bool launched = false;
     IDTO_FUSED_KERNELS(FUSED_LAUNCH)
     if (!launched) return NoKernel("gn_fused_kernel", c->nq);

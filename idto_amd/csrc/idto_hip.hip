@@ -45,6 +45,7 @@
 #include "lin_launch.h"
 #include "track_launch.h"
 #include "host/context_layout.h"
+#include "host/ctx_buffers.h"
 #include "host/fd_plan.h"
 #include "host/model_batch.h"
 #include "host/model_tables.h"
@@ -102,6 +103,29 @@ struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
 };
+
+// The memory calls of host/ctx_buffers.h's owners (and DevAlloc of Alloc's): -2 with g_err written when HIP refuses
+struct HipMem {
+  static int PinAlloc(void** p, size_t bytes) { HIP_OK(hipHostMalloc(p, bytes, hipHostMallocDefault)); return 0; }
+  static void PinFree(void* p) { (void)hipHostFree(p); }
+  static int DevAlloc(void** out, size_t bytes) {
+    void* p = nullptr;
+    HIP_OK(hipMalloc(&p, bytes));
+    // hipMemset on device memory runs on the NULL stream and does not block the host; the context's
+    // stream is non-blocking, i.e. NOT ordered after the NULL stream: without the synchronisation the
+    // zero fill can land after work the caller enqueues next on the context's stream (seen as a
+    // one-in-fifty wrong first solve on the smallest model)
+    hipError_t e = hipMemset(p, 0, bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) (void)hipFree(p);
+    HIP_OK(e);
+    *out = p;
+    return 0;
+  }
+  static void DevFree(void* p) { (void)hipFree(p); }
+};
+template <class T> using Pinned = idto_host::Pinned<T, HipMem>;
+template <class T> using Grown = idto_host::Grown<T, HipMem>;
 }  // namespace
 
 // Host copies of what a context was created from: a batch context builds single-problem child contexts from them for
@@ -199,14 +223,17 @@ static RcclApi& RcclState() {
 
 // idto_hip_mpc_batch_*: the stored plans of a batch of controllers (mpc_batch.h), an allocation of its own
 struct MpcBatchState {
+  explicit MpcBatchState(idto_hip_ctx* ctx) : c(ctx) {}
+  ~MpcBatchState();                          // returns the device buffers below to the device (they are in c->allocs)
+  idto_hip_ctx* c;
   MpcPlanLayout L{};
   std::vector<int> selector;                 // host copy (the host copies of the problems are shifted with it)
   double* breaks = nullptr; int* selector_dev = nullptr; int* actuated_dev = nullptr;
   double* plan[2] = {nullptr, nullptr};      // two planes of [batch][L.len()]; `cur` is the one in force
   int cur = 0;
   double* work = nullptr;                    // spline_fit's work space, [batch][n * dims]
-  double* tick_dev = nullptr; double* tick_pin = nullptr;   // [batch][1 + nq + nv]: time, q0, v0
-  double* io_dev = nullptr; double* io_pin = nullptr; size_t io_count = 0;   // idto_hip_mpc_batch_store / _shift: plans in, plans / guesses out
+  double* tick_dev = nullptr; Pinned<double> tick_pin;      // [batch][1 + nq + nv]: time, q0, v0
+  double* io_dev = nullptr; Pinned<double> io_pin; size_t io_count = 0;   // idto_hip_mpc_batch_store / _shift: plans in, plans / guesses out
 };
 // what idto_hip_mpc_batch_replan hangs behind the batch fetch's own doubles: [guess [B][(N+1) nq] | plans [B][L.len()]]
 struct MpcTickHook {
@@ -225,6 +252,9 @@ struct MpcTickHook {
 // parameter records, their states [B][1 + nq + nv] (the layout of the controllers' tick buffer), the held torques, the state
 // record of a launch, forward dynamics' inputs and outputs, the PD+ gains, the status words
 struct PlantState {
+  explicit PlantState(idto_hip_ctx* ctx) : c(ctx) {}
+  ~PlantState();                             // returns `base` to the device (it is in c->allocs)
+  idto_hip_ctx* c;
   double* base = nullptr;
   double *records = nullptr, *state = nullptr, *tau = nullptr, *record = nullptr;
   double *fd_x = nullptr, *fd_a = nullptr, *fd_M = nullptr, *fd_bias = nullptr, *Kp = nullptr, *Kd = nullptr;
@@ -234,30 +264,52 @@ struct PlantState {
   unsigned mpc_generation = 0;               // (PD+) the idto_hip_mpc_batch_begin whose plans the LDS was sized for
   double h = 0; int mode = 0, feed_forward = 0, block = 64, lds = 0;
   bool begun = false;                         // idto_hip_plant_begin made it (idto_hip_forward_dynamics alone: not)
-  double* pin = nullptr; size_t pin_cap = 0;   // pinned staging of what comes back
+  Pinned<double> pin;                          // pinned staging of what comes back
   size_t fd_pinned = 0;                        // ... its doubles for idto_hip_forward_dynamics (the storage plan's)
-  double* tick_pin = nullptr; size_t tick_pin_cap = 0;   // ... of the plants' states behind a tick (idto_hip_mpc_batch_tick_plants)
+  Pinned<double> tick_pin;                     // ... of the plants' states behind a tick (idto_hip_mpc_batch_tick_plants)
 };
 
 // A device buffer with its pinned mirror, both grown on demand (GrownEnsure): where a call of the scene report, the
 // linearisation or the tracked rollouts keeps its arrays, laid out by host/plant_calls.h's CallPlan
-struct GrownBuffer {
-  double* dev = nullptr; size_t dev_cap = 0;
-  double* pin = nullptr; size_t pin_cap = 0;
-};
+using GrownBuffer = idto_host::GrownPair<HipMem>;
 // idto_hip_scene_report, made at the first report: the body of every geometry, the states (in, whose mirror stages both ways) and the outputs
 struct SceneState { int* geom_body = nullptr; GrownBuffer in, out; };
 // idto_hip_plant_linearize, idto_hip_plant_tvlqr, made at the first call: the context's own parameter record, a call's arrays
 struct LinState { double* record = nullptr; GrownBuffer buf; };
 
-struct idto_hip_ctx {
+// What a context owns besides its arena and its pool (idto_hip_ctx::allocs): every buffer that is made on first use or grown
+// on demand, and the storage of the MPC, plant, scene, linearisation and tracking entries.  idto_hip_destroy empties it in
+// one assignment (ReleaseBuffers), the stream drained and still alive; an entry that needs another buffer adds a member here.
+struct CtxBuffers {
+  std::unique_ptr<MpcBatchState> mpc; std::unique_ptr<PlantState> plant;   // (their destructors return their share of the pool)
+  std::unique_ptr<SceneState> scene; std::unique_ptr<LinState> lin;
+  std::unique_ptr<GrownBuffer> track;   // idto_hip_plant_track, idto_hip_plant_tvlqr_track: a call's arrays, made at the first call
+  Grown<double> stage_rhs, stage_x;     // idto_hip_solve_host (the same capacity, EnsureStage)
+  Pinned<double> pin;                   // pinned host staging of idto_hip_trial_cost: q in, [tau | cost] out
+  Grown<double> ls_arenas, ls_costs;    // idto_hip_costs_along: candidate arenas (linesearch.h LsArena, LsCap of them), their costs
+  Pinned<double> ls_pin;                // ... and the costs' pinned staging ([IDTO_LS_MAX_CANDIDATES])
+  // idto_hip_ls_solve: the statistics rows, the pinned staging of [rows | q | v | tau] and (idto_hip_ls_solve_batch_fetch) its device
+  // side, packed by ls_gather_batch_kernel (a batch context: arenas [batch][LsCap], costs [batch][64], rows [batch][iterations])
+  Grown<double> ls_rows, ls_fetch_dev; Pinned<double> ls_fetch_pin;
+  Pinned<char> prob_pin;                // ... of the problem arrays (UploadProblemArrays)
+  Pinned<double> many_pin;              // ... of idto_hip_get_many
+  Pinned<double> rows_pin;              // ... of idto_hip_tr_solve's statistics rows
+  Pinned<char> up_pin[2];               // option "async_uploads": the two staging buffers taken in turn (UploadStage)
+  Pinned<double> pre_pin;               // idto_hip_prefetch: the staged copies
+  // equality-constraint step (constraints.h): the constrained dofs; [S | J y_g]; dense LDL^T: pivots, [min, max | h], the
+  // factor L (dense_ldl_step_kernel only reads S's panels), L^-1 (h - J y_g), carried along by the factorisation; pinned staging
+  Grown<int> con_dofs;
+  Grown<double> con_S, con_d, con_h, con_L, con_rv;
+  Pinned<double> con_pin;
+  GrownBuffer fetch;                    // idto_hip_tr_solve_fetch's staging (and the batch form's), EnsureFetch
+  Pinned<double> bstate_pin;            // idto_hip_tr_solve_batch_fetch: the initial state words of every problem ([batch][TRS_COUNT])
+  Grown<double> tr_rows;                // idto_hip_tr_solve: the per-iteration statistics rows
+  Pinned<double> tr_pin;                // the trust-region scalars, [16]
+};
+
+struct idto_hip_ctx : CtxBuffers {
   int device = 0;
-  MpcBatchState* mpc = nullptr;
   unsigned mpc_generation = 0;   // calls of idto_hip_mpc_batch_begin so far
-  PlantState* plant = nullptr;
-  SceneState* scene = nullptr;
-  LinState* lin = nullptr;
-  GrownBuffer* track = nullptr;   // idto_hip_plant_track, idto_hip_plant_tvlqr_track: a call's arrays, made at the first call
   // (batch contexts) what the context was created from, and one single-problem context per problem, made on first use
   std::unique_ptr<HostModelCopy> host_model;
   std::vector<std::unique_ptr<HostProblemCopy>> host_problems;
@@ -362,53 +414,32 @@ struct idto_hip_ctx {
   unsigned long long* sync_cnt = nullptr;            // fused launch: [fd blocks done, assembly blocks done] (monotonic)
   unsigned long long sync_steps = 0;                 // fused launches so far
   double* Tst = nullptr;                             // column-major copies of the factor blocks (penta_apply.h)
-  double *stage_rhs = nullptr, *stage_x = nullptr;  // idto_hip_solve_host
   double* pack = nullptr;                            // [tau | cost] of idto_hip_trial_cost (device)
-  double* pin = nullptr;                             // pinned host staging: q in, [tau | cost] out
-  double *ls_arenas = nullptr, *ls_costs = nullptr; int ls_cap = 0;   // idto_hip_costs_along: candidate arenas (linesearch.h LsArena), their costs
-  double* ls_pin = nullptr;                          // ... and the costs' pinned staging ([IDTO_LS_MAX_CANDIDATES])
-  // idto_hip_ls_solve: the loop's state words, the scan, the statistics rows, the trust ratio's [step | H step], the
-  // pinned staging of [rows | q | v | tau]; option "ls_waves"; calls so far (the tests' proof of which loop ran)
-  double *ls_state = nullptr, *ls_rows = nullptr, *ls_work = nullptr; idto_ls::LsScan* ls_scan = nullptr; int ls_rows_cap = 0;
-  double* ls_fetch_pin = nullptr; size_t ls_fetch_cap = 0;
+  // idto_hip_ls_solve: the loop's state words, the scan, the trust ratio's [step | H step] (a batch context: per problem);
+  // option "ls_waves"; calls so far (the tests' proof of which loop ran), of idto_hip_ls_solve_batch_fetch too
+  double *ls_state = nullptr, *ls_work = nullptr; idto_ls::LsScan* ls_scan = nullptr;
   int ls_waves = 0, ls_solves = 0, compute_units = 0;
-  // (a batch context: every one of them per problem - arenas [batch][ls_cap], costs and their staging [batch][64], state
-  // words, scans, rows [batch][ls_rows_cap], work vectors) idto_hip_ls_solve_batch_fetch: the device side of the staging that
-  // ls_gather_batch_kernel packs (ls_fetch.h), calls so far
-  double* ls_fetch_dev = nullptr; size_t ls_fetch_dev_cap = 0;
   int ls_batch_solves = 0;
-  char* prob_pin = nullptr; size_t prob_pin_bytes = 0;   // ... of the problem arrays (UploadProblemArrays)
-  double* many_pin = nullptr; size_t many_cap = 0;        // ... of idto_hip_get_many
-  double* rows_pin = nullptr; size_t rows_cap = 0;        // ... of idto_hip_tr_solve's statistics rows
   // equality-constraint step (constraints.h)
-  int* con_dofs = nullptr; int con_nu = 0, con_neq = 0;
+  int con_nu = 0, con_neq = 0;
   std::vector<int> con_dofs_host;
   bool con_schur_valid = false;            // con_S, con_d, ... are allocated for con_dofs_host
-  int con_dofs_cap = 0;                    // entries con_dofs has room for
-  double *con_S = nullptr, *con_lambda = nullptr, *con_out = nullptr;  // device: [S | J y_g], lambda, [step | J^T lambda]
-  double *con_d = nullptr, *con_h = nullptr;                            // dense LDL^T: pivots, [min, max | h]
-  double* con_rv = nullptr;                                            // ... and L^-1 (h - J y_g), carried along by the factorisation
-  double* con_L = nullptr;                                             // ... and the factor L (dense_ldl_step_kernel only reads S's panels)
+  double *con_lambda = nullptr, *con_out = nullptr;                    // device: lambda, [step | J^T lambda]
   bool con_S_factored = false;                                         // con_S holds the LDL^T factors, not S
   // SolverParameters::linear_solver = kDenseLdlt (idto_hip_solve_dense_ldlt): [H dense | L], pivots, [min, max], [r | y]
   double *dn_S = nullptr, *dn_d = nullptr, *dn_stat = nullptr, *dn_rv = nullptr; int dn_n = 0;
-  double* fetch_dev = nullptr; double* fetch_pin = nullptr; size_t fetch_cap = 0;   // idto_hip_tr_solve_fetch's staging (and the batch form's)
-  double* bstate_pin = nullptr;   // idto_hip_tr_solve_batch_fetch: the initial state words of every problem, pinned ([batch][TRS_COUNT])
   // option "async_uploads": idto_hip_set_q / idto_hip_set_problem copy from pinned staging of the context - two buffers
   // taken in turn, an event each - and return without waiting (everything else the context does is ordered behind them on
   // its stream); a caller that reads device memory on ANOTHER stream keeps the default, the blocking copies
   bool async_uploads = false;
-  char* up_pin[2] = {nullptr, nullptr}; size_t up_cap[2] = {0, 0}; hipEvent_t up_ev[2] = {nullptr, nullptr}; int up_next = 0;
-  double* con_pin = nullptr; size_t con_pin_count = 0;                 // pinned host staging for the above
+  hipEvent_t up_ev[2] = {nullptr, nullptr}; int up_next = 0;
   bool h_assembled = false;                                            // H comes from idto_hip_grad_hess: block row 0 is the identity
   bool con_begun = false;                                              // constraint_schur_begin enqueued for the current H
   // idto_hip_prefetch: copies enqueued on a side stream behind an event of the main stream
   struct Prefetch { int what = -1; size_t off = 0, count = 0; bool pending = false; hipEvent_t ev = nullptr; };
   Prefetch pre[4];
   hipStream_t side = nullptr;
-  double* pre_pin = nullptr; size_t pre_cap = 0;
   bool con_ready = false;                                              // stage_x holds H^-1 [g | J^T] of the current H
-  size_t stage_count = 0;
   std::vector<hipEvent_t> event_pool;  // recycled: creating events in the timed loop costs host time
   double tsum[4] = {0, 0, 0, 0};
   int tcnt[4] = {0, 0, 0, 0};
@@ -426,8 +457,7 @@ struct idto_hip_ctx {
   // device-side trust-region bookkeeping (trust_region.h): scale factors, scaled merit gradient,
   // w = D^-1 H^-1 g_merit, the last step, the trial trajectory; [16] scalars on the device + pinned
   double *tr_Dprev = nullptr, *tr_part = nullptr;   // the adaptive scalings' previous D; per-block-row partial sums
-  // idto_hip_tr_solve: the iteration state and the arrival counter of tr_iter_kernel (device), the
-  // per-iteration statistics rows (device, grown on demand), a pinned staging area for both
+  // idto_hip_tr_solve: the iteration state and the arrival counter of tr_iter_kernel (device)
   double* tr_state = nullptr;
   // second set of fd_kernel's outputs (v, a, N+, slab, products), alt_off bytes behind the first, and
   // the selectors the launches pass (batch.h AltSel): inactive (state == nullptr) outside idto_hip_tr_solve
@@ -437,10 +467,7 @@ struct idto_hip_ctx {
   unsigned long long tr_target = 0;
   double *tr_part_ll = nullptr, *tr_part2 = nullptr;   // tr_iter_kernel: the block rows' sums with the launch's epoch in every word; dq.dq, g~.dqs per row
   unsigned tr_epoch = 0;
-  double* tr_rows = nullptr;
-  int tr_rows_cap = 0;
   double *tr_D = nullptr, *tr_gt = nullptr, *tr_w = nullptr, *tr_dq = nullptr, *q_trial = nullptr, *tr_out = nullptr;
-  double* tr_pin = nullptr;
   int* tr_quat = nullptr; int tr_nquat = 0;
   bool trial_resident = false;         // v / a / tau / cost in device memory belong to q_trial
   // speculation: idto_hip_tr_trial enqueued the next iteration's gn_step + tr_prepare on the trial
@@ -581,13 +608,7 @@ int Upload(idto_hip_ctx* c, const T* host, size_t count, T** dev) {
 template <class T>
 int Alloc(idto_hip_ctx* c, size_t count, T** dev) {
   void* p = nullptr;
-  HIP_OK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
-  // hipMemset on device memory runs on the NULL stream and does not block the host; the context's
-  // stream is non-blocking, i.e. NOT ordered after the NULL stream: without the synchronisation the
-  // zero fill can land after work the caller enqueues next on the context's stream (seen as a
-  // one-in-fifty wrong first solve on the smallest model)
-  HIP_OK(hipMemset(p, 0, std::max<size_t>(count, 1) * sizeof(T)));
-  HIP_OK(hipDeviceSynchronize());
+  if (int rc = HipMem::DevAlloc(&p, std::max<size_t>(count, 1) * sizeof(T))) return rc;   // (zero-filled, behind a device-wide wait)
   c->allocs.push_back(p);
   *dev = static_cast<T*>(p);
   return 0;
@@ -600,6 +621,14 @@ void Release(idto_hip_ctx* c, T** dev) {
   if (it != c->allocs.end()) { (void)hipFree(*it); c->allocs.erase(it); }
   *dev = nullptr;
 }
+}  // namespace
+// (the one place each of them is released: "begin again" resets the context's pointer, idto_hip_destroy resets them all)
+MpcBatchState::~MpcBatchState() {
+  for (double** p : {&breaks, &plan[0], &plan[1], &work, &tick_dev, &io_dev}) Release(c, p);
+  Release(c, &selector_dev); Release(c, &actuated_dev);
+}
+PlantState::~PlantState() { Release(c, &base); }
+namespace {
 
 // pinned staging for an upload that must not wait (option "async_uploads"): the buffer that was used the time before
 // last - its copy has long run, the event only makes that certain
@@ -608,12 +637,7 @@ static int UploadStage(idto_hip_ctx* c, size_t bytes, char** buf, int* slot) {
   c->up_next ^= 1;
   if (c->up_ev[s]) HIP_OK(hipEventSynchronize(c->up_ev[s]));
   else HIP_OK(hipEventCreateWithFlags(&c->up_ev[s], hipEventDisableTiming));
-  if (c->up_cap[s] < bytes) {
-    if (c->up_pin[s]) (void)hipHostFree(c->up_pin[s]);
-    c->up_pin[s] = nullptr; c->up_cap[s] = 0;
-    HIP_OK(hipHostMalloc((void**)&c->up_pin[s], std::max<size_t>(bytes, 4096), hipHostMallocDefault));
-    c->up_cap[s] = std::max<size_t>(bytes, 4096);
-  }
+  if (int rc = c->up_pin[s].Ensure(bytes, 4096)) return rc;
   *buf = c->up_pin[s]; *slot = s;
   return 0;
 }
@@ -643,11 +667,8 @@ int UploadProblemArrays(idto_hip_ctx* c, const idto_problem_t* p, int pb = 0) {
     const size_t bytes = (size_t)(hi - lo);
     char* stage = nullptr; int slot = -1;
     if (c->async_uploads) { if (int rc = UploadStage(c, bytes, &stage, &slot)) return rc; }
-    if (!stage && c->prob_pin_bytes < bytes) {
-      if (c->prob_pin) (void)hipHostFree(c->prob_pin);
-      c->prob_pin = nullptr; c->prob_pin_bytes = 0;
-      HIP_OK(hipHostMalloc((void**)&c->prob_pin, bytes, hipHostMallocDefault));
-      c->prob_pin_bytes = bytes;
+    if (!stage && c->prob_pin.cap() < bytes) {
+      if (int rc = c->prob_pin.Ensure(bytes)) return rc;
       std::memset(c->prob_pin, 0, bytes);
     }
     if (!stage) stage = c->prob_pin;
@@ -802,33 +823,21 @@ int TimeDrain(idto_hip_ctx* c) {
   return 0;
 }
 
-// pinned staging that grows on demand (the superseded, smaller buffer is freed)
-int EnsurePinned(double** p, size_t* cap, size_t count) {
-  if (*cap >= count) return 0;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr; *cap = 0;
-  HIP_OK(hipHostMalloc((void**)p, count * sizeof(double), hipHostMallocDefault));
-  *cap = count;
-  return 0;
-}
 // (the stream is drained before a device buffer that a launch may still read is released)
 int GrownEnsure(idto_hip_ctx* c, GrownBuffer* b, size_t dev_count, size_t pin_count) {
-  if (b->dev_cap < dev_count) {
-    HIP_OK(hipStreamSynchronize(c->stream));
-    Release(c, &b->dev); b->dev_cap = 0;
-    if (Alloc(c, dev_count, &b->dev)) return -2;
-    b->dev_cap = dev_count;
-  }
-  return EnsurePinned(&b->pin, &b->pin_cap, pin_count);
+  if (b->dev.cap() < dev_count) HIP_OK(hipStreamSynchronize(c->stream));
+  return b->Ensure(dev_count, pin_count);
 }
+// staging buffers grow on demand and are reused; the superseded ones, which enqueued work may still read, are freed behind
+// the new ones' device-wide wait
 int EnsureStage(idto_hip_ctx* c, size_t count) {
-  if (count > c->stage_count) {  // staging buffers grow on demand and are reused
-    double *a = nullptr, *b = nullptr;
-    if (Alloc(c, count, &a) || Alloc(c, count, &b)) return -2;
-    c->stage_rhs = a; c->stage_x = b; c->stage_count = count;
+  if (c->stage_rhs.Ensure(count, 0, true) || c->stage_x.Ensure(count, 0, true)) {
+    c->con_ready = false; c->con_begun = false;   // (what stage_x held is gone)
+    return -2;
   }
   return 0;
 }
+void ReleaseBuffers(idto_hip_ctx* c) { static_cast<CtxBuffers&>(*c) = CtxBuffers(); }
 // a pending idto_hip_prefetch of an array is dropped when that array is about to be recomputed
 // (idto_hip_get then reads the new contents instead of the stale staged copy)
 // after a stream synchronisation: did the most recent factorisation report a failed pivot?
@@ -953,7 +962,7 @@ int idto_hip_create_batch(const idto_model_t* model, const idto_problem_t* probl
       if (model->jtype[i] == IDTO_JOINT_FLOATING) qs.push_back(model->qstart[i]);
     c->tr_nquat = (int)qs.size();
     if (!qs.empty() && Upload(c, qs.data(), qs.size(), &c->tr_quat)) { idto_hip_destroy(c); return -2; }
-    if (hipHostMalloc((void**)&c->tr_pin, 16 * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+    if (c->tr_pin.Ensure(16)) {
       g_err = "hipHostMalloc (trust-region scalars) failed";
       idto_hip_destroy(c);
       return -2;
@@ -1033,39 +1042,15 @@ void idto_hip_destroy(idto_hip_ctx* c) {
   if (c->comm) { if (RcclState().handle) (void)RcclState().CommDestroy(c->comm); c->comm = nullptr; }
   (void)TimeDrain(c);
   for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-  for (void* p : c->allocs) (void)hipFree(p);
-  if (c->pin) (void)hipHostFree(c->pin);
-  if (c->ls_pin) (void)hipHostFree(c->ls_pin);
-  if (c->ls_fetch_pin) (void)hipHostFree(c->ls_fetch_pin);
-  if (c->prob_pin) (void)hipHostFree(c->prob_pin);
-  if (c->many_pin) (void)hipHostFree(c->many_pin);
-  if (c->rows_pin) (void)hipHostFree(c->rows_pin);
-  if (c->status_pin) (void)hipHostFree(c->status_pin);
-  if (c->tr_pin) (void)hipHostFree(c->tr_pin);
   if (c->spec_ev) (void)hipEventDestroy(c->spec_ev);
-  if (c->con_pin) (void)hipHostFree(c->con_pin);
-  if (c->fetch_pin) (void)hipHostFree(c->fetch_pin);
-  if (c->bstate_pin) (void)hipHostFree(c->bstate_pin);
-  if (c->plant) {   // (its device allocation is in c->allocs)
-    if (c->plant->pin) (void)hipHostFree(c->plant->pin);
-    if (c->plant->tick_pin) (void)hipHostFree(c->plant->tick_pin);
-    delete c->plant;
-  }
-  for (GrownBuffer* b : {c->scene ? &c->scene->in : nullptr, c->lin ? &c->lin->buf : nullptr, c->track})   // (the device side is in c->allocs)
-    if (b && b->pin) (void)hipHostFree(b->pin);
-  delete c->scene; delete c->lin; delete c->track;
-  if (c->mpc) {   // (its device buffers are in c->allocs)
-    if (c->mpc->tick_pin) (void)hipHostFree(c->mpc->tick_pin);
-    if (c->mpc->io_pin) (void)hipHostFree(c->mpc->io_pin);
-    delete c->mpc;
-  }
-  for (int i = 0; i < 2; ++i) {
-    if (c->up_pin[i]) (void)hipHostFree(c->up_pin[i]);
-    if (c->up_ev[i]) (void)hipEventDestroy(c->up_ev[i]);
-  }
+  for (hipEvent_t e : c->up_ev) if (e) (void)hipEventDestroy(e);
   if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
   for (auto& pf : c->pre) if (pf.ev) (void)hipEventDestroy(pf.ev);
-  if (c->pre_pin) (void)hipHostFree(c->pre_pin);
+  // the memory, both streams drained and the context's own still alive: the owned buffers and the entries' storage (which
+  // returns its share of the pool), then the pool, the arena in it
+  ReleaseBuffers(c);
+  for (void* p : c->allocs) (void)hipFree(p);
+  if (c->status_pin) (void)hipHostFree(c->status_pin);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1260,10 +1245,8 @@ int idto_hip_trial_cost(idto_hip_ctx* c, const double* q_host, double* tau_host,
   DropPrefetch(c, {IDTO_ARR_Q, IDTO_ARR_V, IDTO_ARR_A, IDTO_ARR_NPLUS, IDTO_ARR_SLAB, IDTO_ARR_COST});
   c->trial_resident = false; c->spec_pending = false; c->spec_ready = false;
   const size_t nq_all = (size_t)(c->N + 1) * c->nq, ntau = (size_t)c->N * c->nv;
-  if (!c->pin) {
-    if (Alloc(c, ntau + 1, &c->pack)) return -2;
-    HIP_OK(hipHostMalloc((void**)&c->pin, (nq_all + ntau + 1) * sizeof(double), hipHostMallocDefault));
-  }
+  if (!c->pack && Alloc(c, ntau + 1, &c->pack)) return -2;
+  if (int rc = c->pin.Ensure(nq_all + ntau + 1)) return rc;
   // one stream synchronisation for the whole trial point: q through pinned memory, N
   // inverse-dynamics evaluations, the cost, and [tau | cost] back in one copy
   std::memcpy(c->pin, q_host, nq_all * sizeof(double));
@@ -1298,20 +1281,16 @@ int idto_hip_ls_alphas(int linesearch_method, int m, double* alphas_host) {
 static int LsEnsureArenas(idto_hip_ctx* c, int m) {
   const LsArena A = ls_arena(c->N, c->nq, c->nv);
   const size_t B = (size_t)c->batch;
-  if (c->ls_cap < m) {
-    Release(c, &c->ls_arenas);
-    c->ls_cap = 0;
-    if (Alloc(c, A.stride * (size_t)m * B, &c->ls_arenas)) {
-      g_err = "linesearch: the candidates' arenas could not be allocated (" + std::to_string(A.stride * (size_t)m * B * sizeof(double)) +
-              " bytes for " + std::to_string(B) + " problems x " + std::to_string(m) + " candidates): " + g_err;
-      return -2;
-    }
-    c->ls_cap = m;
+  if (c->ls_arenas.Ensure(A.stride * (size_t)m * B)) {
+    g_err = "linesearch: the candidates' arenas could not be allocated (" + std::to_string(A.stride * (size_t)m * B * sizeof(double)) +
+            " bytes for " + std::to_string(B) + " problems x " + std::to_string(m) + " candidates): " + g_err;
+    return -2;
   }
-  if (!c->ls_costs && Alloc(c, B * IDTO_LS_MAX_CANDIDATES, &c->ls_costs)) return -2;
-  if (!c->ls_pin) HIP_OK(hipHostMalloc((void**)&c->ls_pin, B * IDTO_LS_MAX_CANDIDATES * sizeof(double), hipHostMallocDefault));
-  return 0;
+  if (int rc = c->ls_costs.Ensure(B * IDTO_LS_MAX_CANDIDATES)) return rc;
+  return c->ls_pin.Ensure(B * IDTO_LS_MAX_CANDIDATES);
 }
+// the candidates every problem's stretch of ls_arenas has room for
+static size_t LsCap(const idto_hip_ctx* c, const LsArena& A) { return c->ls_arenas.cap() / (A.stride * (size_t)c->batch); }
 
 // trial points [first, first + m) -> their tau -> their costs (alpha_dev: ONE point at a step length the device holds)
 static int LsEvaluate(idto_hip_ctx* c, const LsAlphas& al, int first, int m, int normalize_quaternions, const double* gate,
@@ -1320,7 +1299,7 @@ static int LsEvaluate(idto_hip_ctx* c, const LsAlphas& al, int first, int m, int
   const LsArena A = ls_arena(N, nq, nv);
   // (a batch context: the same candidates of every problem - the problems' arenas pcstride doubles apart, their costs
   // IDTO_LS_MAX_CANDIDATES, their gate / alpha words LSS_COUNT)
-  const size_t pcstride = (size_t)c->ls_cap * A.stride, gstride = LSS_COUNT, cstride = IDTO_LS_MAX_CANDIDATES;
+  const size_t pcstride = LsCap(c, A) * A.stride, gstride = LSS_COUNT, cstride = IDTO_LS_MAX_CANDIDATES;
   hipLaunchKernelGGL(ls_trial_kernel, dim3(m, c->batch), dim3(256), 0, c->stream, n, nq, c->q, c->step, al, c->tr_quat,
                      normalize_quaternions ? c->tr_nquat : 0, c->ls_arenas, A.stride, first, gate, alpha_dev, c->pstride,
                      pcstride, gstride);
@@ -1445,21 +1424,11 @@ static int LsSolve(idto_hip_ctx* c, int iterations, int method, int max_ls, int 
       return -2;
     c->ls_scan = reinterpret_cast<idto_ls::LsScan*>(scan);
   }
-  if (c->ls_rows_cap < iterations) {
-    Release(c, &c->ls_rows);
-    c->ls_rows_cap = 0;
-    if (Alloc(c, B * iterations * LSR_COUNT, &c->ls_rows)) return -2;
-    c->ls_rows_cap = iterations;
-  }
+  if (int rc = c->ls_rows.Ensure(B * iterations * LSR_COUNT)) return rc;
   const size_t nrow = (size_t)iterations * LSR_COUNT, nqa = (size_t)n, nva = (size_t)(N + 1) * nv, nta = (size_t)N * nv;
   const idto_fetch::LsFetchLayout FL = idto_fetch::LsFetchLayout::Make(c->batch, iterations, LSR_COUNT, N, nq, nv, bo != nullptr);
-  if (int rc = EnsurePinned(&c->ls_fetch_pin, &c->ls_fetch_cap, FL.total())) return rc;
-  if (bo && c->ls_fetch_dev_cap < FL.total()) {
-    Release(c, &c->ls_fetch_dev);
-    c->ls_fetch_dev_cap = 0;
-    if (Alloc(c, FL.total(), &c->ls_fetch_dev)) return -2;
-    c->ls_fetch_dev_cap = FL.total();
-  }
+  if (int rc = c->ls_fetch_pin.Ensure(FL.total())) return rc;
+  if (bo) if (int rc = c->ls_fetch_dev.Ensure(FL.total())) return rc;
   if (!c->compute_units) {
     HIP_OK(hipDeviceGetAttribute(&c->compute_units, hipDeviceAttributeMultiprocessorCount, c->device));
   }
@@ -1482,7 +1451,7 @@ static int LsSolve(idto_hip_ctx* c, int iterations, int method, int max_ls, int 
                             hipMemcpyDeviceToDevice, c->stream));
   }
   LsLoopArgs L;
-  L.pstride = c->pstride; L.rows_stride = nrow; L.costs_stride = IDTO_LS_MAX_CANDIDATES; L.pcstride = (size_t)c->ls_cap * A.stride;
+  L.pstride = c->pstride; L.rows_stride = nrow; L.costs_stride = IDTO_LS_MAX_CANDIDATES; L.pcstride = LsCap(c, A) * A.stride;
   L.n = n; L.nq = nq; L.nv = nv; L.N = N; L.g = c->g; L.dq = c->step; L.HA = c->HA; L.HB = c->HB; L.HC = c->HC;
   L.slab = c->slab; L.slab_stride = c->slab_stride; L.tau_off = 3 * nv * nq; L.dofs = c->una_dofs; L.nu = c->una_nu;
   L.q = c->q; L.cost = c->cost; L.state = c->ls_state; L.scan = c->ls_scan; L.rows = c->ls_rows; L.work = c->ls_work;
@@ -2116,14 +2085,7 @@ static int DeviceDofs(idto_hip_ctx* c, const int* dofs, int nu, const char* who,
     if (dofs[j] < 0 || dofs[j] >= c->nv) { g_err = std::string(who) + ": dof index out of range"; return -1; }
   *changed = !(c->con_dofs && c->con_dofs_host.size() == (size_t)nu && std::equal(dofs, dofs + nu, c->con_dofs_host.begin()));
   if (!*changed) return 0;
-  if (c->con_dofs_cap < nu) {
-    Release(c, &c->con_dofs);
-    void* p = nullptr;
-    HIP_OK(hipMalloc(&p, (size_t)nu * sizeof(int)));
-    c->allocs.push_back(p);
-    c->con_dofs = static_cast<int*>(p);
-    c->con_dofs_cap = nu;
-  }
+  if (int rc = c->con_dofs.Ensure((size_t)nu)) return rc;
   HIP_OK(hipStreamSynchronize(c->stream));   // (work that reads the previous set may still be enqueued)
   HIP_OK(hipMemcpy(c->con_dofs, dofs, (size_t)nu * sizeof(int), hipMemcpyHostToDevice));
   c->con_dofs_host.assign(dofs, dofs + nu);
@@ -2144,18 +2106,13 @@ static int ConstraintBuffers(idto_hip_ctx* c, const int* dofs, int nu) {
   if (int rc = DeviceDofs(c, dofs, nu, "constraint_schur", &changed)) return rc;
   const int N = c->N, n = (N + 1) * c->nq, neq = nu * N;
   if (!c->con_schur_valid) {
-    Release(c, &c->con_S); Release(c, &c->con_d); Release(c, &c->con_h); Release(c, &c->con_L); Release(c, &c->con_rv);
-    if (Alloc(c, (size_t)neq * neq + neq, &c->con_S) ||
-        Alloc(c, (size_t)neq, &c->con_d) || Alloc(c, (size_t)neq + 2, &c->con_h) || Alloc(c, (size_t)neq * neq, &c->con_L) ||
-        Alloc(c, 2 * (size_t)neq, &c->con_rv))   // [r with the finished panels eliminated | y = L^-1 r]
+    // (made again for every new set, zero-filled, not only for a larger one)
+    for (Grown<double>* b : {&c->con_S, &c->con_d, &c->con_h, &c->con_L, &c->con_rv}) b->Reset();
+    if (c->con_S.Ensure((size_t)neq * neq + neq) ||
+        c->con_d.Ensure((size_t)neq) || c->con_h.Ensure((size_t)neq + 2) || c->con_L.Ensure((size_t)neq * neq) ||
+        c->con_rv.Ensure(2 * (size_t)neq))   // [r with the finished panels eliminated | y = L^-1 r]
       return -2;
-    const size_t need = (size_t)neq * neq + neq + 2 * (size_t)n + 2 * (size_t)neq + 4;
-    if (c->con_pin_count < need) {
-      if (c->con_pin) (void)hipHostFree(c->con_pin);
-      c->con_pin = nullptr; c->con_pin_count = 0;
-      HIP_OK(hipHostMalloc((void**)&c->con_pin, need * sizeof(double), hipHostMallocDefault));
-      c->con_pin_count = need;
-    }
+    if (int rc = c->con_pin.Ensure((size_t)neq * neq + neq + 2 * (size_t)n + 2 * (size_t)neq + 4)) return rc;
     c->con_schur_valid = true;
     c->con_begun = false;
   }
@@ -2514,13 +2471,7 @@ bool TrKktRoute(const idto_hip_ctx* c, int nu) {
   return nu > 0 && c->con_kkt && idto_host::SolverBlockSize(c->nq + nu, true) <= 30 && c->weights_diagonal;
 }
 // the fetches' staging on the device and its pinned mirror, grown on demand
-int EnsureFetch(idto_hip_ctx* c, size_t total) {
-  if (c->fetch_cap >= total) return 0;
-  Release(c, &c->fetch_dev);
-  c->fetch_cap = 0;   // (both or neither: the pinned mirror goes with it, in EnsurePinned)
-  if (Alloc(c, total, &c->fetch_dev)) return -2;
-  return EnsurePinned(&c->fetch_pin, &c->fetch_cap, total);
-}
+int EnsureFetch(idto_hip_ctx* c, size_t total) { return c->fetch.Ensure(total, total); }
 // where the batch fetch's parts lie in that staging (tr_fetch.h)
 TrFetchLayout BatchFetchLayout(const idto_hip_ctx* c, const TrRequest& rq) {
   const TrBatchFetch* bf = rq.bfetch;
@@ -2580,11 +2531,8 @@ int TrPlanLaunches(idto_hip_ctx* c, const TrRequest& rq, TrRoute* rt) {
 // The loop's state words - of every problem [Delta, L(q) (resident: the caller evaluated the cost of q), ...] - and the iteration kernel's counter
 int TrBegin(idto_hip_ctx* c, const TrRequest& rq) {
   const int B = c->batch;
-  if (rq.iterations > c->tr_rows_cap) {
-    double* p = nullptr;
-    if (Alloc(c, (size_t)B * rq.iterations * TRR_COUNT, &p)) return -2;   // (the previous, smaller one stays in the context's pool)
-    c->tr_rows = p; c->tr_rows_cap = rq.iterations;
-  }
+  // (the larger one first: the previous, smaller one - an earlier solve's launches may read it - is freed behind its device-wide wait)
+  if (int rc = c->tr_rows.Ensure((size_t)B * rq.iterations * TRR_COUNT, 0, true)) return rc;
   c->spec_pending = false; c->spec_ready = false; c->trial_resident = false;
   // tr_iter_kernel finds its last workgroup by counter == target: both restart with every solve, so that a
   // launch that failed in an earlier solve cannot leave them out of step
@@ -2601,7 +2549,7 @@ int TrBegin(idto_hip_ctx* c, const TrRequest& rq) {
   HIP_OK(hipMemset2DAsync(c->tr_cnt, c->pstride, 0, sizeof(unsigned long long), (size_t)B, c->stream));
   std::vector<double> tmp; double* st = nullptr;
   if (rq.bfetch) {   // (pinned words of the context: no wait here - the call's one wait is behind the loop, and every return in between waits too)
-    if (!c->bstate_pin) HIP_OK(hipHostMalloc((void**)&c->bstate_pin, (size_t)B * TRS_COUNT * sizeof(double), hipHostMallocDefault));
+    if (int rc = c->bstate_pin.Ensure((size_t)B * TRS_COUNT)) return rc;
     st = c->bstate_pin;
     std::fill(st, st + (size_t)B * TRS_COUNT, 0.0);
   } else { tmp.assign((size_t)B * TRS_COUNT, 0.0); st = tmp.data(); }
@@ -2811,7 +2759,7 @@ int TrFinishBatchFetch(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt) 
   TrGatherBatchArgs G;
   G.state = c->tr_state; G.rows = c->tr_rows; G.B = B; G.iterations = rq.iterations; G.nrows = (int)L.nrows; G.only_best = bfetch->only_best ? 1 : 0;
   G.q = c->q; G.v = c->v; G.slab = c->slab; G.dq = c->tr_dq; G.w = c->tr_w; G.nq = c->nq; G.nv = c->nv; G.slab_stride = (int)c->slab_stride;
-  G.alt_off = (long long)c->alt_off; G.pstride = c->pstride; G.L = L; G.out = c->fetch_dev;
+  G.alt_off = (long long)c->alt_off; G.pstride = c->pstride; G.L = L; G.out = c->fetch.dev;
   hipLaunchKernelGGL(tr_gather_batch_kernel, dim3(TR_GATHER_BATCH_GX + 1, B), dim3(256), lds, c->stream, G);
   HIP_OK(hipGetLastError());
   if (hook) {
@@ -2823,15 +2771,15 @@ int TrFinishBatchFetch(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt) 
     S.tau = c->slab + 3 * (size_t)c->nv * c->nq; S.tau_stride = c->pstride; S.tau_row = (int)c->slab_stride;
     S.state = c->tr_state; S.state_stride = c->pstride; S.alt_off = (long long)c->alt_off;
     S.rows = c->tr_rows; S.iterations = rq.iterations; S.nrows = (int)L.nrows; S.times = m->tick_dev; S.times_stride = 1 + c->nq + c->nv;
-    S.plan_old = m->plan[m->cur]; S.plan_new = m->plan[m->cur ^ 1]; S.work = m->work; S.out = c->fetch_dev + L.plans();
+    S.plan_old = m->plan[m->cur]; S.plan_new = m->plan[m->cur ^ 1]; S.work = m->work; S.out = c->fetch.dev + L.plans();
     hipLaunchKernelGGL(mpc_store_kernel, dim3((m->L.dims() + 63) / 64, B), dim3(64), 0, c->stream, S);
     HIP_OK(hipGetLastError());
   }
-  HIP_OK(hipMemcpyAsync(c->fetch_pin, c->fetch_dev, L.total() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipMemcpyAsync(c->fetch.pin, c->fetch.dev, L.total() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   const size_t tick_w = (size_t)(1 + c->nq + c->nv);
   if (hook && hook->plant) {   // one more copy back, the plants' states, in front of the tick's one wait
     PlantState* pl = hook->plant;
-    if (int erc = EnsurePinned(&pl->tick_pin, &pl->tick_pin_cap, (size_t)B * (tick_w + 1))) return erc;   // (+ two status ints a plant)
+    if (int erc = pl->tick_pin.Ensure((size_t)B * (tick_w + 1))) return erc;   // (+ two status ints a plant)
     HIP_OK(hipMemcpyAsync(pl->tick_pin, pl->state, (size_t)B * tick_w * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipMemcpyAsync(pl->tick_pin + (size_t)B * tick_w, pl->status, (size_t)B * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   }
@@ -2840,7 +2788,7 @@ int TrFinishBatchFetch(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt) 
   HIP_OK(hipStreamSynchronize(c->stream));
   TRACE("hip: tr_solve: waited for the device (every problem's state words, rows and solution back)");
   if (hook && hook->plant) MpcPlantsBack(c, *hook);
-  const double* p = c->fetch_pin;
+  const double* p = c->fetch.pin;
   const int best = *bfetch->best = (int)p[L.header()];
   for (int b = 0; b < B; ++b) { bfetch->final_cost[b] = p[L.final_cost() + b]; bfetch->status[b] = (int)p[L.status() + b]; }
   if (hook && hook->guess_out) std::memcpy(hook->guess_out, p + L.guess(), L.nguess * sizeof(double));
@@ -2891,15 +2839,15 @@ int TrFinishFetch(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt) {
   const TrFetchLayout L = TrFetchLayout::Make(1, TRS_COUNT, TrRowDoubles(rq), c->N, c->nq, c->nv, false, false);
   if (int rc = EnsureFetch(c, L.total())) return rc;
   TrGatherArgs G;
-  G.state = c->tr_state; G.rows = c->tr_rows; G.alt_off = rt.lookahead ? (long long)c->alt_off : 0; G.L = L; G.out = c->fetch_dev;
+  G.state = c->tr_state; G.rows = c->tr_rows; G.alt_off = rt.lookahead ? (long long)c->alt_off : 0; G.L = L; G.out = c->fetch.dev;
   G.q = c->q; G.v = c->v; G.slab = c->slab; G.dq = c->tr_dq; G.w = c->tr_w; G.nq = c->nq; G.nv = c->nv; G.slab_stride = (int)c->slab_stride;
   hipLaunchKernelGGL(tr_gather_kernel, dim3(16), dim3(256), 0, c->stream, G);
   HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(c->fetch_pin, c->fetch_dev, L.total() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipMemcpyAsync(c->fetch.pin, c->fetch.dev, L.total() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   TRACE("hip: tr_solve: gather + one copy enqueued");
   HIP_OK(hipStreamSynchronize(c->stream));
   TRACE("hip: tr_solve: waited for the device (state words, rows and the solution back)");
-  const double* p = c->fetch_pin;
+  const double* p = c->fetch.pin;
   std::memcpy(c->tr_pin, p + L.state(0), TRS_COUNT * sizeof(double));
   std::memcpy(rq.rows_host, p + L.rows(0), L.nrows * sizeof(double));
   for (int i = 0; i < 5; ++i)
@@ -2909,7 +2857,7 @@ int TrFinishFetch(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt) {
 // idto_hip_tr_solve: the state words and the statistics rows with ONE wait (the rows through pinned staging of the context)
 int TrFinishRows(idto_hip_ctx* c, const TrRequest& rq, const TrRoute& rt) {
   const size_t nrow = TrRowDoubles(rq);
-  if (int rc = EnsurePinned(&c->rows_pin, &c->rows_cap, std::max<size_t>(nrow, 64 * TRR_COUNT))) return rc;
+  if (int rc = c->rows_pin.Ensure(nrow, 64 * TRR_COUNT)) return rc;
   HIP_OK(hipMemcpyAsync(c->tr_pin, c->tr_state, TRS_COUNT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_OK(hipMemcpyAsync(c->rows_pin, c->tr_rows, nrow * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_OK(hipStreamSynchronize(c->stream));
@@ -3093,16 +3041,8 @@ int idto_hip_mpc_batch_begin(idto_hip_ctx* c, const int* selector, const int* ac
   if (c->N < 1) { g_err = "mpc_batch_begin: a plan needs at least two knots"; return -1; }
   HIP_OK(hipSetDevice(c->device));
   HIP_OK(hipStreamSynchronize(c->stream));
-  if (c->mpc) {
-    MpcBatchState* o = c->mpc;
-    Release(c, &o->breaks); Release(c, &o->selector_dev); Release(c, &o->actuated_dev); Release(c, &o->plan[0]); Release(c, &o->plan[1]);
-    Release(c, &o->work); Release(c, &o->tick_dev); Release(c, &o->io_dev);
-    if (o->tick_pin) (void)hipHostFree(o->tick_pin);
-    if (o->io_pin) (void)hipHostFree(o->io_pin);
-    delete o;
-    c->mpc = nullptr;
-  }
-  auto m = std::make_unique<MpcBatchState>();
+  c->mpc.reset();
+  auto m = std::make_unique<MpcBatchState>(c);   // (a failure below returns what it has made: the context is left without MPC storage)
   const size_t B = (size_t)c->batch;
   const int n = c->N + 1;
   m->L = MpcPlanLayout{n, c->nq, c->nv, nu};
@@ -3117,9 +3057,9 @@ int idto_hip_mpc_batch_begin(idto_hip_ctx* c, const int* selector, const int* ac
       Upload(c, actuated_dofs, (size_t)nu, &m->actuated_dev) || Alloc(c, B * len, &m->plan[0]) || Alloc(c, B * len, &m->plan[1]) ||
       Alloc(c, B * (size_t)n * m->L.dims(), &m->work) || Alloc(c, tick, &m->tick_dev) || Alloc(c, m->io_count, &m->io_dev))
     return -2;
-  HIP_OK(hipHostMalloc((void**)&m->tick_pin, tick * sizeof(double), hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&m->io_pin, m->io_count * sizeof(double), hipHostMallocDefault));
-  c->mpc = m.release();
+  if (int rc = m->tick_pin.Ensure(tick)) return rc;
+  if (int rc = m->io_pin.Ensure(m->io_count)) return rc;
+  c->mpc = std::move(m);
   ++c->mpc_generation;
   return 0;
 }
@@ -3129,7 +3069,7 @@ int idto_hip_mpc_batch_store(idto_hip_ctx* c, const double* q, const double* v, 
   if (int rc = MpcReady(c, "mpc_batch_store")) return rc;
   if (!q || !v || !tau || !start_times) { g_err = "mpc_batch_store: q, v, tau and start_times are required"; return -1; }
   HIP_OK(hipSetDevice(c->device));
-  MpcBatchState* m = c->mpc;
+  MpcBatchState* m = c->mpc.get();
   const size_t B = (size_t)c->batch, len = m->L.len();
   const size_t nqa = (size_t)m->L.n * c->nq, nva = (size_t)m->L.n * c->nv, nta = (size_t)c->N * c->nv;
   double* in = m->io_pin;
@@ -3159,7 +3099,7 @@ int idto_hip_mpc_batch_store(idto_hip_ctx* c, const double* q, const double* v, 
 
 // the copy of times and x0 and the shift, enqueued; guess_dev: [B][(N+1) nq] on the device, or null
 static int MpcShiftEnqueue(idto_hip_ctx* c, const double* times, const double* x0, double* guess_dev) {
-  MpcBatchState* m = c->mpc;
+  MpcBatchState* m = c->mpc.get();
   const int B = c->batch, nq = c->nq, nv = c->nv, n = m->L.n;
   // as idto_hip_set_q_batch + idto_hip_set_problem_batch leave the context
   c->trial_resident = false; c->spec_pending = false; c->spec_ready = false;
@@ -3202,7 +3142,7 @@ int idto_hip_mpc_batch_shift(idto_hip_ctx* c, const double* times, const double*
   if (int rc = MpcReady(c, "mpc_batch_shift")) return rc;
   if (!times || !x0) { g_err = "mpc_batch_shift: times[batch] and x0[batch][nq + nv] are required"; return -1; }
   HIP_OK(hipSetDevice(c->device));
-  MpcBatchState* m = c->mpc;
+  MpcBatchState* m = c->mpc.get();
   const size_t B = (size_t)c->batch, nqa = (size_t)m->L.n * c->nq;
   int rc = MpcShiftEnqueue(c, times, x0, m->io_dev);
   if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
@@ -3231,7 +3171,7 @@ static int TrSolveBatchFetch(idto_hip_ctx* c, const TrRequest& rq) {
     // (the guesses go where the one copy back finds them: behind the fetch's own doubles)
     const TrFetchLayout L = BatchFetchLayout(c, rq);
     if ((rc = EnsureFetch(c, L.total())) != 0) return rc;
-    rc = MpcShiftEnqueue(c, bf->mpc->times, bf->mpc->x0, c->fetch_dev + L.guess());
+    rc = MpcShiftEnqueue(c, bf->mpc->times, bf->mpc->x0, c->fetch.dev + L.guess());
   }
   if (!rc && (rq.nu > 0 || bf->mpc))
     rc = idto_hip_eval_tau(c);   // (as idto_hip_tr_solve_batch_constrained: the loop starts from the cost of the resident q)
@@ -3268,7 +3208,7 @@ static int MpcReplanCheck(idto_hip_ctx* c, const char* who, const MpcReplanArgs&
 static int MpcReplanRun(idto_hip_ctx* c, const double* times, const double* x0, const MpcReplanArgs& a, PlantState* plant, double* x_after_out,
                         int* plant_status_out) {
   TrRequest rq = MpcReplanRequest(a);
-  MpcBatchState* m = c->mpc;
+  MpcBatchState* m = c->mpc.get();
   MpcTickHook hook{m, times, x0, a.guess_out, a.plans_out, (size_t)c->batch * m->L.n * c->nq, (size_t)c->batch * m->L.len()};
   hook.plant = plant; hook.x_after_out = x_after_out; hook.plant_status_out = plant_status_out;
   TrBatchFetch bf{0, {a.q_out, a.v_out, a.tau_out, nullptr, nullptr}, a.final_cost, a.status, a.best, &hook}; rq.bfetch = &bf;
@@ -3277,7 +3217,7 @@ static int MpcReplanRun(idto_hip_ctx* c, const double* times, const double* x0, 
     // the loop returned before its gather (an error, a time-out): the plants have advanced and the device has been shifted all
     // the same - fetch the plants' states and status now, so that the caller and the host copies of the problems have them
     const size_t w = (size_t)(1 + c->nq + c->nv), B = (size_t)c->batch;
-    if (EnsurePinned(&plant->tick_pin, &plant->tick_pin_cap, B * (w + 1)) == 0 && hipStreamSynchronize(c->stream) == hipSuccess &&
+    if (plant->tick_pin.Ensure(B * (w + 1)) == 0 && hipStreamSynchronize(c->stream) == hipSuccess &&
         hipMemcpy(plant->tick_pin, plant->state, B * w * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
         hipMemcpy(plant->tick_pin + B * w, plant->status, B * 2 * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess) {
       const std::string err = g_err;
@@ -3311,7 +3251,7 @@ static idto_host::PlantShape PlantShapeOf(const idto_hip_ctx* c) {
   for (const idto_hip_ctx* ch : c->children) s.children |= ch != nullptr;
   s.model_records = c->model_records != nullptr; s.host_model = c->host_tables && c->host_model;
   if (c->mpc) { s.mpc = true; s.mpc_nu = c->mpc->L.nu; s.mpc_n = c->mpc->L.n; s.mpc_len = c->mpc->L.len(); }
-  if (const PlantState* p = c->plant; p && p->begun) {
+  if (const PlantState* p = c->plant.get(); p && p->begun) {
     s.plants_begun = true; s.plant_mode = p->mode; s.plant_nu = p->nu; s.plant_block = p->block; s.plant_lds = p->lds;
     s.plant_record_capacity = p->record_capacity; s.plant_mpc_current = c->mpc_generation == p->mpc_generation;
   }
@@ -3689,12 +3629,7 @@ int idto_hip_prefetch(idto_hip_ctx* c, int what) {
     slot->what = what; slot->count = (size_t)count;
     size_t total = 0;
     for (auto& pf : c->pre) if (pf.what >= 0) { pf.off = total; total += pf.count; pf.pending = false; }
-    if (total > c->pre_cap) {
-      if (c->pre_pin) (void)hipHostFree(c->pre_pin);
-      c->pre_pin = nullptr;
-      HIP_OK(hipHostMalloc((void**)&c->pre_pin, total * sizeof(double), hipHostMallocDefault));
-      c->pre_cap = total;
-    }
+    if (int rc = c->pre_pin.Ensure(total)) return rc;
     if (!slot->ev) HIP_OK(hipEventCreateWithFlags(&slot->ev, hipEventDisableTiming));
   }
   HIP_OK(hipEventRecord(slot->ev, c->stream));
@@ -3755,12 +3690,7 @@ int idto_hip_get_many(idto_hip_ctx* c, int n, const int* what, double* const* ou
     if (count < 0 || what[i] == IDTO_ARR_STEP) { g_err = "get_many: unknown array id (or IDTO_ARR_STEP: use idto_hip_get)"; return -1; }
     off[i + 1] = off[i] + (size_t)count;
   }
-  if (off[n] > c->many_cap) {
-    if (c->many_pin) (void)hipHostFree(c->many_pin);
-    c->many_pin = nullptr; c->many_cap = 0;
-    HIP_OK(hipHostMalloc((void**)&c->many_pin, std::max<size_t>(off[n], 1) * sizeof(double), hipHostMallocDefault));
-    c->many_cap = off[n];
-  }
+  if (int rc = c->many_pin.Ensure(off[n], 1)) return rc;
   for (int i = 0; i < n; ++i) {
     const int w = what[i];
     for (auto& pf : c->pre) if (pf.what == w) pf.pending = false;   // (a staged copy of it is superseded)

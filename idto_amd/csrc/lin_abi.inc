@@ -45,7 +45,7 @@ static int LinEnsure(idto_hip_ctx* c, const std::string& who, size_t dev_count, 
       Release(c, &s->record);
       return -2;
     }
-    c->lin = s.release();
+    c->lin = std::move(s);
   }
   return GrownEnsure(c, &c->lin->buf, dev_count, pin_count);
 }

@@ -1,17 +1,8 @@
 // plant_abi.inc — the C-ABI of the plants on the device (include/idto_hip.h idto_hip_forward_dynamics, idto_hip_plant_*):
 // host code only, included by idto_hip.hip inside its extern "C" block, where idto_hip_ctx and the helpers it uses
-// (PlantShapeOf, Refused, RecordForDevice, SelectRecords; Alloc, Release, EnsurePinned, UploadStage, HIP_OK, TRACE) are defined.
+// (PlantShapeOf, Refused, RecordForDevice, SelectRecords; Alloc, Release, UploadStage, HIP_OK, TRACE) are defined.
 // What an entry refuses, the block and LDS of a launch and the storage's layout are host/plant_calls.h's.  The kernel is
 // plant.h's, its instantiations plant_launch.hip's.
-
-static void PlantRelease(idto_hip_ctx* c) {
-  if (!c->plant) return;
-  Release(c, &c->plant->base);
-  if (c->plant->pin) (void)hipHostFree(c->plant->pin);
-  if (c->plant->tick_pin) (void)hipHostFree(c->plant->tick_pin);
-  delete c->plant;
-  c->plant = nullptr;
-}
 
 // The plants' one allocation, every plant's parameter record the context's (the base model's, or the context's record b)
 static int PlantAllocate(idto_hip_ctx* c, const idto_plant_params_t& prm) {
@@ -22,8 +13,8 @@ static int PlantAllocate(idto_hip_ctx* c, const idto_plant_params_t& prm) {
   const int B = c->batch, nq = c->nq, nv = c->nv, nu = pd ? c->mpc->L.nu : 0;
   HIP_OK(hipSetDevice(c->device));
   HIP_OK(hipStreamSynchronize(c->stream));   // (a record upload of the context's may be in flight; the old storage may be in use)
-  PlantRelease(c);
-  auto p = std::make_unique<PlantState>();
+  c->plant.reset();
+  auto p = std::make_unique<PlantState>(c);
   p->nu = nu; p->mpc_generation = c->mpc_generation; p->h = prm.h; p->mode = prm.mode; p->feed_forward = prm.feed_forward;
   p->block = idto_host::PlantBlock(s, prm.block_threads, beside); p->lds = idto_host::PlantLdsBytes(s, p->block, beside);
   p->record_capacity = idto_host::PlantRecordCapacity(prm.record_capacity);
@@ -41,7 +32,7 @@ static int PlantAllocate(idto_hip_ctx* c, const idto_plant_params_t& prm) {
   std::vector<double> all((size_t)B * rec_n);
   if (c->model_records) {
     if (hipMemcpy(all.data(), c->model_records, all.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
-      g_err = "plant_begin: hipMemcpy (the context's parameter records) failed"; Release(c, &p->base); return -2;
+      g_err = "plant_begin: hipMemcpy (the context's parameter records) failed"; return -2;
     }
   }
   const size_t mat = model_record_devmodel_at((size_t)c->M.blob_n);
@@ -55,15 +46,14 @@ static int PlantAllocate(idto_hip_ctx* c, const idto_plant_params_t& prm) {
   bool ok = hipMemcpy(p->records, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
   if (ok && pd) ok = hipMemcpy(p->Kp, prm.Kp, (size_t)nu * nq * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
                      hipMemcpy(p->Kd, prm.Kd, (size_t)nu * nv * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) { g_err = "plant_begin: hipMemcpy (parameter records, gains) failed"; Release(c, &p->base); return -2; }
+  if (!ok) { g_err = "plant_begin: hipMemcpy (parameter records, gains) failed"; return -2; }
   // (a launch above 64 KiB of dynamic LDS needs the opt-in: an instantiation that did not get it would fail at its launch)
   if (const hipError_t e = plant_set_max_lds(idto_host::kPlantMaxLds); e != hipSuccess) {
     (void)hipGetLastError();
     g_err = std::string("plant_begin: hipFuncSetAttribute (160 KiB of dynamic LDS for plant_kernel) failed: ") + hipGetErrorString(e);
-    Release(c, &p->base);
     return -2;
   }
-  c->plant = p.release();
+  c->plant = std::move(p);
   return 0;
 }
 
@@ -80,7 +70,7 @@ int idto_hip_plant_set_model(idto_hip_ctx* c, int b, const idto_model_t* model, 
   std::vector<double> record;
   if (int rc = idto_host::BuildModelVariant(base, *c->host_tables, b, model ? model : base, contact ? *contact : c->host_contact, &record, &g_err))
     return rc;
-  PlantState* p = c->plant;
+  PlantState* p = c->plant.get();
   if (record.size() * sizeof(double) != p->mstride) { g_err = "plant_set_model: the record has another size than the plants' records"; return -1; }
   HIP_OK(hipSetDevice(c->device));
   double* dev = at_problem(p->records, (size_t)b * p->mstride);
@@ -146,11 +136,11 @@ int idto_hip_forward_dynamics(idto_hip_ctx* c, const double* x, const double* ta
     if (int rc = PlantAllocate(c, prm)) return rc;
   }
   HIP_OK(hipSetDevice(c->device));
-  PlantState* p = c->plant;
+  PlantState* p = c->plant.get();
   const size_t B = (size_t)c->batch, nq = (size_t)c->nq, nv = (size_t)c->nv;
   // (fd_a, fd_M, fd_bias lie next to each other, each padded to 64 bytes: one copy back, then the status words)
   const size_t span = (size_t)(p->fd_bias + B * nv - p->fd_a);
-  if (int rc = EnsurePinned(&p->pin, &p->pin_cap, p->fd_pinned)) return rc;
+  if (int rc = p->pin.Ensure(p->fd_pinned)) return rc;
   std::memcpy(p->pin, x, B * (nq + nv) * sizeof(double));
   std::memcpy(p->pin + B * (nq + nv), tau_applied, B * nv * sizeof(double));
   HIP_OK(hipMemcpyAsync(p->fd_x, p->pin, B * (nq + nv) * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -179,14 +169,14 @@ int idto_hip_forward_dynamics(idto_hip_ctx* c, const double* x, const double* ta
 
 // the torque's upload (hold mode) and the launch, enqueued; tick_out: where the final [t, q, v] go as well, or null
 static int PlantStepEnqueue(idto_hip_ctx* c, int substeps, const double* tau_hold, int record_every, int nrec, double* tick_out) {
-  PlantState* p = c->plant;
+  PlantState* p = c->plant.get();
   const bool pd = p->mode == IDTO_PLANT_PD_PLUS;
   const size_t B = (size_t)c->batch, nv = (size_t)c->nv;
   PlantArgs A = PlantCommonArgs(c);
   A.state = p->state; A.tau = p->tau; A.substeps = substeps; A.tick_out = tick_out;
   A.record_every = nrec ? record_every : 0; A.record = nrec ? p->record : nullptr;
   if (pd) {
-    const MpcBatchState* m = c->mpc;
+    const MpcBatchState* m = c->mpc.get();
     A.pd = 1; A.n = m->L.n; A.nu = m->L.nu; A.feed_forward = p->feed_forward;
     A.breaks = m->breaks; A.plan = m->plan[m->cur]; A.plan_len = m->L.len();
     for (int s = 0; s < 3; ++s) { A.plan_y[s] = m->L.y(s); A.plan_m[s] = m->L.m(s); }
@@ -207,12 +197,12 @@ int idto_hip_plant_step(idto_hip_ctx* c, int substeps, const double* tau_hold, i
   int nrec = 0;
   if (int rc = Refused(idto_host::RefusePlantStep(PlantShapeOf(c), "plant_step", substeps, tau_hold, record_every, x_record_out != nullptr, &nrec))) return rc;
   HIP_OK(hipSetDevice(c->device));
-  PlantState* p = c->plant;
+  PlantState* p = c->plant.get();
   const size_t B = (size_t)c->batch, nq = (size_t)c->nq, nv = (size_t)c->nv;
   if (int rc = PlantStepEnqueue(c, substeps, tau_hold, record_every, nrec, nullptr)) return rc;
   if (!x_record_out && !status_out) return 0;
   const size_t rec_count = B * (size_t)nrec * (nq + nv);
-  if (int rc = EnsurePinned(&p->pin, &p->pin_cap, rec_count + B)) return rc;
+  if (int rc = p->pin.Ensure(rec_count + B)) return rc;
   if (rec_count) HIP_OK(hipMemcpyAsync(p->pin, p->record, rec_count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_OK(hipMemcpyAsync(p->pin + rec_count, p->status, 2 * B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_OK(hipStreamSynchronize(c->stream));
@@ -235,5 +225,5 @@ int idto_hip_mpc_batch_tick_plants(idto_hip_ctx* c, int substeps, int iterations
   HIP_OK(hipSetDevice(c->device));
   // the plants' substeps under PD+ on the current plans; the kernel's last act writes the tick buffer that mpc_shift_kernel reads
   if (int rc = PlantStepEnqueue(c, substeps, nullptr, 0, 0, c->mpc->tick_dev)) return rc;
-  return MpcReplanRun(c, nullptr, nullptr, a, c->plant, x_after_out, plant_status_out);
+  return MpcReplanRun(c, nullptr, nullptr, a, c->plant.get(), x_after_out, plant_status_out);
 }

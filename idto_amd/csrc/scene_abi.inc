@@ -30,7 +30,7 @@ static int SceneEnsure(idto_hip_ctx* c, const CallPlan& p) {
       Release(c, &s->geom_body);
       return -2;
     }
-    c->scene = s.release();
+    c->scene = std::move(s);
   }
   if (int rc = GrownEnsure(c, &c->scene->in, p.in_n, p.pinned)) return rc;
   return GrownEnsure(c, &c->scene->out, std::max<size_t>(p.total, 8), 0);
@@ -48,7 +48,7 @@ int idto_hip_scene_report(idto_hip_ctx* c, int nstates, const double* x, int mod
 
   HIP_OK(hipSetDevice(c->device));
   if (int rc = SceneEnsure(c, p)) return rc;
-  SceneState* sc = c->scene;
+  SceneState* sc = c->scene.get();
   std::memcpy(sc->in.pin, x, p.in_n * sizeof(double));
   HIP_OK(hipMemcpyAsync(sc->in.dev, sc->in.pin, p.in_n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   SceneLaunch L{};

@@ -17,9 +17,9 @@ static int TrackEnsure(idto_hip_ctx* c, const std::string& who, const CallPlan& 
       g_err = who + ": hipFuncSetAttribute (160 KiB of dynamic LDS for track_kernel) failed: " + hipGetErrorString(e);
       return -2;
     }
-    c->track = new GrownBuffer();
+    c->track = std::make_unique<GrownBuffer>();
   }
-  return GrownEnsure(c, c->track, p.total, p.pinned);
+  return GrownEnsure(c, c->track.get(), p.total, p.pinned);
 }
 
 // the inputs' upload and every launch, enqueued, then the fetch of what was asked for; K_dev: the gains on the device, or null

@@ -91,7 +91,7 @@ int BuildModelVariant(const idto_model_t* base, const ModelTables& base_t, int p
     if (t.float_vs[i] != base_t.float_vs[i]) return Differs(err, problem, "float_vs");
   }
   SCALAR(fast_shape) SCALAR(fast_lo) SCALAR(fast_n) SCALAR(f_maxpp) SCALAR(nxb) SCALAR(nstem) SCALAR(gcommon) SCALAR(gstem)
-  SCALAR(gslots) SCALAR(maxc) SCALAR(capsules)
+  SCALAR(gslots) SCALAR(maxc) SCALAR(capsules) SCALAR(cylinders)
 #undef SCALAR
   if (t.blob.size() != base_t.blob.size()) return Differs(err, problem, "the blob's size");
   *record = ModelRecord(m, t, contact);

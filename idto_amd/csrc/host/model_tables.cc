@@ -25,17 +25,20 @@ bool IdentityRotation(const double* X) {
   return ident;
 }
 
-// ---- 1. the geometry types and the pairs a capsule may take part in (include/idto_model.h).  The one place that checks
+// ---- 1. the geometry types and the pairs a capsule or a cylinder may take part in (include/idto_model.h).  The one place that checks
 // a pair's geometry indices: every later step reads geom_*[pair_a[i]] without asking.
 int CheckGeometry(const idto_model_t* m, std::string* err) {
   for (int g = 0; g < m->ngeoms; ++g) {
     const int t = m->geom_type[g];
-    if (t != IDTO_GEOM_SPHERE && t != IDTO_GEOM_BOX && t != IDTO_GEOM_CAPSULE)
-      return Refuse(err, "unknown geometry type (0 sphere, 1 box, 2 capsule)");
+    if (t != IDTO_GEOM_SPHERE && t != IDTO_GEOM_BOX && t != IDTO_GEOM_CAPSULE && t != IDTO_GEOM_CYLINDER)
+      return Refuse(err, "unknown geometry type (0 sphere, 1 box, 2 capsule, 4 cylinder)");
     const double* s = m->geom_size + (size_t)3 * g;
     if (t == IDTO_GEOM_CAPSULE &&
         !(std::isfinite(s[0]) && std::isfinite(s[1]) && std::isfinite(s[2]) && s[0] > 0 && s[1] >= 0))
       return Refuse(err, "capsule size must be finite with radius > 0 and h >= 0");
+    if (t == IDTO_GEOM_CYLINDER &&
+        !(std::isfinite(s[0]) && std::isfinite(s[1]) && std::isfinite(s[2]) && s[0] > 0 && s[1] > 0))
+      return Refuse(err, "cylinder size must be finite with radius > 0 and H > 0");
   }
   for (int i = 0; i < m->npairs; ++i) {
     const int ga = m->pair_a[i], gb = m->pair_b[i];
@@ -46,6 +49,8 @@ int CheckGeometry(const idto_model_t* m, std::string* err) {
       if (m->geom_body[box] >= 0 || !IdentityRotation(m->geom_X + (size_t)12 * box))
         return Refuse(err, "capsule-box contact pairs need a world-fixed box with identity rotation");
     }
+    if ((ta == IDTO_GEOM_CYLINDER && tb != IDTO_GEOM_SPHERE) || (tb == IDTO_GEOM_CYLINDER && ta != IDTO_GEOM_SPHERE))
+      return Refuse(err, "cylinder contact pairs need a sphere on the other side");
   }
   return 0;
 }
@@ -267,10 +272,10 @@ struct FastShapeOf {
   int shape = 0;
   int w2 = -1;   // a later slot of the (single) path that hangs off the world again (the spinner)
 };
-FastShapeOf RecogniseShape(const idto_model_t* m, const Stem& stem, const Star& star, bool shared, bool capsules) {
+FastShapeOf RecogniseShape(const idto_model_t* m, const Stem& stem, const Star& star, bool shared, bool reduced_geoms) {
   const int K = m->npaths, cbody = m->common_body, cj = cbody >= 0 ? m->jtype[cbody] : -1;
   FastShapeOf f;
-  bool ok = !(cbody >= 0 && cj != IDTO_JOINT_FLOATING) && !shared && stem.n() <= 1 && !capsules;
+  bool ok = !(cbody >= 0 && cj != IDTO_JOINT_FLOATING) && !shared && stem.n() <= 1 && !reduced_geoms;
   for (int p = 0; p < K; ++p) ok = ok && star.nchain[p] == star.maxc;
   int j0 = -1, k0 = -1;
   for (int p = 0; p < K && ok; ++p)
@@ -521,9 +526,12 @@ int BuildModelTables(const idto_model_t* m, ModelTables* out, std::string* err) 
   if (int rc = BuildPairLists(m, stem, star, &lists, err)) return rc;
   const Exchange xch = BuildExchange(m, stem, star, lists);
   const NPlus nplus = BuildNPlus(m);
-  bool capsules = false;
-  for (int g = 0; g < m->ngeoms; ++g) capsules = capsules || m->geom_type[g] == IDTO_GEOM_CAPSULE;
-  FastShapeOf fast = RecogniseShape(m, stem, star, lists.shared, capsules);
+  bool capsules = false, cylinders = false;
+  for (int g = 0; g < m->ngeoms; ++g) {
+    capsules = capsules || m->geom_type[g] == IDTO_GEOM_CAPSULE;
+    cylinders = cylinders || m->geom_type[g] == IDTO_GEOM_CYLINDER;
+  }
+  FastShapeOf fast = RecogniseShape(m, stem, star, lists.shared, capsules || cylinders);
   const FastOrder order = OrderFastPairs(m, star, lists, &fast);
 
   ModelTables& t = *out;
@@ -567,7 +575,7 @@ int BuildModelTables(const idto_model_t* m, ModelTables* out, std::string* err) 
   t.fast_lo = fast.shape ? (int)t.at.f_body : 0;
   t.fast_n = (int)(nd + (fast_end + 1) / 2) - t.fast_lo;
   t.nxb = xch.nxb; t.nstem = stem.n(); t.gslots = star.gslots; t.gcommon = star.gcommon; t.gstem = star.gstem;
-  t.maxc = star.maxc; t.capsules = capsules;
+  t.maxc = star.maxc; t.capsules = capsules; t.cylinders = cylinders;
   t.fd_dedup = dedup.on; t.fd_lanes_at = lanes_at + 2 * nd; t.fd_qpaths = dedup.qpaths; t.fd_vpaths = dedup.vpaths;
   return 0;
 }

@@ -25,9 +25,9 @@ struct ModelTables {
   int maxpp = 1, nfloat = 0, float_qs[4] = {0, 0, 0, 0}, float_vs[4] = {0, 0, 0, 0};
   int fast_shape = 0, fast_lo = 0, fast_n = 0, f_maxpp = 1, nxb = 0, nstem = 0, gcommon = 1, gstem = 0;
   unsigned long long gslots = 0;
-  // the context's: the longest chain, and whether the model has a capsule
+  // the context's: the longest chain, and whether the model has a capsule / a cylinder
   int maxc = 1;
-  bool capsules = false;
+  bool capsules = false, cylinders = false;
   // fd_kernel's forward-difference lane map without the redundant path lanes (model_layout.h tree_shape_dedup): whether the
   // model takes it (then the blob read as int[] holds kFdMainLanes + kFdHelperLanes lane words from fd_lanes_at on, right
   // behind f_seg's words and inside the part a shape's kernel stages; else none), and what it was

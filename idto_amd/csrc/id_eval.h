@@ -263,10 +263,42 @@ IDTO_DEV void capsule_centres(int typeA, V3 uA, double hA, V3* pA, int typeB, V3
   }
 }
 
-// Signed distance between two primitives (restates oracle SignedDistance(); capsules: reduced to spheres first).
+// ---- cylinders (include/idto_model.h): the cylinder side (R, H, axis z of RX, centre *p) of a sphere-cylinder pair
+// becomes, by the region of the sphere's centre x, the primitive whose existing expression is the closed form there:
+//  - the side (|c.z| <= H and r > R, or inside with R - r <= H - |c.z| and r > 0): a sphere of radius R on the axis at the
+//    height of x;
+//  - the rim (|c.z| > H and r > R): a sphere of radius 0 at the rim point;
+//  - the cap (r <= R above or below it, inside nearer to a cap, and r == 0 inside): a box of half extents (R, R, H).
+//    There |c.x|, |c.y| <= r, so the box's x and y faces are never nearer than the side; at r == 0 its x face is the side
+//    in the direction (1, 0, 0) with the box branch's own tie rule (dx <= dz), which is the cylinder's rule.
+// *type, *p and *s are replaced; RX stays (a sphere reads no rotation).
+IDTO_DEV void cylinder_reduce(const M3& RX, V3 x, int* type, V3* p, V3* s) {
+  const double R = s->x, H = s->y;
+  const V3 c = tmul(RX, x - *p);
+  const double r = __builtin_sqrt(c.x * c.x + c.y * c.y), az = __builtin_fabs(c.z);
+  const bool above = az > H;
+  if (above ? (r <= R) : (r <= R && !(R - r <= H - az && r > 0))) {
+    *type = IDTO_GEOM_BOX;
+    *s = mk(R, R, H);
+    return;
+  }
+  *type = IDTO_GEOM_SPHERE;
+  const double k = above ? R / r : 0.0;
+  *p = *p + RX * mk(c.x * k, c.y * k, above ? ((c.z >= 0) ? H : -H) : c.z);
+  *s = mk(above ? 0.0 : R, 0, 0);
+}
+
+// Signed distance between two primitives (restates oracle SignedDistance(); capsules: reduced to spheres first, a
+// cylinder: to the sphere or box of its region).
 IDTO_DEV SdResult signed_distance(int typeA, const M3& RA, V3 pA, V3 sA, int typeB, const M3& RB, V3 pB, V3 sB) {
   SdResult out;
   out.valid = false; out.phi = 0; out.n = mk(0, 0, 1); out.Ca = mk(0, 0, 0); out.Cb = mk(0, 0, 0);
+  // (unlikely: the register allocation of the kernels that compile this text follows the paths of the models without
+  // a cylinder)
+  if (__builtin_expect(typeA == IDTO_GEOM_CYLINDER || typeB == IDTO_GEOM_CYLINDER, 0)) {
+    if (typeA == IDTO_GEOM_CYLINDER) cylinder_reduce(RA, pB, &typeA, &pA, &sA);
+    else cylinder_reduce(RB, pA, &typeB, &pB, &sB);
+  }
   if (typeA == IDTO_GEOM_CAPSULE || typeB == IDTO_GEOM_CAPSULE) {   // (radius: size[0], as a sphere's)
     capsule_centres(typeA, col(RA, 2), sA.y, &pA, typeB, col(RB, 2), sB.y, &pB);
     typeA = (typeA == IDTO_GEOM_CAPSULE) ? IDTO_GEOM_SPHERE : typeA;

@@ -330,6 +330,7 @@ struct idto_hip_ctx : CtxBuffers {
   bool own_stream = false;
   int nb = 0, nq = 0, nv = 0, N = 0, npaths = 1, maxc = 1;
   bool capsules = false;   // the model has a capsule (include/idto_model.h): no fast shape, no fused launch
+  bool cylinders = false;  // the model has a cylinder: the same
   double dt = 0;
   std::vector<void*> allocs;
   DevModel M;
@@ -731,7 +732,7 @@ int UploadModel(idto_hip_ctx* c, const idto_model_t* m, const idto_host::ModelTa
   for (int i = 0; i < 4; ++i) { M.float_qs[i] = t.float_qs[i]; M.float_vs[i] = t.float_vs[i]; }
   M.fast_shape = t.fast_shape; M.fast_lo = t.fast_lo; M.fast_n = t.fast_n; M.f_maxpp = t.f_maxpp;
   M.gslots = t.gslots; M.gcommon = t.gcommon; M.gstem = t.gstem; M.nxb = t.nxb; M.nstem = t.nstem;
-  c->maxc = t.maxc; c->capsules = t.capsules; c->model_has_fd_dedup = t.fd_dedup;
+  c->maxc = t.maxc; c->capsules = t.capsules; c->cylinders = t.cylinders; c->model_has_fd_dedup = t.fd_dedup;
   return 0;
 }
 
@@ -1769,7 +1770,7 @@ static int LaunchLdl(idto_hip_ctx* c, const SolverPlan& p, const double* b, doub
 // ---- one persistent launch for the whole Gauss-Newton iteration (fused.h)
 static int FusedVariant(const idto_hip_ctx* c) {  // instantiated (MAXC, K) combinations: the reference's example models
   if (c->M.nxb || c->M.nstem > 1) return 0;   // (gn_fused_kernel embeds id_eval without the exchange of shared pairs / the stem)
-  if (c->capsules) return 0;   // (capsule models: the three-launch path only)
+  if (c->capsules || c->cylinders) return 0;   // (capsule and cylinder models: the three-launch path only)
   const int mc = idto_host::FdChainBound(c->maxc);   // (what a FUSED plan names)
   int variant = 0, i = 0;
 #define FUSED_IS(MC, KM, PD, GW) ++i; if (mc == MC && c->nq == KM) variant = i;

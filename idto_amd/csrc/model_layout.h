@@ -43,7 +43,7 @@ enum { FP_INFO = 0, FP_XC = 2, FP_SC = 14, FP_XO = 17, FP_SO = 29, FP_STRIDE = 3
 // slot 0 of every path has joint J0 and parent kind K0, and the later slots are revolute on the previous one - but for
 // slot W2 (-1: none) of a single path, which hangs off the world again.  On top of the tuple:
 //   - GS: bodies whose weight is switched off are allowed; a shape without it is chosen only when every body has gravity
-//   - a capsule clears the shape (id_fast.h's pair code has no capsule reduction)
+//   - a capsule or a cylinder clears the shape (id_fast.h's pair code has neither reduction)
 //   - shared pairs or a stem below the common body clear it (the pair records are per path; no shape has a stem)
 // KC: the chain bound fd_kernel<KC, shape> is instantiated with (fd_launch.hip).
 struct TreeShape { int MAXC, NP, CJ, J0, K0, W2, GS, KC; };

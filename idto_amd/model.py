@@ -18,7 +18,9 @@ import numpy as np
 JOINT_TYPES = {"revolute": 0, "prismatic": 1, "planar": 2, "floating": 3}
 JOINT_NQ = {0: 1, 1: 1, 2: 3, 3: 7}
 JOINT_NV = {0: 1, 1: 1, 2: 3, 3: 6}
-GEOM_TYPES = {"sphere": 0, "box": 1, "capsule": 2}   # capsule size: [radius, h = length / 2, 0] (include/idto_model.h)
+# capsule size: [radius, h = length / 2, 0]; cylinder size: [radius, H = length / 2, 0]; 3 is reserved
+# (include/idto_model.h)
+GEOM_TYPES = {"sphere": 0, "box": 1, "capsule": 2, "cylinder": 4}
 MAX_PATHS = 8
 MAX_CHAIN = 8
 MAX_STEM = 4   # bodies of the stem: the common body and its ancestors (include/idto_model.h IDTO_MAX_STEM)
@@ -284,7 +286,8 @@ class Model:
                     f"pair {k} touches body {b} outside path {p}"
         # geometry types; a capsule: radius > 0, h >= 0, finite, and against a box only a world-fixed one of identity
         # rotation (the rules idto_hip_create enforces)
-        cap, box = GEOM_TYPES["capsule"], GEOM_TYPES["box"]
+        # a cylinder: radius > 0, H > 0, finite, and only against a sphere
+        cap, box, cyl, sph = GEOM_TYPES["capsule"], GEOM_TYPES["box"], GEOM_TYPES["cylinder"], GEOM_TYPES["sphere"]
         for g in range(self.ngeoms):
             t = int(self.geom_type[g])
             assert t in GEOM_TYPES.values(), f"geometry {g}: unknown type {t}"
@@ -292,9 +295,15 @@ class Model:
                 s = self.geom_size[g]
                 assert np.isfinite(s).all() and s[0] > 0 and s[1] >= 0, \
                     f"geometry {g}: a capsule needs a finite size with radius > 0 and h >= 0"
+            if t == cyl:
+                s = self.geom_size[g]
+                assert np.isfinite(s).all() and s[0] > 0 and s[1] > 0, \
+                    f"geometry {g}: cylinder size must be finite with radius > 0 and H > 0"
         for k in range(self.npairs):
             ga, gb = int(self.pair_a[k]), int(self.pair_b[k])
             types = {int(self.geom_type[ga]), int(self.geom_type[gb])}
+            assert cyl not in types or types == {cyl, sph}, \
+                f"pair {k}: cylinder contact pairs need a sphere on the other side"
             if types == {cap, box}:
                 bx = ga if int(self.geom_type[ga]) == box else gb
                 assert int(self.geom_body[bx]) == -1 and np.array_equal(self.geom_X[bx][:9], np.eye(3).ravel()), \

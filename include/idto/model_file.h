@@ -125,8 +125,11 @@ class ModelFile {
       expect("body"); m.geom_body.push_back(integer());
       expect("type");
       const std::string& ty = nxt();
-      if (ty != "sphere" && ty != "box" && ty != "capsule") throw std::runtime_error("ModelFile: unknown geometry type " + ty);
-      m.geom_type.push_back(ty == "sphere" ? (int)IDTO_GEOM_SPHERE : (ty == "box" ? (int)IDTO_GEOM_BOX : (int)IDTO_GEOM_CAPSULE));
+      if (ty != "sphere" && ty != "box" && ty != "capsule" && ty != "cylinder")
+        throw std::runtime_error("ModelFile: unknown geometry type " + ty);
+      m.geom_type.push_back(ty == "sphere" ? (int)IDTO_GEOM_SPHERE
+                            : ty == "box" ? (int)IDTO_GEOM_BOX
+                            : ty == "capsule" ? (int)IDTO_GEOM_CAPSULE : (int)IDTO_GEOM_CYLINDER);
       expect("size"); floats(&m.geom_size, 3);
       expect("X_BG"); floats(&m.geom_X, 12);
     }

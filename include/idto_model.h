@@ -38,9 +38,12 @@ enum idto_joint_type {
 enum idto_geom_type {
   IDTO_GEOM_SPHERE = 0, /* size[0] = radius */
   IDTO_GEOM_BOX = 1,    /* size = half extents */
-  IDTO_GEOM_CAPSULE = 2 /* size[0] = radius r > 0, size[1] = h >= 0: half the distance between the two hemisphere
-                         * centres (Drake's length / 2), size[2] unused (0).  The axis is the geometry frame's z: the
-                         * segment is c(s) = p + u s, s in [-h, h], u = column 2 of R_WG */
+  IDTO_GEOM_CAPSULE = 2, /* size[0] = radius r > 0, size[1] = h >= 0: half the distance between the two hemisphere
+                          * centres (Drake's length / 2), size[2] unused (0).  The axis is the geometry frame's z: the
+                          * segment is c(s) = p + u s, s in [-h, h], u = column 2 of R_WG */
+  /* 3 is reserved: it names no geometry and is refused as an unknown type */
+  IDTO_GEOM_CYLINDER = 4 /* size[0] = radius R > 0, size[1] = H > 0: half of Drake's length (a capsule's h convention),
+                          * size[2] unused (0).  The axis is the geometry frame's z; flat caps at z = +-H */
 };
 
 typedef struct idto_model {
@@ -83,8 +86,24 @@ typedef struct idto_model {
    *  - capsule-box (either order) ONLY with a world-fixed box of identity rotation (the condition of box-box): the
    *    segment end with the lower world z, the -h end on a tie.
    * With h = 0 every substitute centre is p itself, bit for bit: a zero-length capsule is its sphere.  idto_hip_create
-   * refuses, before it touches a device, a geometry type other than these three, a capsule with r <= 0, h < 0 or a
-   * non-finite size, and a capsule against any other box. */
+   * refuses, before it touches a device, a geometry type other than the four of idto_geom_type, a capsule with r <= 0,
+   * h < 0 or a non-finite size, and a capsule against any other box.
+   * A cylinder (on the world or on any body, any pose) takes part ONLY in sphere-cylinder pairs, in either order.  The
+   * pair is evaluated in closed form, as Drake does it (DistanceToPoint for a cylinder: the 2-D box [0, R] x [-H, H] of
+   * its cross-section).  With c = RX^T (x - p), x the sphere's centre, rho its radius, p the cylinder's centre and RX its
+   * rotation in the world: r = sqrt(c.x^2 + c.y^2), e = (c.x, c.y, 0) / r, or (1, 0, 0) of the cylinder's frame when
+   * r == 0.
+   *  - outside (r > R or |c.z| > H): the nearest point is (r', z') = (min(r, R), clamp(c.z, -H, H)),
+   *    dv = (r - r', c.z - z'), dist = |dv|, g2 = dv / dist, phi = dist - rho;
+   *  - inside, with dr = R - r and dz = H - |c.z|: if dr <= dz the side, g2 = (1, 0), nearest (R, c.z),
+   *    phi = -dr - rho; otherwise the cap, g2 = (0, c.z >= 0 ? 1 : -1), nearest (r, +-H), phi = -dz - rho (the tie rule
+   *    of the box branch: the lower axis wins).
+   * g = e g2.r + z g2.z, gW = RX g; the witness point on the cylinder is p + RX (e r' + z z'), the one on the sphere is
+   * x - gW rho; n, Ca and Cb are assigned as for sphere-box: with the sphere as A, n = -gW.  The device reaches this
+   * through the existing expressions (csrc/id_eval.h cylinder_reduce): the side region is a sphere of radius R on the
+   * axis, the cap region a box of half extents (R, R, H), the rim a sphere of radius 0 at the rim point.
+   * idto_hip_create refuses, before it touches a device, a cylinder with R <= 0, H <= 0 or a non-finite size, and a
+   * cylinder paired with a box, a capsule or another cylinder. */
 
   /* Evaluation/summation-order specification ("star" decomposition): one
    * optional common body (computed by every path), the stem it sits on, plus npaths disjoint

@@ -134,6 +134,9 @@ def parse_urdf(path, reg):
             elif g.find("capsule") is not None:   # size: radius, half the length (include/idto_model.h)
                 c = g.find("capsule")
                 L.geoms.append(("capsule", [float(c.get("radius")), float(c.get("length")) / 2, 0], Xg, reg[0]))
+            elif g.find("cylinder") is not None:   # size: radius, half the length (include/idto_model.h)
+                c = g.find("cylinder")
+                L.geoms.append(("cylinder", [float(c.get("radius")), float(c.get("length")) / 2, 0], Xg, reg[0]))
             else:
                 raise ValueError(f"unsupported collision geometry in {path}:{L.name}")
             reg[0] += 1
@@ -198,6 +201,9 @@ def parse_sdf(path, reg, prefix=""):
             elif g.find("capsule") is not None:
                 c = g.find("capsule")
                 L.geoms.append(("capsule", [float(c.findtext("radius")), float(c.findtext("length")) / 2, 0], Xg, reg[0]))
+            elif g.find("cylinder") is not None:
+                c = g.find("cylinder")
+                L.geoms.append(("cylinder", [float(c.findtext("radius")), float(c.findtext("length")) / 2, 0], Xg, reg[0]))
             else:
                 raise ValueError("unsupported collision geometry")
             reg[0] += 1
@@ -391,6 +397,13 @@ def build_model(name, links, link_order, joints, actuated, groups, spec, extra_w
             bi, bj = geoms[i][1], geoms[j][1]
             if bi == bj or (min(bi, bj), max(bi, bj)) in adjacent or excluded(geoms[i][5], geoms[j][5]):
                 continue
+            # a cylinder meets spheres only (include/idto_model.h); Drake evaluates its other pairs, this project refuses
+            # them, so they are left out and named
+            kinds = (geoms[i][2], geoms[j][2])
+            if "cylinder" in kinds and "sphere" not in kinds:
+                print(f"{name}: dropped the {kinds[0]}-{kinds[1]} pair of geometries {i} ({geoms[i][5]}) and {j} "
+                      f"({geoms[j][5]}): a cylinder meets spheres only")
+                continue
             paths = {body_path[b] for b in (bi, bj) if b >= 0 and body_path[b] >= 0}
             # a pair between the chains of two paths (shared pair) is evaluated by both; its pair_path names the path of
             # geometry A's body (include/idto_model.h)
@@ -411,6 +424,14 @@ def build_model(name, links, link_order, joints, actuated, groups, spec, extra_w
 def ground_box(reg):
     """Box(25, 25, 10) centred at z = -5 on the world body (hopper.cc:44-49)."""
     g = ("box", [12.5, 12.5, 5.0], X(np.eye(3), [0, 0, -5.0]), reg[0])
+    reg[0] += 1
+    return g
+
+
+def hill(reg, i, spacing, height):
+    """Hill i of the cheetah's terrain: Cylinder(1.0, 25) on the world body, rolled by pi / 2 so that its axis lies along
+    y, centred at (2 + spacing i, 0, -1 + height) (examples/mini_cheetah/mini_cheetah.cc:58-68)."""
+    g = ("cylinder", [1.0, 12.5, 0], X(rpy_to_R(math.pi / 2, 0, 0), [2.0 + spacing * i, 0.0, -1.0 + height]), reg[0])
     reg[0] += 1
     return g
 
@@ -626,6 +647,38 @@ def convert_examples():
     return out
 
 
+OUT_CYLINDER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "cylinder")
+
+
+def convert_cylinder_examples(hills=2, height=0.05, spacing=1.0):
+    """The cheetah on hills as a test fixture (tests/golden/cylinder/): mini_cheetah.cc --hills=2 with the flags'
+    defaults for height and spacing.  The hills are registered after the ground.  Every sphere of the cheetah against every
+    hill is a pair; the torso's box against a hill is a pair in Drake that this project refuses: build_model drops it
+    and says so.  The YAML is the cheetah's."""
+    os.makedirs(OUT_CYLINDER, exist_ok=True)
+    reg = [0]
+    l, o, j, a, g = parse_urdf(f"{REF}/models/mini_cheetah_mesh.urdf", reg)
+    legs = [[f"abduct_{s}", f"thigh_{s}", f"shank_{s}"] for s in ("fl", "fr", "hl", "hr")]
+    world = [ground_box(reg)] + [hill(reg, i, spacing, height) for i in range(hills)]
+    name = "mini_cheetah_hills"
+    m = build_model(name, l, o, j, a, g, dict(common="body", paths=legs), extra_world_geoms=world)
+    m.save(os.path.join(OUT_CYLINDER, f"{name}.model"))
+    print(f"{name}: nb={m.nbodies} nq={m.nq} nv={m.nv} geoms={m.ngeoms} pairs={m.npairs} "
+          f"paths={m.npaths} common={m.common_body} unactuated={m.unactuated_dofs}")
+    src = yaml.safe_load(open(f"{REF}/examples/mini_cheetah/mini_cheetah.yaml"))
+    cfg = {"model": name, "source": f"reference examples/mini_cheetah/mini_cheetah.yaml (--hills={hills} "
+                                    f"--hill_height={height} --hill_spacing={spacing})"}
+    # (the keys that the shipped idto_amd/configs/mini_cheetah.yaml carries: CONFIG_KEYS and the plant's gains and step)
+    shipped = yaml.safe_load(open(os.path.join(OUT_CONFIGS, "mini_cheetah.yaml")))
+    for k in shipped:
+        if k in src and k not in cfg:   # (PyYAML reads the reference's `1e-3` as a string)
+            cfg[k] = float(src[k]) if isinstance(src[k], str) and isinstance(shipped[k], float) else src[k]
+    with open(os.path.join(OUT_CYLINDER, f"{name}.yaml"), "w") as f:
+        yaml.safe_dump(cfg, f, sort_keys=False, default_flow_style=None)
+    return m
+
+
 if __name__ == "__main__":
     convert_all()
     convert_examples()
+    convert_cylinder_examples()

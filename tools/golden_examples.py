@@ -17,6 +17,13 @@ What geometry cannot decide - which end on equal heights, what parallel segments
 the generators refuse a state that comes closer than MIN_DZ / MIN_SIN2.  Only pairs that could act count: a pair whose
 signed distance is beyond the contact threshold whichever end or point is taken exerts no force under any convention.
 
+Cylinders (tools/make_golden.py cylinder; tests/golden/cylinder/).  `sphere_cylinder` is the closed form of
+include/idto_model.h written out once more: the nearest point of the rectangle [0, R] x [-H, H] in the plane through the
+axis and the sphere's centre, and inside the nearer of the side and a cap.  The six stored states of the cheetah on hills
+keep every foot far from a hill's axis (r == 0) and from the dr == dz tie - a foot's centre that is inside a hill is
+centimetres below its side and metres from its caps -, so that neither unpinned choice of the rule is asked of this
+restatement.
+
 States.  The recipes restate the trajectory helpers of the tests (tests/test_model_cross_pairs.py touching_trajectory,
 tests/test_model_stem.py punyo_trajectory, tests/test_gpu_capsule.py frozen_case); tests/test_golden_examples.py
 rebuilds every stored q from those helpers and compares.
@@ -24,6 +31,7 @@ rebuilds every stored q from those helpers and compares.
 Directed contact states (the last section; tools/make_golden.py contact): the labels of a contact pair's branches, the
 margins every stored state keeps from the branch boundaries, and the names of a box's regions."""
 import copy
+import math
 import os
 
 import numpy as np
@@ -33,7 +41,7 @@ from idto_amd.problem import load_config, make_problem, synthetic_trajectory
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 EXAMPLES = os.path.join(ROOT, "tests", "golden", "examples")
-SPHERE, BOX, CAPSULE = 0, 1, 2
+SPHERE, BOX, CAPSULE, CYLINDER = 0, 1, 2, 4
 MIN_DZ = 1e-3      # capsule-box: least |z(+h end) - z(-h end)| [m]
 MIN_SIN2 = 1e-3    # capsule-capsule: least 1 - dot(u1, u2)^2
 UNIQUE = 1e-9      # capsule-capsule: two minimisers count as one below this distance in (s, t) [m]
@@ -140,6 +148,58 @@ def reduce_capsules(tA, XA, sA, bodyA, tB, XB, sB, bodyB, threshold=None, margin
     if tB == CAPSULE:
         cB = against(tB, pB, uB, hB, rB, tA, XA, sA, bodyA)
     return cA, cB
+
+
+# ---- the sphere-cylinder rule, written from include/idto_model.h (Drake's DistanceToPoint for a cylinder: the 2-D box
+# [0, R] x [-H, H] of its cross-section in the plane through the axis and the point)
+def sphere_cylinder(x, rho, X_cyl, R, H):
+    """-> (phi, gW, the witness point on the sphere, the one on the cylinder); gW points from the cylinder's surface to
+    the sphere's centre (outside) or from the centre to the nearest surface (inside), in the world"""
+    RX, p = np.asarray(X_cyl[:3, :3], float), np.asarray(X_cyl[:3, 3], float)
+    c = RX.T @ (np.asarray(x, float) - p)
+    r = math.hypot(c[0], c[1])
+    radial = np.array([c[0] / r, c[1] / r, 0.0]) if r > 0 else np.array([1.0, 0.0, 0.0])
+    axial = np.array([0.0, 0.0, 1.0])
+    if r > R or abs(c[2]) > H:   # outside: the nearest point of the rectangle, in (r, z)
+        near = np.array([min(r, R), max(-H, min(H, c[2]))])
+        away = np.array([r, c[2]]) - near
+        dist = math.hypot(away[0], away[1])
+        g2, phi = away / dist, dist - rho
+    else:                        # inside: the nearer of the side and the cap, the side on a tie
+        to_side, to_cap = R - r, H - abs(c[2])
+        if to_side <= to_cap:
+            g2, near, phi = np.array([1.0, 0.0]), np.array([R, c[2]]), -to_side - rho
+        else:
+            up = 1.0 if c[2] >= 0 else -1.0
+            g2, near, phi = np.array([0.0, up]), np.array([r, up * H]), -to_cap - rho
+    gW = RX @ (radial * g2[0] + axial * g2[1])
+    return phi, gW, np.asarray(x, float) - gW * rho, p + RX @ (radial * near[0] + axial * near[1])
+
+
+# ---- the cheetah on hills (tests/golden/cylinder): six states - feet on a hill, on the ground, in the air
+CYLINDER_DIR = os.path.join(ROOT, "tests", "golden", "cylinder")
+HILLS_STATES = [   # (source, the base's x, its z, pitch about y [rad])
+    ("in the air", -1.0, 1.5, 0.0),
+    ("on the ground in front of the hills", 0.5, 0.27, 0.0),
+    ("front feet on the first hill's flank, rear feet on the ground", 1.55, 0.275, 0.0),
+    ("over the first hill's top", 2.0, 0.315, 0.0),
+    ("between the hills, pitched", 2.5, 0.28, 0.1),
+    ("rear feet on the second hill's far flank, front feet on the ground", 3.42, 0.275, -0.05),
+]
+
+
+def hills_example():
+    return (load_model(os.path.join(CYLINDER_DIR, "mini_cheetah_hills.model")),
+            load_config(os.path.join(CYLINDER_DIR, "mini_cheetah_hills.yaml")))
+
+
+def hills_state(cfg, source):
+    """q of a state of HILLS_STATES: the YAML's q_init with the base moved and pitched"""
+    (x, z, pitch), = [s[1:] for s in HILLS_STATES if s[0] == source]
+    q = np.asarray(cfg["q_init"], float).copy()
+    q[0:4] = [math.cos(pitch / 2), 0.0, math.sin(pitch / 2), 0.0]
+    q[4], q[6] = x, z
+    return q
 
 
 # ---- models

@@ -48,9 +48,13 @@ PUNYO_ROWS = (
     "| an SDF `<inertial>` without `<inertia>` (every link of `models/punyoid.sdf`): libsdformat's default, ixx = iyy = izz = 1 with zero products - the glue links of 0.1 kg included | `tools/convert_models.py parse_sdf`; independently `tools/make_model_fixture.py` (`tests/golden/examples/world_punyo.json`) | none in-tree (the file gives masses only) | `plant.GetBodyByName(\"waist\").default_rotational_inertia()` after `Parser.AddModels` |\n"
     "| an SDF joint `<pose>` is in the child link's frame, the axis in that joint frame; the body frame here is the joint frame, the link hangs in it at the inverse pose (punyo's shoulder, elbow and wrist joints: 0.05 - 0.16 m off the link origin, two turned by pi, so that `shoulderR_joint2` and `elbowR_joint2` turn about -y of the model) | `tools/convert_models.py parse_sdf` (`X_JC`), `build_model`; independently `tools/make_model_fixture.py read_sdf` | SDFormat 1.7 semantics; `models/punyoid.sdf:575-583, 660-668, 695-703` | FK of `hand_R` at q with `shoulderR_joint2` = 0.5 against the model's `X_PF` chain; the sign of the DoF |\n"
     "| punyo's q: height, three torso joints, the arm of `shoulderL_joint1` (declared first), the arm of `shoulderR_joint1`, the ball - depth-first in joint declaration order; `punyo.yaml` comments the first arm as \"right\" | `tools/convert_models.py build_model` (visiting order), `tests/golden/examples/punyo.model` | every vector of `examples/punyo/punyo.yaml` is the same for both arms, so no number of the fixture depends on it | `plant.GetJointByName(\"shoulderL_joint1\").position_start()` against `shoulderR_joint1`'s |\n")
+# (cylinders: Drake is not part of this build; the second row's choices are taken from memory of its source)
+CYLINDER_ROWS = (
+    "| box-cylinder: the cheetah's torso `Box` against a hill `Cylinder` is a candidate pair in Drake (FCL); this project refuses a cylinder against anything but a sphere, and the converter drops the pair and prints that it did | `tools/convert_models.py build_model`, `host/model_tables.cc CheckGeometry` | none in-tree | `QueryObject::ComputeSignedDistancePairwiseClosestPoints` on `mini_cheetah.cc --hills=2` with the torso lowered onto a hill: whether the pair is reported and from which distance its force matters |\n"
+    "| sphere-cylinder: at `r == 0` the radial direction is `(1, 0, 0)` of the cylinder's frame, and inside at `R - r == H - abs(c.z)` the side wins over the cap (`dr <= dz`, the box branch's tie rule) - both from memory of Drake's `DistanceToPoint` for a cylinder, not checked against it | `csrc/id_eval.h cylinder_reduce`, `include/idto_model.h`, `tests/cylinder_ref.py` | none in-tree | `QueryObject::ComputeSignedDistanceToPoint` for points on the axis of a `Cylinder` (above a cap and inside) and at an interior point with equal distance to the side and a cap: compare `grad_W` |\n")
 if WELDED_ROW in text:
     i = text.index(WELDED_ROW)
     j = text.index("\n", i) + 1
-    text = text[:j] + CAPSULE_ROWS + PUNYO_ROWS + text[j:]
+    text = text[:j] + CAPSULE_ROWS + CYLINDER_ROWS + PUNYO_ROWS + text[j:]
 open(os.path.join(ROOT, "DESIGN.md"), "w").write(text)
 print("DESIGN.md:", len(text.splitlines()), "lines")
